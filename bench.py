@@ -29,9 +29,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# one hardware queue per step in flight (the HIP runtime maps streams onto 4 queues by default; launches that share a
-# queue run one after the other).  Read by the runtime when it initialises, i.e. after this line.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 PAIRS_PER_GPU = 64
 ADOPTION_DEFAULT = True        # cvo_batch_set_adoption in the timed loops unless --no-adoption (tests/test_gpu_config3.py runs both modes against the oracle)
@@ -359,11 +356,33 @@ def config5_child():
             "parity": d.get("parity"), "child_seconds": time.perf_counter() - t0, "command": " ".join(cmd[1:])}
 
 
+DUMP_BYTES_MAX = 64 * 10**6          # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, results, first_pair):
+    """--dump-outputs: what cvo_batch_wait handed the caller for the last timed step, one DIR/<name>.npy per field (float32 as
+    returned, integers as float64), pair_index naming the synthetic pair of every row.  rebuilds / dense_fallbacks are left out:
+    they count the kernel's list upkeep, not the alignment.  Above DUMP_BYTES_MAX in all, a fixed seeded sample of the rows."""
+    arrays = {"pair_index": np.arange(first_pair, first_pair + len(results), dtype=np.float64)}
+    for k in ("transform", "R", "T", "ell"):
+        arrays[k] = np.stack([np.asarray(r[k], np.float32) for r in results])
+    for k in ("iter", "A_nonzero", "iterations_run", "status"):
+        arrays[k] = np.array([r[k] for r in results], np.float64)
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    room = DUMP_BYTES_MAX - 256 * len(arrays)
+    if row_bytes * len(results) > room:
+        keep = np.sort(np.random.default_rng(0).choice(len(results), room // row_bytes, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=256)
-    ap.add_argument("--warmup", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 256; 24 with --shape eth3d)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 32; 4 with --shape eth3d)")
     ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="frame pairs per GPU per step")
     ap.add_argument("--workgroups", type=int, default=1, help="workgroups per pair (0 = auto: lowest latency of one batch alone; 1 = highest throughput)")
     ap.add_argument("--streams", type=int, default=8, help="steps in flight (batch objects on separate HIP streams)")
@@ -379,7 +398,14 @@ def main():
     ap.add_argument("--parity-only", action="store_true", help="with --no-cpu-baseline: still check every timed pair against the oracle (parity build, all host threads), without the timed CPU legs")
     ap.add_argument("--no-config5", action="store_true", help="do not append the `config5` object (a short run of BASELINE config 5, --shape eth3d, in a child process) to the default line")
     ap.add_argument("--dry-launch", action="store_true", help="every rank prints its block of the step's pairs (cvo_shard_range) as one JSON line and exits: no GPU needed")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 24 if args.shape == "eth3d" else 256
+    if args.warmup is None:
+        args.warmup = 4 if args.shape == "eth3d" else 32
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "RANK" not in os.environ:      # the bare invocation: this process becomes the launcher of the N ranks (before anything imports torch or touches the GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], collect_stdout=args.dry_launch))
     if args.shape == "eth3d":      # BASELINE config 5 defaults: 4 workgroups per pair, 4 launches side by side, 64 workgroups (16 pair slots) each
@@ -387,8 +413,6 @@ def main():
         if args.workgroups == dflt.workgroups: args.workgroups = 4
         if args.streams == dflt.streams: args.streams = 4
         if args.max_workgroups == dflt.max_workgroups: args.max_workgroups = 64
-        if args.steps == dflt.steps: args.steps = 24
-        if args.warmup == dflt.warmup: args.warmup = 4
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -617,6 +641,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(i)
+    last_bi = inflight[-1]                         # the batch object that ran the last timed step
     drain()
     sync_all()
     elapsed = time.perf_counter() - t0
@@ -633,6 +658,8 @@ def main():
 
     results = batch.wait(n) if n else []
     info = batch.last_launch() if n else {}
+    if args.dump_outputs and rank == 0 and n:
+        dump_outputs(args.dump_outputs, batches[last_bi].wait(n), first_pair)
 
     # Secondary figure ("alignments incl. the post-align score block"): every step also queues the tracker's score
     # block (4 inner products + 1 Hessian per pair, cvo.cpp:475-503) behind its align launch and collects it with the results.

@@ -6,7 +6,6 @@ lower bounds (work / 256, the longest pair behind the last start).  usage: gpu_t
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import bench
 

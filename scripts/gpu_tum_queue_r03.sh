@@ -3,7 +3,7 @@
 run() { # label steps warm env... -- args
   label=$1; steps=$2; warm=$3; shift 3
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  v=$(env GPU_MAX_HW_QUEUES=16 "${envs[@]}" timeout -k 10 300 python bench.py --steps $steps --warmup $warm --no-cpu-baseline --no-latency-probe "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['kernel_ms'])")
+  v=$(env "${envs[@]}" timeout -k 10 300 python bench.py --steps $steps --warmup $warm --no-cpu-baseline --no-latency-probe "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(round(d['value']), d['roofline']['kernel_ms'])")
   echo "rep $rep steps $steps $label: $v"
 }
 for rep in 1 2; do for cfg in "256 32" "20 5"; do read -r steps warm <<< "$cfg"

@@ -1,6 +1,6 @@
-// development aid: which XCD does block p of a launch land on?  Eight streams (GPU_MAX_HW_QUEUES=8), 64 blocks of 512 threads with 140 KB of LDS each (one per CU, like the
+// development aid: which XCD does block p of a launch land on?  Eight streams, 64 blocks of 512 threads with 140 KB of LDS each (one per CU, like the
 // align kernel), every block spins for a time that depends on its index (8 duration classes), launches queued back to back like the bench does.  Each block records its XCC_ID.
-// build + run on the GPU box: hipcc --offload-arch=gfx950 -O2 scripts/micro/xcc_map.hip -o /tmp/xcc_map && GPU_MAX_HW_QUEUES=8 /tmp/xcc_map
+// build + run on an MI355X: hipcc --offload-arch=gfx950 -O2 scripts/micro/xcc_map.hip -o /tmp/xcc_map && /tmp/xcc_map
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <vector>

@@ -11,7 +11,9 @@ run here, so the fixtures are:
   tum_pair_0.npz     one full-size (3072-point) synthetic TUM-shape pair, same content
   pcd_frame_small.npz  a 208x160 crop of a synthetic RGB-D frame + the oracle's point cloud for it (pcd generator,
                      SURVEY 8f next-1)
+  ref_nanoflann_radius.npz, reference_cvo_public_members.json  taken from the reference's source tree (reference_fixtures)
 Run:  python tests/golden/make_golden.py
+      python tests/golden/make_golden.py --reference <reference source tree>     (the two reference fixtures only)
 """
 import json
 import os
@@ -92,11 +94,53 @@ def pcd_fixture():
     print("pcd_frame_small.npz:", r["n"], "points, info", r["info"])
 
 
+def reference_fixtures(ref_tree):
+    """What the tests pin against the reference itself, taken once from its source tree (which the tests never read):
+    ref_nanoflann_radius.npz  its vendored nanoflann's radius search (oracle/_ref, `make -C oracle ref REF=<tree>`) on a seeded
+                              cloud: per radius and query the hit count, then indices and float d2 in the order it returns them
+    reference_cvo_public_members.json  the names of cvo::cvo's public members (thirdparty/cvo/include/cvo.hpp:213-281 functions,
+                              137-145 data), which tests/cpp/adaptor_use.cpp must pin"""
+    import ctypes as C
+    import re
+    import subprocess
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "ref", f"REF={os.path.abspath(ref_tree)}"])
+    ref = po.ref_lib()
+    assert ref is not None, "oracle/_ref/libref_nanoflann.so was not built"
+    rng = np.random.default_rng(9)
+    cloud = np.ascontiguousarray(rng.uniform(-1, 1, size=(3000, 3)).astype(np.float32))
+    queries = np.ascontiguousarray(rng.uniform(-1, 1, size=(64, 3)).astype(np.float32))
+    radii = np.array([0.0004017, 0.0044629, 0.02], np.float32)
+    cap = 1024
+    counts, idx_all, d2_all = [], [], []
+    fp = C.POINTER(C.c_float); ip = C.POINTER(C.c_int)
+    for r2 in radii:
+        cnt = np.zeros(64, np.int32); idx = np.zeros((64, cap), np.int32); d2 = np.zeros((64, cap), np.float32)
+        ref.ref_radius_search(cloud.ctypes.data_as(fp), 3000, queries.ctypes.data_as(fp), 64, C.c_float(r2),
+                              cnt.ctypes.data_as(ip), idx.ctypes.data_as(ip), d2.ctypes.data_as(fp), cap)
+        assert cnt.max() < cap
+        counts.append(cnt)
+        for q in range(64):
+            idx_all.append(idx[q, :cnt[q]]); d2_all.append(d2[q, :cnt[q]])
+    np.savez_compressed(os.path.join(HERE, "ref_nanoflann_radius.npz"), cloud=cloud, queries=queries, r2=radii, counts=np.stack(counts),
+                        idx=np.concatenate(idx_all), d2=np.concatenate(d2_all))
+    strip = lambda s: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", s, flags=re.S))
+    lines = open(os.path.join(ref_tree, "thirdparty", "cvo", "include", "cvo.hpp")).read().splitlines()
+    functions = sorted(set(re.findall(r"\b(\w+)\s*\([^;{]*\)\s*(?:;|\{)", strip("\n".join(lines[212:281])))) - {"cvo"})
+    data = re.findall(r"(\w+)\s*;", strip("\n".join(lines[136:145])))
+    with open(os.path.join(HERE, "reference_cvo_public_members.json"), "w") as f:
+        json.dump({"what": "public members of the reference's cvo::cvo (thirdparty/cvo/include/cvo.hpp): functions of its last public "
+                           "section (lines 213-281) and the public data members (lines 137-145)",
+                   "functions": functions, "data_members": data}, f, indent=1)
+        f.write("\n")
+    print("reference fixtures:", int(sum(c.sum() for c in counts)), "radius hits,", len(functions), "functions,", len(data), "data members")
+
 
 if __name__ == "__main__":
     po.build()
     if "--pcd-only" in sys.argv:
         pcd_fixture(); sys.exit(0)
+    if "--reference" in sys.argv:          # python tests/golden/make_golden.py --reference <reference source tree>
+        reference_fixtures(sys.argv[sys.argv.index("--reference") + 1]); sys.exit(0)
     closed_forms()
     for seed in (11, 12, 13):
         np.savez_compressed(os.path.join(HERE, f"small_pair_{seed}.npz"), **run_pair(synth.make_small_pair(seed, n=300)))

@@ -1,13 +1,12 @@
 """include/cvo_adaptor.hpp -- the drop-in `cvo::cvo` for a box with the reference's dependencies -- against a compiler:
 g++ -fsyntax-only with the stand-in Eigen / OpenCV / data_type.h declarations of tests/stubs/ (this image has neither
 library), and its public interface diffed against the reference's class (thirdparty/cvo/include/cvo.hpp:216-276)."""
+import json
 import os
 import re
 import subprocess
 
-import pytest
-
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 USE = os.path.join(ROOT, "tests", "cpp", "adaptor_use.cpp")
 
@@ -20,20 +19,15 @@ def test_adaptor_compiles_against_the_stand_in_headers():
 
 
 def test_every_public_member_of_the_reference_class_is_pinned():
-    """tests/cpp/adaptor_use.cpp static_asserts the signature of each public member (the compile above is the diff).  Where the
-    reference tree is present (this container, not the GPU box) the list of members it pins is checked to be complete: every
-    function declared in the public section of cvo::cvo (thirdparty/cvo/include/cvo.hpp:213-281) and the public data
-    members (cvo.hpp:137-144)."""
+    """tests/cpp/adaptor_use.cpp static_asserts the signature of each public member (the compile above is the diff).  The list of
+    members it pins is checked to be complete against the reference's class, as recorded in tests/golden/reference_cvo_public_members.json
+    (tests/golden/make_golden.py --reference): every function declared in the public section of cvo::cvo
+    (thirdparty/cvo/include/cvo.hpp:213-281) and the public data members (cvo.hpp:137-144)."""
     pinned = set(re.findall(r"SAME\((\w+),", open(USE).read()))
     assert len(pinned) >= 19
-    ref = "/root/reference/thirdparty/cvo/include/cvo.hpp"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree absent")
-    lines = open(ref).read().splitlines()
-    pub = "\n".join(lines[212:281])                                   # the class's last `public:` section
-    pub = re.sub(r"/\*.*?\*/", "", pub, flags=re.S); pub = re.sub(r"//[^\n]*", "", pub)
-    declared = set(re.findall(r"\b(\w+)\s*\([^;{]*\)\s*(?:;|\{)", pub)) - {"cvo"}
+    with open(os.path.join(GOLDEN, "reference_cvo_public_members.json")) as f:
+        ref = json.load(f)
+    declared = set(ref["functions"])
     assert declared and declared <= pinned, sorted(declared - pinned)
-    data = "\n".join(lines[136:145])
     for d in ("first_frame", "init", "iter", "transform", "prev_transform", "accum_transform"):
-        assert re.search(r"\b" + d + r"\b", data) and d in open(USE).read()
+        assert d in ref["data_members"] and d in open(USE).read()

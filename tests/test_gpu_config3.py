@@ -57,7 +57,6 @@ ADOPTION_MODES = [False, True]
 
 @pytest.mark.parametrize("adoption", ADOPTION_MODES)
 def test_config3_as_benchmarked_every_concurrent_launch_matches_the_oracle(hiplib, oracle, adoption):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")          # read when the runtime initialises; harmless later
     clouds, want = _inputs_and_oracle()
 
     batches = []

@@ -27,7 +27,6 @@ def _oracle_result(args):
 
 
 def test_config5_as_benchmarked_every_concurrent_launch_matches_the_oracle(hiplib, oracle):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     from cvo_slam_amd import synth
     pairs = [synth.make_pair(i, cam=synth.ETH3D) for i in range(N_PAIRS)]     # the pairs `bench.py --shape eth3d` times
     assert min(p.fixed.n for p in pairs) > 8000

@@ -1,5 +1,5 @@
 """Oracle vs known answers from numpy/scipy (tests/golden/closed_forms.json) and vs the
-reference's own nanoflann radius search (oracle/_ref), SURVEY.md 8c."""
+reference's own nanoflann radius search (tests/golden/ref_nanoflann_radius.npz), SURVEY.md 8c."""
 import json
 import os
 
@@ -79,27 +79,19 @@ def test_radius_search_kdtree_equals_brute(oracle):
 
 
 def test_radius_search_matches_reference_nanoflann(oracle):
-    """Pin against the reference's own vendored nanoflann (oracle/_ref, built from
-    /root/reference/thirdparty/cvo/thirdparty/nanoflann.hpp): same index set, same
-    float d2 values, same distance-sorted order (nanoflann.hpp:249-253,403-406,1285-1286)."""
-    ref = oracle.ref_lib()
-    if ref is None:
-        pytest.skip("oracle/_ref/libref_nanoflann.so not built (reference tree absent)")
-    import ctypes as C
-    rng = np.random.default_rng(9)
-    cloud = np.ascontiguousarray(rng.uniform(-1, 1, size=(3000, 3)).astype(np.float32))
-    queries = np.ascontiguousarray(rng.uniform(-1, 1, size=(64, 3)).astype(np.float32))
-    cap = 1024
-    for r2 in (0.0004017, 0.0044629, 0.02):
-        cnt = np.zeros(64, np.int32); idx = np.zeros((64, cap), np.int32); d2 = np.zeros((64, cap), np.float32)
-        fp = C.POINTER(C.c_float); ip = C.POINTER(C.c_int)
-        ref.ref_radius_search(cloud.ctypes.data_as(fp), 3000, queries.ctypes.data_as(fp), 64, C.c_float(r2),
-                              cnt.ctypes.data_as(ip), idx.ctypes.data_as(ip), d2.ctypes.data_as(fp), cap)
-        for q in range(64):
-            io, do = oracle.radius_search(cloud, queries[q], r2, use_kdtree=True)
-            n = cnt[q]
+    """Pin against the reference's own vendored nanoflann (thirdparty/cvo/thirdparty/nanoflann.hpp): its answers on a seeded
+    cloud are stored in tests/golden/ref_nanoflann_radius.npz (tests/golden/make_golden.py --reference, through oracle/_ref).
+    Same index set, same float d2 values, same distance-sorted order (nanoflann.hpp:249-253,403-406,1285-1286)."""
+    g = np.load(os.path.join(GOLDEN, "ref_nanoflann_radius.npz"))
+    cloud, queries, radii, counts, idx_all, d2_all = (g[k] for k in ("cloud", "queries", "r2", "counts", "idx", "d2"))
+    assert counts.shape == (len(radii), len(queries)) and counts.sum() == len(idx_all) == len(d2_all)
+    off = 0
+    for r2, cnt in zip(radii, counts):
+        for q in range(len(queries)):
+            n = int(cnt[q]); idx = idx_all[off:off + n]; d2 = d2_all[off:off + n]; off += n
+            io, do = oracle.radius_search(cloud, queries[q], float(r2), use_kdtree=True)
             assert n == len(io)
-            ref_pairs = sorted(zip(idx[q, :n].tolist(), d2[q, :n].tolist()))
+            ref_pairs = sorted(zip(idx.tolist(), d2.tolist()))
             orc_pairs = sorted(zip(io.tolist(), do.tolist()))
             assert ref_pairs == orc_pairs                                 # bit-identical d2 per index
-            np.testing.assert_array_equal(d2[q, :n], do)                   # same distance-sorted sequence
+            np.testing.assert_array_equal(d2, do)                          # same distance-sorted sequence
