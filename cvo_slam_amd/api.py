@@ -18,6 +18,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CVO_OK, CVO_ERR_NOT_INITIALIZED, CVO_ERR_EMPTY_CLOUD, CVO_ERR_HIP, CVO_ERR_INVALID, CVO_ERR_NO_DEVICE, CVO_ERR_TIMEOUT, CVO_ERR_PADDING, CVO_ERR_RANK_FAILED = range(9)
 SLOT_FIXED, SLOT_MOVING, SLOT_PREVIOUS = 0, 1, 2
 RESULT_FLOATS = 16
+# arithmetic modes (cvo_hip.h: CVO_ARITH_*; the same bits as the test oracle's reference-noise variants)
+ARITH_BASE, ARITH_F32_ROOTS, ARITH_F32_LOGM, ARITH_ROW_LAZY16 = 0, 2, 4, 8
+ARITH_EIGEN337 = ARITH_F32_ROOTS | ARITH_F32_LOGM | ARITH_ROW_LAZY16
+ARITH_NAMES = {"base": ARITH_BASE, "eigen337": ARITH_EIGEN337}
+
+
+def arith_flags(mode) -> int:
+    """An arithmetic mode as its CVO_ARITH_* bits: an int, or one of the names in ARITH_NAMES."""
+    if isinstance(mode, str):
+        if mode not in ARITH_NAMES:
+            raise ValueError(f"unknown arithmetic mode {mode!r} (known: {', '.join(ARITH_NAMES)})")
+        return ARITH_NAMES[mode]
+    return int(mode)
 
 
 class CvoError(RuntimeError):
@@ -95,6 +108,8 @@ ABI_SYMBOLS = [
     "cvo_gather_results", "cvo_multi_create", "cvo_multi_destroy", "cvo_multi_batch", "cvo_multi_align_async", "cvo_multi_wait",
     "cvo_batch_set_pairs", "cvo_batch_result_records", "cvo_shard_block", "cvo_batch_gather_results_padded", "cvo_batch_padded_records",
     "cvo_compact_records", "cvo_gather_results_padded", "cvo_multi_align_async_v", "cvo_batch_done", "cvo_batch_set_tail_scores", "cvo_batch_last_tail_answers", "cvo_batch_last_pair_seconds", "cvo_batch_last_pair_spans", "cvo_batch_last_tail_seconds", "cvo_set_tail_scores", "cvo_batch_last_cull_masks", "cvo_batch_last_nonzeros",
+    "cvo_set_arith_mode", "cvo_get_arith_mode", "cvo_batch_set_arith_mode", "cvo_batch_get_arith_mode",
+    "cvo_selftest_cubic_step_f32eig", "cvo_selftest_dist_se3_f32logm",
 ]
 
 _lib = None
@@ -184,13 +199,18 @@ def load_library():
     L.cvo_batch_enqueue_innerproduct.argtypes = [vp, C.c_int]
     L.cvo_batch_innerproduct_results.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
     L.cvo_batch_compute_innerproduct.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
-    for name in ("cvo_selftest_cubic_step", "cvo_selftest_exp_sek3", "cvo_selftest_dist_se3", "cvo_selftest_libm"):
+    for name in ("cvo_selftest_cubic_step", "cvo_selftest_exp_sek3", "cvo_selftest_dist_se3", "cvo_selftest_libm", "cvo_selftest_cubic_step_f32eig",
+                 "cvo_selftest_dist_se3_f32logm"):
         getattr(L, name).argtypes = [C.c_int, C.c_int, fp, fp]
     L.cvo_selftest_pair_values.argtypes = [C.c_int, C.POINTER(Params), C.c_float, C.c_int, fp, fp, fp]
     L.cvo_function_inner_product_clouds.argtypes = [vp, fp, fp, C.c_int, fp, fp, C.c_int, C.POINTER(InnP)]
     L.cvo_se3_hessian_clouds.argtypes = [vp, fp, fp, C.c_int, fp, fp, C.c_int, dp, ip]
     L.cvo_batch_set_max_workgroups.argtypes = [vp, C.c_int]
     L.cvo_batch_set_adoption.argtypes = [vp, C.c_int]
+    for name in ("cvo_set_arith_mode", "cvo_batch_set_arith_mode"):
+        getattr(L, name).argtypes = [vp, C.c_int]
+    for name in ("cvo_get_arith_mode", "cvo_batch_get_arith_mode"):
+        getattr(L, name).argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_batch_last_adoptions.argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_batch_last_adoption_retractions.argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_adaptive_default_params.argtypes = [C.POINTER(AdaptiveParams)]
@@ -275,6 +295,22 @@ def selftest_dist_se3(dR_dT, device: int = 0):
     a = np.ascontiguousarray(dR_dT, np.float32).reshape(-1, 12); out = np.zeros(a.shape[0], np.float32)
     fp = C.POINTER(C.c_float)
     _check(load_library().cvo_selftest_dist_se3(device, a.shape[0], a.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+    return out
+
+
+def selftest_cubic_step_f32eig(coef_minstep, device: int = 0):
+    """cubic_step_f32eig on the device (CVO_ARITH_F32_ROOTS: the f32 companion-matrix eigenvalues) for n x {c3, c2, c1, c0, min_step}."""
+    a = np.ascontiguousarray(coef_minstep, np.float32).reshape(-1, 5); out = np.zeros(a.shape[0], np.float32)
+    fp = C.POINTER(C.c_float)
+    _check(load_library().cvo_selftest_cubic_step_f32eig(device, a.shape[0], a.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+    return out
+
+
+def selftest_dist_se3_f32logm(dR_dT, device: int = 0):
+    """dist_se3_f32logm on the device (CVO_ARITH_F32_LOGM: the f32 matrix logarithm's norm) for n x {dR row-major, dT}; NaN where the logarithm fails."""
+    a = np.ascontiguousarray(dR_dT, np.float32).reshape(-1, 12); out = np.zeros(a.shape[0], np.float32)
+    fp = C.POINTER(C.c_float)
+    _check(load_library().cvo_selftest_dist_se3_f32logm(device, a.shape[0], a.ctypes.data_as(fp), out.ctypes.data_as(fp)))
     return out
 
 
@@ -534,6 +570,13 @@ class Cvo:
     def set_workgroups(self, g: int):
         _check(self.L.cvo_set_workgroups(self.h, int(g)))
 
+    def set_arith_mode(self, mode):
+        """arithmetic mode of this handle's alignments (cvo_hip.h: cvo_set_arith_mode): CVO_ARITH_* bits, or "base" / "eigen337"."""
+        _check(self.L.cvo_set_arith_mode(self.h, arith_flags(mode)))
+
+    def arith_mode(self) -> int:
+        v = C.c_int(); _check(self.L.cvo_get_arith_mode(self.h, C.byref(v))); return v.value
+
     def set_tail_scores(self, on):
         """cvo_set_tail_scores: the alignment queues the tracker's score block behind itself and compute_innerproduct(the result) only collects.
         False / 0 never, True / 1 every alignment, 2 (the handle's default) when the previous alignment was followed by that question"""
@@ -752,6 +795,13 @@ class CvoBatch:
     def set_adoption(self, on: bool):
         """finished workgroups help with the pairs of their launch that still run (cvo_hip.h: cvo_batch_set_adoption)"""
         _check(self.L.cvo_batch_set_adoption(self.h, int(bool(on))))
+
+    def set_arith_mode(self, mode):
+        """arithmetic mode of the launches queued from now on (cvo_hip.h: cvo_batch_set_arith_mode): CVO_ARITH_* bits, or "base" / "eigen337"."""
+        _check(self.L.cvo_batch_set_arith_mode(self.h, arith_flags(mode)))
+
+    def arith_mode(self) -> int:
+        v = C.c_int(); _check(self.L.cvo_batch_get_arith_mode(self.h, C.byref(v))); return v.value
 
     def set_tail_scores(self, on: bool):
         """the tracker's score block answered by the align launch itself (cvo_hip.h: cvo_batch_set_tail_scores)"""

@@ -29,7 +29,22 @@
 #include "cvo_device.h"
 #include "cvo_math.hpp"
 
-// the align kernel's translation unit is in the library twice (cvo_kernels.hip, head comment): cvohip = two waves per SIMD, cvohip_w3 = three
+// the align kernel's translation unit is in the library four times (cvo_kernels.hip, head comment): cvohip = two waves per SIMD, cvohip_w3 = three;
+// cvohip_e337 and cvohip_e337_w3 = the same two with the arithmetic modes (CVO_ARITH_*; the default builds refuse any mode bit)
+#define CVO_DECLARE_ALIGN_BUILD(ns) \
+namespace ns { \
+using cvohip::PairDesc; using cvohip::DevParams; \
+size_t align_shared_bytes(int tile, int rows_cap, int y_mode, int y_cap, int tab_cols); \
+int align_min_tile(int rows_cap, int y_mode, int y_cap); \
+int align_tile_granule(); \
+int align_block_max(); \
+hipError_t launch_align(int grid, int block, int tile, int rows_cap, int y_mode, int y_cap, int tab_cols, hipStream_t stream, const PairDesc* descs, int n_pairs, int G, \
+                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table, \
+                        int arith); \
+}
+CVO_DECLARE_ALIGN_BUILD(cvohip_e337)
+CVO_DECLARE_ALIGN_BUILD(cvohip_e337_w3)
+#undef CVO_DECLARE_ALIGN_BUILD
 namespace cvohip_w3 {
 using cvohip::PairDesc; using cvohip::DevParams;
 size_t align_shared_bytes(int tile, int rows_cap, int y_mode, int y_cap, int tab_cols);
@@ -37,7 +52,8 @@ int align_min_tile(int rows_cap, int y_mode, int y_cap);
 int align_tile_granule();
 int align_block_max();
 hipError_t launch_align(int grid, int block, int tile, int rows_cap, int y_mode, int y_cap, int tab_cols, hipStream_t stream, const PairDesc* descs, int n_pairs, int G,
-                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table);
+                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table,
+                        int arith);
 }
 namespace cvohip {
 size_t align_shared_bytes(int tile, int rows_cap, int y_mode, int y_cap, int tab_cols);
@@ -46,7 +62,8 @@ int align_tile_granule();
 int align_blocks_per_cu();
 int align_block_max();
 hipError_t launch_align(int grid, int block, int tile, int rows_cap, int y_mode, int y_cap, int tab_cols, hipStream_t stream, const PairDesc* descs, int n_pairs, int G,
-                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table);
+                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table,
+                        int arith);
 int align_adopt_gmax();
 hipError_t launch_fill_records(float* rec, int from, int to, int status, hipStream_t stream);
 hipError_t launch_copy_records(const float* src, float* dst, int n, hipStream_t stream);
@@ -359,6 +376,7 @@ struct Engine {
     // 64-byte result records, one per pair, written by the align kernel (PairDesc::record); the block a rank contributes to the
     // cross-GPU gather may be longer than its pairs (padding records: pad_from .. pad_to carry pad_status, see padded_records)
     DevBuf d_records;
+    int arith = 0;               // CVO_ARITH_* bits of the launches from now on (cvo_set_arith_mode / cvo_batch_set_arith_mode); 0 = the default builds
     int rec_hint = 0;            // records to make room for beyond the pairs of a launch (a batch: its max_pairs + 1)
     int pad_from = 0, pad_to = 0, pad_status = 0;
     PinBuf h_descs, h_states, h_states_in, h_stage, h_partials;   // h_states: final states, written by the kernel itself (mapped pinned memory)
@@ -793,9 +811,16 @@ struct Engine {
         // Which build of the kernel runs the launch, and its LDS plan.  Clouds that only fit in the plane layout (9 k points) run with three waves per SIMD:
         // their walks wait for memory more than they issue (+5.8 %; the 3 k-point shape loses 3 % to the waves' uneven shares and stays with two).
         struct KSet { size_t (*shared_bytes)(int, int, int, int, int); int (*min_tile)(int, int, int); int (*tile_granule)(); int (*block_max)();
-                      hipError_t (*launch)(int, int, int, int, int, int, int, hipStream_t, const PairDesc*, int, int, unsigned, unsigned long long*, const DevParams&, const unsigned*, unsigned*, const float* const*); };
+                      hipError_t (*launch)(int, int, int, int, int, int, int, hipStream_t, const PairDesc*, int, int, unsigned, unsigned long long*, const DevParams&, const unsigned*, unsigned*, const float* const*,
+                                          int); };
         static const KSet KS2 = {align_shared_bytes, align_min_tile, align_tile_granule, align_block_max, launch_align};
         static const KSet KS3 = {cvohip_w3::align_shared_bytes, cvohip_w3::align_min_tile, cvohip_w3::align_tile_granule, cvohip_w3::align_block_max, cvohip_w3::launch_align};
+        // a launch in an arithmetic mode (cvo_set_arith_mode / cvo_batch_set_arith_mode) runs the builds that have the modes, planned by their own LDS figures
+        static const KSet KSE2 = {cvohip_e337::align_shared_bytes, cvohip_e337::align_min_tile, cvohip_e337::align_tile_granule, cvohip_e337::align_block_max, cvohip_e337::launch_align};
+        static const KSet KSE3 = {cvohip_e337_w3::align_shared_bytes, cvohip_e337_w3::align_min_tile, cvohip_e337_w3::align_tile_granule, cvohip_e337_w3::align_block_max,
+                                  cvohip_e337_w3::launch_align};
+        const int arith_l = arith;                                   // (taken once: the launch keeps the mode it was queued with)
+        const KSet& K2 = arith_l ? KSE2 : KS2; const KSet& K3 = arith_l ? KSE3 : KS3;
         struct Plan { int y_mode = 0, tile = 0, tab_cols = 0, block = 0; bool err = false; };
         const int rows_per_w = ((((std::max(nf_max, 1) + 127) / 128) + G - 1) / G) * 128;   // rows are dealt to the workgroups in blocks of 128 (ROW_DEAL)
         const int rows_cap = round_up(std::max(rows_per_w, 1), 128) + 64;
@@ -838,12 +863,12 @@ struct Engine {
 
         return pl;
         };
-        const KSet* K = &KS2;
-        Plan pl = plan(KS2);
+        const KSet* K = &K2;
+        Plan pl = plan(K2);
         if (pl.err) return fail(CVO_ERR_INVALID, "CVO_HIP_Y_MODE: the requested LDS layout does not fit");
         if ((pl.y_mode == 2 || (wide_all && pl.y_mode == 1)) && wide_waves && per_cu == 1) {
-            const Plan p3 = plan(KS3);
-            if (!p3.err && p3.y_mode == pl.y_mode) { pl = p3; K = &KS3; }
+            const Plan p3 = plan(K3);
+            if (!p3.err && p3.y_mode == pl.y_mode) { pl = p3; K = &K3; }
         }
         const int y_mode = pl.y_mode, tile = pl.tile, tab_cols = pl.tab_cols, block = pl.block, rows_per = rows_per_w;
 
@@ -1037,10 +1062,10 @@ struct Engine {
             std::lock_guard<std::mutex> lk(adopt_submit_mutex());
             *qc->submitted_host += (unsigned)grid;
             e = K->launch(grid, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl,
-                             qc->submitted_dev, qc->started_dev, rawtab);
+                             qc->submitted_dev, qc->started_dev, rawtab, arith_l);
             if (e != hipSuccess) resync_adopt_counters(qc);
         } else {
-            e = K->launch(grid, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl, nullptr, nullptr, rawtab);
+            e = K->launch(grid, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl, nullptr, nullptr, rawtab, arith_l);
         }
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("align kernel launch: ") + hipGetErrorString(e));
         HIP_TRY(hipEventRecord(ev1, s));
@@ -1912,6 +1937,12 @@ int cvo_set_workgroups(cvo_handle h, int workgroups_per_pair) {
     if (!h || workgroups_per_pair < 0) return fail(CVO_ERR_INVALID, "bad argument");
     h->eng.wg_request = workgroups_per_pair; return CVO_OK;
 }
+int cvo_set_arith_mode(cvo_handle h, int flags) {
+    if (!h) return fail(CVO_ERR_INVALID, "null handle");
+    if (flags & ~CVO_ARITH_EIGEN337) return fail(CVO_ERR_INVALID, "unknown arithmetic mode bit");
+    h->eng.arith = flags; return CVO_OK;
+}
+int cvo_get_arith_mode(cvo_handle h, int* flags) { if (!h || !flags) return fail(CVO_ERR_INVALID, "null argument"); *flags = h->eng.arith; return CVO_OK; }
 
 // ------------------------------------------------------------------ batches
 namespace {
@@ -2002,6 +2033,8 @@ int cvo_selftest_cubic_step(int device, int n, const float* coef_minstep, float*
 int cvo_selftest_exp_sek3(int device, int n, const float* omega_v_dt, float* dR_dT_out) { return selftest(device, 1, n, omega_v_dt, 7, dR_dT_out, 12); }
 int cvo_selftest_dist_se3(int device, int n, const float* dR_dT, float* dist_out) { return selftest(device, 2, n, dR_dT, 12, dist_out, 1); }
 int cvo_selftest_libm(int device, int n, const float* x, float* out6) { return selftest(device, 3, n, x, 1, out6, 6); }
+int cvo_selftest_cubic_step_f32eig(int device, int n, const float* coef_minstep, float* step_out) { return selftest(device, 4, n, coef_minstep, 5, step_out, 1); }
+int cvo_selftest_dist_se3_f32logm(int device, int n, const float* dR_dT, float* dist_out) { return selftest(device, 5, n, dR_dT, 12, dist_out, 1); }
 int cvo_selftest_pair_values(int device, const cvo_params* params, float ell, int n, const float* y_g, float* a_out, float* d2_d2c_out) {
     int rc = check_device(device, nullptr); if (rc) return rc;
     if (n <= 0 || !y_g || !a_out || !(ell > 0.f)) return fail(CVO_ERR_INVALID, "bad self-test arguments");
@@ -2117,6 +2150,12 @@ int cvo_batch_set_max_workgroups(cvo_batch b, int max_workgroups) {
     b->eng.max_wgs = max_workgroups; return CVO_OK;
 }
 int cvo_batch_set_adoption(cvo_batch b, int on) { if (!b) return fail(CVO_ERR_INVALID, "null batch"); b->eng.adopt = on != 0; return CVO_OK; }
+int cvo_batch_set_arith_mode(cvo_batch b, int flags) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    if (flags & ~CVO_ARITH_EIGEN337) return fail(CVO_ERR_INVALID, "unknown arithmetic mode bit");
+    b->eng.arith = flags; return CVO_OK;
+}
+int cvo_batch_get_arith_mode(cvo_batch b, int* flags) { if (!b || !flags) return fail(CVO_ERR_INVALID, "null argument"); *flags = b->eng.arith; return CVO_OK; }
 int cvo_batch_last_adoptions(cvo_batch b, int* pairs_helped) {
     if (!b || !pairs_helped) return fail(CVO_ERR_INVALID, "null argument");
     int rc = b->eng.wait(); if (rc) return rc;

@@ -81,6 +81,9 @@ struct TraceRow {        // == cvo_trace_row (include/cvo_hip.h)
     int pad_;
 };
 
+// arithmetic modes (include/cvo_hip.h: CVO_ARITH_*, the bits of the test oracle's ORC_VAR_*): run by the CVO_ARITH_MODES builds of the align kernel
+constexpr int ARITH_F32_ROOTS = 2, ARITH_F32_LOGM = 4, ARITH_ROW_LAZY16 = 8, ARITH_ALL = ARITH_F32_ROOTS | ARITH_F32_LOGM | ARITH_ROW_LAZY16;
+
 constexpr int TAIL_PRE = 1, TAIL_POST = 2, TAIL_FIXED = 4, TAIL_MOVING = 8, TAIL_HESSIAN = 16;   // PairDesc::score_out[23]
 
 // exchange area for the G workgroups that cooperate on one pair: two buffers

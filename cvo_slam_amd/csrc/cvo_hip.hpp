@@ -71,6 +71,10 @@ public:
     void stage_next_frame(const unsigned char* bgr8, const unsigned short* depth16, int width, int height, const cvo_camera& cam) {
         if (cvo_stage_next_frame(h_, bgr8, depth16, width, height, &cam) != CVO_OK) throw std::runtime_error(std::string("stage_next_frame: ") + cvo_last_error());
     }
+    // not in the reference: the arithmetic mode of this object's alignments (cvo_set_arith_mode in include/cvo_hip.h)
+    void set_arith_mode(int flags) {
+        if (cvo_set_arith_mode(h_, flags) != CVO_OK) throw std::runtime_error(std::string("set_arith_mode: ") + cvo_last_error());
+    }
     void match_keyframe(const unsigned char* bgr8, const unsigned short* depth16, int width, int height, const cvo_camera& cam, Affine3d& transformd) {
         const int rc = cvo_match_keyframe_images(h_, bgr8, depth16, width, height, &cam, transformd.m);
         if (rc == CVO_ERR_NOT_INITIALIZED) { std::printf("cvo not initialized !\n"); return; }

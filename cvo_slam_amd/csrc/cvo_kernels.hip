@@ -45,6 +45,11 @@
 // The file is compiled twice into the library: as namespace cvohip with workgroups of up to 512 threads (two waves per SIMD, 256 VGPRs: the 3 k-point
 // shape, bound by issue) and, with -DCVO_KNS=cvohip_w3 -DCVO_BLOCK_MAX=768, as namespace cvohip_w3 with up to 768 threads (three waves per SIMD, 168
 // VGPRs: clouds in the plane layout, whose walks wait for memory more than they issue -- +5.8 % at 9 k points, -3 % at 3 k; profiles/r03_block_size_ab.txt).
+// Both are compiled once more with -DCVO_ARITH_MODES (namespaces cvohip_e337, cvohip_e337_w3): the "Eigen 3.3.7" arithmetic modes (include/cvo_hip.h,
+// CVO_ARITH_*), chosen per launch by a kernel argument of their own -- the default builds above carry none of it, so their code is not touched by the modes.
+#ifdef CVO_ARITH_MODES
+#include "cvo_eigen337.hpp"
+#endif
 #ifndef CVO_KNS
 #define CVO_KNS cvohip
 #else
@@ -185,6 +190,9 @@ struct __attribute__((aligned(16))) Shared {
     // this workgroup's view of the current pair (struct Ctx), worked out once per pair (and again when the pair gains a member): every phase is a
     // function of its own and would otherwise fetch the descriptor's fields from global memory first thing, a round trip per phase call
     unsigned long long ctx_store[16];
+#ifdef CVO_ARITH_MODES
+    int arith;             // this launch's CVO_ARITH_* bits (cvo_align_kernel's argument)
+#endif
 };
 
 // Pointers read out of a PairDesc are generic to the compiler, which then emits FLAT loads/stores
@@ -1542,7 +1550,30 @@ static __device__ __noinline__ void phase_sort(const PairDesc* Dp_in, int g_in, 
 // one coalesced run.  The point gather y_j comes from the LDS-resident cloud, x_i and the row sums live in registers, so
 // a candidate costs no scattered global access and the f32 sums add up in column order (cvo.cpp:213-223) without a
 // second pass.  Survivors {x_i,a},{y_j} are compacted per wave (ballot + prefix popcount) for the line-search phase.
-struct RowSums { float sw[3], sv[3]; };
+struct RowSums {
+    float sw[3], sv[3];
+#ifdef CVO_ARITH_MODES
+    // CVO_ARITH_ROW_LAZY16: Eigen 3.3.7 forms `1/c*Ai*cross_xy` (cvo.cpp:222-223) with the coefficient-based lazy product for rows of fewer than 16
+    // nonzeros -- 1/c (1/d) folded into every a_j before the sequential sum -- and with gebp (alpha after the sum) for longer rows.  A row's length is
+    // known at its end only, so both sums are carried: fw, fv = sum_j fl(fl(inv_c a_j) cross_j), sum_j fl(fl(inv_d a_j) (y_j - x_i)); n = nonzeros so far
+    float fw[3], fv[3];
+    float ic, id;          // inv_c, inv_d
+    int n;
+#endif
+};
+#ifdef CVO_ARITH_MODES
+#define CVO_ROW_INIT(rs) do { (rs).ic = inv_c; (rs).id = inv_d; } while (0)
+// the row's contribution to omega, v (cvo.cpp:222-223): alpha first for a short row when the mode asks for it, alpha after the sum otherwise
+__device__ __forceinline__ void add_row(double (&acc8)[8], const RowSums& rs, float inv_c, float inv_d, bool lazy16) {
+    const bool af = lazy16 && rs.n < 16;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { acc8[q] += (double)(af ? rs.fw[q] : inv_c * rs.sw[q]); acc8[3 + q] += (double)(af ? rs.fv[q] : inv_d * rs.sv[q]); }
+}
+#define CVO_ADD_ROW(acc8, rs) add_row(acc8, rs, inv_c, inv_d, lazy16)
+#else
+#define CVO_ROW_INIT(rs) (void)0
+#define CVO_ADD_ROW(acc8, rs) _Pragma("unroll") for (int q = 0; q < 3; ++q) { acc8[q] += (double)(inv_c * (rs).sw[q]); acc8[3 + q] += (double)(inv_d * (rs).sv[q]); }
+#endif
 
 __device__ __forceinline__ void fold_entry(const float* xi, const float4 y4, float a, unsigned tag /* slot << 16 | column */, RowSums& rs, gv2u* sp /* the wave's segment of nonzero records: wave-uniform */,
                                            int& wcount, int lane) {
@@ -1551,6 +1582,12 @@ __device__ __forceinline__ void fold_entry(const float* xi, const float4 y4, flo
         float cr[3]; cross3(xi, yv, cr);                            // cvo.cpp:216
         rs.sw[0] += a * cr[0]; rs.sw[1] += a * cr[1]; rs.sw[2] += a * cr[2];
         rs.sv[0] += a * (yv[0] - xi[0]); rs.sv[1] += a * (yv[1] - xi[1]); rs.sv[2] += a * (yv[2] - xi[2]);   // cvo.cpp:217
+#ifdef CVO_ARITH_MODES
+        const float aw = rs.ic * a, av = rs.id * a;
+        rs.fw[0] += aw * cr[0]; rs.fw[1] += aw * cr[1]; rs.fw[2] += aw * cr[2];
+        rs.fv[0] += av * (yv[0] - xi[0]); rs.fv[1] += av * (yv[1] - xi[1]); rs.fv[2] += av * (yv[2] - xi[2]);
+        rs.n += (a > 0.f) ? 1 : 0;
+#endif
     }
     const unsigned long long mask = __ballot(a > 0.f);
     if (a > 0.f) {
@@ -1584,6 +1621,12 @@ __device__ __forceinline__ void fold_entry_e(const float* xi, const float4 y4, c
         float cr[3]; cross3(xi, yv, cr);                            // cvo.cpp:216
         rs.sw[0] += a * cr[0]; rs.sw[1] += a * cr[1]; rs.sw[2] += a * cr[2];
         rs.sv[0] -= a * e[0]; rs.sv[1] -= a * e[1]; rs.sv[2] -= a * e[2];     // cvo.cpp:217
+#ifdef CVO_ARITH_MODES
+        const float aw = rs.ic * a, av = rs.id * a;
+        rs.fw[0] += aw * cr[0]; rs.fw[1] += aw * cr[1]; rs.fw[2] += aw * cr[2];
+        rs.fv[0] -= av * e[0]; rs.fv[1] -= av * e[1]; rs.fv[2] -= av * e[2];
+        rs.n += (a > 0.f) ? 1 : 0;
+#endif
     }
     const unsigned long long mask = __ballot(a > 0.f);
 #ifndef CVO_BRANCHY_REC
@@ -1614,6 +1657,9 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
     const __amdgpu_buffer_rsrc_t seg = record_segment(sp, (unsigned)uni(sh->wtot[wave]));   // (a wave has no more nonzeros than listed candidates)
     const bool x_lds = sh->x_lds != 0;
     int wcount = 0;
+#ifdef CVO_ARITH_MODES
+    const bool lazy16 = (sh->arith & ARITH_ROW_LAZY16) != 0;
+#endif
     const int nb = sh->wnb[wave];
     int kept_w = 0, nb_left = 0;
 #ifdef CVO_EXP7
@@ -1638,6 +1684,7 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
         const int lw = uni((int)sh->blk_lmax[blk]);                  // longest list of the block (phase_sort / refine_lists)
         float xi[3]; load_x(c, L, x_lds, slot, xi);
         RowSums rs = {{0, 0, 0}, {0, 0, 0}};
+        CVO_ROW_INIT(rs);
         const gv4u* eb = uni_ptr((const gv4u*)c.ent + (slot - lane)); // scalar base of the block's entries + 32-bit lane offsets
         unsigned eo = (unsigned)lane;
         const unsigned stag = (unsigned)slot << 16;
@@ -1728,8 +1775,7 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
 #pragma unroll
             for (int u = 0; u < PF / 2; ++u) eq4[u] = en4[u];
         }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { acc8[q] += (double)(inv_c * rs.sw[q]); acc8[3 + q] += (double)(inv_d * rs.sv[q]); }   // cvo.cpp:222-223
+        CVO_ADD_ROW(acc8, rs);                                       // cvo.cpp:222-223
         if (REFINE) {                                               // the block's lists as they are walked from the next iteration on (cf. refine_lists)
             L.lenS[slot] = (uint16_t)cnt;
             kept_w += cnt;
@@ -1761,6 +1807,9 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
     const __amdgpu_buffer_rsrc_t seg = record_segment(sp, (unsigned)uni(sh->wtot[wave]));
     const __amdgpu_buffer_rsrc_t jseg = whole_region((const void*)uni_ptr(c.jT4)), eseg = whole_region((const void*)uni_ptr(c.ent));
     int wcount = 0;
+#ifdef CVO_ARITH_MODES
+    const bool lazy16 = (sh->arith & ARITH_ROW_LAZY16) != 0;
+#endif
     const int nb = sh->wnb[wave];
 #ifdef CVO_EXP7
     const Exp7 e7 = make_exp7(gates);
@@ -1777,6 +1826,7 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
         const float xi[3] = {lo.x, lo.y, lo.z};
         const float fi[5] = {lo.w, hi.x, hi.y, hi.z, hi.w};
         RowSums rs = {{0, 0, 0}, {0, 0, 0}};
+        CVO_ROW_INIT(rs);
         static_assert(PF == 4, "the cull packs four columns per word");
 #ifdef CVO_BRANCHY_REC
         const gv2u* jp = c.jT4 + li;                                // entries 4q .. 4q+3 of this row: jp[q * rows_pad]
@@ -1858,8 +1908,7 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
 #pragma unroll
             for (int u = 0; u < PF; ++u) { j0[u] = j1[u]; j1[u] = j2[u]; g0[u] = g1[u]; }
         }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { acc8[q] += (double)(inv_c * rs.sw[q]); acc8[3 + q] += (double)(inv_d * rs.sv[q]); }   // cvo.cpp:222-223
+        CVO_ADD_ROW(acc8, rs);                                       // cvo.cpp:222-223
     }
     if (lane == 0) { sh->wcnt[wave] = wcount; acc8[6] = (double)wcount; }
 }
@@ -2206,6 +2255,9 @@ CVO_PHASE_FN(8) void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in,
             const float xi[3] = {lo.x, lo.y, lo.z};
             const float fi[5] = {lo.w, hi.x, hi.y, hi.z, hi.w};
             float sw[3] = {0, 0, 0}, sv[3] = {0, 0, 0};
+#ifdef CVO_ARITH_MODES
+            float fw[3] = {0, 0, 0}, fv[3] = {0, 0, 0};               // alpha first (RowSums::fw, fv)
+#endif
             int nz = 0;
             for (int j = 0; j < c.nm; ++j) {
                 float4 yj = load_y_rt(c, L, y_lds, j);
@@ -2216,11 +2268,22 @@ CVO_PHASE_FN(8) void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in,
                     float cr[3]; cross3(xi, yv, cr);
                     sw[0] += a * cr[0]; sw[1] += a * cr[1]; sw[2] += a * cr[2];
                     sv[0] += a * (yv[0] - xi[0]); sv[1] += a * (yv[1] - xi[1]); sv[2] += a * (yv[2] - xi[2]);
+#ifdef CVO_ARITH_MODES
+                    const float aw = inv_c * a, av = inv_d * a;
+                    fw[0] += aw * cr[0]; fw[1] += aw * cr[1]; fw[2] += aw * cr[2];
+                    fv[0] += av * (yv[0] - xi[0]); fv[1] += av * (yv[1] - xi[1]); fv[2] += av * (yv[2] - xi[2]);
+#endif
                     ++nz;
                 }
             }
+#ifdef CVO_ARITH_MODES
+            const bool af = (sh->arith & ARITH_ROW_LAZY16) != 0 && nz < 16;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) { acc8[q] += (double)(af ? fw[q] : inv_c * sw[q]); acc8[3 + q] += (double)(af ? fv[q] : inv_d * sv[q]); }
+#else
 #pragma unroll
             for (int q = 0; q < 3; ++q) { acc8[q] += (double)(inv_c * sw[q]); acc8[3 + q] += (double)(inv_d * sv[q]); }
+#endif
             acc8[6] += (double)nz;
             acc8[7] += (double)(y_lds == 2 ? c.nm : (int)L.rowlen[li]);   // statistics only (in the plane layout the row lengths have been overwritten by now)
         }
@@ -2462,7 +2525,11 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
 #ifdef CVO_KTRACE_EPI
         const unsigned long long kq0 = CVO_NOW();
 #endif
+#ifdef CVO_ARITH_MODES
+        step = (sh->arith & ARITH_F32_ROOTS) ? cubic_step_f32eig(c3, c2, c1, c0, P.min_step) : cubic_step(c3, c2, c1, c0, P.min_step);
+#else
         step = cubic_step(c3, c2, c1, c0, P.min_step);
+#endif
 #ifdef CVO_KTRACE_EPI
         __builtin_amdgcn_sched_barrier(0); sh->ksub[0] = CVO_NOW() - kq0 + (step == 12345.f ? 1 : 0);
 #endif
@@ -2498,7 +2565,11 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
         int stop = 0;
         if (stop_a) stop = 1;
         else {
+#ifdef CVO_ARITH_MODES
+            dist = (sh->arith & ARITH_F32_LOGM) ? dist_se3_f32logm(dR, dT) : dist_se3(dR, dT);
+#else
             dist = dist_se3(dR, dT);
+#endif
             if (dist < P.eps_2) stop = 1;                                               // cvo.cpp:804
         }
         if (stop) sh->iter_at_break = k;
@@ -3180,7 +3251,11 @@ static __device__ __noinline__ void queue_pull(gu64* queue, int slot_in, int g_i
 __global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD) void cvo_align_kernel(const PairDesc* __restrict__ descs, int n_pairs, int G, int tile, int y_lds, int rows_cap, int y_cap,
                                                                          unsigned launch_tag, int tab_cols, unsigned long long* __restrict__ queue_in, DevParams P,
                                                                          const unsigned* wgs_submitted /* host-mapped */, unsigned* wgs_started,
-                                                                         const float* const* __restrict__ raw_table /* pinned host memory, or null */) {
+                                                                         const float* const* __restrict__ raw_table /* pinned host memory, or null */
+#ifdef CVO_ARITH_MODES
+                                                                         , int arith      /* CVO_ARITH_* bits of this launch */
+#endif
+                                                                         ) {
     Shared* sh = reinterpret_cast<Shared*>(cvo_smem);
     const int tid = threadIdx.x;
     const int slots = gridDim.x / G;
@@ -3193,6 +3268,9 @@ __global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD
     if (wgs_started != nullptr && tid == 0) atomicAdd(wgs_started, 1u);
     if (slot >= slots) return;                                      // gridDim.x is a multiple of G; defensive
     if (tid == 0) { sh->rc_ell = -1.f; sh->P = P; sh->skin0 = P.skin; sh->alpha0 = P.skin_alpha; sh->launch_tag = launch_tag; sh->rows_cap = rows_cap; sh->y_cap = y_cap; sh->tab_cols = tab_cols; }
+#ifdef CVO_ARITH_MODES
+    if (tid == 0) sh->arith = arith;
+#endif
     __syncthreads();                                                // (run_pair reads the parameters from there)
     const bool adopting = wgs_started != nullptr && P.adopt_on != 0;   // set by the host for launches of one workgroup and one slot per pair
     const int tgeo = pack_geometry(tile, rows_cap, y_cap);
@@ -3534,12 +3612,20 @@ size_t align_shared_bytes(int tile, int rows_cap, int y_mode, int y_cap, int tab
 int align_tile_granule() { return 128; }                            // keeps every LDS section 16-byte aligned
 
 hipError_t launch_align(int grid, int block, int tile, int rows_cap, int y_mode, int y_cap, int tab_cols, hipStream_t stream, const PairDesc* descs, int n_pairs, int G,
-                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table) {
+                        unsigned launch_tag, unsigned long long* queue, const DevParams& P, const unsigned* wgs_submitted, unsigned* wgs_started, const float* const* raw_table,
+                        int arith) {
+#ifndef CVO_ARITH_MODES
+    if (arith != 0) return hipErrorInvalidValue;                    // the default builds have no arithmetic modes
+#endif
     const size_t shmem = align_shared_bytes(tile, rows_cap, y_mode, y_cap, tab_cols);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(cvo_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(cvo_align_kernel, dim3(grid), dim3(block), shmem, stream, descs, n_pairs, G, tile, y_mode, rows_cap, y_cap, launch_tag, tab_cols, queue, P,
-                       wgs_submitted, wgs_started, raw_table);
+                       wgs_submitted, wgs_started, raw_table
+#ifdef CVO_ARITH_MODES
+                       , arith
+#endif
+                       );
     return hipGetLastError();
 }
 

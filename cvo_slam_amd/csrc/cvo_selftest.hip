@@ -5,6 +5,7 @@
 // scipy expm / logm) without going through the oracle, whose source text the device functions share.
 #include <hip/hip_runtime.h>
 #include "cvo_math.hpp"
+#include "cvo_eigen337.hpp"
 
 namespace cvohip {
 
@@ -30,6 +31,20 @@ __global__ void selftest_dist_kernel(const float* __restrict__ in, float* __rest
     out[i] = dist_se3(dR, dT);
 }
 
+// the "Eigen 3.3.7" arithmetic mode's two epilogue pieces (cvo_eigen337.hpp: CVO_ARITH_F32_ROOTS, CVO_ARITH_F32_LOGM), same input layouts as above
+__global__ void selftest_cubic_f32eig_kernel(const float* __restrict__ in, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = cubic_step_f32eig(in[i * 5 + 0], in[i * 5 + 1], in[i * 5 + 2], in[i * 5 + 3], in[i * 5 + 4]);
+}
+__global__ void selftest_dist_f32logm_kernel(const float* __restrict__ in, float* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float dR[9], dT[3];
+    for (int q = 0; q < 9; ++q) dR[q] = in[i * 12 + q];
+    for (int q = 0; q < 3; ++q) dT[q] = in[i * 12 + 9 + q];
+    out[i] = dist_se3_f32logm(dR, dT);
+}
+
 // the device's float routines where the epilogue and the gates call them (OCML: sinf, cosf in exp_sek3 -- LieGroup.cpp:174-175 --, logf in the gates,
 // cvo.cpp:125-126), element by element: out[6 i ..] = {sinf(x), cosf(x), logf(x), sin_f32_cr(x), cos_f32_cr(x), log_f32_cr(x)} -- the last three are what exp_sek3 and the gates call
 __global__ void selftest_libm_kernel(const float* __restrict__ in, float* __restrict__ out, int n) {
@@ -44,6 +59,8 @@ hipError_t launch_selftest(int kind, const float* in, float* out, int n, hipStre
     if (kind == 0) hipLaunchKernelGGL(selftest_cubic_kernel, grid, block, 0, s, in, out, n);
     else if (kind == 1) hipLaunchKernelGGL(selftest_exp_kernel, grid, block, 0, s, in, out, n);
     else if (kind == 3) hipLaunchKernelGGL(selftest_libm_kernel, grid, block, 0, s, in, out, n);
+    else if (kind == 4) hipLaunchKernelGGL(selftest_cubic_f32eig_kernel, grid, block, 0, s, in, out, n);
+    else if (kind == 5) hipLaunchKernelGGL(selftest_dist_f32logm_kernel, grid, block, 0, s, in, out, n);
     else hipLaunchKernelGGL(selftest_dist_kernel, grid, block, 0, s, in, out, n);
     return hipGetLastError();
 }

@@ -179,13 +179,14 @@ def write_trajectory(path: str, stamps, poses) -> None:
 
 
 # ----------------------------------------------------------------------------- frame-to-frame odometry replay
-def replay_odometry(frames, camera, params=None, device: int = 0, num_want: int = 3000):
+def replay_odometry(frames, camera, params=None, device: int = 0, num_want: int = 3000, arith="base"):
     """frames: iterable of (bgr8, depth16).  Returns (poses, info): poses[k] = (4, 4) pose of camera k in the frame of camera 0
     (chained like accum_transform, cvo.cpp:816, but from the final transform of every alignment), info[k] = dict(iterations,
-    nnz, points)."""
+    nnz, points).  arith: the alignments' arithmetic mode ("base", "eigen337" or CVO_ARITH_* bits; cvo_hip.h: cvo_set_arith_mode)."""
     import cvo_slam_amd as ca
     g = ca.Cvo(params, device=device)
     g.set_num_want(num_want)
+    g.set_arith_mode(arith)
     pose = np.eye(4)
     poses, info = [], []
     for k, (bgr, dep) in enumerate(frames):
@@ -203,13 +204,13 @@ def replay_odometry(frames, camera, params=None, device: int = 0, num_want: int 
     return poses, info
 
 
-def replay_sequence(folder: str, assoc: str, calib: str, out_path: str, max_frames: int = 0, device: int = 0):
+def replay_sequence(folder: str, assoc: str, calib: str, out_path: str, max_frames: int = 0, device: int = 0, arith="base"):
     """The `cvo_main` loop (thirdparty/cvo/src/cvo_main.cpp:28-66) on a TUM-format sequence; writes the trajectory file."""
     entries = read_associations(assoc)
     if max_frames > 0:
         entries = entries[:max_frames]
     cam = read_calibration(calib)
     frames = (load_frame(folder, r, d) for (_, r, d) in entries)
-    poses, info = replay_odometry(frames, cam, device=device)
+    poses, info = replay_odometry(frames, cam, device=device, arith=arith)
     write_trajectory(out_path, [e[0] for e in entries], poses)
     return poses, info

@@ -149,6 +149,11 @@ public:
             std::cerr << "cvo stage_next_frame: " << cvo_last_error() << "\n";
     }
 #endif
+    // NOT a member of the reference's class: the arithmetic mode of this object's alignments (CVO_ARITH_* in include/cvo_hip.h; CVO_ARITH_EIGEN337 = the
+    // reading of an Eigen 3.3.7 build of the reference, for comparisons against one -- INTEGRATION.md).  Default CVO_ARITH_BASE.
+    void set_arith_mode(int flags) {
+        if (cvo_set_arith_mode(h_, flags) != CVO_OK) std::cerr << "cvo set_arith_mode: " << cvo_last_error() << "\n";
+    }
     void align() { if (cvo_align(h_) != CVO_OK) std::cerr << "cvo align: " << cvo_last_error() << "\n"; sync(); }   // cvo.cpp:763-821
 
     void match_odometry(const cv::Mat& RGB_img, const cv::Mat& dep_img, Eigen::Affine3d& transformd) {   // cvo.cpp:461-473

@@ -207,6 +207,24 @@ int cvo_set_state(cvo_handle h, const float R[9], const float T[3], float ell);
 /* number of workgroups that cooperate on this handle's alignment (latency knob; 0 = auto) */
 int cvo_set_workgroups(cvo_handle h, int workgroups_per_pair);
 
+/* ---- arithmetic modes: where a build of the reference with Eigen 3.3.7 rounds differently from this library's default (INTEGRATION.md,
+ * "Eigen 3.3.7 arithmetic mode").  Each bit switches one part on its own; any subset is valid.  The bits equal the test oracle's
+ * reference-noise variants (ORC_VAR_*), so one number selects the same reading on both sides.
+ *   CVO_ARITH_F32_ROOTS   the step (cvo.cpp:76-92, 324-333) from the f32 eigenvalues of the companion matrix (f32 Hessenberg + Francis QR)
+ *                         instead of the closed-form cubic
+ *   CVO_ARITH_F32_LOGM    the second stop test's distance (cvo.cpp:94-104) as the Frobenius norm of an f32 matrix logarithm (Schur + Pade)
+ *                         instead of the closed form
+ *   CVO_ARITH_ROW_LAZY16  compute_flow's row sums `1/c*Ai*cross_xy`, `1/d*Ai*diff_yx` (cvo.cpp:222-223) with 1/c, 1/d folded into every
+ *                         a_j before the sum in rows of fewer than 16 nonzeros (Eigen 3.3.7's lazy product), after it in longer rows
+ * Default CVO_ARITH_BASE.  A handle's mode covers cvo_align(_traced), cvo_match_* (and their _images forms) and the score block in the
+ * alignment's tail; a batch's covers cvo_batch_align_async and what is computed from its results (cvo_batch_compute_innerproduct_lc, the
+ * gathered records).  The mode is taken when a launch is queued: launches already in flight keep theirs.  The adaptive-ell path
+ * (cvo_adaptive_align) and the score kernels' own arithmetic have no modes.  Any other bit: CVO_ERR_INVALID. */
+enum { CVO_ARITH_BASE = 0, CVO_ARITH_F32_ROOTS = 2, CVO_ARITH_F32_LOGM = 4, CVO_ARITH_ROW_LAZY16 = 8,
+       CVO_ARITH_EIGEN337 = 2 | 4 | 8 };
+int cvo_set_arith_mode(cvo_handle h, int flags);
+int cvo_get_arith_mode(cvo_handle h, int* flags);
+
 /* ---- adaptive-ell variant of the alignment: acvo::align, thirdparty/cvo/src/adaptive_cvo.cpp:490-555, with its
  * own constants (adaptive_cvo.cpp:27-46).  Per iteration the kernel matrices Axy, Axx and Ayy at the current ell give the length-scale
  * gradient dl (:154-272); ell moves by dl_step*dl inside [ell_min, ell_max], ell_max shrinking by 0.7 whenever it is hit (:538-545).
@@ -237,6 +255,10 @@ int cvo_adaptive_align(int device, const cvo_adaptive_params* p /* NULL = defaul
 int cvo_selftest_cubic_step(int device, int n, const float* coef_minstep, float* step_out);
 int cvo_selftest_exp_sek3(int device, int n, const float* omega_v_dt, float* dR_dT_out);
 int cvo_selftest_dist_se3(int device, int n, const float* dR_dT, float* dist_out);
+/*   cubic_step_f32eig / dist_se3_f32logm: the same two in the arithmetic of CVO_ARITH_F32_ROOTS / CVO_ARITH_F32_LOGM (same layouts; a
+ *               logarithm that fails gives NaN) */
+int cvo_selftest_cubic_step_f32eig(int device, int n, const float* coef_minstep, float* step_out);
+int cvo_selftest_dist_se3_f32logm(int device, int n, const float* dR_dT, float* dist_out);
 /*   libm:       the device's float routines element by element: OCML's sinf, cosf, logf (logf: the gates, cvo.cpp:125-126) and the correctly rounded
  *               float sine and cosine Exp_SEK3 is evaluated with (LieGroup.cpp:174-175; cvo_math.hpp: sin_f32_cr, cos_f32_cr) and the correctly rounded logarithm of the
  *               gates (log_f32_cr)     in: n floats   out: n x {sinf, cosf, logf, sin_f32_cr, cos_f32_cr, log_f32_cr}
@@ -301,6 +323,9 @@ int cvo_batch_set_max_workgroups(cvo_batch b, int max_workgroups);
  * acceptance back and carries on with the workgroups it has -- a helper that disappears cannot turn a healthy pair into CVO_ERR_TIMEOUT.
  * cvo_batch_last_adoptions: pairs of the last launch that were helped; cvo_batch_last_adoption_retractions: acceptances taken back. */
 int cvo_batch_set_adoption(cvo_batch b, int on);
+/* arithmetic mode of the batch's launches queued after the call (CVO_ARITH_*, see cvo_set_arith_mode) */
+int cvo_batch_set_arith_mode(cvo_batch b, int flags);
+int cvo_batch_get_arith_mode(cvo_batch b, int* flags);
 int cvo_batch_last_adoptions(cvo_batch b, int* pairs_helped);
 int cvo_batch_last_adoption_retractions(cvo_batch b, int* retractions);
 /* restore every pair's (R,T,ell) to what set_pair/set_state last gave it (bench loops re-run the same inputs) */

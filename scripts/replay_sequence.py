@@ -15,12 +15,14 @@ ap.add_argument("--assoc", required=True, help="association file: rgb_time rgb_p
 ap.add_argument("--calib", required=True, help="yaml with Camera.fx/fy/cx/cy and DepthMapFactor")
 ap.add_argument("--out", default=None, help="trajectory file (default <folder>/cvo_poses_qt.txt)")
 ap.add_argument("--max-frames", type=int, default=0)
+ap.add_argument("--arith", choices=["base", "eigen337"], default="base",
+                help="arithmetic mode of the alignments: eigen337 follows an Eigen 3.3.7 build of the reference (INTEGRATION.md)")
 args = ap.parse_args()
 folder = args.folder if args.folder.endswith("/") else args.folder + "/"
 assoc = args.assoc if os.path.isabs(args.assoc) else os.path.join(folder, args.assoc)
 out = args.out or os.path.join(folder, "cvo_poses_qt.txt")
 t0 = time.perf_counter()
-poses, info = replay.replay_sequence(folder, assoc, args.calib, out, args.max_frames)
+poses, info = replay.replay_sequence(folder, assoc, args.calib, out, args.max_frames, arith=args.arith)
 dt = time.perf_counter() - t0
 its = [i["iterations"] for i in info[1:]]
 print(f"{len(poses)} frames in {dt:.2f} s ({len(poses) / dt:.1f} frames/s incl. PNG decoding), mean iterations {sum(its) / max(1, len(its)):.1f}; trajectory -> {out}")
