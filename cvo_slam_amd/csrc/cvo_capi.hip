@@ -324,14 +324,18 @@ struct SlotBook {
 SlotBook& slot_book() { static SlotBook b; return b; }
 
 // Adoption (cvo_kernels.hip: finished workgroups help with pairs that still run): a workgroup only offers its help when nothing is
-// queued on the device, i.e. when every workgroup the library has submitted there has started.  Two counters per device: submitted
-// (host-written before each launch, pinned host memory the kernels read) and started (device memory, bumped by every workgroup).
-// EVERY align launch of the process counts (with or without adoption, cooperative, queue mode), and so does every score launch: those are
-// the kernels whose workgroups wait for a compute unit while persistent align workgroups hold them.  The two counters only ever move
-// together: a launch adds its grid to `submitted` before it is submitted (and takes it back when the submission fails), and every one of
-// its workgroups adds itself to `started` first thing -- no host read of the device counter on any healthy path; a launch call that reports an error re-synchronises
-// them once the device has drained (resync_adopt_counters).
-struct AdoptCounters { int device = -1; unsigned* submitted_host = nullptr; unsigned* submitted_dev = nullptr; unsigned* started_dev = nullptr; };
+// queued on the device that could start now, i.e. when every workgroup the library has submitted there has started.  Three counters per
+// device: submitted (host-written before each launch, pinned host memory the kernels read), started and deferred (device memory, one
+// word after the other, bumped by the workgroups).  EVERY align launch of the process counts (with or without adoption, cooperative, queue
+// mode), and so does every score launch: those are the kernels whose workgroups wait for a compute unit while persistent align workgroups
+// hold them.  A launch adds its grid to `submitted` before it is submitted (and takes it back when the submission fails), and every one of
+// its workgroups adds itself to `started` first thing -- except an align launch the host expects to wait behind launches of this library on
+// every hardware queue (DevParams::adopt_on, Engine::launch_share): it is not counted as submitted, and its workgroups add themselves to
+// `deferred` as well as to `started` when they do start.  Work queued behind a running launch on a shared hardware queue cannot take a
+// compute unit before that launch ends, so it must not silence the running launch's helpers.  Healthy paths keep
+// submitted + deferred == started whenever nothing counted waits; no host read of the device counters on any healthy path; a launch call
+// that reports an error re-synchronises them once the device has drained (resync_adopt_counters).
+struct AdoptCounters { int device = -1; unsigned* submitted_host = nullptr; unsigned* submitted_dev = nullptr; unsigned* started_dev = nullptr; };   // started_dev[1]: deferred
 AdoptCounters* adopt_counters(int device) {                          // null when they cannot be made: launches then run without adoption
     static std::mutex mu; static std::vector<AdoptCounters*> all;
     std::lock_guard<std::mutex> lk(mu);
@@ -339,7 +343,7 @@ AdoptCounters* adopt_counters(int device) {                          // null whe
     AdoptCounters* a = new AdoptCounters; a->device = device;
     void* h = nullptr; void* d = nullptr; void* s = nullptr;
     if (hipHostMalloc(&h, sizeof(unsigned), hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&d, h, 0) == hipSuccess &&
-        hipMalloc(&s, sizeof(unsigned)) == hipSuccess && hipMemset(s, 0, sizeof(unsigned)) == hipSuccess) {
+        hipMalloc(&s, 2 * sizeof(unsigned)) == hipSuccess && hipMemset(s, 0, 2 * sizeof(unsigned)) == hipSuccess) {
         a->submitted_host = static_cast<unsigned*>(h); *a->submitted_host = 0u; a->submitted_dev = static_cast<unsigned*>(d); a->started_dev = static_cast<unsigned*>(s);
     } else { (void)hipGetLastError(); }
     all.push_back(a);
@@ -347,16 +351,26 @@ AdoptCounters* adopt_counters(int device) {                          // null whe
 }
 std::mutex& adopt_submit_mutex() { static std::mutex m; return m; }
 // A launch call has reported an error.  It may still have been enqueued (hipGetLastError can hand out an earlier, sticky error), so "take the grid back from
-// `submitted`" could leave the two counters apart for the life of the process -- and the helpers silent (submitted != started reads "work is queued").  Errors are
-// rare: let the device drain and set `submitted` to what has really started.  Called with the submit lock held (nothing counted is submitted meanwhile).
+// `submitted`" could leave the counters apart for the life of the process -- and the helpers silent (submitted + deferred != started reads "work is queued").  Errors are
+// rare: let the device drain and set `submitted` to what has really started and was not deferred.  Called with the submit lock held (nothing counted is submitted meanwhile).
 void resync_adopt_counters(AdoptCounters* a) {
     (void)hipDeviceSynchronize();
-    unsigned st = 0;
-    if (hipMemcpy(&st, a->started_dev, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
-        if (*a->submitted_host != st) std::fprintf(stderr, "cvo_hip: launch error on device %d: adoption counters re-synchronised (submitted %u, started %u)\n", a->device, *a->submitted_host, st);
-        *a->submitted_host = st;
+    unsigned st[2] = {0u, 0u};                                       // started, deferred
+    if (hipMemcpy(st, a->started_dev, sizeof(st), hipMemcpyDeviceToHost) == hipSuccess) {
+        if (*a->submitted_host + st[1] != st[0])
+            std::fprintf(stderr, "cvo_hip: launch error on device %d: adoption counters re-synchronised (submitted %u, deferred %u, started %u)\n", a->device, *a->submitted_host, st[1], st[0]);
+        *a->submitted_host = st[0] - st[1];
     }
     (void)hipGetLastError();
+}
+
+// Align launches of this library in flight, per device (Engine::launch_share).  Engines register while they live; whether an engine's last launch is
+// still on the device is its completion event ev1, recorded under adopt_submit_mutex like the launch itself.  Guarded by adopt_submit_mutex.
+std::vector<const struct Engine*>& live_engines() { static std::vector<const Engine*> v; return v; }
+// Hardware queues the HIP runtime gives this process: GPU_MAX_HW_QUEUES when set, else the runtime's default of 4.  Read, never set.
+int hw_queue_count() {
+    static const int q = [] { const char* e = std::getenv("GPU_MAX_HW_QUEUES"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 4; }();
+    return q;
 }
 
 // Launch machinery shared by single-object handles and batches.
@@ -396,6 +410,36 @@ struct Engine {
     bool last_tail = false;      // ... and the last launch did
     PinBuf h_tail;               // n x 5 x 24 doubles, written by the kernel
     bool adopt = false;          // finished workgroups help with the pairs of their launch that still run (one workgroup and one slot per pair; CVO_HIP_ADOPT)
+    int last_grid = 0, last_helpers = 0, last_concurrent = 0;   // the last align launch: its workgroups, those of them launched as helpers, launch_share's estimate
+    bool registered = false;     // in live_engines() (guarded by adopt_submit_mutex)
+
+    // How much of the device an align launch about to be submitted can count on (called under adopt_submit_mutex).  The HIP runtime maps
+    // streams onto Q hardware queues (hw_queue_count) by a rule of its own; launches on one hardware queue run one after the other.
+    // So with `inflight` align launches of this library on this device still running or queued (this engine's earlier launch is ahead of
+    // this one on its stream and does not count), about concurrent = min(Q, inflight + 1) of them run side by side, each on a share of
+    // capacity / concurrent workgroup slots, and when inflight >= Q this one waits behind one of them: deferred.  It is an estimate -- the
+    // queue mapping is the runtime's, and launches of other processes are not seen.  When it is wrong, only speed suffers (helpers hold back,
+    // or take a compute unit a later launch wanted); results do not depend on it.
+    void launch_share(int* concurrent, bool* deferred) {
+        std::vector<const Engine*>& live = live_engines();
+        if (!registered) { live.push_back(this); registered = true; }
+        int inflight = 0;
+        for (const Engine* o : live) {
+            if (o == this || o->device != device || !o->launched) continue;
+            const hipError_t e = hipEventQuery(o->ev1);
+            if (e == hipErrorNotReady) { ++inflight; (void)hipGetLastError(); }
+        }
+        const int Q = hw_queue_count();
+        *concurrent = std::min(Q, inflight + 1);
+        *deferred = inflight >= Q;
+    }
+    void forget() {
+        if (!registered) return;
+        std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+        std::vector<const Engine*>& live = live_engines();
+        live.erase(std::remove(live.begin(), live.end(), this), live.end());
+        registered = false;
+    }
 
     void release_slots() {
         SlotBook& b = slot_book();
@@ -463,6 +507,7 @@ struct Engine {
         return CVO_OK;
     }
     void destroy() {
+        forget();                                                    // before ev1 goes: other engines query it
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (last_stream && last_stream != stream) (void)hipStreamSynchronize(last_stream);
@@ -1057,18 +1102,29 @@ struct Engine {
         // of the bench's pairs alone -2.2 %.  Not for single handles: a tracker's consecutive frames cull once either way and the wider lists ADD 5 % to their alignments
         // (profiles/r04_single_pair_phases.txt).  CVO_HIP_FIRST_SCALE sets it for every launch.
         if (coop_first_scale > 0.f && !first_scale_set && G >= 4 && y_mode == 1) Pl.first_scale = coop_first_scale;
-        Pl.adopt_on = ac ? 1 : 0;
+        Pl.adopt_on = ac ? ADOPT_ON_HELP : 0;
+        int grid_l = grid, concurrent = 1;
         if (qc) {                                                     // count the workgroups as submitted, then submit them: in that order, under one lock per process
             std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            *qc->submitted_host += (unsigned)grid;
-            e = K->launch(grid, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl,
+            bool deferred = false;
+            launch_share(&concurrent, &deferred);
+            // An adoption launch whose share of the device holds more workgroups than it has pairs brings helpers along: workgroups n ... grid - 1 join
+            // pairs from their first iterations (cvo_align_kernel), up to ADOPT_GMAX workgroups per pair.  Otherwise the launch is what it always was.
+            const int share = std::min(num_cus * per_cu / concurrent, max_wgs > 0 ? max_wgs : num_cus * per_cu);
+            if (ac && share > n) grid_l = std::min(share, gmax * n);
+            if (deferred) Pl.adopt_on |= ADOPT_ON_DEFERRED;
+            if (!deferred) *qc->submitted_host += (unsigned)grid_l;
+            e = K->launch(grid_l, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl,
                              qc->submitted_dev, qc->started_dev, rawtab, arith_l);
             if (e != hipSuccess) resync_adopt_counters(qc);
+            else e = hipEventRecord(ev1, s);                          // under the lock: launch_share of other engines queries it
+            launched = launched || e == hipSuccess;
         } else {
             e = K->launch(grid, block, tile, rows_cap, y_mode, nm_pad, tab_cols, s, static_cast<const PairDesc*>(d_descs.p), n, G, launch_seq << 16, static_cast<unsigned long long*>(d_queue.p), Pl, nullptr, nullptr, rawtab, arith_l);
+            if (e == hipSuccess) e = hipEventRecord(ev1, s);
         }
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("align kernel launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipEventRecord(ev1, s));
+        last_grid = grid_l; last_helpers = grid_l - grid; last_concurrent = concurrent;
         launched = true;
         last_stream = s;
         last_tail = tails;
@@ -2216,6 +2272,13 @@ int cvo_batch_last_launch(cvo_batch b, float* kernel_ms, long long* iterations_t
     for (int i = 0; i < b->last_n; ++i) { it += r[i].iterations_run; ca += r[i].candidates_total; }
     if (iterations_total) *iterations_total = it;
     if (candidates_total) *candidates_total = ca;
+    return CVO_OK;
+}
+int cvo_batch_last_launch_shape(cvo_batch b, int* grid, int* helpers, int* concurrent) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    if (grid) *grid = b->eng.last_grid;
+    if (helpers) *helpers = b->eng.last_helpers;
+    if (concurrent) *concurrent = b->eng.last_concurrent;
     return CVO_OK;
 }
 int cvo_batch_last_nonzeros(cvo_batch b, long long* nonzeros_total) {

@@ -35,13 +35,16 @@ struct DevParams {           // cvo.cpp:35-51
                              // L2 twice per iteration.  Takes a launch whose pair slots are a multiple of 8; 0 = consecutive blocks (four XCDs for G = 4)
     int adopt_kmax;          // adoption: a finished workgroup only offers its help to pairs with fewer iterations than this behind them (the heavy
                              // early iterations divide well between workgroups; the light late ones are bound by the iteration's fixed latency)
-    int adopt_on;            // set per launch by the host: finished workgroups of this launch may help with its pairs that still run (one workgroup and one slot per pair)
+    int adopt_on;            // set per launch by the host, two bits.  ADOPT_ON_HELP: finished workgroups of this launch may help with its pairs that still run (one
+                             // workgroup and one slot per pair).  ADOPT_ON_DEFERRED: the launch was queued behind launches of this library on every hardware queue,
+                             // so it was not counted as submitted; its workgroups count themselves as deferred when they start (cvo_capi.hip, AdoptCounters)
     int adopt_inject;        // test knob (CVO_HIP_ADOPT_INJECT): 1 = a helper whose offer has been accepted leaves instead of confirming -- the owner must take the
                              // acceptance back and carry on with the members it has
     int adopt_dwell;         // adoption: a finished workgroup offers its help only when nothing has been queued on the device for this long (ticks of 10 ns; 0 = at once):
                              // a caller that resubmits as launches complete leaves the queue dry for a moment each time, and a helper that joins then holds its CU
                              // for the rest of the pair while the next launch's workgroups wait for one (CVO_HIP_ADOPT_DWELL_US)
 };
+constexpr int ADOPT_ON_HELP = 1, ADOPT_ON_DEFERRED = 2;   // DevParams::adopt_on
 
 // per-pair state, read at kernel start and written back at the end (Q1, Q2)
 struct PairState {

@@ -105,6 +105,7 @@ constexpr int BLOCK_MAX = CVO_BLOCK_MAX;
 constexpr int MAX_WAVES = BLOCK_MAX / 64;
 constexpr unsigned ADOPT_FREE = 0u, ADOPT_REQUEST = 1u, ADOPT_ACCEPT = 2u, ADOPT_CLOSED = 3u, ADOPT_CONFIRMED = 4u;   // states of a pair's adoption word (cvo_align_kernel)
 constexpr unsigned long long ADOPT_CONFIRM_TICKS = 5000ull;   // 50 us at 100 MHz: how long an owner waits for an accepted helper to confirm before it takes the acceptance back
+constexpr unsigned long long ADOPT_HELPER_WAIT_TICKS = 50000ull;   // 500 us: how long a helper launched with the pairs waits for its first pair to take an offer (adopt_search)
 #ifndef CVO_ADOPT_GMAX
 #define CVO_ADOPT_GMAX 4
 #endif
@@ -3152,33 +3153,57 @@ static __device__ __noinline__ void run_pair(const PairDesc* descs_in, int ps_in
 }
 
 
-// A workgroup whose pair is done looks for a pair of its launch that still runs alone and offers to help (cvo_align_kernel, adoption): wave 0 -- a lane per
-// slot looks, lane 0 asks.  Leaves the slot found (or -1) in sh->cand and the owner's answer in sh->adopt_k.  (A function of its own: the kernel's loop around
-// run_pair then keeps nothing in vector registers across its calls.)
+// A workgroup whose pair is done, or a helper launched with the pairs, looks for a pair of its launch that still runs alone and offers to help (cvo_align_kernel,
+// adoption): wave 0 -- a lane per slot looks, lane 0 asks.  It only looks while nothing is queued on the device that could start now: every workgroup the host
+// counted as submitted has started (submitted + deferred == started; cvo_capi.hip, AdoptCounters).
+// Leaves the slot found (or -1) in sh->cand and the owner's answer in sh->adopt_k.  (A function of its own: the kernel's loop around run_pair then keeps
+// nothing in vector registers across its calls.)
 static __device__ __noinline__ void adopt_search(gu64* queue, const unsigned* wgs_submitted, unsigned* wgs_started, int slots_in, int slot_in, unsigned launch_tag_in) {
     Shared* sh = reinterpret_cast<Shared*>(cvo_smem);
     const int tid = threadIdx.x, slots = uni(slots_in), slot = uni(slot_in);
+    const int prefer = slot >= slots ? (slot - slots) % slots : -1;   // a helper launched with the pairs (slot = its block index >= the pair slots): the pair it asks first
     const unsigned launch_tag = (unsigned)uni((int)launch_tag_in);
     if (tid < 64) {                                           // wave 0: a lane per slot looks, lane 0 asks
         int found = -1; unsigned kj = 0;
-        unsigned sub = __hip_atomic_load(wgs_submitted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        unsigned sta = __hip_atomic_load(wgs_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (sub == sta && sh->P.adopt_dwell > 0) {                // dry right now: is it the end of the job, or the moment between a completion and the caller's next launch?
+        auto dry = [&]() {                                    // nothing counted is waiting for a compute unit
+            const unsigned sub = __hip_atomic_load(wgs_submitted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            const unsigned def = __hip_atomic_load(wgs_started + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned sta = __hip_atomic_load(wgs_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return sub + def == sta;
+        };
+        bool idle = dry();
+        if (prefer >= 0) {
+            // A helper launched with the pairs: the rest of its own launch may still be starting, the owner of its pair may not have opened the pair's word yet,
+            // or another helper's offer may be pending there (it is answered in the owner's next epilogue).  Wait for that, a bounded time.
+            const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+            for (;;) {
+                const unsigned st = (unsigned)(__hip_atomic_load(&queue[1 + prefer], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> 32) - launch_tag;
+                if ((idle && st == ADOPT_FREE) || st == ADOPT_CLOSED || __builtin_amdgcn_s_memrealtime() - t_start > ADOPT_HELPER_WAIT_TICKS) break;
+                __builtin_amdgcn_s_sleep(8);
+                idle = dry();
+            }
+        } else if (idle && sh->P.adopt_dwell > 0) {           // dry right now: is it the end of the job, or the moment between a completion and the caller's next launch?
             const unsigned long long t_dry = __builtin_amdgcn_s_memrealtime();
             while (__builtin_amdgcn_s_memrealtime() - t_dry < (unsigned long long)sh->P.adopt_dwell) {
                 __builtin_amdgcn_s_sleep(64);
-                sub = __hip_atomic_load(wgs_submitted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                sta = __hip_atomic_load(wgs_started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (sub != sta) break;                        // new work has been queued: leave, its workgroups want this CU
+                idle = dry();
+                if (!idle) break;                             // new work has been queued: leave, its workgroups want this CU
             }
         }
-        for (int attempt = 0; attempt < 4 && found < 0 && sub == sta; ++attempt) {
-            // the pair that runs alone and has the most left to do, as far as one can tell: the one with the fewest iterations behind it
+        for (int attempt = 0; attempt < 4 && found < 0 && idle; ++attempt) {
+            // the preferred pair (a launched helper's first try), else the pair that runs alone and has the most left to do, as far as one can tell: the one
+            // with the fewest iterations behind it
             unsigned key = 0xFFFFFFFFu;                     // iteration << 12 | slot
-            for (int s2 = tid; s2 < slots; s2 += 64) {
-                if (s2 == slot) continue;
-                const unsigned long long w = __hip_atomic_load(&queue[1 + s2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned)(w >> 32) == (launch_tag | ADOPT_FREE)) key = min(key, (min((unsigned)w, 0xFFFFFu) << 12) | (unsigned)s2);
+            if (attempt == 0 && prefer >= 0) {
+                const unsigned long long w = __hip_atomic_load(&queue[1 + prefer], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((unsigned)(w >> 32) == (launch_tag | ADOPT_FREE)) key = (min((unsigned)w, 0xFFFFFu) << 12) | (unsigned)prefer;
+            }
+            if (key == 0xFFFFFFFFu) {
+                for (int s2 = tid; s2 < slots; s2 += 64) {
+                    if (s2 == slot) continue;
+                    const unsigned long long w = __hip_atomic_load(&queue[1 + s2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if ((unsigned)(w >> 32) == (launch_tag | ADOPT_FREE)) key = min(key, (min((unsigned)w, 0xFFFFFu) << 12) | (unsigned)s2);
+                }
             }
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, off, 64));
@@ -3258,21 +3283,25 @@ __global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD
                                                                          ) {
     Shared* sh = reinterpret_cast<Shared*>(cvo_smem);
     const int tid = threadIdx.x;
-    const int slots = gridDim.x / G;
+    // pair slots: gridDim.x / G, except in an adoption launch that brings helpers along (cvo_capi.hip, Engine::launch_share): there blocks
+    // n_pairs ... gridDim.x - 1 are helpers and own no slot
+    const int slots = min((int)gridDim.x / G, n_pairs);
     int slot = blockIdx.x / G, g = blockIdx.x % G;
     if (P.colocate && G > 1 && (slots & 7) == 0) {                  // members of a slot at blocks congruent mod 8: one XCD, one L2 (DevParams::colocate)
         const int t = blockIdx.x >> 3;
         g = t % G; slot = (blockIdx.x & 7) + 8 * (t / G);
     }
-    // "is anything queued on the device?" (adoption): every workgroup the library submits counts itself as started, whatever kind of launch it belongs to
-    if (wgs_started != nullptr && tid == 0) atomicAdd(wgs_started, 1u);
-    if (slot >= slots) return;                                      // gridDim.x is a multiple of G; defensive
+    // "is anything queued on the device?" (adoption): every workgroup the library submits counts itself as started, whatever kind of launch it belongs to,
+    // and as deferred when the host did not count its launch as submitted (DevParams::adopt_on)
+    if (wgs_started != nullptr && tid == 0) { if (P.adopt_on & ADOPT_ON_DEFERRED) atomicAdd(wgs_started + 1, 1u); atomicAdd(wgs_started, 1u); }
+    const bool adopting = wgs_started != nullptr && (P.adopt_on & ADOPT_ON_HELP) != 0;   // set by the host for launches of one workgroup and one slot per pair
+    const bool helper = slot >= slots;                              // launched as a helper (adoption launches of G = 1 only)
+    if (helper && !(adopting && G == 1)) return;                    // defensive: the host makes no such launch
     if (tid == 0) { sh->rc_ell = -1.f; sh->P = P; sh->skin0 = P.skin; sh->alpha0 = P.skin_alpha; sh->launch_tag = launch_tag; sh->rows_cap = rows_cap; sh->y_cap = y_cap; sh->tab_cols = tab_cols; }
 #ifdef CVO_ARITH_MODES
     if (tid == 0) sh->arith = arith;
 #endif
     __syncthreads();                                                // (run_pair reads the parameters from there)
-    const bool adopting = wgs_started != nullptr && P.adopt_on != 0;   // set by the host for launches of one workgroup and one slot per pair
     const int tgeo = pack_geometry(tile, rows_cap, y_cap);
     gu64* queue = (gu64*)queue_in;
 
@@ -3287,11 +3316,13 @@ __global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD
         int p;
         int ge = g, Ge = G;                                             // this workgroup's place in the pair it works on
         unsigned k_join = 0;                                            // > 0: it joins a running pair of another slot at that iteration
-        if (!dynamic && pull == 0) p = slot;
+        if (!dynamic && pull == 0 && !helper) p = slot;
         else if (!dynamic) {
             if (!adopt_launch) break;
-            // this workgroup's pair is done.  With nothing queued on the device (every workgroup submitted so far has started), look for
-            // a pair of the launch that still runs alone and offer to help; leave when there is none.
+            // this workgroup's pair is done, or it is a helper launched with the pairs.  With nothing queued on the device that could start now, look
+            // for a pair of the launch that still runs alone and offer to help; leave when there is none.  A launched helper first asks for pair
+            // slot (its index - n_pairs) mod n_pairs: block b of a launch runs on XCD (h + b) mod 8, so with a multiple of 8 pairs that pair's owner
+            // shares its XCD and L2, and the low slots hold the densest pairs of every XCD class (the host's pair order, cvo_capi.hip).
             adopt_search(queue, wgs_submitted, wgs_started, slots, slot, launch_tag);
             __syncthreads();
             p = sh->cand;

@@ -319,6 +319,11 @@ int cvo_batch_set_max_workgroups(cvo_batch b, int max_workgroups);
  * more workgroup (a pair can grow to four).  "Nothing queued" counts every align and score launch this library has submitted on the
  * device in this process, whatever its kind (not other processes, not other libraries' kernels).  Shortens the tail of a job whose
  * alignments take different numbers of iterations (33 ... 150); the results are those of any other workgroup count.
+ * Helpers may also be launched with the pairs: when the launch's share of the device -- its workgroup slots divided by the align launches of
+ * this library on the device that are estimated to run side by side, at most the hardware queues the runtime gives the process
+ * (GPU_MAX_HW_QUEUES, read and never set; 4 when unset) -- holds more workgroups than it has pairs, the launch takes min(share,
+ * 4 x pairs) workgroups and the extra ones join pairs from their first iterations.  A launch queued behind such launches on every hardware
+ * queue does not count as "queued" for the helpers of the launches it waits for: it could not start before they end anyway.
  * A pair only counts on a helper that has CONFIRMED the acceptance of its offer; when no confirmation comes within 50 us the owner takes the
  * acceptance back and carries on with the workgroups it has -- a helper that disappears cannot turn a healthy pair into CVO_ERR_TIMEOUT.
  * cvo_batch_last_adoptions: pairs of the last launch that were helped; cvo_batch_last_adoption_retractions: acceptances taken back. */
@@ -339,6 +344,9 @@ int cvo_batch_wait(cvo_batch b, cvo_pair_result* results, int n);
 int cvo_batch_done(cvo_batch b, int* done);
 /* device time of the last launch in ms (HIP events on the launch stream), total loop trips it executed */
 int cvo_batch_last_launch(cvo_batch b, float* kernel_ms, long long* iterations_total, long long* candidates_total);
+/* the shape of the last launch: its workgroups, how many of them were launched as helpers (adoption), and the number of launches
+ * (this one included) it was estimated to share the device with when it was submitted */
+int cvo_batch_last_launch_shape(cvo_batch b, int* grid, int* helpers, int* concurrent);
 /* nonzeros of the kernel matrix A (cvo.cpp:166-175) summed over every executed iteration of every pair of the last launch: the work the
  * reference's arithmetic is defined on (bench.py prices the kernel's instructions per nonzero with it) */
 int cvo_batch_last_nonzeros(cvo_batch b, long long* nonzeros_total);
