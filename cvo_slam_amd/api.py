@@ -110,6 +110,7 @@ ABI_SYMBOLS = [
     "cvo_compact_records", "cvo_gather_results_padded", "cvo_multi_align_async_v", "cvo_batch_done", "cvo_batch_set_tail_scores", "cvo_batch_last_tail_answers", "cvo_batch_last_pair_seconds", "cvo_batch_last_pair_spans", "cvo_batch_last_tail_seconds", "cvo_set_tail_scores", "cvo_batch_last_cull_masks", "cvo_batch_last_nonzeros",
     "cvo_set_arith_mode", "cvo_get_arith_mode", "cvo_batch_set_arith_mode", "cvo_batch_get_arith_mode",
     "cvo_selftest_cubic_step_f32eig", "cvo_selftest_dist_se3_f32logm",
+    "cvo_batch_set_pairs_images", "cvo_batch_set_num_want", "cvo_batch_get_cloud", "cvo_batch_get_selected_points",
 ]
 
 _lib = None
@@ -196,6 +197,10 @@ def load_library():
     L.cvo_match_keyframe_images.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(Camera), dp]
     L.cvo_get_cloud.argtypes = [vp, C.c_int, fp, fp, C.c_int, ip]
     L.cvo_get_selected_points.argtypes = [vp, C.c_int, vp, C.c_int, ip]
+    L.cvo_batch_set_pairs_images.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip, ip, ip]
+    L.cvo_batch_set_num_want.argtypes = [vp, C.c_int]
+    L.cvo_batch_get_cloud.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.c_int, ip]
+    L.cvo_batch_get_selected_points.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, ip]
     L.cvo_batch_enqueue_innerproduct.argtypes = [vp, C.c_int]
     L.cvo_batch_innerproduct_results.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
     L.cvo_batch_compute_innerproduct.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
@@ -782,6 +787,49 @@ class CvoBatch:
         """cvo_batch_set_pairs: one hand-over for all pairs of `prepared` (prepare_pairs), or of a sequence of cloud tuples."""
         pr = prepared if isinstance(prepared, dict) else self.prepare_pairs(prepared)
         _check(self.L.cvo_batch_set_pairs(self.h, first, pr["n"], pr["fx"], pr["ff"], pr["nf"], pr["mx"], pr["mf"], pr["nm"]))
+
+    def set_pairs_images(self, images, fixed_image, moving_image, camera, first: int = 0):
+        """cvo_batch_set_pairs_images: pairs first .. first+len(fixed_image)-1 from RGB-D images.  images: list of (bgr8, depth16), all of one
+        size, each generated once on the GPU; pair k takes images[fixed_image[k]] as its fixed cloud and images[moving_image[k]] as its moving
+        one.  camera = (scaling_factor, fx, fy, cx, cy).  Returns the points of each image's cloud."""
+        ims = [Cvo._images(b, d) for b, d in images]
+        if not ims:
+            raise ValueError("no images")
+        fi = np.ascontiguousarray(fixed_image, np.int32).reshape(-1); mi = np.ascontiguousarray(moving_image, np.int32).reshape(-1)
+        if fi.shape != mi.shape:
+            raise ValueError("fixed_image and moving_image must have one entry per pair")
+        w, h = ims[0][2], ims[0][3]
+        if any((q[2], q[3]) != (w, h) for q in ims):
+            raise ValueError("all images of one call must have the same size")
+        n = len(ims); cam = Camera(*[float(v) for v in camera])
+        bgr = (C.c_void_p * n)(*[q[0].ctypes.data for q in ims]); dep = (C.c_void_p * n)(*[q[1].ctypes.data for q in ims])
+        pts = np.zeros(n, np.int32); ip = C.POINTER(C.c_int)
+        _check(self.L.cvo_batch_set_pairs_images(self.h, int(first), int(fi.shape[0]), n, bgr, dep, w, h, C.byref(cam),
+                                                 fi.ctypes.data_as(ip), mi.ctypes.data_as(ip), pts.ctypes.data_as(ip)))
+        return pts
+
+    def set_num_want(self, num_want: int):
+        """pcd_generator::num_want of the later set_pairs_images calls (3000 by default)"""
+        _check(self.L.cvo_batch_set_num_want(self.h, int(num_want)))
+
+    def get_cloud(self, p: int, slot: int):
+        """pair p's cloud in slot SLOT_FIXED / SLOT_MOVING: xyz (n, 3), feat (5, n)"""
+        n = C.c_int(0)
+        _check(self.L.cvo_batch_get_cloud(self.h, int(p), int(slot), None, None, 0, C.byref(n)))
+        xyz = np.zeros((n.value, 3), np.float32); feat = np.zeros((5, n.value), np.float32)
+        if n.value:
+            _check(self.L.cvo_batch_get_cloud(self.h, int(p), int(slot), xyz.ctypes.data_as(C.POINTER(C.c_float)), feat.ctypes.data_as(C.POINTER(C.c_float)),
+                                              n.value, C.byref(n)))
+        return xyz, feat
+
+    def get_selected_points(self, p: int, slot: int):
+        """the pixel (x, y) of every point of pair p's cloud in `slot`, for clouds made by set_pairs_images (empty otherwise)"""
+        n = C.c_int(0)
+        _check(self.L.cvo_batch_get_selected_points(self.h, int(p), int(slot), None, 0, C.byref(n)))
+        px = np.zeros((n.value, 2), np.uint16)
+        if n.value:
+            _check(self.L.cvo_batch_get_selected_points(self.h, int(p), int(slot), px.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return px
 
     def set_state(self, p, R, T, ell):
         r, rp = _f(np.asarray(R).reshape(9)); t, tp = _f(np.asarray(T).reshape(3))

@@ -70,8 +70,8 @@ hipError_t launch_copy_records(const float* src, float* dst, int n, hipStream_t 
 hipError_t launch_pack_clouds(const float* raw, const PackDesc* descs, int n_clouds, int n_max, hipStream_t s);
 SelfCacheEntry* score_self_cache(float* gbox, int n);
 hipError_t pcd_launch_pyramid(const uint8_t* bgr, int w, int h, float* I0, float* I1, float* I2, float* dx0, float* dy0, float* abs0, float* abs1, float* abs2,
-                              hipStream_t s);
-hipError_t pcd_launch_thresholds(const float* abs0, int w, int h, float* ths, float* ths_smoothed, hipStream_t s);
+                              int n_img, hipStream_t s);
+hipError_t pcd_launch_thresholds(const float* abs0, int w, int h, float* ths, float* ths_smoothed, int n_img, hipStream_t s);
 hipError_t pcd_launch_select(const float* abs0, const float* abs1, const float* abs2, const float* ths_smoothed, int w, int h, int pot, uint8_t* map, int* counts,
                              hipStream_t s);
 int pcd_tiles(int w, int h);
@@ -79,6 +79,13 @@ hipError_t pcd_launch_subsample(uint8_t* map, const uint8_t* pattern, int subsam
 hipError_t pcd_launch_cloud(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
                             const int* tile_counts, int n_points, float* cloud, uint16_t* px, hipStream_t s);
 hipError_t pcd_launch_unpack(const float* cloud, int n, float* xyz, float* feat, hipStream_t s);
+hipError_t pcd_launch_select_batch(const float* abs0, const float* abs1, const float* abs2, const float* ths_smoothed, int w, int h, uint8_t* map, PcdImgRec* rec,
+                                   int n_img, int num_want, hipStream_t s);
+hipError_t pcd_launch_subsample_batch(uint8_t* map, const uint8_t* pattern, const PcdImgRec* rec, int num_want, const uint16_t* depth, int w, int h, int* tile_counts,
+                                      int n_img, hipStream_t s);
+hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
+                                  const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s);
+hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -741,8 +748,8 @@ struct Engine {
         HIP_TRY(hipMemsetAsync(d_ths.p, 0, sizeof(float) * nths, stream));
         HIP_TRY(hipMemsetAsync(d_thsS.p, 0, sizeof(float) * nths, stream));
         float* I0 = (float*)d_I0.p; float* dx0 = (float*)d_dx0.p; float* dy0 = (float*)d_dy0.p; float* abs0 = (float*)d_abs0.p;
-        hipError_t e = pcd_launch_pyramid((const uint8_t*)d_bgr.p, w, h, I0, (float*)d_I1.p, (float*)d_I2.p, dx0, dy0, abs0, (float*)d_abs1.p, (float*)d_abs2.p, stream);
-        if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)d_ths.p, (float*)d_thsS.p, stream);
+        hipError_t e = pcd_launch_pyramid((const uint8_t*)d_bgr.p, w, h, I0, (float*)d_I1.p, (float*)d_I2.p, dx0, dy0, abs0, (float*)d_abs1.p, (float*)d_abs2.p, 1, stream);
+        if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)d_ths.p, (float*)d_thsS.p, 1, stream);
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
         lap();                                                          // [0] buffers, colour staging + copy + kernels queued
         std::memcpy(st + 3 * n, depth16, 2 * n);
@@ -1429,11 +1436,27 @@ struct cvo_handle_s {
     float tail_ell = 0.f, tail_tran[12];
 };
 
+// Scratch of cvo_batch_set_pairs_images: every buffer holds n_cap images of w x h one behind the other (the strides of cvo_pcd_kernels.hip),
+// and one slot of PCD_CLOUD_CAP points per image for its cloud.  Grows with the largest call, released by cvo_batch_destroy.
+constexpr int PCD_CLOUD_CAP = 65535;
+struct BatchImages {
+    DevBuf bgr, depth, I0, I1, I2, dx0, dy0, abs0, abs1, abs2, ths, thsS, map, pattern, tiles, rec, cloud, px;
+    PinBuf stage, h_rec;
+    int n_cap = 0, w = 0, h = 0;
+    int num_want = 3000;                                            // pcd_generator::num_want (pcd_generator.cpp:22)
+    void release() {
+        for (DevBuf* b : {&bgr, &depth, &I0, &I1, &I2, &dx0, &dy0, &abs0, &abs1, &abs2, &ths, &thsS, &map, &pattern, &tiles, &rec, &cloud, &px}) b->release();
+        stage.release(); h_rec.release();
+        n_cap = w = h = 0;
+    }
+};
+
 struct cvo_batch_s {
     cvo_params prm;
     Engine eng;
     int max_pairs = 0;
     std::vector<std::unique_ptr<Cloud>> fixed, moving;
+    BatchImages img;
     std::vector<PairState> init_states;     // what set_pair / set_state last gave
     bool states_dirty = true;               // device states differ from init_states
     int last_n = 0;
@@ -1738,34 +1761,43 @@ int cvo_staged_frame_count(cvo_handle h, int* count) { if (!h || !count) return 
 int cvo_queued_score_count(cvo_handle h, int* count) { if (!h || !count) return fail(CVO_ERR_INVALID, "null argument"); *count = h->queued_hits; return CVO_OK; }
 int cvo_shared_cloud_count(cvo_handle h, int* count) { if (!h || !count) return fail(CVO_ERR_INVALID, "null argument"); *count = h->shared_hits; return CVO_OK; }
 
-int cvo_get_cloud(cvo_handle h, int slot, float* xyz, float* feat, int cap, int* n) {
-    if (!h || !n) return fail(CVO_ERR_INVALID, "null argument");
-    Cloud* c = slot_cloud(h, slot);
+namespace {
+// a cloud back to the reference layout on the host (cvo_get_cloud, cvo_batch_get_cloud), queued on the engine's stream behind whatever wrote it
+int download_cloud(Engine& E, const Cloud* c, float* xyz, float* feat, int cap, int* n) {
     *n = c ? c->n : 0;
     if (!c || c->n == 0 || cap < c->n) return CVO_OK;
     if (!xyz || !feat) return fail(CVO_ERR_INVALID, "null output array");
-    HIP_TRY(hipSetDevice(h->eng.device));
+    HIP_TRY(hipSetDevice(E.device));
     DevBuf tmp; int rc = tmp.ensure(sizeof(float) * 8 * (size_t)c->n); if (rc) return rc;
     float* dx = static_cast<float*>(tmp.p); float* df = dx + 3 * (size_t)c->n;
-    hipError_t e = pcd_launch_unpack(c->rec(), c->n, dx, df, h->eng.stream);
+    hipError_t e = pcd_launch_unpack(c->rec(), c->n, dx, df, E.stream);
     if (e != hipSuccess) { tmp.release(); return fail(CVO_ERR_HIP, std::string("unpack kernel: ") + hipGetErrorString(e)); }
-    hipError_t e1 = hipMemcpyAsync(xyz, dx, sizeof(float) * 3 * (size_t)c->n, hipMemcpyDeviceToHost, h->eng.stream);
-    hipError_t e2 = hipMemcpyAsync(feat, df, sizeof(float) * 5 * (size_t)c->n, hipMemcpyDeviceToHost, h->eng.stream);
-    hipError_t e3 = hipStreamSynchronize(h->eng.stream);
+    hipError_t e1 = hipMemcpyAsync(xyz, dx, sizeof(float) * 3 * (size_t)c->n, hipMemcpyDeviceToHost, E.stream);
+    hipError_t e2 = hipMemcpyAsync(feat, df, sizeof(float) * 5 * (size_t)c->n, hipMemcpyDeviceToHost, E.stream);
+    hipError_t e3 = hipStreamSynchronize(E.stream);
     tmp.release();
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return fail(CVO_ERR_HIP, "cloud download failed");
     return CVO_OK;
 }
-
-int cvo_get_selected_points(cvo_handle h, int slot, unsigned short* px, int cap, int* n) {
-    if (!h || !n) return fail(CVO_ERR_INVALID, "null argument");
-    Cloud* c = slot_cloud(h, slot);
+int download_selected_points(Engine& E, const Cloud* c, unsigned short* px, int cap, int* n) {
     *n = c ? c->n_px : 0;
     if (!c || c->n_px == 0 || cap < c->n_px) return CVO_OK;
     if (!px) return fail(CVO_ERR_INVALID, "null output array");
-    HIP_TRY(hipSetDevice(h->eng.device));
-    HIP_TRY(hipMemcpy(px, c->px.p, sizeof(unsigned short) * 2 * (size_t)c->n_px, hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(E.device));
+    HIP_TRY(hipMemcpyAsync(px, c->px.p, sizeof(unsigned short) * 2 * (size_t)c->n_px, hipMemcpyDeviceToHost, E.stream));
+    HIP_TRY(hipStreamSynchronize(E.stream));
     return CVO_OK;
+}
+}  // namespace
+
+int cvo_get_cloud(cvo_handle h, int slot, float* xyz, float* feat, int cap, int* n) {
+    if (!h || !n) return fail(CVO_ERR_INVALID, "null argument");
+    return download_cloud(h->eng, slot_cloud(h, slot), xyz, feat, cap, n);
+}
+
+int cvo_get_selected_points(cvo_handle h, int slot, unsigned short* px, int cap, int* n) {
+    if (!h || !n) return fail(CVO_ERR_INVALID, "null argument");
+    return download_selected_points(h->eng, slot_cloud(h, slot), px, cap, n);
 }
 
 int cvo_align_traced(cvo_handle h, cvo_trace_row* trace, int trace_cap, int* trace_len) {
@@ -2131,6 +2163,7 @@ int cvo_batch_destroy(cvo_batch b) {
     (void)hipSetDevice(b->eng.device);
     if (b->eng.stream) (void)hipStreamSynchronize(b->eng.stream);
     b->fixed.clear(); b->moving.clear();
+    b->img.release();
     b->eng.destroy();
     delete b;
     return CVO_OK;
@@ -2163,6 +2196,128 @@ int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* f
     b->states_dirty = true;
     return CVO_OK;
 }
+
+// ---- pairs from RGB-D images: every image generated once by the batched generator (cvo_pcd_kernels.hip, a fixed list of launches over all
+// images, makeMaps decided on the device), ONE host sync for the point counts, then each pair's clouds copied from their images' slots
+int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
+    if (!b || first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
+    if (!bgr8 || !depth16 || !cam || !fixed_image || !moving_image) return fail(CVO_ERR_INVALID, "null argument");
+    if (n_images <= 0 || n_images > 65535) return fail(CVO_ERR_INVALID, "bad image count");
+    if (width < 64 || height < 64 || (size_t)width * height > (size_t)1 << 26) return fail(CVO_ERR_INVALID, "image size out of range");
+    for (int k = 0; k < n_images; ++k) if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+    for (int k = 0; k < count; ++k)
+        if (fixed_image[k] < 0 || fixed_image[k] >= n_images || moving_image[k] < 0 || moving_image[k] >= n_images) return fail(CVO_ERR_INVALID, "image index out of range");
+    Engine& E = b->eng; BatchImages& S = b->img;
+    HIP_TRY(hipSetDevice(E.device));
+    const int N = n_images, w = width, h = height, num_want = S.num_want;
+    const size_t n = (size_t)w * h, n1 = (size_t)(w / 2) * (h / 2), n2 = (size_t)(w / 4) * (h / 4), nths = (size_t)(w / 32) * (h / 32) + 100;
+    const int nt = pcd_tiles(w, h), cap = PCD_CLOUD_CAP;
+    int rc;
+    if (N > S.n_cap || w != S.w || h != S.h) {
+        HIP_TRY(hipStreamSynchronize(E.stream));                       // the previous call's copies to the pairs may still read the slots
+        const size_t m = (size_t)std::max(N, S.n_cap);
+        if ((rc = S.bgr.ensure(3 * n * m)) || (rc = S.depth.ensure(2 * n * m)) || (rc = S.map.ensure(n * m))) return rc;
+        for (DevBuf* x : {&S.I0, &S.dx0, &S.dy0, &S.abs0}) if ((rc = x->ensure(sizeof(float) * n * m))) return rc;
+        for (DevBuf* x : {&S.I1, &S.abs1}) if ((rc = x->ensure(sizeof(float) * n1 * m))) return rc;
+        for (DevBuf* x : {&S.I2, &S.abs2}) if ((rc = x->ensure(sizeof(float) * n2 * m))) return rc;
+        for (DevBuf* x : {&S.ths, &S.thsS}) if ((rc = x->ensure(sizeof(float) * nths * m))) return rc;
+        if ((rc = S.tiles.ensure(sizeof(int) * 3 * (size_t)nt * m)) || (rc = S.rec.ensure(sizeof(PcdImgRec) * m))) return rc;
+        if ((rc = S.cloud.ensure(sizeof(float) * REC * (size_t)cap * m)) || (rc = S.px.ensure(sizeof(uint16_t) * 2 * (size_t)cap * m))) return rc;
+        if ((rc = S.stage.ensure(5 * n * m)) || (rc = S.h_rec.ensure(sizeof(PcdImgRec) * m))) return rc;
+        if (w != S.w || h != S.h) {                                   // the byte pattern only depends on w*h: made once per size, shared by every image
+            if ((rc = S.pattern.ensure(n))) return rc;
+            std::vector<unsigned char> pat(n);
+            Engine::rand_pattern(3141592u, pat.data(), n);
+            HIP_TRY(hipMemcpy(S.pattern.p, pat.data(), n, hipMemcpyHostToDevice));
+        }
+        S.n_cap = (int)m; S.w = w; S.h = h;
+    }
+    hipStream_t s = E.stream;
+    unsigned char* st = static_cast<unsigned char*>(S.stage.p);
+    {
+        // every return from here on leaves nothing of this call in flight: the next call overwrites the pinned stage the copies read from
+        struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
+        // the colour images first: their copy and the pyramid / threshold / select kernels (which need nothing else) run while the host stages the depth images
+        for (int k = 0; k < N; ++k) std::memcpy(st + 3 * n * k, bgr8[k], 3 * n);
+        HIP_TRY(hipMemcpyAsync(S.bgr.p, st, 3 * n * N, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemsetAsync(S.ths.p, 0, sizeof(float) * nths * N, s));
+        HIP_TRY(hipMemsetAsync(S.thsS.p, 0, sizeof(float) * nths * N, s));
+        HIP_TRY(hipMemsetAsync(S.map.p, 0, n * N, s));
+        HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(PcdImgRec) * N, s));
+        float* abs0 = (float*)S.abs0.p; float* abs1 = (float*)S.abs1.p; float* abs2 = (float*)S.abs2.p; PcdImgRec* rec = (PcdImgRec*)S.rec.p;
+        hipError_t e = pcd_launch_pyramid((const uint8_t*)S.bgr.p, w, h, (float*)S.I0.p, (float*)S.I1.p, (float*)S.I2.p, (float*)S.dx0.p, (float*)S.dy0.p, abs0, abs1, abs2, N, s);
+        if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)S.ths.p, (float*)S.thsS.p, N, s);
+        if (e == hipSuccess) e = pcd_launch_select_batch(abs0, abs1, abs2, (const float*)S.thsS.p, w, h, (uint8_t*)S.map.p, rec, N, num_want, s);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
+        unsigned char* sd = st + 3 * n * N;
+        for (int k = 0; k < N; ++k) std::memcpy(sd + 2 * n * k, depth16[k], 2 * n);
+        HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
+        const float camv[5] = {cam->scaling_factor, cam->fx, cam->fy, cam->cx, cam->cy};
+        e = pcd_launch_subsample_batch((uint8_t*)S.map.p, (const uint8_t*)S.pattern.p, rec, num_want, (const uint16_t*)S.depth.p, w, h, (int*)S.tiles.p, N, s);
+        if (e == hipSuccess) e = pcd_launch_cloud_batch((const uint8_t*)S.map.p, (const uint16_t*)S.depth.p, (const uint8_t*)S.bgr.p, (const float*)S.dx0.p, (const float*)S.dy0.p,
+                                                        w, h, camv, (const int*)S.tiles.p, rec, cap, (float*)S.cloud.p, (uint16_t*)S.px.p, N, s);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
+        HIP_TRY(hipMemcpyAsync(S.h_rec.p, S.rec.p, sizeof(PcdImgRec) * N, hipMemcpyDeviceToHost, s));
+    }                                                                 // (the one sync: Drain)
+    HIP_TRY(hipStreamSynchronize(s));                                 // (reports an error of the queued work; nothing left to wait for)
+    const PcdImgRec* R = static_cast<const PcdImgRec*>(S.h_rec.p);
+    for (int k = 0; k < N; ++k)
+        if (R[k].npts > cap) return fail(CVO_ERR_INVALID, "image " + std::to_string(k) + ": more than 65535 points per cloud is not supported (16-bit column indices)");
+    // commit: the pairs take their clouds (a launch on a caller's stream may still read the clouds they had)
+    if (E.launched && E.last_stream && E.last_stream != s) HIP_TRY(hipStreamSynchronize(E.last_stream));
+    for (int k = 0; k < count; ++k) {
+        const int p = first + k;
+        if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
+        if (!b->moving[p]) b->moving[p].reset(new Cloud());
+        for (int side = 0; side < 2; ++side) {
+            Cloud& c = side ? *b->moving[p] : *b->fixed[p];
+            const int np = R[side ? moving_image[k] : fixed_image[k]].npts;
+            if (np > 0 && ((rc = c.buf.ensure((size_t)np * REC * sizeof(float))) || (rc = c.px.ensure((size_t)np * 2 * sizeof(uint16_t))))) return rc;
+        }
+    }
+    PcdScatter sc; std::memset(&sc, 0, sizeof(sc));
+    sc.src = (const float*)S.cloud.p; sc.src_px = (const uint16_t*)S.px.p; sc.rec = (const PcdImgRec*)S.rec.p; sc.cap = cap;
+    int n_max = 0;
+    auto flush = [&]() -> int {
+        const hipError_t e = pcd_launch_scatter(sc, n_max, s);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd scatter: ") + hipGetErrorString(e));
+        sc.n = 0; n_max = 0; return CVO_OK;
+    };
+    for (int k = 0; k < count; ++k) {
+        const int p = first + k;
+        for (int side = 0; side < 2; ++side) {
+            Cloud& c = side ? *b->moving[p] : *b->fixed[p];
+            const int im = side ? moving_image[k] : fixed_image[k];
+            const PcdImgRec& r = R[im];
+            c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr;   // (a hand-over not packed yet is dropped)
+            c.cost_hint = r.cost_n > 0 ? (float)(r.cost / r.cost_n) : 0.f;
+            if (c.n <= 0) continue;
+            sc.img[sc.n] = im; sc.dst[sc.n] = c.rec(); sc.dst_px[sc.n] = (uint16_t*)c.px.p; ++sc.n; n_max = std::max(n_max, c.n);
+            if (sc.n == PCD_SCATTER_MAX && (rc = flush())) return rc;
+        }
+    }
+    if (sc.n > 0 && (rc = flush())) return rc;
+    E.uploads_pending = true;                                         // (a launch on another stream waits for the copies: settle_uploads)
+    for (int k = 0; k < count; ++k) fresh_state(b->init_states[first + k], b->prm.ell);
+    b->states_dirty = true;
+    if (points_out) for (int k = 0; k < N; ++k) points_out[k] = R[k].npts;
+    return CVO_OK;
+}
+int cvo_batch_set_num_want(cvo_batch b, int num_want) {
+    if (!b || num_want <= 0) return fail(CVO_ERR_INVALID, "bad argument");
+    b->img.num_want = num_want; return CVO_OK;
+}
+int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n) {
+    if (!b || !n || p < 0 || p >= b->max_pairs || (slot != CVO_SLOT_FIXED && slot != CVO_SLOT_MOVING)) return fail(CVO_ERR_INVALID, "bad argument");
+    int rc = b->eng.flush_pending(b->eng.stream); if (rc) return rc;   // (clouds handed over by cvo_batch_set_pair(s) are packed by the next launch: here first)
+    return download_cloud(b->eng, (slot == CVO_SLOT_FIXED ? b->fixed[p] : b->moving[p]).get(), xyz, feat, cap, n);
+}
+int cvo_batch_get_selected_points(cvo_batch b, int p, int slot, unsigned short* px, int cap, int* n) {
+    if (!b || !n || p < 0 || p >= b->max_pairs || (slot != CVO_SLOT_FIXED && slot != CVO_SLOT_MOVING)) return fail(CVO_ERR_INVALID, "bad argument");
+    return download_selected_points(b->eng, (slot == CVO_SLOT_FIXED ? b->fixed[p] : b->moving[p]).get(), px, cap, n);
+}
+
 int cvo_host_register(void* ptr, size_t bytes) {
     if (!ptr || bytes == 0) return fail(CVO_ERR_INVALID, "bad argument");
     const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);

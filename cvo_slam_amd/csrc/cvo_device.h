@@ -187,6 +187,25 @@ struct PackDesc {
                                   // handed over in caller-registered memory (cvo_host_register), whose two arrays lie where the caller has them
 };
 
+// the batched point-cloud generator (cvo_batch_set_pairs_images): one record per image, zeroed before the select pass, read back by the host
+// after the cloud kernel -- the decisions the single-frame path takes on the host (Engine::generate_pcd) stay on the device in between
+struct PcdImgRec {
+    int sel1[4];                  // n2, n3, n4 of the select pass at potential 3
+    int sel2[4];                  // the same for the re-selection
+    int pot2;                     // potential of the re-selection, 0 = none (PixelSelector::makeMaps' decision, pcd_decide_kernel)
+    int npts;                     // points of the cloud (kept pixels with a valid depth)
+    int cost_n, pad_;             // points sampled for cost
+    double cost;                  // sum of 1/z^2 over every 16th point with z > 1e-3 (Cloud::cost_hint = cost / cost_n)
+    double pad2_;
+};
+static_assert(sizeof(PcdImgRec) == 64, "PcdImgRec layout");
+// pairs' clouds from their images' slots (pcd_scatter_kernel), by value: up to PCD_SCATTER_MAX clouds per launch
+constexpr int PCD_SCATTER_MAX = 32;
+struct PcdScatter {
+    const float* src; const uint16_t* src_px; const PcdImgRec* rec; int cap, n;
+    int img[PCD_SCATTER_MAX]; float* dst[PCD_SCATTER_MAX]; uint16_t* dst_px[PCD_SCATTER_MAX];
+};
+
 // a score block: up to 8 inner-product / Hessian requests evaluated by one launch
 constexpr int SCORE_MAXREQ = 8;
 struct ScoreBatch {

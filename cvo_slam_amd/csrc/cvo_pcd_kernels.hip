@@ -11,8 +11,12 @@
 // direction table is read but unused, setting_selectDirectionDistribution = false), so 16
 // lanes share one 4pot x 4pot block.  The cloud is written straight into the two float4
 // planes the alignment kernels read: no host round trip for the points.
+// Batches of images (cvo_batch_set_pairs_images): every kernel takes the image as blockIdx.y, each image's buffers lying at a fixed
+// stride behind the first one's (the single-frame path is image 0 of a grid one image high); makeMaps' decisions run on the device
+// (pcd_decide_kernel, and the sub-sampling kernel derives its own threshold), so a batch is a fixed list of launches and one host sync.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include "cvo_device.h"
 
 namespace cvohip {
@@ -21,14 +25,17 @@ namespace cvohip {
 __global__ void pcd_gray_kernel(const uint8_t* __restrict__ bgr, float* __restrict__ I0, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    bgr += 3 * (size_t)n * blockIdx.y; I0 += (size_t)n * blockIdx.y;
     const int c0 = bgr[3 * (size_t)i], c1 = bgr[3 * (size_t)i + 1], c2 = bgr[3 * (size_t)i + 2];
     I0[i] = (float)((c0 * 4899 + c1 * 9617 + c2 * 1868 + (1 << 13)) >> 14);
 }
 
 // ---- make_pyramid: 2x2 box down-sampling (pcd_generator.cpp:103-118)
-__global__ void pcd_down_kernel(const float* __restrict__ P, int pw, float* __restrict__ I, int wl, int hl) {
+// (pn: elements of the parent level's plane, the stride of its images)
+__global__ void pcd_down_kernel(const float* __restrict__ P, int pw, int pn, float* __restrict__ I, int wl, int hl) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= wl * hl) return;
+    P += (size_t)pn * blockIdx.y; I += (size_t)wl * hl * blockIdx.y;
     const int x = i % wl, y = i / wl;
     const float* p = P + (size_t)2 * x + (size_t)2 * y * pw;
     I[i] = 0.25f * (p[0] + p[1] + p[pw] + p[pw + 1]);
@@ -40,6 +47,8 @@ __global__ void pcd_grad_kernel(const float* __restrict__ I, int wl, int hl, flo
                                 float* __restrict__ abs2) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= wl * hl) return;
+    const size_t o = (size_t)wl * hl * blockIdx.y;
+    I += o; abs2 += o;
     float dx = 0.f, dy = 0.f, a = 0.f;
     if (idx >= wl && idx < wl * (hl - 1)) {
         dx = 0.5f * (I[idx + 1] - I[idx - 1]);
@@ -48,7 +57,7 @@ __global__ void pcd_grad_kernel(const float* __restrict__ I, int wl, int hl, flo
         if (!__builtin_isfinite(dy)) dy = 0.f;
         a = dx * dx + dy * dy;
     }
-    if (dx_out) { dx_out[idx] = dx; dy_out[idx] = dy; }
+    if (dx_out) { dx_out[o + idx] = dx; dy_out[o + idx] = dy; }
     abs2[idx] = a;
 }
 
@@ -56,6 +65,7 @@ __global__ void pcd_grad_kernel(const float* __restrict__ I, int wl, int hl, flo
 __global__ __launch_bounds__(256) void pcd_hist_kernel(const float* __restrict__ abs0, int w, int h, int w32, float* __restrict__ ths) {
     __shared__ int hist[100];
     const int tid = threadIdx.x, bx = blockIdx.x % w32, by = blockIdx.x / w32;
+    abs0 += (size_t)w * h * blockIdx.y; ths += (size_t)(w32 * (h / 32) + 100) * blockIdx.y;   // (+100: the zeroed slack, pcd_smooth_kernel)
     if (tid < 100) hist[tid] = 0;
     __syncthreads();
     for (int k = tid; k < 1024; k += 256) {
@@ -77,6 +87,7 @@ __global__ __launch_bounds__(256) void pcd_hist_kernel(const float* __restrict__
 __global__ void pcd_smooth_kernel(const float* __restrict__ ths, int w32, int h32, float* __restrict__ ths_smoothed) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= w32 * h32) return;
+    ths += (size_t)(w32 * h32 + 100) * blockIdx.y; ths_smoothed += (size_t)(w32 * h32 + 100) * blockIdx.y;
     const int x = i % w32, y = i / w32;
     float sum = 0.f, num = 0.f;
     for (int dy = -1; dy <= 1; ++dy)
@@ -97,10 +108,17 @@ __global__ void pcd_smooth_kernel(const float* __restrict__ ths, int w32, int h3
 // (In the reference a level-0 hit sets bestIdx3 = bestIdx4 = -2 for good and a level-1 hit sets bestIdx4 = -2 for good: whatever
 // was found at the coarser levels before is dropped, and nothing is looked for after.)
 // map: 0 / 1 / 2 / 4 per pixel (pre-zeroed); counts[0..2] += n2, n3, n4.
+// Batches: image blockIdx.y counts at counts + cstride * image; pot_img (not null: the re-selection pass) gives each image's potential at the
+// same stride, 0 = the image keeps its first selection, and the grid is sized for the smallest potential -- workgroups past an image's blocks leave.
 __global__ __launch_bounds__(256) void pcd_select_kernel(const float* __restrict__ abs0, const float* __restrict__ abs1, const float* __restrict__ abs2,
-                                                         const float* __restrict__ ths_smoothed, int w, int h, int pot, uint8_t* __restrict__ map,
-                                                         int* __restrict__ counts) {
+                                                         const float* __restrict__ ths_smoothed, int w, int h, int pot, const int* __restrict__ pot_img,
+                                                         uint8_t* __restrict__ map, int* __restrict__ counts, int cstride) {
+    const int img = blockIdx.y;
+    if (pot_img) { pot = pot_img[(size_t)cstride * img]; if (pot <= 0) return; }
     const int nbx = (w + 4 * pot - 1) / (4 * pot), nby = (h + 4 * pot - 1) / (4 * pot);
+    if ((int)((blockIdx.x * blockDim.x) >> 4) >= nbx * nby) return;    // (uniform: the whole workgroup)
+    abs0 += (size_t)w * h * img; abs1 += (size_t)(w / 2) * (h / 2) * img; abs2 += (size_t)(w / 4) * (h / 4) * img;
+    ths_smoothed += (size_t)((w / 32) * (h / 32) + 100) * img; map += (size_t)w * h * img; counts += (size_t)cstride * img;
     const int gt = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = gt >> 4, sub = gt & 15, lane = threadIdx.x & 63;
     const int b3 = sub >> 2, c2 = sub & 3;                            // 2pot block inside the 4pot block, cell inside the 2pot block
@@ -153,6 +171,44 @@ __global__ __launch_bounds__(256) void pcd_select_kernel(const float* __restrict
     if (lane == 0) { atomicAdd(&counts[0], n2); atomicAdd(&counts[1], n3); atomicAdd(&counts[2], n4); }
 }
 
+// ---- makeMaps' potential / re-selection state machine (PixelSelector2.cpp:186-229), a fresh selector per frame as in Engine::generate_pcd:
+// the first pass ran at potential 3 with one re-selection allowed.  One thread per image; f32 arithmetic exactly as the host writes it
+// (-ffp-contract=off, IEEE division and square root: num_have == 0 gives quotia = inf and a re-selection at potential 1).
+__global__ void pcd_decide_kernel(PcdImgRec* __restrict__ rec, int n_img, int num_want) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_img) return;
+    const int pot = 3;
+    const float num_want_f = (float)num_want;
+    const float num_have = (float)(rec[i].sel1[0] + rec[i].sel1[1] + rec[i].sel1[2]);   // :191
+    const float quotia = num_want_f / num_have;                     // :192
+    const float K = num_have * (pot + 1) * (pot + 1);               // :195
+    int ideal = (int)(sqrtf(K / num_want_f) - 1);                   // :196
+    if (ideal < 1) ideal = 1;
+    int pot2 = 0;
+    if (quotia > 1.25 && pot > 1) {                                 // :199-213
+        if (ideal >= pot) ideal = pot - 1;
+        pot2 = ideal;
+    } else if (quotia < 0.25) {                                     // :214-229
+        if (ideal <= pot) ideal = pot + 1;
+        pot2 = ideal;
+    }
+    rec[i].pot2 = pot2;
+}
+// an image that re-selects starts from an empty map again
+__global__ void pcd_reclear_kernel(uint8_t* __restrict__ map, int n, const PcdImgRec* __restrict__ rec) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || rec[blockIdx.y].pot2 == 0) return;
+    map[(size_t)n * blockIdx.y + i] = 0;
+}
+// the sub-sampling of the last selection (:252-268), from its counts
+__device__ __forceinline__ void pcd_subsample_rule(const PcdImgRec& r, int num_want, int& subsample, int& char_th) {
+    const int* c = r.pot2 ? r.sel2 : r.sel1;
+    const float num_have = (float)(c[0] + c[1] + c[2]);
+    const float quotia = (float)num_want / num_have;
+    subsample = (quotia < 0.95) ? 1 : 0;
+    char_th = subsample ? (int)(unsigned char)(255 * quotia) : 255;
+}
+
 // ---- makeMaps sub-sampling (PixelSelector2.cpp:252-268) + get_points_from_pixels' filter (pcd_generator.cpp:471), order
 // preserving and coalesced: a workgroup owns a tile of PCD_TILE consecutive pixels, its waves take 64 consecutive pixels at a
 // time (ballot + popcount give every marked pixel its rank), tiles are chained by per-tile counts (a tile adds up the counts
@@ -165,6 +221,7 @@ constexpr int PCD_TILE = 4096;
 constexpr int PCD_TILE_THREADS = 256;
 
 struct PcdCam { float scaling_factor, fx, fy, cx, cy; };
+
 
 // exclusive prefix of `flag` over the workgroup's current 256 pixels, in pixel order; `run` carries on across chunks
 __device__ __forceinline__ int chunk_rank(bool flag, int* wsum, int& run) {
@@ -193,9 +250,11 @@ __device__ __forceinline__ int tiles_before(const int* counts, int tile, int* ld
     return s;
 }
 
+// (batches: image blockIdx.y's tile counts at 3 * tiles * image, its map and depth image at w * h * image)
 __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_count_marked_kernel(const uint8_t* __restrict__ map, int n, int* __restrict__ tile_marked) {
     __shared__ int wsum[PCD_TILE_THREADS / 64];
-    const int base = blockIdx.x * PCD_TILE;
+    const int base = blockIdx.x * PCD_TILE, nt = (n + PCD_TILE - 1) / PCD_TILE;
+    map += (size_t)n * blockIdx.y; tile_marked += (size_t)3 * nt * blockIdx.y;
     int cnt = 0;
     for (int k = threadIdx.x; k < PCD_TILE; k += PCD_TILE_THREADS) { const int i = base + k; cnt += (i < n && map[i] != 0) ? 1 : 0; }
 #pragma unroll
@@ -205,11 +264,16 @@ __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_count_marked_kernel(cons
     if (threadIdx.x == 0) { int s = 0; for (int k = 0; k < PCD_TILE_THREADS / 64; ++k) s += wsum[k]; tile_marked[blockIdx.x] = s; }
 }
 
+// rec (not null, batches): each image's subsample / char_th follow from its own counts, and the arguments are ignored
 __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_subsample_kernel(uint8_t* __restrict__ map, const uint8_t* __restrict__ pattern, int subsample, int char_th,
+                                                                         const PcdImgRec* __restrict__ rec, int num_want,
                                                                          const uint16_t* __restrict__ depth, int n, const int* __restrict__ tile_marked,
                                                                          int* __restrict__ tile_valid, int* __restrict__ tile_kept) {
     __shared__ int wsum[PCD_TILE_THREADS / 64];
-    const int base = blockIdx.x * PCD_TILE;
+    const int base = blockIdx.x * PCD_TILE, nt = (n + PCD_TILE - 1) / PCD_TILE, img = blockIdx.y;
+    if (rec) pcd_subsample_rule(rec[img], num_want, subsample, char_th);
+    const size_t to = (size_t)3 * nt * img;
+    map += (size_t)n * img; depth += (size_t)n * img; tile_marked += to; tile_valid += to; tile_kept += to;
     int run = tiles_before(tile_marked, blockIdx.x, wsum);            // marked pixels in front of this tile = index into the byte pattern
     int valid = 0, kept = 0;
     for (int k0 = 0; k0 < PCD_TILE; k0 += PCD_TILE_THREADS) {
@@ -234,12 +298,23 @@ __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_subsample_kernel(uint8_t
     }
 }
 
+// rec (not null, batches): the point count comes from the image's tile counts (and goes to rec), the cloud to the image's slot of `cap`
+// points (a count above cap writes nothing: the host refuses the call), and the points sampled for Cloud::cost_hint add up in rec
 __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_cloud_kernel(const uint8_t* __restrict__ map, const uint16_t* __restrict__ depth, const uint8_t* __restrict__ bgr,
                                                                      const float* __restrict__ dx0, const float* __restrict__ dy0, int w, int n, PcdCam cam,
                                                                      const int* __restrict__ tile_valid, int n_points, float* __restrict__ cloud,
-                                                                     uint16_t* __restrict__ px) {
+                                                                     uint16_t* __restrict__ px, PcdImgRec* __restrict__ rec, int cap) {
     __shared__ int wsum[PCD_TILE_THREADS / 64];
-    const int base = blockIdx.x * PCD_TILE;
+    const int base = blockIdx.x * PCD_TILE, nt = (n + PCD_TILE - 1) / PCD_TILE, img = blockIdx.y;
+    map += (size_t)n * img; depth += (size_t)n * img; bgr += (size_t)3 * n * img; dx0 += (size_t)n * img; dy0 += (size_t)n * img;
+    tile_valid += (size_t)3 * nt * img;
+    if (rec) {
+        n_points = tiles_before(tile_valid, nt, wsum);
+        if (blockIdx.x == 0 && threadIdx.x == 0) rec[img].npts = n_points;
+        if (n_points > cap) return;                                   // (uniform)
+        cloud += (size_t)cap * REC * img; px += (size_t)cap * 2 * img;
+    }
+    double cost = 0.0; int cost_n = 0;
     int run = tiles_before(tile_valid, blockIdx.x, wsum);
     for (int k0 = 0; k0 < PCD_TILE; k0 += PCD_TILE_THREADS) {
         const int i = base + k0 + threadIdx.x;
@@ -256,8 +331,25 @@ __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_cloud_kernel(const uint8
             hi[0] = (float)bgr[3 * (size_t)i + 1]; hi[1] = (float)bgr[3 * (size_t)i + 2];        // G, R
             hi[2] = dx0[i]; hi[3] = dy0[i];                                                      // :608-609
             px[2 * at] = (uint16_t)x; px[2 * at + 1] = (uint16_t)y;
+            if (rec && (at & 15) == 0 && p2 > 1e-3f) { cost += 1.0 / ((double)p2 * p2); ++cost_n; }   // Engine::upload_many's sample
         }
     }
+    if (rec) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { cost += __shfl_xor(cost, off, 64); cost_n += __shfl_xor(cost_n, off, 64); }
+        if ((threadIdx.x & 63) == 0 && cost_n > 0) { atomicAdd(&rec[img].cost, cost); atomicAdd(&rec[img].cost_n, cost_n); }
+    }
+}
+
+// each pair's cloud of a batch from its image's slot: two planes of n float4 and n pixel pairs, one workgroup row (grid.y) per cloud
+__global__ __launch_bounds__(256) void pcd_scatter_kernel(PcdScatter S) {
+    const int k = blockIdx.y, im = S.img[k], np = S.rec[im].npts;
+    if (np > S.cap) return;
+    const float4* src = reinterpret_cast<const float4*>(S.src + (size_t)S.cap * REC * im);
+    const unsigned* spx = reinterpret_cast<const unsigned*>(S.src_px + (size_t)S.cap * 2 * im);
+    float4* dst = reinterpret_cast<float4*>(S.dst[k]); unsigned* dpx = reinterpret_cast<unsigned*>(S.dst_px[k]);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * np; i += gridDim.x * 256) dst[i] = src[i];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < np; i += gridDim.x * 256) dpx[i] = spx[i];
 }
 
 // cloud planes back to the reference layout (tests, get_*_selected_points callers)
@@ -298,29 +390,48 @@ hipError_t launch_pack_clouds(const float* raw, const PackDesc* descs, int n_clo
 // ------------------------------------------------------------------------------------------------ host-side launchers
 #define PCD_LAUNCH_1D(kernel, n, stream, ...) hipLaunchKernelGGL(kernel, dim3(((n) + 255) / 256), dim3(256), 0, stream, __VA_ARGS__)
 
+// n_img images one behind the other in every buffer (the strides of the kernels above); the single-frame path passes 1
+#define PCD_LAUNCH_2D(kernel, n, n_img, stream, ...) hipLaunchKernelGGL(kernel, dim3(((n) + 255) / 256, (n_img)), dim3(256), 0, stream, __VA_ARGS__)
+
 hipError_t pcd_launch_pyramid(const uint8_t* bgr, int w, int h, float* I0, float* I1, float* I2, float* dx0, float* dy0, float* abs0, float* abs1, float* abs2,
-                              hipStream_t s) {
+                              int n_img, hipStream_t s) {
     const int w1 = w / 2, h1 = h / 2, w2 = w1 / 2, h2 = h1 / 2;
-    PCD_LAUNCH_1D(pcd_gray_kernel, w * h, s, bgr, I0, w * h);
-    PCD_LAUNCH_1D(pcd_grad_kernel, w * h, s, I0, w, h, dx0, dy0, abs0);
-    PCD_LAUNCH_1D(pcd_down_kernel, w1 * h1, s, I0, w, I1, w1, h1);
-    PCD_LAUNCH_1D(pcd_grad_kernel, w1 * h1, s, I1, w1, h1, (float*)nullptr, (float*)nullptr, abs1);
-    PCD_LAUNCH_1D(pcd_down_kernel, w2 * h2, s, I1, w1, I2, w2, h2);
-    PCD_LAUNCH_1D(pcd_grad_kernel, w2 * h2, s, I2, w2, h2, (float*)nullptr, (float*)nullptr, abs2);
+    PCD_LAUNCH_2D(pcd_gray_kernel, w * h, n_img, s, bgr, I0, w * h);
+    PCD_LAUNCH_2D(pcd_grad_kernel, w * h, n_img, s, I0, w, h, dx0, dy0, abs0);
+    PCD_LAUNCH_2D(pcd_down_kernel, w1 * h1, n_img, s, I0, w, w * h, I1, w1, h1);
+    PCD_LAUNCH_2D(pcd_grad_kernel, w1 * h1, n_img, s, I1, w1, h1, (float*)nullptr, (float*)nullptr, abs1);
+    PCD_LAUNCH_2D(pcd_down_kernel, w2 * h2, n_img, s, I1, w1, w1 * h1, I2, w2, h2);
+    PCD_LAUNCH_2D(pcd_grad_kernel, w2 * h2, n_img, s, I2, w2, h2, (float*)nullptr, (float*)nullptr, abs2);
     return hipGetLastError();
 }
-hipError_t pcd_launch_thresholds(const float* abs0, int w, int h, float* ths, float* ths_smoothed, hipStream_t s) {
+// ths / ths_smoothed: w/32 * h/32 + 100 floats per image, the slack zeroed
+hipError_t pcd_launch_thresholds(const float* abs0, int w, int h, float* ths, float* ths_smoothed, int n_img, hipStream_t s) {
     const int w32 = w / 32, h32 = h / 32;
     if (w32 * h32 > 0) {
-        hipLaunchKernelGGL(pcd_hist_kernel, dim3(w32 * h32), dim3(256), 0, s, abs0, w, h, w32, ths);
-        PCD_LAUNCH_1D(pcd_smooth_kernel, w32 * h32, s, ths, w32, h32, ths_smoothed);
+        hipLaunchKernelGGL(pcd_hist_kernel, dim3(w32 * h32, n_img), dim3(256), 0, s, abs0, w, h, w32, ths);
+        PCD_LAUNCH_2D(pcd_smooth_kernel, w32 * h32, n_img, s, ths, w32, h32, ths_smoothed);
     }
     return hipGetLastError();
 }
 hipError_t pcd_launch_select(const float* abs0, const float* abs1, const float* abs2, const float* ths_smoothed, int w, int h, int pot, uint8_t* map, int* counts,
                              hipStream_t s) {
     const int nb = ((w + 4 * pot - 1) / (4 * pot)) * ((h + 4 * pot - 1) / (4 * pot));
-    hipLaunchKernelGGL(pcd_select_kernel, dim3((nb * 16 + 255) / 256), dim3(256), 0, s, abs0, abs1, abs2, ths_smoothed, w, h, pot, map, counts);
+    hipLaunchKernelGGL(pcd_select_kernel, dim3((nb * 16 + 255) / 256), dim3(256), 0, s, abs0, abs1, abs2, ths_smoothed, w, h, pot, (const int*)nullptr, map, counts, 0);
+    return hipGetLastError();
+}
+// makeMaps for n_img images on the device (rec zeroed, map zeroed): the pass at potential 3, each image's decision, the re-selection of the
+// images that ask for one -- its grid sized for potential 1, the smallest a re-selection can take
+hipError_t pcd_launch_select_batch(const float* abs0, const float* abs1, const float* abs2, const float* ths_smoothed, int w, int h, uint8_t* map, PcdImgRec* rec,
+                                   int n_img, int num_want, hipStream_t s) {
+    constexpr int RS = (int)(sizeof(PcdImgRec) / sizeof(int));
+    int* r = reinterpret_cast<int*>(rec);
+    const int nb3 = ((w + 11) / 12) * ((h + 11) / 12), nb1 = ((w + 3) / 4) * ((h + 3) / 4);
+    hipLaunchKernelGGL(pcd_select_kernel, dim3((nb3 * 16 + 255) / 256, n_img), dim3(256), 0, s, abs0, abs1, abs2, ths_smoothed, w, h, 3, (const int*)nullptr, map,
+                       r + offsetof(PcdImgRec, sel1) / sizeof(int), RS);
+    PCD_LAUNCH_1D(pcd_decide_kernel, n_img, s, rec, n_img, num_want);
+    PCD_LAUNCH_2D(pcd_reclear_kernel, w * h, n_img, s, map, w * h, (const PcdImgRec*)rec);
+    hipLaunchKernelGGL(pcd_select_kernel, dim3((nb1 * 16 + 255) / 256, n_img), dim3(256), 0, s, abs0, abs1, abs2, ths_smoothed, w, h, 0,
+                       (const int*)(r + offsetof(PcdImgRec, pot2) / sizeof(int)), map, r + offsetof(PcdImgRec, sel2) / sizeof(int), RS);
     return hipGetLastError();
 }
 int pcd_tiles(int w, int h) { return (w * h + PCD_TILE - 1) / PCD_TILE; }
@@ -328,15 +439,37 @@ int pcd_tiles(int w, int h) { return (w * h + PCD_TILE - 1) / PCD_TILE; }
 hipError_t pcd_launch_subsample(uint8_t* map, const uint8_t* pattern, int subsample, int char_th, const uint16_t* depth, int w, int h, int* tile_counts, hipStream_t s) {
     const int nt = pcd_tiles(w, h);
     hipLaunchKernelGGL(pcd_count_marked_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, w * h, tile_counts);
-    hipLaunchKernelGGL(pcd_subsample_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, pattern, subsample, char_th, depth, w * h, tile_counts, tile_counts + nt,
-                       tile_counts + 2 * nt);
+    hipLaunchKernelGGL(pcd_subsample_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, pattern, subsample, char_th, (const PcdImgRec*)nullptr, 0, depth, w * h,
+                       tile_counts, tile_counts + nt, tile_counts + 2 * nt);
+    return hipGetLastError();
+}
+// tile_counts: 3 * pcd_tiles() ints per image; each image's sub-sampling follows from its counts in rec
+hipError_t pcd_launch_subsample_batch(uint8_t* map, const uint8_t* pattern, const PcdImgRec* rec, int num_want, const uint16_t* depth, int w, int h, int* tile_counts,
+                                      int n_img, hipStream_t s) {
+    const int nt = pcd_tiles(w, h);
+    hipLaunchKernelGGL(pcd_count_marked_kernel, dim3(nt, n_img), dim3(PCD_TILE_THREADS), 0, s, map, w * h, tile_counts);
+    hipLaunchKernelGGL(pcd_subsample_kernel, dim3(nt, n_img), dim3(PCD_TILE_THREADS), 0, s, map, pattern, 0, 255, rec, num_want, depth, w * h,
+                       tile_counts, tile_counts + nt, tile_counts + 2 * nt);
     return hipGetLastError();
 }
 hipError_t pcd_launch_cloud(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
                             const int* tile_counts, int n_points, float* cloud, uint16_t* px, hipStream_t s) {
     const int nt = pcd_tiles(w, h);
     PcdCam c{cam[0], cam[1], cam[2], cam[3], cam[4]};
-    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, tile_counts + nt, n_points, cloud, px);
+    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, tile_counts + nt, n_points, cloud, px,
+                       (PcdImgRec*)nullptr, 0);
+    return hipGetLastError();
+}
+// every image's cloud into its slot of `cap` points (cap * REC floats, cap * 2 pixel coordinates); counts and cost samples into rec
+hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
+                                  const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s) {
+    const int nt = pcd_tiles(w, h);
+    PcdCam c{cam[0], cam[1], cam[2], cam[3], cam[4]};
+    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt, n_img), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, tile_counts + nt, 0, cloud, px, rec, cap);
+    return hipGetLastError();
+}
+hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s) {
+    if (S.n > 0 && n_max > 0) hipLaunchKernelGGL(pcd_scatter_kernel, dim3(min(64, (2 * n_max + 255) / 256), S.n), dim3(256), 0, s, S);
     return hipGetLastError();
 }
 hipError_t pcd_launch_unpack(const float* cloud, int n, float* xyz, float* feat, hipStream_t s) {

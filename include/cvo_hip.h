@@ -307,6 +307,23 @@ int cvo_host_register(void* ptr, size_t bytes);
 int cvo_host_unregister(void* ptr);
 int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* fixed_xyz, const float* const* fixed_feat, const int* n_fixed,
                         const float* const* moving_xyz, const float* const* moving_feat, const int* n_moving);
+/* Pairs first .. first+count-1 from RGB-D images (the loop-closure batch of keyframe_graph.cpp:693-700 without a host round trip):
+ * n_images distinct frames, all width x height, one camera, bgr8[i] (h x w x 3 bytes) and depth16[i] (h x w) each; every image is
+ * generated ONCE on the GPU exactly as cvo_set_pcd_images would (pcd_generator + PixelSelector, the batch's num_want), all images by
+ * one fixed list of launches with one host sync; pair k takes image fixed_image[k] as its fixed cloud and moving_image[k] as its moving
+ * cloud (a reference frame shared by all candidates is listed once).  Fresh-object state like cvo_batch_set_pair (R = I, T = 0,
+ * ell = params.ell); cvo_batch_set_state afterwards for reset_initial.  The images may be reused when the call returns.
+ * points_out (n_images ints, may be NULL): the points of each generated cloud.  A bad index, a null pointer, a size below 64 or a
+ * cloud above 65535 points fail with CVO_ERR_INVALID and no pair changes; an image that yields no points gives an empty cloud (the
+ * align result of its pairs carries CVO_ERR_EMPTY_CLOUD).  Pairs outside the range keep their clouds. */
+int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out);
+/* pcd_generator::num_want (3000, pcd_generator.cpp:22) of this batch's later cvo_batch_set_pairs_images calls */
+int cvo_batch_set_num_want(cvo_batch b, int num_want);
+/* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
+ * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
+int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
+int cvo_batch_get_selected_points(cvo_batch b, int p, int slot, unsigned short* px, int cap, int* n);
 /* warm start / carried ell for pair p (reset_initial + Q1) */
 int cvo_batch_set_state(cvo_batch b, int p, const float R[9], const float T[3], float ell);
 int cvo_batch_set_workgroups(cvo_batch b, int workgroups_per_pair /* 0 = auto: fill the CUs */);
