@@ -58,58 +58,26 @@ namespace CVO_KNS { using namespace cvohip; }
 namespace CVO_KNS {
 
 // phase timers (PairState::phase_ticks): a read of the 100 MHz clock is a scalar memory instruction every wave waits for
-#ifdef CVO_NO_TIMERS
-#define CVO_NOW() 0ull
-#else
 #define CVO_NOW() __builtin_amdgcn_s_memrealtime()
-#endif
 
-#ifndef CVO_WAVES_PER_SIMD
-#define CVO_WAVES_PER_SIMD 2      // 2: 256 VGPRs, one 512-thread workgroup per CU (measured faster); 4: 128 VGPRs, two per CU
-#endif
 #ifndef CVO_BLOCK_MAX
 #define CVO_BLOCK_MAX 512         // threads of the largest workgroup: 512 = 2 waves per SIMD with 256 VGPRs each.  (1024 = 4 waves per SIMD with 128 each
 #endif                            //  is an experiment knob: measured, no phase gets faster -- DESIGN.md "Measured in round 2")
 constexpr int BLOCK_MAX = CVO_BLOCK_MAX;
-// Phases are functions of their own (own register allocation).  CVO_INLINE_PHASES: a bit mask of phases compiled INTO run_pair instead (experiment builds):
-// 1 line search, 2 epilogue, 4 transform (all three measured: run_pair then spills around its remaining calls), 8 below -- a call costs the callee-saved
-// saves and, at its return, a wait for their reloads from scratch
-#ifndef CVO_INLINE_PHASES
+// Phases are functions of their own (own register allocation); a call costs the callee-saved saves and, at its return, a wait for their reloads from scratch.
+// The two-wave build compiles the candidate walk, line search and epilogue into ONE function, phase_iteration (one call per iteration instead of three:
+// +1.2 % in the long run, -2.2 % on one pair's latency, profiles/r05_one_call_per_iteration_ab.txt).  The three-wave build (168 registers) keeps them
+// apart: the merged function spills inside its loops.
 #if CVO_BLOCK_MAX > 512
-#define CVO_INLINE_PHASES 0       // the three-wave build (168 registers): the merged function spills inside its loops
+#define CVO_ITERATION_PHASE static __device__ __attribute__((noinline))
 #else
-#define CVO_INLINE_PHASES 8       // measured: +1.2 % in the long run, -2.2 % on one pair's latency (profiles/r05_one_call_per_iteration_ab.txt)
-#endif
-#endif
-#define CVO_PHASE_FN(bit) static __device__ __attribute__((CVO_PHASE_ATTR_##bit))
-#if CVO_INLINE_PHASES & 8     // 8: candidate walk + line search + epilogue compiled into ONE function, phase_iteration (one call per iteration instead of three)
-#define CVO_PHASE_ATTR_8 always_inline
-#else
-#define CVO_PHASE_ATTR_8 noinline
-#endif
-#if CVO_INLINE_PHASES & (1 | 8)
-#define CVO_PHASE_ATTR_1 always_inline
-#else
-#define CVO_PHASE_ATTR_1 noinline
-#endif
-#if CVO_INLINE_PHASES & (2 | 8)
-#define CVO_PHASE_ATTR_2 always_inline
-#else
-#define CVO_PHASE_ATTR_2 noinline
-#endif
-#if CVO_INLINE_PHASES & 4
-#define CVO_PHASE_ATTR_4 always_inline
-#else
-#define CVO_PHASE_ATTR_4 noinline
+#define CVO_ITERATION_PHASE static __device__ __attribute__((always_inline))
 #endif
 constexpr int MAX_WAVES = BLOCK_MAX / 64;
 constexpr unsigned ADOPT_FREE = 0u, ADOPT_REQUEST = 1u, ADOPT_ACCEPT = 2u, ADOPT_CLOSED = 3u, ADOPT_CONFIRMED = 4u;   // states of a pair's adoption word (cvo_align_kernel)
 constexpr unsigned long long ADOPT_CONFIRM_TICKS = 5000ull;   // 50 us at 100 MHz: how long an owner waits for an accepted helper to confirm before it takes the acceptance back
 constexpr unsigned long long ADOPT_HELPER_WAIT_TICKS = 50000ull;   // 500 us: how long a helper launched with the pairs waits for its first pair to take an offer (adopt_search)
-#ifndef CVO_ADOPT_GMAX
-#define CVO_ADOPT_GMAX 4
-#endif
-constexpr int ADOPT_GMAX = CVO_ADOPT_GMAX;                                    // workgroups a pair can grow to by adoption (the host sizes the exchange area and the buffers' slack for it)
+constexpr int ADOPT_GMAX = 4;                                                 // workgroups a pair can grow to by adoption (the host sizes the exchange area and the buffers' slack for it)
 constexpr float SKIN_DENSE_SCENE = 0.25f;   // list radius margin a pair falls back to when the lists of the launch's margin overflow (round 2's value)
 constexpr float FAR_ROW = 3.0e18f;    // coordinates of padding rows / columns: d2 overflows, never < threshold
 constexpr float FAR_COL = -3.0e18f;
@@ -182,7 +150,6 @@ struct __attribute__((aligned(16))) Shared {
     unsigned long long nnz_total;   // nonzeros of A so far (PairState::nonzeros_total)
 #ifdef CVO_KTRACE
     unsigned long long ksub[4];  // experiment builds: line-search walk, line-search reduction, epilogue scalar part, epilogue transform (ticks, this iteration)
-    unsigned long long kabs[16];  // CVO_KTRACE_EPI == 2: absolute times inside the epilogue (lane 0: part A done, part B done, staleness maximum there, decision made; thread 64: past the first barrier, its points done)
 #endif
     float omega[3];        // this iteration's twist (f32, cvo.cpp:234-235)
     float v[3];
@@ -224,48 +191,17 @@ __device__ __forceinline__ float4 ld4(const gfloat* p) { const v4f t = *reinterp
 //  * nonzero records (written by the candidate walk, read by the line search tens of microseconds later), the cull's raw lists (written, then read once by
 //    the first pass) and the in-place refinement: plain -- streaming them loses 2 ... 8 % (they are re-read soon enough to hit).
 // profiles/r03_cache_policy_ab.txt, r03_entry_stores_ab.txt, r03_raw_list_and_refine_policy_ab.txt, r03_eth3d_entries_nt_ab.txt, r03_masked_entry_loads_ab.txt.
-// -DCVO_NT_REC / _LD / _ST, -DCVO_NT_JT, -DCVO_NT_REFINE, -DCVO_PLAIN_ENT_LD, -DCVO_PLAIN_ENT_ST build the alternatives.
 // Entries of a list in slot order: entry n of slot s is ent[2 * ((n >> 1) * rows_pad + s) + (n & 1)] -- two consecutive entries of a row are neighbours, so the
 // steady walk fetches its four entries per step with two 16-byte loads per lane (the vector memory pipe is as busy as the VALU in that walk: four loads and
 // up to four record stores per step; see DESIGN.md, "Measured in round 3").  ent_ix(n, rows_pad) is the offset from the slot's base ent + 2 * s.
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef CVO_GLOBAL v4u gv4u;
 __device__ __forceinline__ size_t ent_ix(int n, size_t rows_pad) { return (size_t)(n >> 1) * rows_pad * 2 + (size_t)(n & 1); }
-// the in-place filter of the lists after an ell drop (refine_lists): -DCVO_NT_REFINE streams its reads and writes
-__device__ __forceinline__ v2u ld_rf(const gv2u* p) {
-#ifdef CVO_NT_REFINE
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-__device__ __forceinline__ void st_rf(gv2u* p, const v2u v) {
-#ifdef CVO_NT_REFINE
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-// the cull's raw lists are written once and read once (by the first candidate pass after the cull): -DCVO_NT_JT marks both as streams
-__device__ __forceinline__ void st_jt(gv2u* p, const v2u v) {
-#ifdef CVO_NT_JT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ v2u ld_jt(const gv2u* p) {
-#ifdef CVO_NT_JT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-#ifdef CVO_PLAIN_ENT_LD
-#define ENT_NT(YM) false
-#else
-#define ENT_NT(YM) true      // every layout: +2 % at 3 k points, +3.5 % at 9 k (profiles/r03_cache_policy_ab.txt, r03_eth3d_entries_nt_ab.txt)
-#endif
+// the in-place filter of the lists after an ell drop (refine_lists)
+__device__ __forceinline__ v2u ld_rf(const gv2u* p) { return *p; }
+__device__ __forceinline__ void st_rf(gv2u* p, const v2u v) { *p = v; }
+// the cull's raw lists are written once and read once (by the first candidate pass after the cull)
+__device__ __forceinline__ void st_jt(gv2u* p, const v2u v) { *p = v; }
 template <bool NT>
 __device__ __forceinline__ v4u ld_ent2(const gv4u* p) {
     if (NT) return __builtin_nontemporal_load(p);
@@ -276,31 +212,15 @@ __device__ __forceinline__ v4u ld_ent2(const gv4u* p) {
 typedef CVO_GLOBAL char gchar;
 template <typename T>
 __device__ __forceinline__ T* at_off(T* base, unsigned index) {
-#ifdef CVO_ADDR64
-    return base + index;
-#else
     return reinterpret_cast<T*>(reinterpret_cast<gchar*>(const_cast<typename std::remove_const<T>::type*>(base)) + index * (unsigned)sizeof(T));
-#endif
 }
 template <bool NT>
 __device__ __forceinline__ v2u ld_ent(const gv2u* p) {
     if (NT) return __builtin_nontemporal_load(p);
     return *p;
 }
-__device__ __forceinline__ void st_rec(gv2u* p, const v2u v) {
-#if defined(CVO_NT_REC) || defined(CVO_NT_REC_ST)
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-__device__ __forceinline__ v2u ld_rec(const gv2u* p) {
-#if defined(CVO_NT_REC) || defined(CVO_NT_REC_LD)
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ void st_rec(gv2u* p, const v2u v) { *p = v; }
+__device__ __forceinline__ v2u ld_rec(const gv2u* p) { return *p; }
 
 // ---------------------------------------------------------------- reductions
 // butterfly inside the wave (every lane ends with the wave total), one LDS slot
@@ -588,6 +508,7 @@ __device__ __forceinline__ void se_kernel_values_flat(const float* xi, const flo
         a_out[u] = (pass[u] & (a > G.sp)) ? a : 0.f;
     }
 }
+// Self-test route 3 only: the walks keep the 12-term chain (this form was no faster, DESIGN.md "Measured in round 5").
 // The steady walk's k = (float)(s2 * exp(x)), x in [-0.25, 0] (Gates::poly_ok), from a SHORTER polynomial -- with a guard that makes the f32 result the one the
 // long polynomial gives.  The double is rounded to f32 right away (cvo.cpp:172), so all the f32 result needs of it is which side of a rounding boundary it
 // lies on: a degree-7 interpolant of exp on [-1/4, 0] (Chebyshev nodes, scripts/derive/exp7_coefficients.py: 1.3e-14 relative, measured on 2e6 points) times s2
@@ -763,13 +684,6 @@ __device__ __forceinline__ void ls_pair(const float (&df)[3] /* x_i - y_j, cvo.c
     const float gamma_ij = L.s_gamma * (t0.w + sum3f(t1.x * df[0], t1.y * df[1], t1.z * df[2]));  // cvo.cpp:290-291
     const float delta_ij = L.s_delta * (t1.w + sum3f(t2.x * df[0], t2.y * df[1], t2.z * df[2]));  // cvo.cpp:293-294
     const float epsil_ij = L.s_gamma * (t2.w + sum3f(t3.x * df[0], t3.y * df[1], t3.z * df[2]));  // cvo.cpp:296-297
-#ifdef CVO_LS_FULL      // the brackets operation by operation as cvo.cpp:301-305 writes them (experiment builds; the default is the condensed form below)
-    Bi += double(A_ij * beta_ij);                                                                                              // cvo.cpp:301
-    Ci += double(A_ij * (gamma_ij + beta_ij * beta_ij / 2.0));                                                                 // cvo.cpp:302
-    Di += double(A_ij * (delta_ij + beta_ij * gamma_ij + div6((double)(beta_ij * beta_ij * beta_ij))));                        // cvo.cpp:303
-    Ei += double(A_ij * (epsil_ij + beta_ij * delta_ij + 1 / 2.0 * beta_ij * beta_ij * gamma_ij                                // cvo.cpp:304-305
-                         + 1 / 2.0 * gamma_ij * gamma_ij + 1 / 24.0 * beta_ij * beta_ij * beta_ij * beta_ij));
-#else
     // The same four terms with the double-precision part of the brackets condensed (cvo.cpp:301-305).  Everything the reference rounds to FLOAT stays as
     // it is (A*beta, beta*beta, delta + beta*gamma, beta*beta*beta, epsil + beta*delta: each a float product or sum converted afterwards); what it evaluates
     // in DOUBLE -- because of the 2.0, 6.0, 24.0 literals -- is a polynomial in beta, gamma whose value these lines give to within 2-3 ulps of a double:
@@ -786,7 +700,6 @@ __device__ __forceinline__ void ls_pair(const float (&df)[3] /* x_i - y_j, cvo.c
     double e = __builtin_fma(0.5, gd * (q + gd), (double)(epsil_ij + beta_ij * delta_ij));                                     // cvo.cpp:304-305
     e = __builtin_fma(q * q, 1.0 / 24.0, e);
     Ei = __builtin_fma(Ad, e, Ei);
-#endif
 }
 // one nonzero of A: adds its B, C, D, E terms (cvo.cpp:282-306)
 __device__ __forceinline__ void ls_terms(const float* xi, const float4 yj, float A_ij, const LsConsts& L, double& Bi, double& Ci, double& Di, double& Ei) {
@@ -805,21 +718,8 @@ __device__ __forceinline__ void ls_terms(const float* xi, const float4 yj, float
 // broadcast); a lane carries SWEEP_R rows (consecutive 64-row blocks) so one read feeds
 // SWEEP_R tests.
 constexpr int SWEEP_R = 2;
-#ifndef CVO_LS_TAB_FACTOR
-#define CVO_LS_TAB_FACTOR 4        // phase_linesearch: the per-column table is made when the workgroup has more than this many nonzeros per column
-#endif
-#ifndef CVO_LS_EVEN_MIN
-#define CVO_LS_EVEN_MIN 512        // ... when the workgroup has at least this many records per wave
-#endif
-#ifndef CVO_LS_EVEN
-#define CVO_LS_EVEN 1              // phase_linesearch: every wave an equal share of the workgroup's nonzero records (0 = the segment it compacted itself)
-#endif
-#ifndef CVO_PAIR_XMAX
-#define CVO_PAIR_XMAX 1            // phase_cull: the farthest row that bounds later list margins is the pair's, not the member's (members rebuild their lists together)
-#endif
-#ifndef CVO_CULL_SPLIT
-#define CVO_CULL_SPLIT 1           // phase_cull: single 64-row blocks as units of work when block pairs are scarce (one pair on many workgroups)
-#endif
+constexpr int LS_TAB_FACTOR = 4;   // phase_linesearch: the per-column table is made when the workgroup has more than this many nonzeros per column
+constexpr int LS_EVEN_MIN = 512;   // phase_linesearch: every wave an equal share of the workgroup's nonzero records when the workgroup has at least this many per wave
 
 template <int NR = SWEEP_R>                                    // NR = 1: the lane's first row only (phase_cull's single-block units); w[1] is left at 0
 __device__ __forceinline__ void sweep_group(const float* lx, const float* ly, const float* lz, int c0 /* wave-uniform */,
@@ -869,13 +769,11 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 // little more than half of the SIMD's issue slots.  With the wave that has more left ranked higher, the waves of a SIMD reach their (short) last blocks
 // together: the walk of one pair alone ends 5-8 % earlier (profiles/r05_wave_priority_ab.txt).  With every CU busy the gain is gone (the lone wave's
 // stalls are memory stalls then): on in the three-wave build only.  s_setprio takes an immediate.
-#ifndef CVO_WAVE_PRIO
-#define CVO_WAVE_PRIO (CVO_BLOCK_MAX > 512)   // measured: one pair alone walks 5-8 % faster either way; under load +0.6 % with three waves per SIMD (config 5), -0.7 % with two
-#endif
+// (Under load: +0.6 % with three waves per SIMD, config 5; -0.7 % with two.)
 __device__ __forceinline__ void prio_by_remaining(int r) {
-#if CVO_WAVE_PRIO
-    if (r >= 3) __builtin_amdgcn_s_setprio(3); else if (r == 2) __builtin_amdgcn_s_setprio(2); else if (r == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
+    if constexpr (BLOCK_MAX > 512) {
+        if (r >= 3) __builtin_amdgcn_s_setprio(3); else if (r == 2) __builtin_amdgcn_s_setprio(2); else if (r == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
+    }
 }
 __device__ __forceinline__ float uni_f(float v) { return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); }
 template <class T> __device__ __forceinline__ T* uni_ptr(T* p) {
@@ -929,10 +827,7 @@ __device__ __forceinline__ Lds lds_layout(int tgeo, int y_mode) {
 // one pair as seen by workgroup g of its G: the fixed cloud is cut into blocks of ROW_DEAL consecutive rows (scan order:
 // a thin slab of the image, so the cull's boxes stay tight) and the blocks are dealt round-robin (near surfaces have many
 // more neighbours per row than far ones: whole bands of the image per workgroup would be unbalanced)
-#ifndef CVO_ROW_DEAL
-#define CVO_ROW_DEAL 128
-#endif
-constexpr int ROW_DEAL = CVO_ROW_DEAL;
+constexpr int ROW_DEAL = 128;
 struct Ctx {
     const gfloat* fixed; const gfloat* moving;
     int nf, nm, nrows, rows_per, rows_pad, capn, nm_pad, flat_cap, g, G;
@@ -1015,9 +910,6 @@ __device__ __forceinline__ float4 load_y_rt(const Ctx& c, const Lds& L, int y_mo
 // built (exact displacement of the very positions the tests use); rebuild decision.  The first PRE_T points of a thread may
 // arrive pre-loaded (the epilogue of the previous iteration fetches them while one lane does the scalar work).
 constexpr int PRE_T = 4096 / BLOCK_MAX;
-#ifndef CVO_FUSE_PLANES
-#define CVO_FUSE_PLANES 1          // the epilogue's fused transform (begun before the second stop test is done, lane 0 off its critical path) also in the plane layout of large clouds
-#endif
 // first_worker = 64: wave 0 takes no points (the epilogue's lane 0 is still busy with the stop test of the iteration when the others start): the points are dealt
 // to threads first_worker .. nthreads - 1, `pre` as the caller loaded it with the same deal.  keep_M_on_stop: the transform was started before the stop test was
 // known; if the iteration turns out to be the pair's last, cvo::transform of that iteration (Shared::M, cvo.cpp:815) stays.
@@ -1081,9 +973,6 @@ __device__ __forceinline__ void transform_body_t(const Ctx& c, const Lds& L, Sha
         for (int u = 0; u < PRE_T; ++u) { if (j < c.nm) one(j, pre[u], have_preb, have_preb ? preb[u] : make_float4(0.f, 0.f, 0.f, 0.f)); j += wstride; }
     }
     for (; j < c.nm; j += wstride) one(j, ld4(c.moving + lo_off(j)), false, make_float4(0.f, 0.f, 0.f, 0.f));
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-    if (tid == 64) { __builtin_amdgcn_sched_barrier(0); sh->kabs[5] = CVO_NOW() + (dmax == 12345.f ? 1 : 0); }
-#endif
     // What lane 0's decision needs besides the maximum is in its registers before the barrier; the new transform is kept for the next phases by the first worker
     // (in Shared::Mn when lane 0's second stop test may still fire: Shared::M stays the transform of the last executed iteration then).
     float r_c = 0.f, Rb_l = 0.f, ell_b = 0.f, skin_l = 0.f, ell = 0.f;
@@ -1104,14 +993,7 @@ __device__ __forceinline__ void transform_body_t(const Ctx& c, const Lds& L, Sha
     // the workgroup's maximum with ONE barrier: only lane 0 needs it, and the barrier that publishes its decision closes the phase anyway
     if (worker) { dmax = wave_max_nonneg(dmax); if ((tid & 63) == 0) sh->fred[tid >> 6] = dmax; }
     else if ((tid & 63) == 0) sh->fred[tid >> 6] = 0.f;
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-    if (tid == 0) { __builtin_amdgcn_sched_barrier(0); sh->kabs[8] = CVO_NOW(); }
-    if (tid == 64) { __builtin_amdgcn_sched_barrier(0); sh->kabs[9] = CVO_NOW(); }
-#endif
     __syncthreads();                                                // (also makes ybuf / ylds visible to the workgroup)
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-    if (tid == 0) { __builtin_amdgcn_sched_barrier(0); sh->kabs[2] = CVO_NOW() + (dmax == 12345.f ? 1 : 0); }
-#endif
     if (keep_M_on_stop && tid < 12) { if (!sh->stop) sh->M[tid] = sh->Mn[tid]; }   // (wave 0: it sees lane 0's sh->stop, LDS operations of one wave complete in order)
     if (tid == 0) {
         unsigned mx = 0u;
@@ -1134,9 +1016,6 @@ __device__ __forceinline__ void transform_body_t(const Ctx& c, const Lds& L, Sha
             sh->reach = reach;                                      // phase_refine works the margins of the filtered lists out from it
         }
         sh->rebuild = rb;
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-        __builtin_amdgcn_sched_barrier(0); sh->kabs[3] = CVO_NOW() + (sh->rebuild == 12345 ? 1 : 0);
-#endif
     }
     __syncthreads();
 }
@@ -1150,7 +1029,7 @@ static __device__ __noinline__ void transform_large(const PairDesc* Dp_in, int g
     for (int u = 0; u < PRE_T; ++u) none[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (y_lds == 2) transform_body_t<2>(c, L, L.sh, none, false); else transform_body_t<0>(c, L, L.sh, none, false);
 }
-CVO_PHASE_FN(4) void phase_transform(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in) {
+static __device__ __noinline__ void phase_transform(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in) {
     const PairDesc* Dp = uni_ptr(Dp_in); const int g = uni(g_in), G = uni(G_in), tgeo = uni(tile_in), y_lds = uni(y_lds_in);
     const Lds L = lds_layout(tgeo, y_lds);
     const Ctx c = make_ctx(Dp, g, G);
@@ -1212,9 +1091,6 @@ static __device__ __noinline__ void phase_cull(const PairDesc* Dp_in, int g_in, 
             predicted = true;
         }
     }
-#ifdef CVO_KTRACE_CULL
-    if (tid == 0) sh->kabs[0] = CVO_NOW();
-#endif
     const bool planes = y_lds == 2;                                 // columns come straight from the resident y planes: one pass over the whole cloud
     const int span = planes ? max(c.nm, 1) : tile;
     const float* colx = planes ? L.ysx : L.lx; const float* coly = planes ? L.ysy : L.ly; const float* colz = planes ? L.ysz : L.lz;
@@ -1268,9 +1144,6 @@ static __device__ __noinline__ void phase_cull(const PairDesc* Dp_in, int g_in, 
         }
         if (tid == 0) sh->cull_next = 0;
         __syncthreads();
-#ifdef CVO_KTRACE_CULL
-        if (tid == 0) sh->kabs[1] = CVO_NOW();
-#endif
         if (predicted) {
             // (all of the cloud is in this one tile when the prediction is on: tile >= nm is required below)
             off_l = block_max(off_l, sh, tid, nthreads >> 6);
@@ -1282,7 +1155,7 @@ static __device__ __noinline__ void phase_cull(const PairDesc* Dp_in, int g_in, 
         // row's list is made by one lane in column order whichever wave runs it: the lists do not depend on the order.
         // With fewer block pairs than half the waves (one pair on eight workgroups: three block pairs for eight waves) a unit of work is ONE 64-row block: the
         // lane's second row is padding and is not swept, twice the waves take part, each with half the arithmetic and only the groups near its own 64 rows.
-        const int halves = (CVO_CULL_SPLIT == 2 || (CVO_CULL_SPLIT && nblk2 * 2 <= (nthreads >> 6))) ? 2 : 1;   // (CVO_CULL_SPLIT=2, experiment builds: always)
+        const int halves = (nblk2 * 2 <= (nthreads >> 6)) ? 2 : 1;
         auto units = [&](auto single_t) {
         for (;;) {
             int unit = 0;
@@ -1407,15 +1280,10 @@ static __device__ __noinline__ void phase_cull(const PairDesc* Dp_in, int g_in, 
     }
     if (again) predicted = false;
     } while (again);
-#ifdef CVO_KTRACE_CULL
-    if (tid == 0) sh->kabs[2] = CVO_NOW();
-    __syncthreads();
-    if (tid == 0) sh->kabs[3] = CVO_NOW();
-#endif
     // The margins that later list refinements may take (phase_refine, the filtering walk) depend on the farthest row.  A pair's members must agree on them -- a
     // member with near rows only would give itself a wider margin, find its lists stale at another iteration than the others and rebuild alone, with every other
     // member waiting for it in the exchange (seen: 67 us of one pair's 1.6 ms) -- so the farthest row is the PAIR's, whichever workgroup owns it.
-    if (alpha > 0.f && c.G > 1 && CVO_PAIR_XMAX) {
+    if (alpha > 0.f && c.G > 1) {
         for (int i = tid; i < c.nf; i += nthreads) {
             const float4 lo4 = ld4(c.fixed + lo_off(i));
             xmax_l = fmaxf(xmax_l, sqrtf(__builtin_fmaf(lo4.z, lo4.z, __builtin_fmaf(lo4.y, lo4.y, lo4.x * lo4.x))));
@@ -1630,20 +1498,12 @@ __device__ __forceinline__ void fold_entry_e(const float* xi, const float4 y4, c
 #endif
     }
     const unsigned long long mask = __ballot(a > 0.f);
-#ifndef CVO_BRANCHY_REC
     {
         const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
         v2u rec; rec.x = __float_as_uint(a); rec.y = tag;
         const unsigned off = (a > 0.f) ? ((unsigned)wcount + below) * 8u : REC_DROP;
         __builtin_amdgcn_raw_buffer_store_b64(rec, seg, (int)off, 0, 0);
     }
-#else
-    if (a > 0.f) {
-        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-        v2u rec; rec.x = __float_as_uint(a); rec.y = tag;
-        st_rec(at_off(sp, (unsigned)wcount + below), rec);
-    }
-#endif
     wcount += __popcll(mask);
 }
 
@@ -1663,9 +1523,6 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
 #endif
     const int nb = sh->wnb[wave];
     int kept_w = 0, nb_left = 0;
-#ifdef CVO_EXP7
-    const Exp7 e7 = make_exp7(gates);
-#endif
     const float inv_1ma_n = 1.0f / (1.0f - alpha_n);
     const unsigned rp = (unsigned)c.rows_pad, estep = (PF / 2) * rp;      // in 16-byte words
     // the first entries of a block are fetched while the block before it is walked: in the late iterations a row holds only a
@@ -1675,7 +1532,7 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
     if (nb > 0) {
         const gv4u* eb0 = uni_ptr((const gv4u*)c.ent + wave_block(0, wave, nwaves) * 64);
 #pragma unroll
-        for (int u = 0; u < PF / 2; ++u) ehead[u] = ld_ent2<(NT && ENT_NT(YM))>(at_off(eb0, (unsigned)lane + (unsigned)u * rp));
+        for (int u = 0; u < PF / 2; ++u) ehead[u] = ld_ent2<NT>(at_off(eb0, (unsigned)lane + (unsigned)u * rp));
     }
     for (int bi = 0; bi < nb; ++bi) {
         prio_by_remaining(uni(nb) - 1 - bi);
@@ -1711,26 +1568,20 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
         if (bi + 1 < nb) {
             const gv4u* eb1 = uni_ptr((const gv4u*)c.ent + wave_block(bi + 1, wave, nwaves) * 64);
 #pragma unroll
-            for (int u = 0; u < PF / 2; ++u) ehead[u] = ld_ent2<(NT && ENT_NT(YM))>(at_off(eb1, (unsigned)lane + (unsigned)u * rp));
+            for (int u = 0; u < PF / 2; ++u) ehead[u] = ld_ent2<NT>(at_off(eb1, (unsigned)lane + (unsigned)u * rp));
         }
         for (int n0 = 0; n0 < lw; n0 += PF) {
             v4u en4[PF / 2];
-#ifndef CVO_ALWAYS_PREFETCH
             // the next step's entries -- when there is a next step.  (The last step of a block used to fetch entries nobody reads and to wait for them at its end:
             // in the light iterations, where a block is one step, every step ended with a round trip to memory.)
             if (n0 + PF < lw) {
                 eo += estep;
 #pragma unroll
-                for (int u = 0; u < PF / 2; ++u) en4[u] = ld_ent2<(NT && ENT_NT(YM))>(at_off(eb, eo + (unsigned)u * rp));
+                for (int u = 0; u < PF / 2; ++u) en4[u] = ld_ent2<NT>(at_off(eb, eo + (unsigned)u * rp));
             } else {
 #pragma unroll
                 for (int u = 0; u < PF / 2; ++u) en4[u] = eq4[u];
             }
-#else
-            if (n0 + 2 * PF <= c.capn) eo += estep;                 // the prefetch stays inside the lists (the last step re-reads its own entries)
-#pragma unroll
-            for (int u = 0; u < PF / 2; ++u) en4[u] = ld_ent2<(NT && ENT_NT(YM))>(at_off(eb, eo + (unsigned)u * rp));
-#endif
             v2u eq[PF];
 #pragma unroll
             for (int u = 0; u < PF / 2; ++u) { eq[2 * u].x = eq4[u].x; eq[2 * u].y = eq4[u].y; eq[2 * u + 1].x = eq4[u].z; eq[2 * u + 1].y = eq4[u].w; }
@@ -1744,11 +1595,7 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
             }
             if (FLAT) {
                 float ev[PF][3], d2v[PF];
-#ifdef CVO_EXP7
-                se_kernel_values_flat7<PF>(xi, yv4, ckv, actv, gates, e7, av, ev, REFINE ? d2v : nullptr);   // PF exp chains side by side
-#else
                 se_kernel_values_flat<PF>(xi, yv4, ckv, actv, gates, av, ev, REFINE ? d2v : nullptr);   // PF exp chains side by side
-#endif
 #pragma unroll
                 for (int u = 0; u < PF; ++u) fold_entry_e(xi, yv4[u], ev[u], av[u], stag | (eq[u].y & 0xFFFFu), rs, sp, seg, wcount, lane);
                 if (REFINE) {
@@ -1756,15 +1603,11 @@ __device__ __forceinline__ void cand_steady(const Ctx& c, const Lds& L, Shared* 
                     for (int u = 0; u < PF; ++u) {
                         float dn = d2v[u];
                         if (do_shift) { const float q0 = xs[0] - yv4[u].x, q1 = xs[1] - yv4[u].y, q2 = xs[2] - yv4[u].z; dn = __builtin_fmaf(q2, q2, __builtin_fmaf(q1, q1, q0 * q0)); }
-#ifndef CVO_BRANCHY_REC
                         {   // (unconditional store, dropped by the range check for an entry that is not kept: see record_segment)
                             const bool keep = actv[u] && dn < thr_n;
                             __builtin_amdgcn_raw_buffer_store_b64(eq[u], wseg, (int)(keep ? woff * 8u : REC_DROP), 0, 0);
                             woff += keep ? ((cnt & 1) ? 2u * rp - 1u : 1u) : 0u; cnt += keep ? 1 : 0;
                         }
-#else
-                        if (actv[u] && dn < thr_n) { st_rf(at_off(wp, woff), eq[u]); woff += (cnt & 1) ? 2u * rp - 1u : 1u; ++cnt; }
-#endif
                     }
                 }
             } else {
@@ -1812,9 +1655,6 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
     const bool lazy16 = (sh->arith & ARITH_ROW_LAZY16) != 0;
 #endif
     const int nb = sh->wnb[wave];
-#ifdef CVO_EXP7
-    const Exp7 e7 = make_exp7(gates);
-#endif
     for (int bi = 0; bi < nb; ++bi) {
         prio_by_remaining(uni(nb) - 1 - bi);
         const int blk = wave_block(bi, wave, nwaves);
@@ -1829,29 +1669,16 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
         RowSums rs = {{0, 0, 0}, {0, 0, 0}};
         CVO_ROW_INIT(rs);
         static_assert(PF == 4, "the cull packs four columns per word");
-#ifdef CVO_BRANCHY_REC
-        const gv2u* jp = c.jT4 + li;                                // entries 4q .. 4q+3 of this row: jp[q * rows_pad]
-        gv2u* ep = c.ent + 2 * slot;
-#endif
         const unsigned stag = (unsigned)slot << 16;
         auto cols = [&](int n0, int (&jo)[PF]) {
 #pragma unroll
             for (int u = 0; u < PF; ++u) jo[u] = 0;
-#ifndef CVO_BRANCHY_REC
             {   // (unconditional load: a lane whose row has ended reads beyond the range and gets zeros -- no branch, so the loads in flight stay countable)
                 const v2u w = __builtin_amdgcn_raw_buffer_load_b64(jseg, (int)(n0 < len ? ((unsigned)(n0 >> 2) * (unsigned)c.rows_pad + (unsigned)li) * 8u : REC_DROP), 0, 0);
                 const int q[PF] = {(int)(w.x & 0xFFFFu), (int)(w.x >> 16), (int)(w.y & 0xFFFFu), (int)(w.y >> 16)};
 #pragma unroll
                 for (int u = 0; u < PF; ++u) jo[u] = (n0 + u < len) ? q[u] : 0;
             }
-#else
-            if (n0 < len) {
-                const v2u w = ld_jt(&jp[(size_t)(n0 >> 2) * c.rows_pad]);
-                const int q[PF] = {(int)(w.x & 0xFFFFu), (int)(w.x >> 16), (int)(w.y & 0xFFFFu), (int)(w.y >> 16)};
-#pragma unroll
-                for (int u = 0; u < PF; ++u) jo[u] = (n0 + u < len) ? q[u] : 0;
-            }
-#endif
         };
         auto feats = [&](const int (&ji)[PF], float4 (&go)[PF]) {
 #pragma unroll
@@ -1875,29 +1702,13 @@ __device__ __forceinline__ void cand_fresh(const Ctx& c, const Lds& L, Shared* s
             }
             colour_factors<PF>(d2c, gates, ckv);
 #pragma unroll
-#ifndef CVO_BRANCHY_REC
             for (int u = 0; u < PF; u += 2) {                         // two entries per 16-byte store (the second may lie beyond the row's end: stale there anyway)
                 v4u e; e.x = __float_as_uint(ckv[u]); e.y = (unsigned)j0[u]; e.z = __float_as_uint(ckv[u + 1]); e.w = (unsigned)j0[u + 1];
                 __builtin_amdgcn_raw_buffer_store_b128(e, eseg, (int)(actv[u] ? (2u * (unsigned)slot + (unsigned)ent_ix(n0 + u, (size_t)c.rows_pad)) * 8u : REC_DROP), 0, 2 /* nt */);
             }
-#else
-            for (int u = 0; u < PF; u += 2)                           // two entries per 16-byte store (the second may lie beyond the row's end: stale there anyway)
-                if (actv[u]) {
-                    v4u e; e.x = __float_as_uint(ckv[u]); e.y = (unsigned)j0[u]; e.z = __float_as_uint(ckv[u + 1]); e.w = (unsigned)j0[u + 1];
-#ifndef CVO_PLAIN_ENT_ST
-                    __builtin_nontemporal_store(e, reinterpret_cast<gv4u*>(&ep[ent_ix(n0 + u, (size_t)c.rows_pad)]));
-#else
-                    *reinterpret_cast<gv4u*>(&ep[ent_ix(n0 + u, (size_t)c.rows_pad)]) = e;
-#endif
-                }
-#endif
             if (FLAT) {
                 float ev[PF][3];
-#ifdef CVO_EXP7
-                se_kernel_values_flat7<PF>(xi, yv4, ckv, actv, gates, e7, av, ev);
-#else
                 se_kernel_values_flat<PF>(xi, yv4, ckv, actv, gates, av, ev);
-#endif
 #pragma unroll
                 for (int u = 0; u < PF; ++u) fold_entry_e(xi, yv4[u], ev[u], av[u], stag | (unsigned)j0[u], rs, sp, seg, wcount, lane);
             } else {
@@ -2144,7 +1955,7 @@ static __device__ __noinline__ void phase_resort(const PairDesc* Dp_in, int g_in
     __syncthreads();
 }
 
-CVO_PHASE_FN(8) void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) {
+CVO_ITERATION_PHASE void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) {
     const PairDesc* Dp = uni_ptr(Dp_in); const int g = uni(g_in), G = uni(G_in), tgeo = uni(tile_in), y_lds = uni(y_lds_in), k = uni(k_in);
     const Lds L = lds_layout(tgeo, y_lds); Shared* sh = L.sh;
     const Ctx c = make_ctx(Dp, g, G);
@@ -2164,15 +1975,12 @@ CVO_PHASE_FN(8) void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in,
 #define CVO_CAND(fn, flat) do { if (y_lds == 1) fn<1, flat>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8); \
                                 else if (y_lds == 2) fn<2, flat>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8); \
                                 else fn<0, flat>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8); } while (0)
-#ifndef CVO_NO_FEATURE_STAGING
         if (fresh_list && y_lds == 1 && sh->tab_cols >= c.nm) {
             for (int j = tid; j < c.nm; j += nthreads) L.tab[j] = ld4(c.moving + hi_off(c.nm, j));
             __syncthreads();
             if (gates.poly_ok) cand_fresh<1, true, true>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8);
             else cand_fresh<1, false, true>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8);
-        } else
-#endif
-        if (fresh_list) { if (gates.poly_ok) CVO_CAND(cand_fresh, true); else CVO_CAND(cand_fresh, false); }
+        } else if (fresh_list) { if (gates.poly_ok) CVO_CAND(cand_fresh, true); else CVO_CAND(cand_fresh, false); }
         else if (y_lds == 1 && gates.poly_ok && sh->total < sh->P.nt_min) cand_steady<1, true, false>(c, L, sh, gates, lane, wave, nwaves, inv_c, inv_d, acc8);   // short lists: plain loads (DevParams::nt_min)
         else {
             // Is this the last iteration at the present ell (cvo.cpp:810-812: the schedule goes by the iteration count), and do the lists hold everything within the
@@ -2290,9 +2098,6 @@ CVO_PHASE_FN(8) void phase_candidates(const PairDesc* Dp_in, int g_in, int G_in,
         }
     }
     const unsigned long long ts2 = CVO_NOW();
-#ifdef CVO_KTRACE_WAVES   // experiment builds: when every wave left its walk (ticks since the walk's start), for the trace row written by run_pair
-    if (lane == 0) sh->kabs[wave] = ts2 - ts1;
-#endif
     // (no barrier before the reduction: its own barrier is the one every wave reaches after its walk)
     const double mine = dense_mode ? block_reduce<8, 8, false>(acc8, sh, tid, nwaves) : block_reduce<8, 6, false>(acc8, sh, tid, nwaves);   // list mode: nnz and candidates are per-wave counts in lane 0
     const unsigned long long ts3 = CVO_NOW();
@@ -2361,7 +2166,7 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
         // instructions) is tabulated once per iteration, 16 bytes per column in LDS over the rebuild scratch.  (Tabulating all of
         // the point part was measured: its four 16-byte gathers per nonzero make the LDS the bottleneck -- 88 against 118 cycles
         // per 64 nonzeros -- and two table passes need the records binned by column in the candidate phase; one gather does not.)
-        const bool use_table = sh->tab_cols >= c.nm && cnt_wg > CVO_LS_TAB_FACTOR * c.nm && y_lds != 0;
+        const bool use_table = sh->tab_cols >= c.nm && cnt_wg > LS_TAB_FACTOR * c.nm && y_lds != 0;
         if (use_table) {
             for (int j = tid; j < c.nm; j += nthreads) {
                 const float4 yj = y_lds == 1 ? load_y<1>(c, L, j) : load_y<2>(c, L, j);
@@ -2373,10 +2178,7 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
         }
         // records stream from L2 / HBM: four steps of them are in flight per lane (under load one step's arithmetic is shorter
         // than a memory round trip)
-#ifndef CVO_LS_RD
-#define CVO_LS_RD 4
-#endif
-        constexpr int RD = CVO_LS_RD;
+        constexpr int RD = 4;
         auto walk = [&](auto ym, auto tb) {
             constexpr int YM = decltype(ym)::value;
             constexpr bool TAB = decltype(tb)::value;
@@ -2453,9 +2255,7 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
     // own lanes wrote them; the next workgroup barrier is the epilogue's
     block_reduce<4, 4, false>(acc4, sh, tid, nwaves);
 #ifdef CVO_KTRACE
-#ifndef CVO_KTRACE_EPI
     if (tid == 0) { sh->ksub[0] = kt1 - kt0; sh->ksub[1] = CVO_NOW() - kt1; }
-#endif
 #endif
     if (G > 1) {
         if (tid < 64) { if (!group_exchange<4>(sh, c.xch, G, g, sh->launch_tag | (2u * (unsigned)k + 2u), lane)) sh->status = 6; }
@@ -2468,25 +2268,25 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
 __device__ __forceinline__ bool ls_even_shares(int y_lds) {
     const Shared* sh = reinterpret_cast<const Shared*>(cvo_smem);
     const int nwaves = (int)blockDim.x >> 6;
-    if (!CVO_LS_EVEN || y_lds != 1 || sh->dense_mode || ((sh->ctx_nrows + 63) >> 6) >= 2 * nwaves) return false;
+    if (y_lds != 1 || sh->dense_mode || ((sh->ctx_nrows + 63) >> 6) >= 2 * nwaves) return false;
     int cnt_wg = 0;
     for (int w = 0; w < nwaves; ++w) cnt_wg += sh->wcnt[w];
-    return cnt_wg >= CVO_LS_EVEN_MIN * nwaves;
+    return cnt_wg >= LS_EVEN_MIN * nwaves;
 }
-CVO_PHASE_FN(1) void phase_linesearch(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<false>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
+CVO_ITERATION_PHASE void phase_linesearch(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<false>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
 // (a function of its own whatever the build: the common path's function does not carry its code)
 static __device__ __noinline__ void phase_linesearch_even(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<true>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
 
 // ---- E: one lane finishes the iteration (every workgroup of the pair computes the same bits)
-CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in, int max_iter_in) {
+CVO_ITERATION_PHASE void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in, int max_iter_in) {
     const PairDesc* Dp = uni_ptr(Dp_in); const int g = uni(g_in), G = uni(G_in), tgeo = uni(tile_in), y_lds = uni(y_lds_in), k = uni(k_in), max_iter = uni(max_iter_in);
     const Lds L = lds_layout(tgeo, y_lds); Shared* sh = L.sh;
     const Ctx c = make_ctx(Dp, g, G);
     // every lane fetches its share of the moving cloud for the NEXT iteration's transform while lane 0 does the scalar work
-    // In the resident float4 layout waves 1 .. n-1 take all the points: they transform them while lane 0 of wave 0 is still at the second stop test (dist_se3,
-    // a third of its scalar work), which the transform does not need -- only R and T.
+    // In the resident float4 layout (and the plane layout of large clouds) waves 1 .. n-1 take all the points: they transform them while lane 0 of wave 0 is still
+    // at the second stop test (dist_se3, a third of its scalar work), which the transform does not need -- only R and T.
     const bool next_T = k + 1 < max_iter;
-    const int first_worker = ((y_lds == 1 || (y_lds == 2 && CVO_FUSE_PLANES)) && blockDim.x > 64 && sh->P.overlap_stop_test) ? 64 : 0;
+    const int first_worker = ((y_lds == 1 || y_lds == 2) && blockDim.x > 64 && sh->P.overlap_stop_test) ? 64 : 0;
     float4 pre[PRE_T];
     {
         int j = (int)threadIdx.x >= first_worker ? (int)threadIdx.x - first_worker : c.nm;
@@ -2523,16 +2323,10 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
         for (int q = 0; q < 3; ++q) { omega[q] = sh->omega[q]; v[q] = sh->v[q]; }
         ell = sh->ell;
         const float c3 = (float)(4.0 * float(E)), c2 = (float)(3.0 * float(Dd)), c1 = (float)(2.0 * float(C)), c0 = float(B);   // cvo.cpp:318
-#ifdef CVO_KTRACE_EPI
-        const unsigned long long kq0 = CVO_NOW();
-#endif
 #ifdef CVO_ARITH_MODES
         step = (sh->arith & ARITH_F32_ROOTS) ? cubic_step_f32eig(c3, c2, c1, c0, P.min_step) : cubic_step(c3, c2, c1, c0, P.min_step);
 #else
         step = cubic_step(c3, c2, c1, c0, P.min_step);
-#endif
-#ifdef CVO_KTRACE_EPI
-        __builtin_amdgcn_sched_barrier(0); sh->ksub[0] = CVO_NOW() - kq0 + (step == 12345.f ? 1 : 0);
 #endif
         stop_a = norm3f(omega) < P.eps && norm3f(v) < P.eps;                            // cvo.cpp:782
         if (!stop_a) {
@@ -2546,21 +2340,9 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
             for (int i = 0; i < 9; ++i) sh->R[i] = Rn[i];                                // cvo.cpp:801
         }
         sh->stop = 0;
-#ifdef CVO_KTRACE_EPI
-        __builtin_amdgcn_sched_barrier(0); sh->ksub[1] = CVO_NOW() - kq0 - sh->ksub[0];
-#if CVO_KTRACE_EPI == 2
-        sh->kabs[0] = CVO_NOW();
-#endif
-#endif
     }
     __syncthreads();                                                 // R, T are out
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-    if (threadIdx.x == 64) sh->kabs[4] = CVO_NOW();
-#endif
     if (threadIdx.x == 0) {
-#ifdef CVO_KTRACE_EPI
-        const unsigned long long kq2 = CVO_NOW();
-#endif
         const DevParams& P = sh->P;
         float dist = -1.f;
         int stop = 0;
@@ -2595,12 +2377,6 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
             tr.step = step; tr.ell = ell; tr.dist = dist; tr.pad_ = 0;
             *c.trace_len = k + 1;
         }
-#ifdef CVO_KTRACE_EPI
-        __builtin_amdgcn_sched_barrier(0); sh->ksub[2] = CVO_NOW() - kq2 + (dist == 12345.f ? 1 : 0);
-#if CVO_KTRACE_EPI == 2
-        sh->kabs[1] = CVO_NOW();
-#endif
-#endif
     }
 #ifdef CVO_KTRACE
     const unsigned long long ke1 = CVO_NOW();
@@ -2617,22 +2393,11 @@ CVO_PHASE_FN(2) void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, i
         }
     }
 #ifdef CVO_KTRACE
-#ifdef CVO_KTRACE_EPI
-    if (threadIdx.x == 0) sh->ksub[3] = CVO_NOW() - ke0;
-#if CVO_KTRACE_EPI == 2     // times from the end of lane 0's part A: part B done | thread 64 past the barrier | its points done | lane 0 has the staleness maximum | decision made | end
-    if (threadIdx.x == 0) {
-        const unsigned long long a = sh->kabs[0], e = CVO_NOW();
-        sh->ksub[0] = a - ke0; sh->ksub[1] = sh->kabs[1] - a; sh->ksub[2] = sh->kabs[5] - a; sh->ksub[3] = sh->kabs[2] - a;
-        sh->kabs[6] = sh->kabs[3] - a; sh->kabs[7] = e - a; sh->kabs[4] = sh->kabs[4] - a; sh->kabs[10] = sh->kabs[8] - a; sh->kabs[11] = sh->kabs[9] - a;
-    }
-#endif
-#else
     if (threadIdx.x == 0) { sh->ksub[2] = ke1 - ke0; sh->ksub[3] = CVO_NOW() - ke1; }
-#endif
 #endif
 }
 
-#if CVO_INLINE_PHASES & 8
+#if CVO_BLOCK_MAX <= 512
 // one iteration's three regular phases as ONE function: a phase call costs its callee-saved saves (the line search keeps ~50 constants in callee-saved scalar
 // registers, the candidate walk uses two dozen callee-saved vector registers) and, at its return, a wait for their reloads from scratch memory
 static __device__ __noinline__ void phase_iteration(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in, int max_iter_in) {
@@ -3005,7 +2770,7 @@ static __device__ __noinline__ void run_pair(const PairDesc* descs_in, int ps_in
             else { __syncthreads(); if (tid == 0) sh->resort_pending = 0; __syncthreads(); }   // (the lists have been rebuilt or filtered again meanwhile)
         }
         CVO_PHASE(0);
-#if CVO_INLINE_PHASES & 8
+#if CVO_BLOCK_MAX <= 512
         phase_iteration(Dp, ge, Ge, tgeo, y_lds, k, max_iter);
         t_prev = CVO_NOW();
         if (sh->status != 0) break;
@@ -3029,19 +2794,6 @@ static __device__ __noinline__ void run_pair(const PairDesc* descs_in, int ps_in
             // omega = candidate phase (prologue, row walk, wait + reduction), v = line-search walk, its reduction, epilogue scalar part; step = fused transform
             tr.omega[0] = (float)(sh->sub[0] - ksub_prev[0]); tr.omega[1] = (float)(sh->sub[1] - ksub_prev[1]); tr.omega[2] = (float)(sh->sub[2] - ksub_prev[2]);
             tr.v[0] = (float)sh->ksub[0]; tr.v[1] = (float)sh->ksub[1]; tr.v[2] = (float)sh->ksub[2]; tr.step = (float)sh->ksub[3];
-#ifdef CVO_KTRACE_CULL
-            tr.omega[0] = (float)(sh->kabs[1] - sh->kabs[0]); tr.omega[1] = (float)(sh->kabs[2] - sh->kabs[1]); tr.omega[2] = (float)(sh->kabs[3] - sh->kabs[2]); tr.v[0] = (float)(CVO_NOW() - sh->kabs[3]);
-#endif
-#ifdef CVO_KTRACE_WAVES
-            {   // omega = min / mean / max over the waves of the walk's end, v[0] = wave 0's, v[1] = the latest wave's index
-                unsigned long long mn = ~0ull, mx = 0, sm = 0; int wmx = 0; const int nw = (int)blockDim.x >> 6;
-                for (int w = 0; w < nw; ++w) { const unsigned long long t = sh->kabs[w]; mn = t < mn ? t : mn; if (t > mx) { mx = t; wmx = w; } sm += t; }
-                tr.omega[0] = (float)mn; tr.omega[1] = (float)(sm / (unsigned long long)nw); tr.omega[2] = (float)mx; tr.v[0] = (float)sh->kabs[0]; tr.v[1] = (float)wmx;
-            }
-#endif
-#if defined(CVO_KTRACE_EPI) && CVO_KTRACE_EPI == 2
-            tr.omega[0] = (float)sh->kabs[6]; tr.omega[1] = (float)sh->kabs[7]; tr.omega[2] = (float)sh->kabs[4]; tr.ell = (float)sh->kabs[10]; tr.dist = (float)sh->kabs[11];
-#endif
             for (int q = 0; q < 4; ++q) ksub_prev[q] = sh->sub[q];
             for (int q = 0; q < 10; ++q) kt_prev[q] = ticks[q];
         }
@@ -3273,7 +3025,7 @@ static __device__ __noinline__ void queue_pull(gu64* queue, int slot_in, int g_i
     }
 }
 
-__global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD) void cvo_align_kernel(const PairDesc* __restrict__ descs, int n_pairs, int G, int tile, int y_lds, int rows_cap, int y_cap,
+__global__ __launch_bounds__(BLOCK_MAX, BLOCK_MAX > 512 ? 1 : 2) void cvo_align_kernel(const PairDesc* __restrict__ descs, int n_pairs, int G, int tile, int y_lds, int rows_cap, int y_cap,
                                                                          unsigned launch_tag, int tab_cols, unsigned long long* __restrict__ queue_in, DevParams P,
                                                                          const unsigned* wgs_submitted /* host-mapped */, unsigned* wgs_started,
                                                                          const float* const* __restrict__ raw_table /* pinned host memory, or null */
@@ -3618,7 +3370,7 @@ hipError_t launch_selftest_pairs(const float* in, float* out, float* aux, int n,
     return hipGetLastError();
 }
 
-int align_blocks_per_cu() { return BLOCK_MAX > 512 ? 1 : CVO_WAVES_PER_SIMD / 2; }
+int align_blocks_per_cu() { return 1; }   // one workgroup of up to BLOCK_MAX threads per CU (two waves per SIMD at 512, three at 768)
 int align_block_max() { return BLOCK_MAX; }
 int align_adopt_gmax() { return ADOPT_GMAX; }
 
