@@ -12,6 +12,12 @@ every rank owns its own 64 pairs (weak scaling: BASELINE config 3 at N=1, config
 = 512 pairs at N=8); the only collective is an RCCL all-gather of the 64-byte
 result records.  Rank 0 prints one JSON line.
 
+A plain run does only what that line's headline needs: it renders the pairs, sets up, warms up, times the steps,
+writes --dump-outputs and prints the line.  --full adds everything else the benchmark measures or checks on one GPU:
+the secondary loops (with_score_block, with_host_upload, distinct_pairs), the latency probes, the CPU baseline with the
+parity of every timed pair against the oracle, and the `config5` object; --no-cpu-baseline, --no-latency-probe,
+--no-config5 and --parity-only narrow it.
+
 Launch: python bench.py --gpus N            N > 1 without RANK in the environment: this process starts the N ranks itself (child
                                             processes, one per GPU, rendezvous on 127.0.0.1) and passes rank 0's line through;
                                             under torch.distributed.run (RANK set) it is one of the ranks.
@@ -335,9 +341,9 @@ def parity_check(pairs, results, its, threads):
 
 def config5_child():
     """BASELINE config 5 (the largest single-GPU configuration: 736x456 ETH3D shape, ~9.3 k points per cloud) as a short run of this very script in a child process,
-    after the main measurement has left the device: value, roofline and the parity of the 64 pairs it timed, for the driver's line."""
+    after the main measurement has left the device: value, roofline and the parity of the 64 pairs it timed, for the --full line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--shape", "eth3d", "--steps", "12", "--warmup", "4", "--no-cpu-baseline", "--parity-only", "--no-latency-probe"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--shape", "eth3d", "--steps", "12", "--warmup", "4", "--full", "--no-cpu-baseline", "--parity-only", "--no-latency-probe"]
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
@@ -387,16 +393,18 @@ def main():
     ap.add_argument("--workgroups", type=int, default=1, help="workgroups per pair (0 = auto: lowest latency of one batch alone; 1 = highest throughput)")
     ap.add_argument("--streams", type=int, default=8, help="steps in flight (batch objects on separate HIP streams)")
     ap.add_argument("--max-workgroups", type=int, default=0, help="cap on the workgroups of one launch (0 = none): its share of the device when several launches run side by side")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the secondary loops, the latency probes, the CPU baseline with the parity check and the `config5` child "
+                                                        "(a plain run times the steps and prints the headline line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no timed CPU baseline (and no parity check unless --parity-only)")
     ap.add_argument("--shape", choices=("tum", "eth3d"), default="tum", help="tum: 640x480, ~3 k points per cloud (the metric's configuration); eth3d: 736x456, ~9.3 k points (BASELINE config 5)")
     ap.add_argument("--gen-workers", type=int, default=0, help="host processes rendering the synthetic pairs (0 = one per host thread, 1 = no fork)")
     ap.add_argument("--no-adoption", action="store_true", help="do not let finished workgroups help with the pairs of their launch that still run (cvo_batch_set_adoption)")
     ap.add_argument("--adoption", action="store_true", help="force adoption on (whatever ADOPTION_DEFAULT says)")
     ap.add_argument("--reuse", choices=("any", "oldest"), default="any", help="which batch object in flight the next step reuses: whichever has completed first (cvo_batch_done), or strictly the oldest")
     ap.add_argument("--total-pairs", type=int, default=0, help="pairs per step over ALL ranks, dealt in contiguous blocks (cvo_shard_range: blocks may differ by one, the gather pads); 0 = --pairs per rank")
-    ap.add_argument("--no-latency-probe", action="store_true", help="skip the single-pair / loop-closure / point-cloud latency measurements (counter passes)")
-    ap.add_argument("--parity-only", action="store_true", help="with --no-cpu-baseline: still check every timed pair against the oracle (parity build, all host threads), without the timed CPU legs")
-    ap.add_argument("--no-config5", action="store_true", help="do not append the `config5` object (a short run of BASELINE config 5, --shape eth3d, in a child process) to the default line")
+    ap.add_argument("--no-latency-probe", action="store_true", help="with --full: skip the secondary loops and the single-pair / loop-closure / point-cloud latency measurements (counter passes)")
+    ap.add_argument("--parity-only", action="store_true", help="with --full --no-cpu-baseline: still check every timed pair against the oracle (parity build, all host threads), without the timed CPU legs")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: do not append the `config5` object (a short run of BASELINE config 5, --shape eth3d, in a child process)")
     ap.add_argument("--dry-launch", action="store_true", help="every rank prints its block of the step's pairs (cvo_shard_range) as one JSON line and exits: no GPU needed")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
@@ -406,6 +414,10 @@ def main():
         args.warmup = 4 if args.shape == "eth3d" else 32
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        if args.parity_only:
+            ap.error("--parity-only needs --full")
+        args.no_cpu_baseline = args.no_latency_probe = args.no_config5 = True
     if args.gpus > 1 and "RANK" not in os.environ:      # the bare invocation: this process becomes the launcher of the N ranks (before anything imports torch or touches the GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], collect_stdout=args.dry_launch))
     if args.shape == "eth3d":      # BASELINE config 5 defaults: 4 workgroups per pair, 4 launches side by side, 64 workgroups (16 pair slots) each

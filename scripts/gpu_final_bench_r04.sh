@@ -3,9 +3,9 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r4_final; mkdir -p $O; hostname > $O/lease.txt; date -u +%FT%TZ >> $O/lease.txt
 timeout -k 10 700 python -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; echo "pytest rc=$? $(tail -1 $O/pytest.txt)"
 timeout -k 10 120 python __graft_entry__.py --smoke 2>&1 | tail -1
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
-timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"
-timeout -k 10 400 python bench.py --shape eth3d > $O/bench_eth3d.json 2> $O/bench_eth3d.err; echo "eth3d rc=$?"
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?"
+timeout -k 10 400 python bench.py --full --shape eth3d > $O/bench_eth3d.json 2> $O/bench_eth3d.err; echo "eth3d rc=$?"
 python - <<'PY'
 import json
 for f in ("bench_driver", "bench_default", "bench_eth3d"):

@@ -7,7 +7,7 @@ benchmark's pairs with every variant of the oracle that restates one of those so
 ORC_VAR_*; the FMA member is the -O3 -march=native -ffp-contract=fast build of the same source) and records, per
 pair, how far each variant's final pose lies from the base oracle's: that spread is the envelope the real
 reference sits in, and the bound any implementation can be held to.  tests/test_gpu_noise_envelope.py asserts
-that the HIP result lies inside it; bench.py prints it beside its parity figures.
+that the HIP result lies inside it; bench.py --full prints it beside its parity figures.
 
 usage: python scripts/make_noise_envelope.py [--pairs 64] [--threads 8]
 """

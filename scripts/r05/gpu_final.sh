@@ -3,9 +3,9 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r5_final; mkdir -p $O; date -u +%FT%TZ > $O/lease.txt
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; rc=$?; echo "pytest rc=$rc $(tail -2 $O/pytest.txt | tr '\n' ' ')"; if [ $rc -ne 0 ]; then tail -30 $O/pytest.txt; exit 1; fi
 timeout -k 10 300 python __graft_entry__.py --smoke > $O/smoke.txt 2>&1; echo "smoke rc=$? $(tail -1 $O/smoke.txt | cut -c1-200)"
-t0=$(date +%s); timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 1; echo "driver's command: $(( $(date +%s) - t0 )) s wall"
-timeout -k 10 900 python bench.py --no-config5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
-timeout -k 10 900 python bench.py --shape eth3d > $O/bench_eth3d.json 2> $O/bench_eth3d.err || exit 1
+t0=$(date +%s); timeout -k 10 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || exit 1; echo "driver's command: $(( $(date +%s) - t0 )) s wall"
+timeout -k 10 900 python bench.py --full --no-config5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
+timeout -k 10 900 python bench.py --full --shape eth3d > $O/bench_eth3d.json 2> $O/bench_eth3d.err || exit 1
 python - <<'PY'
 import json
 for n in ("driver", "default", "eth3d"):

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r5_g; mkdir -p $O; date -u +%FT%TZ > $O/lease.txt
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1; rc=$?; echo "pytest rc=$rc $(tail -3 $O/pytest.txt | tr '\n' ' ')"; if [ $rc -eq 124 ]; then exit 1; fi
 timeout -k 10 120 python __graft_entry__.py --smoke 2>&1 | tail -1
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r5_g/bench_driver.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # round 5, call I: hand-over from registered memory, staged frames, gather stream: their tests; then the driver's command
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r5_i; mkdir -p $O; date -u +%FT%TZ > $O/lease.txt
 timeout -k 10 900 python -m pytest tests/test_gpu_handover.py tests/test_gpu_pcd.py tests/test_gpu_multi.py tests/test_gpu_replay.py -x -q > $O/pytest.txt 2>&1; rc=$?; echo "pytest rc=$rc $(tail -3 $O/pytest.txt | tr '\n' ' ')"; if [ $rc -eq 124 ]; then exit 1; fi
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err; echo "driver rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r5_i/bench_driver.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_adopt
 : > $O/latency.txt
 for rep in 1 2 3; do for v in new prev; do
   if [ $v = prev ]; then export CVO_HIP_LIB=$PWD/tmp_libs/libcvo_hip_prev.so; else unset CVO_HIP_LIB; fi
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-config5 > $O/bench_$v.json 2> $O/bench_$v.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-config5 > $O/bench_$v.json 2> $O/bench_$v.err || exit 1
   python - $v <<'PY' | tee -a $O/latency.txt
 import json, sys; d=json.loads(open(f'gpurun_out/r5_y/bench_{sys.argv[1]}.json').read().strip().splitlines()[-1]); l=d['latency']; print(sys.argv[1], round(d['value']), {k: round(l[k],3) for k in ('single_pair_align_ms','tracker_frame_from_images_ms','tracker_frame_next_frame_staged_ms','lc_batch_align_ms')})
 PY

@@ -57,3 +57,24 @@ def test_under_an_external_launcher_it_is_one_rank(hiplib):
 def test_a_failing_rank_fails_the_launcher(hiplib):
     out = _run(["--gpus", "2", "--dry-launch", "--total-pairs", "-5"])
     assert out.returncode != 0
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_only(hiplib, tmp_path):
+    """Without --full the benchmark times its steps, writes --dump-outputs and prints its line: no secondary loops, latency probes,
+    CPU baseline, parity check or config5 child (those are --full's)."""
+    out = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "8", "--dump-outputs", str(tmp_path / "dump")])
+    assert out.returncode == 0, out.stderr
+    lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = lines[0]
+    assert d["unit"] == "alignments/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0
+    assert (d["steps"], d["warmup"], d["config"]["pairs_per_gpu"]) == (2, 1, 8)
+    assert d["with_score_block"] is None and d["with_host_upload"] is None and d["distinct_pairs"] is None
+    assert not {"latency", "cpu_baseline", "parity", "speedup_vs_cpu_baseline", "config5"} & set(d), sorted(d)
+    assert os.path.exists(tmp_path / "dump" / "transform.npy")
+
+
+def test_the_parity_check_needs_full():
+    out = _run(["--parity-only", "--no-cpu-baseline"])
+    assert out.returncode != 0 and "--full" in out.stderr
