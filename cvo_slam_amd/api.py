@@ -111,6 +111,7 @@ ABI_SYMBOLS = [
     "cvo_set_arith_mode", "cvo_get_arith_mode", "cvo_batch_set_arith_mode", "cvo_batch_get_arith_mode",
     "cvo_selftest_cubic_step_f32eig", "cvo_selftest_dist_se3_f32logm",
     "cvo_batch_set_pairs_images", "cvo_batch_set_num_want", "cvo_batch_get_cloud", "cvo_batch_get_selected_points",
+    "cvo_batch_advance_images", "cvo_batch_reset_stream", "cvo_batch_align_pairs_async", "cvo_batch_get_prev_accum_transform",
 ]
 
 _lib = None
@@ -199,6 +200,10 @@ def load_library():
     L.cvo_get_selected_points.argtypes = [vp, C.c_int, vp, C.c_int, ip]
     L.cvo_batch_set_pairs_images.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip, ip, ip]
     L.cvo_batch_set_num_want.argtypes = [vp, C.c_int]
+    L.cvo_batch_advance_images.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip, ip]
+    L.cvo_batch_reset_stream.argtypes = [vp, C.c_int]
+    L.cvo_batch_align_pairs_async.argtypes = [vp, C.c_int, ip, vp]
+    L.cvo_batch_get_prev_accum_transform.argtypes = [vp, C.c_int, fp, fp]
     L.cvo_batch_get_cloud.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.c_int, ip]
     L.cvo_batch_get_selected_points.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, ip]
     L.cvo_batch_enqueue_innerproduct.argtypes = [vp, C.c_int]
@@ -808,8 +813,53 @@ class CvoBatch:
                                                  fi.ctypes.data_as(ip), mi.ctypes.data_as(ip), pts.ctypes.data_as(ip)))
         return pts
 
+    # -- K-stream frame-to-frame odometry (cvo_hip.h: cvo_batch_advance_images & co): slot p is one cvo::cvo odometry object
+    def advance_images(self, slots, images, cameras, cam_index=None):
+        """cvo_batch_advance_images: images[k] = (bgr8, depth16), all of one size, is the next frame of slot slots[k], generated with camera
+        cameras[cam_index[k]] (cam_index None: cameras[0] for all).  cameras: a list of (scaling_factor, fx, fy, cx, cy), or one such tuple.
+        A slot's first frame becomes its fixed cloud; after that the moving cloud moves to fixed and the frame becomes the moving cloud.
+        Returns the points of each image's cloud."""
+        ims = [Cvo._images(b, d) for b, d in images]
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        if not ims or sl.shape[0] != len(ims):
+            raise ValueError("one slot per image, at least one image")
+        w, h = ims[0][2], ims[0][3]
+        if any((q[2], q[3]) != (w, h) for q in ims):
+            raise ValueError("all images of one call must have the same size")
+        if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+            cameras = [cameras]
+        cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+        ci = None if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+        if ci is not None and (ci.shape[0] != len(ims) or ci.min() < 0 or ci.max() >= len(cameras)):
+            raise ValueError("cam_index: one index into cameras per image")
+        n = len(ims); ip = C.POINTER(C.c_int)
+        bgr = (C.c_void_p * n)(*[q[0].ctypes.data for q in ims]); dep = (C.c_void_p * n)(*[q[1].ctypes.data for q in ims])
+        pts = np.zeros(n, np.int32)
+        _check(self.L.cvo_batch_advance_images(self.h, n, sl.ctypes.data_as(ip), bgr, dep, w, h, cams, None if ci is None else ci.ctypes.data_as(ip),
+                                               pts.ctypes.data_as(ip)))
+        return pts
+
+    def reset_stream(self, p: int):
+        """cvo_batch_reset_stream: slot p becomes a fresh odometry object (no clouds, R = I, T = 0, ell = params.ell)"""
+        _check(self.L.cvo_batch_reset_stream(self.h, int(p)))
+
+    def align_pairs_async(self, slots, stream: int | None = None):
+        """cvo_batch_align_pairs_async: one launch over the listed slots; results come back in list order"""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        _check(self.L.cvo_batch_align_pairs_async(self.h, sl.shape[0], sl.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(stream) if stream else None))
+        return sl.shape[0]
+
+    def align_pairs(self, slots):
+        return self.wait(self.align_pairs_async(slots))
+
+    def prev_accum_transform(self, p: int):
+        """cvo_batch_get_prev_accum_transform of stream slot p: (prev, accum), (3, 4) each"""
+        a = np.zeros(12, np.float32); b = np.zeros(12, np.float32); fp = C.POINTER(C.c_float)
+        _check(self.L.cvo_batch_get_prev_accum_transform(self.h, int(p), a.ctypes.data_as(fp), b.ctypes.data_as(fp)))
+        return a.reshape(3, 4), b.reshape(3, 4)
+
     def set_num_want(self, num_want: int):
-        """pcd_generator::num_want of the later set_pairs_images calls (3000 by default)"""
+        """pcd_generator::num_want of the later set_pairs_images / advance_images calls (3000 by default)"""
         _check(self.L.cvo_batch_set_num_want(self.h, int(num_want)))
 
     def get_cloud(self, p: int, slot: int):

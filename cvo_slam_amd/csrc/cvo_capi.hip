@@ -84,7 +84,7 @@ hipError_t pcd_launch_select_batch(const float* abs0, const float* abs1, const f
 hipError_t pcd_launch_subsample_batch(uint8_t* map, const uint8_t* pattern, const PcdImgRec* rec, int num_want, const uint16_t* depth, int w, int h, int* tile_counts,
                                       int n_img, hipStream_t s);
 hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
-                                  const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s);
+                                  const float* cam_table, const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s);
 hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
@@ -834,14 +834,18 @@ struct Engine {
 
     // One persistent launch aligning n pairs.  states (host, n entries) are uploaded
     // first when upload_states is set; results land in h_states after wait().
+    // state_index (may be null = position i): the device state a position starts from and writes back, d_states[state_index[i]] -- a batch
+    // keeps one per pair slot, whichever launch positions its pairs take.  upload_each (may be null = upload_states for every position):
+    // position i starts from states_in[i] instead of its device state.
+    int state_slots = 0;              // device states kept (at least the launch's pairs): a batch's max_pairs
     int launch(const std::vector<PairIn>& pairs, const PairState* states_in, bool upload_states, hipStream_t on_stream,
-               bool want_trace, int trace_cap) {
-        const int rc = launch_impl(pairs, states_in, upload_states, on_stream, want_trace, trace_cap);
+               bool want_trace, int trace_cap, const int* state_index = nullptr, const unsigned char* upload_each = nullptr) {
+        const int rc = launch_impl(pairs, states_in, upload_states, on_stream, want_trace, trace_cap, state_index, upload_each);
         if (rc != CVO_OK) release_slots();                            // nothing of this call is on the device
         return rc;
     }
     int launch_impl(const std::vector<PairIn>& pairs, const PairState* states_in, bool upload_states, hipStream_t on_stream,
-                    bool want_trace, int trace_cap) {
+                    bool want_trace, int trace_cap, const int* state_index, const unsigned char* upload_each) {
         HIP_TRY(hipSetDevice(device));
         const int n = (int)pairs.size();
         if (n <= 0) return fail(CVO_ERR_INVALID, "no pairs to align");
@@ -927,7 +931,7 @@ struct Engine {
         int rc;
         if ((rc = d_descs.ensure(sizeof(PairDesc) * n))) return rc;
         if ((rc = h_descs.ensure(sizeof(PairDesc) * n))) return rc;
-        if ((rc = d_states.ensure(sizeof(PairState) * n))) return rc;
+        if ((rc = d_states.ensure(sizeof(PairState) * (size_t)std::max(n, state_slots)))) return rc;
         if ((rc = d_records.grow_keep(sizeof(float) * CVO_RESULT_FLOATS * (size_t)std::max(n, rec_hint), 0, s))) return rc;
         if (n > pad_from) pad_from = pad_to = 0;                     // this launch writes over (some of) the padding records
         if ((rc = h_states.ensure(sizeof(PairState) * n))) return rc;
@@ -1055,8 +1059,8 @@ struct Engine {
             D.ent = static_cast<uint2*>(d_ent.p);
             D.surv = static_cast<uint2*>(d_surv.p);
             D.xch = static_cast<unsigned long long*>(d_xch.p) + (size_t)i * 2 * Gx * XCH_WORDS;
-            D.state = static_cast<PairState*>(d_states.p) + i;
-            D.state_in = upload_states ? static_cast<const PairState*>(h_states_in.p) + i : D.state;
+            D.state = static_cast<PairState*>(d_states.p) + (state_index ? state_index[i] : i);
+            D.state_in = (upload_each ? upload_each[i] != 0 : upload_states) ? static_cast<const PairState*>(h_states_in.p) + i : D.state;
             D.state_host = static_cast<PairState*>(h_states.p) + i;
             D.trace = (want_trace && i == 0) ? static_cast<TraceRow*>(d_trace.p) : nullptr;
             D.trace_cap = want_trace ? trace_cap : 0;
@@ -1080,7 +1084,9 @@ struct Engine {
             HIP_TRY(hipMemcpyAsync(d_descs.p, h_descs.p, sizeof(PairDesc) * n, hipMemcpyHostToDevice, s));
             descs_uploaded.assign(reinterpret_cast<const unsigned char*>(hd), reinterpret_cast<const unsigned char*>(hd) + sizeof(PairDesc) * n);
         }
-        if (upload_states) {
+        bool any_upload = upload_states && !upload_each;
+        for (int i = 0; upload_each && i < n && !any_upload; ++i) any_upload = upload_each[i] != 0;
+        if (any_upload) {
             if (launched) HIP_TRY(hipStreamSynchronize(last_stream));  // a queued launch of this engine may not have read its start states yet
             std::memcpy(h_states_in.p, states_in, sizeof(PairState) * n);
         }
@@ -1440,15 +1446,26 @@ struct cvo_handle_s {
 // and one slot of PCD_CLOUD_CAP points per image for its cloud.  Grows with the largest call, released by cvo_batch_destroy.
 constexpr int PCD_CLOUD_CAP = 65535;
 struct BatchImages {
-    DevBuf bgr, depth, I0, I1, I2, dx0, dy0, abs0, abs1, abs2, ths, thsS, map, pattern, tiles, rec, cloud, px;
-    PinBuf stage, h_rec;
+    DevBuf bgr, depth, I0, I1, I2, dx0, dy0, abs0, abs1, abs2, ths, thsS, map, pattern, tiles, rec, cloud, px, cams;
+    PinBuf stage, h_rec, h_cams;
     int n_cap = 0, w = 0, h = 0;
     int num_want = 3000;                                            // pcd_generator::num_want (pcd_generator.cpp:22)
     void release() {
-        for (DevBuf* b : {&bgr, &depth, &I0, &I1, &I2, &dx0, &dy0, &abs0, &abs1, &abs2, &ths, &thsS, &map, &pattern, &tiles, &rec, &cloud, &px}) b->release();
-        stage.release(); h_rec.release();
+        for (DevBuf* b : {&bgr, &depth, &I0, &I1, &I2, &dx0, &dy0, &abs0, &abs1, &abs2, &ths, &thsS, &map, &pattern, &tiles, &rec, &cloud, &px, &cams}) b->release();
+        stage.release(); h_rec.release(); h_cams.release();
         n_cap = w = h = 0;
     }
+};
+
+// A pair slot run as one cvo::cvo odometry object (cvo_batch_advance_images): the fields a handle carries from one align() into the next
+// (cvo_handle_s, do_align), kept on the host and uploaded as the slot's start state by every launch that lists it.
+struct StreamSlot {
+    bool on = false;                        // the slot is a stream (else a plain pair)
+    bool init = false;                      // its first frame is in: the FIXED cloud (cvo.cpp:352-360)
+    bool has_moving = false;                // a later frame is in: the MOVING cloud, possibly empty
+    float R[9], T[3], ell;
+    int iter = 0;
+    Aff transform, prev_transform, accum_transform;
 };
 
 struct cvo_batch_s {
@@ -1458,8 +1475,13 @@ struct cvo_batch_s {
     std::vector<std::unique_ptr<Cloud>> fixed, moving;
     BatchImages img;
     std::vector<PairState> init_states;     // what set_pair / set_state last gave
-    bool states_dirty = true;               // device states differ from init_states
+    std::vector<unsigned char> dirty;       // per slot: the plain pair's device state differs from init_states (set for every slot by any set_*, as one flag was)
+    std::vector<StreamSlot> streams;
     int last_n = 0;
+    std::vector<int> last_slots;            // the slot of every position of the last launch (positions = the caller's list order)
+    std::vector<unsigned char> last_stream_pos, last_not_run;   // ... which were stream slots, which had no moving cloud (not run: CVO_ERR_NOT_INITIALIZED)
+    bool settled = true;                    // the last launch's results have been taken in (batch_settle)
+    bool clouds_changed = false;            // a slot of the last launch has new clouds since: answers computed from its clouds would be for others
 };
 
 namespace {
@@ -1479,13 +1501,17 @@ void fresh_state(PairState& s, float ell) {
     s.R[0] = s.R[4] = s.R[8] = 1.f; s.ell = ell;
     s.transform[0] = s.transform[5] = s.transform[10] = 1.f;
 }
+// the start state of an alignment from the fields an odometry object carries (cvo_handle_s, cvo_batch_s::streams)
+void carried_state(PairState& st, const float R[9], const float T[3], float ell, int iter, const Aff& transform) {
+    fresh_state(st, ell);
+    std::memcpy(st.R, R, sizeof(st.R)); std::memcpy(st.T, T, sizeof(st.T));
+    st.iter = iter;
+    std::memcpy(st.transform, transform.m, sizeof(st.transform));
+}
 int do_align(cvo_handle_s* h, cvo_trace_row* trace, int trace_cap, int* trace_len) {
     if (trace_len) *trace_len = 0;
     if (!h->fixed || !h->moving || h->fixed->n <= 0 || h->moving->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "align: empty fixed or moving cloud");
-    PairState st; fresh_state(st, h->ell);
-    std::memcpy(st.R, h->R, sizeof(st.R)); std::memcpy(st.T, h->T, sizeof(st.T));
-    st.iter = h->iter;
-    std::memcpy(st.transform, h->transform.m, sizeof(st.transform));
+    PairState st; carried_state(st, h->R, h->T, h->ell, h->iter, h->transform);
     std::vector<Engine::PairIn> pairs{{h->fixed.get(), h->moving.get()}};
     const bool want_trace = trace && trace_cap > 0;
     h->tail_valid = false; h->queued_valid = false;
@@ -2142,6 +2168,87 @@ int cvo_selftest_pair_values(int device, const cvo_params* params, float ell, in
     return CVO_OK;
 }
 
+namespace {
+// The last launch's results taken in once it is over: listed slots that had no moving cloud get CVO_ERR_NOT_INITIALIZED (cvo.cpp:463-466),
+// and every stream slot that was aligned carries what its alignment left behind, exactly as do_align takes it into a handle (a failed
+// alignment leaves the object as it was).  A no-op unless the last launch listed stream slots.
+int batch_settle(cvo_batch b) {
+    if (b->settled) return CVO_OK;
+    b->settled = true;
+    int rc = b->eng.wait(); if (rc) return rc;
+    PairState* r = static_cast<PairState*>(b->eng.h_states.p);      // (pinned host memory the kernel wrote)
+    for (int i = 0; i < b->last_n; ++i) {
+        if (b->last_not_run[i]) { r[i].status = CVO_ERR_NOT_INITIALIZED; continue; }
+        if (!b->last_stream_pos[i] || r[i].status != CVO_OK) continue;
+        StreamSlot& S = b->streams[b->last_slots[i]];
+        std::memcpy(S.R, r[i].R, sizeof(S.R)); std::memcpy(S.T, r[i].T, sizeof(S.T));
+        S.ell = r[i].ell; S.iter = r[i].iter;
+        Aff prev; std::memcpy(prev.m, r[i].prev_transform, sizeof(prev.m));
+        S.prev_transform = prev;                                     // cvo.cpp:815
+        S.accum_transform = aff_mul(S.accum_transform, prev);        // cvo.cpp:816
+        std::memcpy(S.transform.m, r[i].transform, sizeof(S.transform.m));   // update_tf, cvo.cpp:817
+    }
+    return CVO_OK;
+}
+// a fresh cvo::cvo in slot p (cvo.cpp:28-70): no clouds, R = I, T = 0, ell = params.ell, every transform I
+void fresh_stream(cvo_batch b, int p) {
+    StreamSlot& S = b->streams[p];
+    S = StreamSlot();
+    S.on = true;
+    const float I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::memcpy(S.R, I, sizeof(I)); S.T[0] = S.T[1] = S.T[2] = 0.f; S.ell = b->prm.ell;
+    S.transform = S.prev_transform = S.accum_transform = aff_identity();
+    for (Cloud* c : {b->fixed[p].get(), b->moving[p].get()})
+        if (c) { c->n = 0; c->n_px = 0; c->boxes_valid = false; c->raw = nullptr; c->raw_feat = nullptr; c->cost_hint = 0.f; }
+}
+// what every set_* did to the single flag it had: each plain pair starts its next launch from init_states again.  Slots set here stop being streams.
+void states_dirty(cvo_batch b) { std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)1); }
+void end_stream(cvo_batch b, int p) { if (b->streams[p].on) { b->streams[p] = StreamSlot(); fresh_state(b->init_states[p], b->prm.ell); } }
+// A slot of the last launch got new clouds: answers held for them (score blocks computed from the slots' clouds) would be for others
+void slot_clouds_changed(cvo_batch b, int p) {
+    for (int i = 0; i < b->last_n && !b->clouds_changed; ++i) b->clouds_changed = b->last_slots[i] == p;
+}
+int check_last_clouds(cvo_batch b) {
+    return b->clouds_changed ? fail(CVO_ERR_INVALID, "the clouds of a slot of the last launch have changed since (cvo_batch_advance_images / cvo_batch_reset_stream)") : CVO_OK;
+}
+// One persistent launch over the listed slots, position i = slots[i].  Plain pairs start from init_states when marked dirty, else from their
+// device state; stream slots from the state they carry, like a handle's align(); a stream slot without a moving cloud takes a position that
+// runs nothing (no moving cloud: the kernel leaves at once) and its entry reads CVO_ERR_NOT_INITIALIZED.  clean_all: every plain pair counts as
+// started afterwards (cvo_batch_align_async, as the single flag was cleared), else only the listed ones.
+int batch_launch(cvo_batch b, const int* slots, int n, hipStream_t stream, bool clean_all) {
+    int rc = batch_settle(b); if (rc) return rc;
+    std::vector<Engine::PairIn> pairs(n);
+    std::vector<PairState> st(n);
+    std::vector<unsigned char> up(n, 0), is_stream(n, 0), not_run(n, 0);
+    bool any_stream = false;
+    for (int i = 0; i < n; ++i) {
+        const int p = slots[i];
+        const StreamSlot& S = b->streams[p];
+        pairs[i] = Engine::PairIn{b->fixed[p].get(), b->moving[p].get()};
+        if (S.on) {
+            any_stream = true; is_stream[i] = 1; up[i] = 1;
+            carried_state(st[i], S.R, S.T, S.ell, S.iter, S.transform);
+            if (!S.has_moving) { not_run[i] = 1; pairs[i].moving = nullptr; if (!S.init) pairs[i].fixed = nullptr; }
+        } else {
+            up[i] = b->dirty[p]; st[i] = b->init_states[p];
+        }
+    }
+    rc = b->eng.launch(pairs, st.data(), false, stream, false, 0, slots, up.data());
+    if (rc) return rc;
+    if (clean_all) std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)0);   // device states now evolve launch to launch (warm start) until reset
+    else for (int i = 0; i < n; ++i) if (!is_stream[i]) b->dirty[slots[i]] = 0;
+    b->last_n = n;
+    b->last_slots.assign(slots, slots + n); b->last_stream_pos = is_stream; b->last_not_run = not_run;
+    b->settled = !any_stream; b->clouds_changed = false;
+    for (int i = 0; i < n; ++i) {
+        if (!not_run[i]) continue;
+        const hipError_t e = launch_fill_records(static_cast<float*>(b->eng.d_records.p), i, i + 1, CVO_ERR_NOT_INITIALIZED, b->eng.last_stream);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("record fill kernel launch: ") + hipGetErrorString(e));
+    }
+    return CVO_OK;
+}
+}  // namespace
+
 int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* out) {
     if (!out || max_pairs <= 0) return fail(CVO_ERR_INVALID, "bad argument");
     *out = nullptr;
@@ -2155,6 +2262,9 @@ int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* 
     b->fixed.resize(max_pairs); b->moving.resize(max_pairs);
     b->init_states.resize(max_pairs);
     for (auto& s : b->init_states) fresh_state(s, b->prm.ell);
+    b->dirty.assign(max_pairs, 1);
+    b->streams.resize(max_pairs);
+    b->eng.state_slots = max_pairs;                                 // a device state per slot, whichever positions its launches give it
     *out = b.release();
     return CVO_OK;
 }
@@ -2171,46 +2281,46 @@ int cvo_batch_destroy(cvo_batch b) {
 int cvo_batch_set_pair(cvo_batch b, int p, const float* fixed_xyz, const float* fixed_feat, int n_fixed,
                        const float* moving_xyz, const float* moving_feat, int n_moving) {
     if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair index");
+    int rc = batch_settle(b); if (rc) return rc;
     if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
     if (!b->moving[p]) b->moving[p].reset(new Cloud());
-    int rc = b->eng.upload(*b->fixed[p], fixed_xyz, fixed_feat, n_fixed); if (rc) return rc;
+    end_stream(b, p);
+    rc = b->eng.upload(*b->fixed[p], fixed_xyz, fixed_feat, n_fixed); if (rc) return rc;
     rc = b->eng.upload(*b->moving[p], moving_xyz, moving_feat, n_moving); if (rc) return rc;
     fresh_state(b->init_states[p], b->prm.ell);
-    b->states_dirty = true;
+    states_dirty(b);
     return CVO_OK;
 }
 int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* fixed_xyz, const float* const* fixed_feat, const int* n_fixed,
                         const float* const* moving_xyz, const float* const* moving_feat, const int* n_moving) {
     if (!b || first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
     if (!fixed_xyz || !fixed_feat || !n_fixed || !moving_xyz || !moving_feat || !n_moving) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = batch_settle(b); if (rc) return rc;
     std::vector<Engine::UploadItem> items; items.reserve(2 * (size_t)count);
     for (int k = 0; k < count; ++k) {
         const int p = first + k;
+        end_stream(b, p);
         if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
         if (!b->moving[p]) b->moving[p].reset(new Cloud());
         items.push_back(Engine::UploadItem{b->fixed[p].get(), fixed_xyz[k], fixed_feat[k], n_fixed[k]});
         items.push_back(Engine::UploadItem{b->moving[p].get(), moving_xyz[k], moving_feat[k], n_moving[k]});
     }
-    int rc = b->eng.upload_many(items.data(), (int)items.size()); if (rc) return rc;
+    rc = b->eng.upload_many(items.data(), (int)items.size()); if (rc) return rc;
     for (int k = 0; k < count; ++k) fresh_state(b->init_states[first + k], b->prm.ell);
-    b->states_dirty = true;
+    states_dirty(b);
     return CVO_OK;
 }
 
-// ---- pairs from RGB-D images: every image generated once by the batched generator (cvo_pcd_kernels.hip, a fixed list of launches over all
-// images, makeMaps decided on the device), ONE host sync for the point counts, then each pair's clouds copied from their images' slots
-int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
-                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
-    if (!b || first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
-    if (!bgr8 || !depth16 || !cam || !fixed_image || !moving_image) return fail(CVO_ERR_INVALID, "null argument");
-    if (n_images <= 0 || n_images > 65535) return fail(CVO_ERR_INVALID, "bad image count");
-    if (width < 64 || height < 64 || (size_t)width * height > (size_t)1 << 26) return fail(CVO_ERR_INVALID, "image size out of range");
-    for (int k = 0; k < n_images; ++k) if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
-    for (int k = 0; k < count; ++k)
-        if (fixed_image[k] < 0 || fixed_image[k] >= n_images || moving_image[k] < 0 || moving_image[k] >= n_images) return fail(CVO_ERR_INVALID, "image index out of range");
+// ---- clouds from RGB-D images: every image generated once by the batched generator (cvo_pcd_kernels.hip, a fixed list of launches over all
+// images, makeMaps decided on the device), ONE host sync for the point counts, then each destination cloud copied from its image's slot
+namespace {
+// The clouds of N images (all w x h) into the images' slots of b->img.cloud / px; *recs: their records on the host.  cam: one camera for all,
+// or cam_table (host, N cameras): a camera per image.  Nothing of the batch's pairs changes.
+int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height, const cvo_camera* cam,
+                   const cvo_camera* cam_table, const PcdImgRec** recs) {
     Engine& E = b->eng; BatchImages& S = b->img;
     HIP_TRY(hipSetDevice(E.device));
-    const int N = n_images, w = width, h = height, num_want = S.num_want;
+    const int w = width, h = height, num_want = S.num_want;
     const size_t n = (size_t)w * h, n1 = (size_t)(w / 2) * (h / 2), n2 = (size_t)(w / 4) * (h / 4), nths = (size_t)(w / 32) * (h / 32) + 100;
     const int nt = pcd_tiles(w, h), cap = PCD_CLOUD_CAP;
     int rc;
@@ -2233,6 +2343,7 @@ int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, 
         }
         S.n_cap = (int)m; S.w = w; S.h = h;
     }
+    if (cam_table && ((rc = S.cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)) || (rc = S.h_cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)))) return rc;
     hipStream_t s = E.stream;
     unsigned char* st = static_cast<unsigned char*>(S.stage.p);
     {
@@ -2253,10 +2364,16 @@ int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, 
         unsigned char* sd = st + 3 * n * N;
         for (int k = 0; k < N; ++k) std::memcpy(sd + 2 * n * k, depth16[k], 2 * n);
         HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
-        const float camv[5] = {cam->scaling_factor, cam->fx, cam->fy, cam->cx, cam->cy};
+        const cvo_camera& c0 = cam ? *cam : cam_table[0];
+        const float camv[5] = {c0.scaling_factor, c0.fx, c0.fy, c0.cx, c0.cy};
+        if (cam_table) {
+            std::memcpy(S.h_cams.p, cam_table, sizeof(cvo_camera) * (size_t)N);
+            HIP_TRY(hipMemcpyAsync(S.cams.p, S.h_cams.p, sizeof(cvo_camera) * (size_t)N, hipMemcpyHostToDevice, s));
+        }
         e = pcd_launch_subsample_batch((uint8_t*)S.map.p, (const uint8_t*)S.pattern.p, rec, num_want, (const uint16_t*)S.depth.p, w, h, (int*)S.tiles.p, N, s);
         if (e == hipSuccess) e = pcd_launch_cloud_batch((const uint8_t*)S.map.p, (const uint16_t*)S.depth.p, (const uint8_t*)S.bgr.p, (const float*)S.dx0.p, (const float*)S.dy0.p,
-                                                        w, h, camv, (const int*)S.tiles.p, rec, cap, (float*)S.cloud.p, (uint16_t*)S.px.p, N, s);
+                                                        w, h, camv, cam_table ? (const float*)S.cams.p : nullptr, (const int*)S.tiles.p, rec, cap, (float*)S.cloud.p,
+                                                        (uint16_t*)S.px.p, N, s);
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
         HIP_TRY(hipMemcpyAsync(S.h_rec.p, S.rec.p, sizeof(PcdImgRec) * N, hipMemcpyDeviceToHost, s));
     }                                                                 // (the one sync: Drain)
@@ -2264,17 +2381,19 @@ int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, 
     const PcdImgRec* R = static_cast<const PcdImgRec*>(S.h_rec.p);
     for (int k = 0; k < N; ++k)
         if (R[k].npts > cap) return fail(CVO_ERR_INVALID, "image " + std::to_string(k) + ": more than 65535 points per cloud is not supported (16-bit column indices)");
-    // commit: the pairs take their clouds (a launch on a caller's stream may still read the clouds they had)
+    *recs = R;
+    return CVO_OK;
+}
+// clouds dst[j] <- image img[j]'s cloud of the last batch_generate (the scatter kernel, up to PCD_SCATTER_MAX clouds per launch); buffers are made first
+int batch_scatter(cvo_batch b, const std::vector<Cloud*>& dst, const std::vector<int>& img, const PcdImgRec* R) {
+    Engine& E = b->eng; BatchImages& S = b->img;
+    const hipStream_t s = E.stream; const int cap = PCD_CLOUD_CAP;
+    int rc;
+    // (a launch on a caller's stream may still read the clouds they had)
     if (E.launched && E.last_stream && E.last_stream != s) HIP_TRY(hipStreamSynchronize(E.last_stream));
-    for (int k = 0; k < count; ++k) {
-        const int p = first + k;
-        if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
-        if (!b->moving[p]) b->moving[p].reset(new Cloud());
-        for (int side = 0; side < 2; ++side) {
-            Cloud& c = side ? *b->moving[p] : *b->fixed[p];
-            const int np = R[side ? moving_image[k] : fixed_image[k]].npts;
-            if (np > 0 && ((rc = c.buf.ensure((size_t)np * REC * sizeof(float))) || (rc = c.px.ensure((size_t)np * 2 * sizeof(uint16_t))))) return rc;
-        }
+    for (size_t j = 0; j < dst.size(); ++j) {
+        const int np = R[img[j]].npts;
+        if (np > 0 && ((rc = dst[j]->buf.ensure((size_t)np * REC * sizeof(float))) || (rc = dst[j]->px.ensure((size_t)np * 2 * sizeof(uint16_t))))) return rc;
     }
     PcdScatter sc; std::memset(&sc, 0, sizeof(sc));
     sc.src = (const float*)S.cloud.p; sc.src_px = (const uint16_t*)S.px.p; sc.rec = (const PcdImgRec*)S.rec.p; sc.cap = cap;
@@ -2284,24 +2403,106 @@ int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, 
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd scatter: ") + hipGetErrorString(e));
         sc.n = 0; n_max = 0; return CVO_OK;
     };
-    for (int k = 0; k < count; ++k) {
-        const int p = first + k;
-        for (int side = 0; side < 2; ++side) {
-            Cloud& c = side ? *b->moving[p] : *b->fixed[p];
-            const int im = side ? moving_image[k] : fixed_image[k];
-            const PcdImgRec& r = R[im];
-            c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr;   // (a hand-over not packed yet is dropped)
-            c.cost_hint = r.cost_n > 0 ? (float)(r.cost / r.cost_n) : 0.f;
-            if (c.n <= 0) continue;
-            sc.img[sc.n] = im; sc.dst[sc.n] = c.rec(); sc.dst_px[sc.n] = (uint16_t*)c.px.p; ++sc.n; n_max = std::max(n_max, c.n);
-            if (sc.n == PCD_SCATTER_MAX && (rc = flush())) return rc;
-        }
+    for (size_t j = 0; j < dst.size(); ++j) {
+        Cloud& c = *dst[j];
+        const PcdImgRec& r = R[img[j]];
+        c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr;   // (a hand-over not packed yet is dropped)
+        c.cost_hint = r.cost_n > 0 ? (float)(r.cost / r.cost_n) : 0.f;
+        if (c.n <= 0) continue;
+        sc.img[sc.n] = img[j]; sc.dst[sc.n] = c.rec(); sc.dst_px[sc.n] = (uint16_t*)c.px.p; ++sc.n; n_max = std::max(n_max, c.n);
+        if (sc.n == PCD_SCATTER_MAX && (rc = flush())) return rc;
     }
     if (sc.n > 0 && (rc = flush())) return rc;
     E.uploads_pending = true;                                         // (a launch on another stream waits for the copies: settle_uploads)
+    return CVO_OK;
+}
+bool image_size_ok(int width, int height) { return width >= 64 && height >= 64 && (size_t)width * height <= (size_t)1 << 26; }
+}  // namespace
+
+int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
+    if (!b || first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
+    if (!bgr8 || !depth16 || !cam || !fixed_image || !moving_image) return fail(CVO_ERR_INVALID, "null argument");
+    if (n_images <= 0 || n_images > 65535) return fail(CVO_ERR_INVALID, "bad image count");
+    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
+    for (int k = 0; k < n_images; ++k) if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+    for (int k = 0; k < count; ++k)
+        if (fixed_image[k] < 0 || fixed_image[k] >= n_images || moving_image[k] < 0 || moving_image[k] >= n_images) return fail(CVO_ERR_INVALID, "image index out of range");
+    int rc = batch_settle(b); if (rc) return rc;
+    const PcdImgRec* R = nullptr;
+    if ((rc = batch_generate(b, n_images, bgr8, depth16, width, height, cam, nullptr, &R))) return rc;
+    // commit: the pairs take their clouds
+    std::vector<Cloud*> dst; std::vector<int> img;
+    for (int k = 0; k < count; ++k) {
+        const int p = first + k;
+        end_stream(b, p);
+        if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
+        if (!b->moving[p]) b->moving[p].reset(new Cloud());
+        dst.push_back(b->fixed[p].get()); img.push_back(fixed_image[k]);
+        dst.push_back(b->moving[p].get()); img.push_back(moving_image[k]);
+    }
+    if ((rc = batch_scatter(b, dst, img, R))) return rc;
     for (int k = 0; k < count; ++k) fresh_state(b->init_states[first + k], b->prm.ell);
-    b->states_dirty = true;
-    if (points_out) for (int k = 0; k < N; ++k) points_out[k] = R[k].npts;
+    states_dirty(b);
+    if (points_out) for (int k = 0; k < n_images; ++k) points_out[k] = R[k].npts;
+    return CVO_OK;
+}
+// ---- K-stream odometry: slot p is one cvo::cvo object that takes a frame per call (cvo_main's loop, cvo.cpp:352-386 + 461-473 + 578-582)
+int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                             const cvo_camera* cams, const int* cam_index, int* points_out) {
+    if (!b || count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad image count");
+    if (!slots || !bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
+    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
+    std::vector<unsigned char> seen(b->max_pairs, 0);
+    for (int k = 0; k < count; ++k) {
+        if (slots[k] < 0 || slots[k] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
+        if (seen[slots[k]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
+        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+        if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
+    }
+    int rc = batch_settle(b); if (rc) return rc;
+    std::vector<cvo_camera> cam_of(count);
+    for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
+    const PcdImgRec* R = nullptr;
+    if ((rc = batch_generate(b, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (fails before any slot changes)
+    // commit.  A started slot's moving cloud becomes its fixed cloud by a move of ownership (update_fixed_pcd, cvo.cpp:578-582); the cloud object it
+    // held as the fixed one is taken for the new moving cloud, whose points the scatter overwrites (its boxes and cached self products are dropped)
+    std::vector<Cloud*> dst; std::vector<int> img;
+    for (int k = 0; k < count; ++k) {
+        const int p = slots[k];
+        if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
+        if (!b->moving[p]) b->moving[p].reset(new Cloud());
+        if (!b->streams[p].on) fresh_stream(b, p);
+        StreamSlot& S = b->streams[p];
+        slot_clouds_changed(b, p);
+        if (!S.init) {                                                // cvo.cpp:352-360: the first frame only fills the fixed cloud
+            S.init = true;
+            dst.push_back(b->fixed[p].get());
+        } else {
+            if (S.has_moving) std::swap(b->fixed[p], b->moving[p]);
+            S.has_moving = true;
+            dst.push_back(b->moving[p].get());
+        }
+        img.push_back(k);
+    }
+    if ((rc = batch_scatter(b, dst, img, R))) return rc;
+    if (points_out) for (int k = 0; k < count; ++k) points_out[k] = R[k].npts;
+    return CVO_OK;
+}
+int cvo_batch_reset_stream(cvo_batch b, int p) {
+    if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad slot index");
+    int rc = batch_settle(b); if (rc) return rc;
+    if (b->eng.launched && b->eng.last_stream) HIP_TRY(hipStreamSynchronize(b->eng.last_stream));   // (a launch may still read the clouds; their memory is kept)
+    slot_clouds_changed(b, p);
+    fresh_stream(b, p);
+    return CVO_OK;
+}
+int cvo_batch_get_prev_accum_transform(cvo_batch b, int p, float prev_transform[12], float accum_transform[12]) {
+    if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad slot index");
+    int rc = batch_settle(b); if (rc) return rc;
+    if (!b->streams[p].on) return fail(CVO_ERR_INVALID, "slot is not a stream (cvo_batch_advance_images / cvo_batch_reset_stream)");
+    if (prev_transform) std::memcpy(prev_transform, b->streams[p].prev_transform.m, sizeof(float) * 12);
+    if (accum_transform) std::memcpy(accum_transform, b->streams[p].accum_transform.m, sizeof(float) * 12);
     return CVO_OK;
 }
 int cvo_batch_set_num_want(cvo_batch b, int num_want) {
@@ -2347,9 +2548,11 @@ int cvo_host_unregister(void* ptr) {
 }
 int cvo_batch_set_state(cvo_batch b, int p, const float R[9], const float T[3], float ell) {
     if (!b || p < 0 || p >= b->max_pairs || !R || !T) return fail(CVO_ERR_INVALID, "bad argument");
+    int rc = batch_settle(b); if (rc) return rc;
+    end_stream(b, p);
     std::memcpy(b->init_states[p].R, R, sizeof(float) * 9); std::memcpy(b->init_states[p].T, T, sizeof(float) * 3);
     b->init_states[p].ell = ell;
-    b->states_dirty = true;
+    states_dirty(b);
     return CVO_OK;
 }
 int cvo_batch_set_workgroups(cvo_batch b, int workgroups_per_pair) {
@@ -2381,21 +2584,31 @@ int cvo_batch_last_adoption_retractions(cvo_batch b, int* retractions) {
     for (int i = 0; i < b->last_n; ++i) n += r[i].adopt_retracted;
     *retractions = n; return CVO_OK;
 }
-int cvo_batch_reset_states(cvo_batch b) { if (!b) return fail(CVO_ERR_INVALID, "null batch"); b->states_dirty = true; return CVO_OK; }
+int cvo_batch_reset_states(cvo_batch b) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    int rc = batch_settle(b); if (rc) return rc;
+    states_dirty(b);                                                  // (stream slots carry their own state: untouched)
+    return CVO_OK;
+}
 
 int cvo_batch_align_async(cvo_batch b, int n_pairs, void* stream) {
     if (!b || n_pairs <= 0 || n_pairs > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair count");
-    std::vector<Engine::PairIn> pairs(n_pairs);
-    for (int i = 0; i < n_pairs; ++i) pairs[i] = Engine::PairIn{b->fixed[i].get(), b->moving[i].get()};
-    int rc = b->eng.launch(pairs, b->init_states.data(), b->states_dirty, static_cast<hipStream_t>(stream), false, 0);
-    if (rc) return rc;
-    b->states_dirty = false;      // device states now evolve launch to launch (warm start) until reset
-    b->last_n = n_pairs;
-    return CVO_OK;
+    std::vector<int> slots(n_pairs);
+    for (int i = 0; i < n_pairs; ++i) slots[i] = i;
+    return batch_launch(b, slots.data(), n_pairs, static_cast<hipStream_t>(stream), true);
+}
+int cvo_batch_align_pairs_async(cvo_batch b, int count, const int* slots, void* stream) {
+    if (!b || !slots || count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad slot list");
+    std::vector<unsigned char> seen(b->max_pairs, 0);
+    for (int i = 0; i < count; ++i) {
+        if (slots[i] < 0 || slots[i] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
+        if (seen[slots[i]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
+    }
+    return batch_launch(b, slots, count, static_cast<hipStream_t>(stream), false);
 }
 int cvo_batch_wait(cvo_batch b, cvo_pair_result* results, int n) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");
-    int rc = b->eng.wait(); if (rc) return rc;
+    int rc = b->settled ? b->eng.wait() : batch_settle(b); if (rc) return rc;
     if (results) {
         if (n > b->last_n) return fail(CVO_ERR_INVALID, "more results requested than pairs launched");
         const PairState* r = b->eng.results();
@@ -2487,11 +2700,13 @@ int cvo_batch_compute_innerproduct_lc(cvo_batch b, int n, const float* prior_tra
                                       cvo_lc_scores* out) {
     if (!b || !prior_tran || !lc_prior_tran || !lc_prior_tran_2 || !out) return fail(CVO_ERR_INVALID, "null argument");
     if (n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
-    int rc = b->eng.wait(); if (rc) return rc;
+    int rc = check_last_clouds(b); if (rc) return rc;
+    rc = b->settled ? b->eng.wait() : batch_settle(b); if (rc) return rc;
     const PairState* res = b->eng.results();
     std::vector<Engine::ScoreReq> rq((size_t)n * 8);
     for (int i = 0; i < n; ++i) {
-        const Cloud* fx = b->fixed[i].get(); const Cloud* mv = b->moving[i].get();
+        const int p = b->last_slots[i];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
         if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "compute_innerproduct_lc: empty cloud in the batch");
         const float* lc_tran = res[i].transform;                     // lc_post = result.transform, keyframe_graph.cpp:702
         const float ell = res[i].ell;                                // the ell align() left behind (Q1), cvo.cpp:395
@@ -2528,16 +2743,18 @@ int cvo_batch_compute_innerproduct_lc(cvo_batch b, int n, const float* prior_tra
 int cvo_batch_enqueue_innerproduct(cvo_batch b, int n) {
     if (!b) return fail(CVO_ERR_INVALID, "null argument");
     if (n <= 0 || n > b->last_n || !b->eng.launched) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
+    int rc = check_last_clouds(b); if (rc) return rc;
     std::vector<Engine::ScoreReq> rq((size_t)n * 5);
     for (int i = 0; i < n; ++i) {
-        const Cloud* fx = b->fixed[i].get(); const Cloud* mv = b->moving[i].get();
+        const int p = b->last_slots[i];                              // (its device state: the slot's, Engine::launch's state_index)
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
         if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "compute_innerproduct: empty cloud in the batch");
         Engine::ScoreReq* q = &rq[(size_t)i * 5];
-        q[0] = {mv, nullptr, fx, false, 0.f, i, false};              // cvo.cpp:489
-        q[1] = {mv, nullptr, fx, false, 0.f, i, true};               // cvo.cpp:491
-        q[2] = {fx, nullptr, fx, false, 0.f, i, false};              // cvo.cpp:496
-        q[3] = {mv, nullptr, mv, false, 0.f, i, false};              // cvo.cpp:497
-        q[4] = {mv, nullptr, fx, true, 0.f, i, true};                // cvo.cpp:500
+        q[0] = {mv, nullptr, fx, false, 0.f, p, false};              // cvo.cpp:489
+        q[1] = {mv, nullptr, fx, false, 0.f, p, true};               // cvo.cpp:491
+        q[2] = {fx, nullptr, fx, false, 0.f, p, false};              // cvo.cpp:496
+        q[3] = {mv, nullptr, mv, false, 0.f, p, false};              // cvo.cpp:497
+        q[4] = {mv, nullptr, fx, true, 0.f, p, true};                // cvo.cpp:500
     }
     return b->eng.score_enqueue(rq.data(), n * 5, b->eng.last_stream);
 }
@@ -2547,15 +2764,17 @@ namespace {
 // computed by the score kernel now, all missing requests of the batch in one launch
 int collect_tail_scores(cvo_batch b, int n, double* r /* n x 5 x 24 */) {
     if (n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
-    int rc = b->eng.wait(); if (rc) return rc;
+    int rc = check_last_clouds(b); if (rc) return rc;
+    rc = b->settled ? b->eng.wait() : batch_settle(b); if (rc) return rc;
     std::memcpy(r, b->eng.h_tail.p, sizeof(double) * (size_t)n * 5 * 24);
     static const int bit_of[5] = {TAIL_PRE, TAIL_POST, TAIL_FIXED, TAIL_MOVING, TAIL_HESSIAN};
     std::vector<Engine::ScoreReq> rq; std::vector<int> where;
     for (int i = 0; i < n; ++i) {
         const int mask = (int)r[(size_t)i * 120 + 23];
-        const Cloud* fx = b->fixed[i].get(); const Cloud* mv = b->moving[i].get();
-        const Engine::ScoreReq all[5] = {{mv, nullptr, fx, false, 0.f, i, false}, {mv, nullptr, fx, false, 0.f, i, true}, {fx, nullptr, fx, false, 0.f, i, false},
-                                         {mv, nullptr, mv, false, 0.f, i, false}, {mv, nullptr, fx, true, 0.f, i, true}};   // cvo.cpp:489, 491, 496, 497, 500
+        const int p = b->last_slots[i];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
+        const Engine::ScoreReq all[5] = {{mv, nullptr, fx, false, 0.f, p, false}, {mv, nullptr, fx, false, 0.f, p, true}, {fx, nullptr, fx, false, 0.f, p, false},
+                                         {mv, nullptr, mv, false, 0.f, p, false}, {mv, nullptr, fx, true, 0.f, p, true}};   // cvo.cpp:489, 491, 496, 497, 500
         for (int q = 0; q < 5; ++q) if (!(mask & bit_of[q])) { rq.push_back(all[q]); where.push_back(i * 5 + q); }
     }
     if (!rq.empty()) {

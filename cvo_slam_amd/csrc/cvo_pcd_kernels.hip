@@ -299,13 +299,16 @@ __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_subsample_kernel(uint8_t
 }
 
 // rec (not null, batches): the point count comes from the image's tile counts (and goes to rec), the cloud to the image's slot of `cap`
-// points (a count above cap writes nothing: the host refuses the call), and the points sampled for Cloud::cost_hint add up in rec
+// points (a count above cap writes nothing: the host refuses the call), and the points sampled for Cloud::cost_hint add up in rec.
+// cams (not null, batches of several cameras: cvo_batch_advance_images): image blockIdx.y is back-projected with cams[blockIdx.y], else with cam0
 __global__ __launch_bounds__(PCD_TILE_THREADS) void pcd_cloud_kernel(const uint8_t* __restrict__ map, const uint16_t* __restrict__ depth, const uint8_t* __restrict__ bgr,
-                                                                     const float* __restrict__ dx0, const float* __restrict__ dy0, int w, int n, PcdCam cam,
+                                                                     const float* __restrict__ dx0, const float* __restrict__ dy0, int w, int n, PcdCam cam0,
+                                                                     const PcdCam* __restrict__ cams,
                                                                      const int* __restrict__ tile_valid, int n_points, float* __restrict__ cloud,
                                                                      uint16_t* __restrict__ px, PcdImgRec* __restrict__ rec, int cap) {
     __shared__ int wsum[PCD_TILE_THREADS / 64];
     const int base = blockIdx.x * PCD_TILE, nt = (n + PCD_TILE - 1) / PCD_TILE, img = blockIdx.y;
+    const PcdCam cam = cams ? cams[img] : cam0;
     map += (size_t)n * img; depth += (size_t)n * img; bgr += (size_t)3 * n * img; dx0 += (size_t)n * img; dy0 += (size_t)n * img;
     tile_valid += (size_t)3 * nt * img;
     if (rec) {
@@ -456,16 +459,19 @@ hipError_t pcd_launch_cloud(const uint8_t* map, const uint16_t* depth, const uin
                             const int* tile_counts, int n_points, float* cloud, uint16_t* px, hipStream_t s) {
     const int nt = pcd_tiles(w, h);
     PcdCam c{cam[0], cam[1], cam[2], cam[3], cam[4]};
-    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, tile_counts + nt, n_points, cloud, px,
-                       (PcdImgRec*)nullptr, 0);
+    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, (const PcdCam*)nullptr, tile_counts + nt, n_points,
+                       cloud, px, (PcdImgRec*)nullptr, 0);
     return hipGetLastError();
 }
-// every image's cloud into its slot of `cap` points (cap * REC floats, cap * 2 pixel coordinates); counts and cost samples into rec
+// every image's cloud into its slot of `cap` points (cap * REC floats, cap * 2 pixel coordinates); counts and cost samples into rec.
+// cam_table (device, n_img x 5 floats, may be null): a camera per image instead of `cam` for all
 hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
-                                  const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s) {
+                                  const float* cam_table, const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s) {
+    static_assert(sizeof(PcdCam) == 5 * sizeof(float), "camera table layout");
     const int nt = pcd_tiles(w, h);
     PcdCam c{cam[0], cam[1], cam[2], cam[3], cam[4]};
-    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt, n_img), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, tile_counts + nt, 0, cloud, px, rec, cap);
+    hipLaunchKernelGGL(pcd_cloud_kernel, dim3(nt, n_img), dim3(PCD_TILE_THREADS), 0, s, map, depth, bgr, dx0, dy0, w, w * h, c, reinterpret_cast<const PcdCam*>(cam_table),
+                       tile_counts + nt, 0, cloud, px, rec, cap);
     return hipGetLastError();
 }
 hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s) {

@@ -214,3 +214,95 @@ def replay_sequence(folder: str, assoc: str, calib: str, out_path: str, max_fram
     poses, info = replay_odometry(frames, cam, device=device, arith=arith)
     write_trajectory(out_path, [e[0] for e in entries], poses)
     return poses, info
+
+
+# ----------------------------------------------------------------------------- many sequences at once (cvo_batch_advance_images)
+def plan_replay(lengths, n_slots: int, starts=None):
+    """Which sequence is in which slot at which step of `replay_odometry_many`: a pure function, so that it can be checked without a GPU.
+
+    lengths[i]: frames of sequence i; starts[i] (default 0): the first step it may take; n_slots: the batch's slots.  A waiting sequence takes
+    the lowest free slot, in sequence order; a slot is free again one step after its sequence's last frame.  Returns one dict per step that
+    does something: step (its number), resets (slots that held another sequence before: cvo_batch_reset_stream first), advance (a list of
+    (slot, sequence, frame)), align (the (slot, sequence, frame) of the advanced frames with frame >= 1, in slot order)."""
+    lengths = [int(n) for n in lengths]
+    starts = [0] * len(lengths) if starts is None else [int(s) for s in starts]
+    if len(starts) != len(lengths) or any(n < 0 for n in lengths) or any(s < 0 for s in starts) or n_slots <= 0:
+        raise ValueError("plan_replay: one non-negative length and start per sequence, at least one slot")
+    waiting = [i for i in range(len(lengths)) if lengths[i] > 0]
+    slot_seq = [None] * n_slots            # (sequence, next frame) per slot
+    used = [False] * n_slots
+    plan, step = [], 0
+    while waiting or any(s is not None for s in slot_seq):
+        resets = []
+        for i in [i for i in waiting if starts[i] <= step]:
+            free = [p for p in range(n_slots) if slot_seq[p] is None]
+            if not free:
+                break
+            p = free[0]
+            if used[p]:
+                resets.append(p)
+            slot_seq[p] = (i, 0); used[p] = True
+            waiting.remove(i)
+        advance = [(p, q[0], q[1]) for p, q in enumerate(slot_seq) if q is not None]
+        if advance:
+            plan.append(dict(step=step, resets=resets, advance=advance, align=[a for a in advance if a[2] >= 1]))
+        for p, i, f in advance:
+            slot_seq[p] = (i, f + 1) if f + 1 < lengths[i] else None
+        step += 1
+    return plan
+
+
+def group_by_size(items, size_of):
+    """items grouped by size_of(item), in the order the sizes first occur: one advance call per image size (cvo_batch_advance_images takes one size)."""
+    groups = {}
+    for it in items:
+        groups.setdefault(size_of(it), []).append(it)
+    return list(groups.values())
+
+
+def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None):
+    """`replay_odometry` for many sequences at once on one CvoBatch: each slot is one odometry object (cvo_batch_advance_images), every step
+    advances each running sequence by one frame -- one advance call per image size -- and aligns all of them in ONE launch
+    (cvo_batch_align_pairs_async).  sequences[i]: a sequence of (bgr8, depth16) frames (len() and indexing; frames are read in order, once);
+    cameras[i]: its (scaling_factor, fx, fy, cx, cy).  slots: the batch's slots (default: one per sequence; fewer reuse slots through
+    cvo_batch_reset_stream); starts: the step each sequence may start at (plan_replay).  Returns [(poses, info), ...], per sequence what
+    `replay_odometry` returns for it alone (poses chained on the host the same way).  A failed alignment raises CvoError as it does there."""
+    import cvo_slam_amd as ca
+    from .api import CVO_OK, CvoError
+    n_seq = len(sequences)
+    if len(cameras) != n_seq:
+        raise ValueError("one camera per sequence")
+    n_slots = n_seq if slots is None else int(slots)
+    plan = plan_replay([len(s) for s in sequences], max(1, n_slots), starts)
+    B = ca.CvoBatch(max(1, n_slots), params, device=device)
+    try:
+        B.set_num_want(num_want)
+        B.set_arith_mode(arith)
+        out = [([], []) for _ in range(n_seq)]
+        pose = [np.eye(4) for _ in range(n_seq)]
+        for st in plan:
+            for p in st["resets"]:
+                B.reset_stream(p)
+            frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
+            points = {}
+            for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
+                cams = [tuple(cameras[i]) for _, i, _ in grp]
+                uniq = list(dict.fromkeys(cams))
+                pts = B.advance_images([p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams])
+                points.update({a: int(n) for a, n in zip(grp, pts)})
+            for a in st["advance"]:
+                if a[2] == 0:                                       # cvo.cpp:352-360: the first frame only fills the fixed cloud
+                    out[a[1]][0].append(pose[a[1]].copy()); out[a[1]][1].append(dict(iterations=0, nnz=0, points=points[a]))
+            if not st["align"]:
+                continue
+            res = B.align_pairs([p for p, _, _ in st["align"]])
+            for (p, i, f), r in zip(st["align"], res):
+                if r["status"] != CVO_OK:
+                    raise CvoError(r["status"], f"sequence {i}, frame {f}: alignment failed")
+                step = np.eye(4); step[:3, :] = r["transform"].astype(np.float64)
+                pose[i] = pose[i] @ step
+                out[i][0].append(pose[i].copy())
+                out[i][1].append(dict(iterations=r["iter"] + 1, nnz=r["A_nonzero"], points=points[(p, i, f)]))
+    finally:
+        B.close()
+    return out

@@ -318,8 +318,44 @@ int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* f
  * align result of its pairs carries CVO_ERR_EMPTY_CLOUD).  Pairs outside the range keep their clouds. */
 int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
                                int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out);
-/* pcd_generator::num_want (3000, pcd_generator.cpp:22) of this batch's later cvo_batch_set_pairs_images calls */
+/* pcd_generator::num_want (3000, pcd_generator.cpp:22) of this batch's later cvo_batch_set_pairs_images / cvo_batch_advance_images calls */
 int cvo_batch_set_num_want(cvo_batch b, int num_want);
+
+/* ---- K-stream frame-to-frame odometry: a pair slot as one cvo::cvo odometry object (the cvo_main loop: set_pcd, match_odometry,
+ * update_fixed_pcd per frame, cvo.cpp:352-386, 461-473, 578-582), advanced by one frame per call, many slots per call.  Every result is
+ * bit-identical to a handle given the same frames (cvo_set_pcd_images, cvo_match_odometry_images, cvo_update_fixed_pcd).
+ *
+ * cvo_batch_advance_images: image k (width x height, bgr8[k] and depth16[k] as for cvo_set_pcd_images) goes to slot slots[k], generated
+ * once by the batched generator with camera cams[cam_index[k]] (cam_index NULL: cams[0] for every image) and the batch's num_want: cloud
+ * and selected pixels are those cvo_set_pcd_images makes with that camera.  Per slot:
+ *   - not started (a new slot, a plain pair, or after cvo_batch_reset_stream): the image becomes the FIXED cloud, nothing is aligned
+ *     (cvo.cpp:352-360); a plain pair becomes a fresh stream first;
+ *   - started: the moving cloud, if there is one, becomes the fixed cloud (update_fixed_pcd: a move of ownership, no copy and no new
+ *     generation), the image becomes the MOVING cloud; R, T, ell, iter and the transforms carry on (cvo.cpp:461-473, 800-817).
+ * A slot out of range or listed twice, a null pointer, a negative camera index, a size below 64 or a cloud above 65535 points fail with
+ * CVO_ERR_INVALID and no slot changes.  An image with no points gives an empty cloud; the slot's alignments then carry the status a
+ * handle's cvo_match_odometry_images returns (CVO_ERR_EMPTY_CLOUD).  points_out (count ints, may be NULL): the points of each cloud.
+ *
+ * cvo_batch_align_pairs_async: one persistent launch over the `count` listed slots, any subset in any order.  cvo_batch_wait results,
+ * the tail scores / cvo_batch_innerproduct_results, the result records and the cvo_batch_last_* diagnostics are indexed in list order.
+ * A listed stream slot without a moving cloud yet is not run: its entry carries CVO_ERR_NOT_INITIALIZED (cvo.cpp:463-466).  Slots not
+ * listed keep their clouds and device states.  A stream slot starts from what it carries; a failed alignment leaves the slot as it was
+ * (like a handle's).  Score blocks of the launch (cvo_batch_enqueue_innerproduct & co) fail with CVO_ERR_INVALID once one of its slots
+ * has been advanced or reset.
+ *
+ * cvo_batch_reset_stream(b, p): slot p becomes a fresh object: no clouds, R = I, T = 0, ell = params.ell, every transform I -- the way to
+ * reuse a slot for the next sequence.  cvo_batch_get_prev_accum_transform: cvo_get_prev_accum_transform of a stream slot (cvo.cpp:815-816).
+ *
+ * Interaction with the plain-pair calls: cvo_batch_set_pair, _set_pairs, _set_pairs_images and _set_state behave as before on any slot,
+ * and on a stream slot they end the stream (the slot is a plain pair again).  cvo_batch_reset_states restores the plain pairs as before and
+ * leaves the carried state of stream slots alone.  cvo_batch_align_async(b, n) is cvo_batch_align_pairs_async over slots 0 .. n-1, except
+ * that every plain pair counts as started afterwards, as before. */
+int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                             int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */,
+                             int* points_out /* may be NULL */);
+int cvo_batch_reset_stream(cvo_batch b, int p);
+int cvo_batch_align_pairs_async(cvo_batch b, int count, const int* slots, void* stream);
+int cvo_batch_get_prev_accum_transform(cvo_batch b, int p, float prev_transform[12], float accum_transform[12]);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
