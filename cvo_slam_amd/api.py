@@ -88,6 +88,12 @@ class TrackScores(C.Structure):
                 ("inliers", C.c_int), ("cos_angle", C.c_float)]
 
 
+class TrackStep(C.Structure):
+    """cvo_track_step: one stream's share of a tracker step (cvo_hip.h: cvo_tracks_wait)."""
+    _fields_ = [("phase", C.c_int), ("points", C.c_int), ("odometry", PairResult), ("odometry_scores", TrackScores),
+                ("keyframe", PairResult), ("keyframe_scores", TrackScores), ("initial_guess", C.c_float * 12)]
+
+
 # every symbol include/cvo_hip.h declares (tests check the .so exports exactly these)
 ABI_SYMBOLS = [
     "cvo_last_error", "cvo_device_count", "cvo_default_params", "cvo_create", "cvo_destroy", "cvo_set_pcd", "cvo_align",
@@ -112,6 +118,9 @@ ABI_SYMBOLS = [
     "cvo_selftest_cubic_step_f32eig", "cvo_selftest_dist_se3_f32logm",
     "cvo_batch_set_pairs_images", "cvo_batch_set_num_want", "cvo_batch_get_cloud", "cvo_batch_get_selected_points",
     "cvo_batch_advance_images", "cvo_batch_reset_stream", "cvo_batch_align_pairs_async", "cvo_batch_get_prev_accum_transform",
+    "cvo_selftest_reset_initial", "cvo_tracks_create", "cvo_tracks_destroy", "cvo_tracks_set_num_want", "cvo_tracks_set_arith_mode", "cvo_tracks_reset",
+    "cvo_tracks_step_async", "cvo_tracks_done", "cvo_tracks_wait", "cvo_tracks_commit", "cvo_tracks_get_cloud", "cvo_tracks_get_selected_points",
+    "cvo_tracks_get_state",
 ]
 
 _lib = None
@@ -210,7 +219,7 @@ def load_library():
     L.cvo_batch_innerproduct_results.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
     L.cvo_batch_compute_innerproduct.argtypes = [vp, C.c_int, C.POINTER(TrackScores)]
     for name in ("cvo_selftest_cubic_step", "cvo_selftest_exp_sek3", "cvo_selftest_dist_se3", "cvo_selftest_libm", "cvo_selftest_cubic_step_f32eig",
-                 "cvo_selftest_dist_se3_f32logm"):
+                 "cvo_selftest_dist_se3_f32logm", "cvo_selftest_reset_initial"):
         getattr(L, name).argtypes = [C.c_int, C.c_int, fp, fp]
     L.cvo_selftest_pair_values.argtypes = [C.c_int, C.POINTER(Params), C.c_float, C.c_int, fp, fp, fp]
     L.cvo_function_inner_product_clouds.argtypes = [vp, fp, fp, C.c_int, fp, fp, C.c_int, C.POINTER(InnP)]
@@ -261,6 +270,18 @@ def load_library():
     L.cvo_batch_last_pair_spans.argtypes = [vp, C.c_int, dp, dp, C.POINTER(C.c_int)]
     L.cvo_batch_last_cull_masks.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     L.cvo_batch_last_nonzeros.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.cvo_tracks_create.argtypes = [C.POINTER(Params), C.c_int, C.c_int, C.POINTER(vp)]
+    L.cvo_tracks_destroy.argtypes = [vp]
+    L.cvo_tracks_set_num_want.argtypes = [vp, C.c_int]
+    L.cvo_tracks_set_arith_mode.argtypes = [vp, C.c_int]
+    L.cvo_tracks_reset.argtypes = [vp, C.c_int]
+    L.cvo_tracks_step_async.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip, vp]
+    L.cvo_tracks_done.argtypes = [vp, ip]
+    L.cvo_tracks_wait.argtypes = [vp, C.POINTER(TrackStep), C.c_int]
+    L.cvo_tracks_commit.argtypes = [vp, C.c_int, ip, ip]
+    L.cvo_tracks_get_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, ip]
+    L.cvo_tracks_get_selected_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
+    L.cvo_tracks_get_state.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
     _lib = L
     return L
 
@@ -323,6 +344,15 @@ def selftest_dist_se3_f32logm(dR_dT, device: int = 0):
     fp = C.POINTER(C.c_float)
     _check(load_library().cvo_selftest_dist_se3_f32logm(device, a.shape[0], a.ctypes.data_as(fp), out.ctypes.data_as(fp)))
     return out
+
+
+def selftest_reset_initial(transform, odometry, device: int = 0):
+    """cvo::reset_initial (cvo.cpp:611-618) on the device, as the tracker streams' link kernel evaluates it, for n objects with the given
+    `transform` (n, 3, 4) and odometry transforms (n, 3, 4): R (n, 3, 3), T (n, 3) and the returned init.inverse() (n, 3, 4)."""
+    a = np.ascontiguousarray(np.concatenate([np.asarray(transform, np.float32).reshape(-1, 12), np.asarray(odometry, np.float32).reshape(-1, 12)], axis=1))
+    out = np.zeros((a.shape[0], 24), np.float32); fp = C.POINTER(C.c_float)
+    _check(load_library().cvo_selftest_reset_initial(device, a.shape[0], a.ctypes.data_as(fp), out.ctypes.data_as(fp)))
+    return out[:, :9].reshape(-1, 3, 3), out[:, 9:12].copy(), out[:, 12:].reshape(-1, 3, 4)
 
 
 def selftest_libm(x, device: int = 0):
@@ -1013,3 +1043,127 @@ class CvoBatch:
 
     def results_to_device(self, dst_device_ptr: int, n: int, stream: int | None = None):
         _check(self.L.cvo_batch_results_to_device(self.h, C.c_void_p(dst_device_ptr), n, C.c_void_p(stream) if stream else None))
+
+
+def _pair_result_dict(r):
+    return dict(transform=np.array(r.transform[:], np.float32).reshape(3, 4), R=np.array(r.R[:], np.float32).reshape(3, 3),
+                T=np.array(r.T[:], np.float32), ell=r.ell, iter=r.iter, A_nonzero=r.A_nonzero,
+                iterations_run=r.iterations_run, status=r.status, rebuilds=r.rebuilds, dense_fallbacks=r.dense_fallbacks)
+
+
+def _track_scores_dict(o):
+    tup = lambda r: (r.value, r.num, r.num_e)
+    return dict(inn_pre=tup(o.inn_pre), inn_post=tup(o.inn_post), inn_fixed_pcd=tup(o.inn_fixed_pcd), inn_moving_pcd=tup(o.inn_moving_pcd),
+                post_hessian=np.array(o.post_hessian[:]).reshape(6, 6), inliers=o.inliers, cos_angle=o.cos_angle)
+
+
+class CvoTracks:
+    """K tracker streams (cvo_hip.h: cvo_tracks_*): each stream is the pair of cvo::cvo objects local_tracker owns -- cvo_odometry (object 0) and
+    cvo_keyframe (object 1) -- and a step advances every listed stream by one frame: generation, one odometry launch, reset_initial on the device,
+    one keyframe launch.  The accept rule stays with the caller: `commit` takes its decision for the frames just waited for."""
+    ODOMETRY, KEYFRAME = 0, 1
+
+    def __init__(self, max_streams: int, params: Params | None = None, device: int = 0):
+        self.L = load_library()
+        self.params = params or default_params()
+        self.max_streams = max_streams
+        self.h = C.c_void_p()
+        self._n = 0
+        _check(self.L.cvo_tracks_create(C.byref(self.params), device, max_streams, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.cvo_tracks_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_num_want(self, num_want: int):
+        _check(self.L.cvo_tracks_set_num_want(self.h, int(num_want)))
+
+    def set_arith_mode(self, mode):
+        _check(self.L.cvo_tracks_set_arith_mode(self.h, arith_flags(mode)))
+
+    def reset(self, s: int):
+        """stream s = two fresh objects"""
+        _check(self.L.cvo_tracks_reset(self.h, int(s)))
+
+    def step_async(self, streams, images, cameras, cam_index=None, stream: int | None = None):
+        """cvo_tracks_step_async: images[k] = (bgr8, depth16), all of one size, is the next frame of stream streams[k], generated with camera
+        cameras[cam_index[k]] (cam_index None: cameras[0] for all; cameras: a list of (scaling_factor, fx, fy, cx, cy), or one such tuple)."""
+        ims = [Cvo._images(b, d) for b, d in images]
+        sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if not ims or sl.shape[0] != len(ims):
+            raise ValueError("one stream per image, at least one image")
+        w, h = ims[0][2], ims[0][3]
+        if any((q[2], q[3]) != (w, h) for q in ims):
+            raise ValueError("all images of one call must have the same size")
+        if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+            cameras = [cameras]
+        cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+        ci = None if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+        if ci is not None and (ci.shape[0] != len(ims) or ci.min() < 0 or ci.max() >= len(cameras)):
+            raise ValueError("cam_index: one index into cameras per image")
+        n = len(ims); ip = C.POINTER(C.c_int)
+        bgr = (C.c_void_p * n)(*[q[0].ctypes.data for q in ims]); dep = (C.c_void_p * n)(*[q[1].ctypes.data for q in ims])
+        _check(self.L.cvo_tracks_step_async(self.h, n, sl.ctypes.data_as(ip), bgr, dep, w, h, cams, None if ci is None else ci.ctypes.data_as(ip),
+                                            C.c_void_p(stream) if stream else None))
+        self._n = n
+        return n
+
+    def done(self) -> bool:
+        d = C.c_int(0)
+        _check(self.L.cvo_tracks_done(self.h, C.byref(d)))
+        return bool(d.value)
+
+    def wait_raw(self):
+        """cvo_tracks_wait into a ctypes array of TrackStep, one per stream of the step in list order"""
+        out = (TrackStep * max(1, self._n))()
+        _check(self.L.cvo_tracks_wait(self.h, out, self._n))
+        return out
+
+    def wait(self):
+        """One dict per stream of the step, in list order: phase, points, odometry / keyframe (the fields of CvoBatch.wait), odometry_scores /
+        keyframe_scores (the fields of compute_innerproduct), initial_guess (3, 4)."""
+        n = self._n
+        return [dict(phase=o.phase, points=o.points, odometry=_pair_result_dict(o.odometry), odometry_scores=_track_scores_dict(o.odometry_scores),
+                     keyframe=_pair_result_dict(o.keyframe), keyframe_scores=_track_scores_dict(o.keyframe_scores),
+                     initial_guess=np.array(o.initial_guess[:], np.float32).reshape(3, 4)) for o in self.wait_raw()[:n]]
+
+    def step(self, streams, images, cameras, cam_index=None):
+        self.step_async(streams, images, cameras, cam_index)
+        return self.wait()
+
+    def commit(self, streams, accept):
+        """the caller's decision for the phase-2 frames just waited for: accept -> update_previous_pcd, reject -> reset_keyframe(t_odometry)"""
+        sl = np.ascontiguousarray(streams, np.int32).reshape(-1); ac = np.ascontiguousarray([1 if a else 0 for a in accept], np.int32).reshape(-1)
+        if sl.shape != ac.shape:
+            raise ValueError("one decision per stream")
+        ip = C.POINTER(C.c_int)
+        _check(self.L.cvo_tracks_commit(self.h, sl.shape[0], sl.ctypes.data_as(ip), ac.ctypes.data_as(ip)))
+
+    def get_cloud(self, s: int, obj: int, slot: int):
+        """the cloud of stream s, object ODOMETRY / KEYFRAME, slot SLOT_FIXED / SLOT_MOVING / SLOT_PREVIOUS: xyz (n, 3), feat (5, n)"""
+        n = C.c_int(0); fp = C.POINTER(C.c_float)
+        _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), int(slot), None, None, 0, C.byref(n)))
+        xyz = np.zeros((n.value, 3), np.float32); feat = np.zeros((5, n.value), np.float32)
+        if n.value:
+            _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), int(slot), xyz.ctypes.data_as(fp), feat.ctypes.data_as(fp), n.value, C.byref(n)))
+        return xyz, feat
+
+    def get_selected_points(self, s: int, obj: int, slot: int):
+        n = C.c_int(0)
+        _check(self.L.cvo_tracks_get_selected_points(self.h, int(s), int(obj), int(slot), None, 0, C.byref(n)))
+        px = np.zeros((n.value, 2), np.uint16)
+        if n.value:
+            _check(self.L.cvo_tracks_get_selected_points(self.h, int(s), int(obj), int(slot), px.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return px
+
+    def get_state(self, s: int, obj: int):
+        R = np.zeros(9, np.float32); T = np.zeros(3, np.float32); tf = np.zeros(12, np.float32); ell = C.c_float(0); fp = C.POINTER(C.c_float)
+        _check(self.L.cvo_tracks_get_state(self.h, int(s), int(obj), R.ctypes.data_as(fp), T.ctypes.data_as(fp), C.byref(ell), tf.ctypes.data_as(fp)))
+        return dict(R=R.reshape(3, 3), T=T, ell=ell.value, transform=tf.reshape(3, 4))

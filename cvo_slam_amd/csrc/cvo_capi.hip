@@ -94,6 +94,8 @@ hipError_t launch_cloud_boxes(const float* rec, int n, float* gbox, hipStream_t 
 hipError_t launch_adaptive(const AdaptiveArgs& A, int iterations, hipStream_t stream);
 int adaptive_partial_records(int nf, int nm);
 hipError_t launch_selftest(int kind, const float* in, float* out, int n, hipStream_t s);
+hipError_t launch_selftest_reset_initial(const float* in, float* out, int n, hipStream_t s);
+hipError_t launch_track_link(const TrackLinkIn* in, const PairState* odo_states, PairState* key_states, TrackLinkOut* out, int n, hipStream_t s);
 hipError_t launch_selftest_pairs(const float* in, float* out, float* aux, int n, float ell, const DevParams& P, hipStream_t s);
 hipError_t launch_score(const ScoreBatch& B, const ScoreDesc* more, int nreq, int row_blocks, int chunks, const DevParams& P, double* partials,
                         double* out_pinned, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
@@ -419,6 +421,8 @@ struct Engine {
     bool adopt = false;          // finished workgroups help with the pairs of their launch that still run (one workgroup and one slot per pair; CVO_HIP_ADOPT)
     int last_grid = 0, last_helpers = 0, last_concurrent = 0;   // the last align launch: its workgroups, those of them launched as helpers, launch_share's estimate
     bool registered = false;     // in live_engines() (guarded by adopt_submit_mutex)
+    bool queue_behind = false;   // tracker streams (cvo_tracks_step_async): this engine's launches are queued on a stream that holds other work of the step, which the
+                                 // host must not wait for; the engine's own previous launch is what its descriptor table has to be safe from, and that is ev1
 
     // How much of the device an align launch about to be submitted can count on (called under adopt_submit_mutex).  The HIP runtime maps
     // streams onto Q hardware queues (hw_queue_count) by a rule of its own; launches on one hardware queue run one after the other.
@@ -1079,7 +1083,8 @@ struct Engine {
         // are read by the kernel from pinned host memory, final states are written by it to pinned host memory, and the
         // exchange area is cleared only when it is new (tags carry the launch number).
         if (descs_uploaded.size() != sizeof(PairDesc) * n || std::memcmp(descs_uploaded.data(), hd, sizeof(PairDesc) * n) != 0) {
-            HIP_TRY(hipStreamSynchronize(s));                         // an earlier launch on this stream may still read d_descs / h_descs
+            if (!queue_behind) HIP_TRY(hipStreamSynchronize(s));      // an earlier launch on this stream may still read d_descs / h_descs
+            else if (launched) HIP_TRY(hipEventSynchronize(ev1));
             std::memcpy(h_descs.p, hd, sizeof(PairDesc) * n);
             HIP_TRY(hipMemcpyAsync(d_descs.p, h_descs.p, sizeof(PairDesc) * n, hipMemcpyHostToDevice, s));
             descs_uploaded.assign(reinterpret_cast<const unsigned char*>(hd), reinterpret_cast<const unsigned char*>(hd) + sizeof(PairDesc) * n);
@@ -1304,50 +1309,8 @@ struct Engine {
 // ---- host-side pieces of the reference's state helpers ----------------------
 struct Aff { float m[12]; };
 Aff aff_identity() { Aff a; std::memset(a.m, 0, sizeof(a.m)); a.m[0] = a.m[5] = a.m[10] = 1.f; return a; }
-Aff aff_mul(const Aff& a, const Aff& b) {   // Affine3f * Affine3f
-    Aff c;
-    for (int r = 0; r < 3; ++r) {
-        for (int k = 0; k < 3; ++k)
-            c.m[r * 4 + k] = (a.m[r * 4 + 0] * b.m[0 * 4 + k] + a.m[r * 4 + 1] * b.m[1 * 4 + k]) + (a.m[r * 4 + 2] * b.m[2 * 4 + k] + a.m[r * 4 + 3] * 0.f);
-        c.m[r * 4 + 3] = (a.m[r * 4 + 0] * b.m[0 * 4 + 3] + a.m[r * 4 + 1] * b.m[1 * 4 + 3]) + (a.m[r * 4 + 2] * b.m[2 * 4 + 3] + a.m[r * 4 + 3] * 1.f);
-    }
-    return c;
-}
-Aff aff_inverse(const Aff& a) {             // Affine3f::inverse(), Affine mode: cofactor inverse of the linear part
-    float L[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) L[r * 3 + c] = a.m[r * 4 + c];
-    const float c00 = L[4] * L[8] - L[5] * L[7], c01 = L[5] * L[6] - L[3] * L[8], c02 = L[3] * L[7] - L[4] * L[6];
-    const float det = sum3f(L[0] * c00, L[1] * c01, L[2] * c02), id = 1.f / det;
-    float Li[9];
-    Li[0] = c00 * id; Li[1] = (L[2] * L[7] - L[1] * L[8]) * id; Li[2] = (L[1] * L[5] - L[2] * L[4]) * id;
-    Li[3] = c01 * id; Li[4] = (L[0] * L[8] - L[2] * L[6]) * id; Li[5] = (L[2] * L[3] - L[0] * L[5]) * id;
-    Li[6] = c02 * id; Li[7] = (L[1] * L[6] - L[0] * L[7]) * id; Li[8] = (L[0] * L[4] - L[1] * L[3]) * id;
-    const float t[3] = {a.m[3], a.m[7], a.m[11]}; float nt[3];
-    mat3_vec(Li, t, nt);
-    Aff r;
-    for (int i = 0; i < 3; ++i) { for (int k = 0; k < 3; ++k) r.m[i * 4 + k] = Li[i * 3 + k]; r.m[i * 4 + 3] = -nt[i]; }
-    return r;
-}
-// Affine3f::rotation(): orthogonal polar factor of the linear part (Eigen uses an
-// SVD); Newton iteration X <- (X + X^-T)/2 in double reaches the same matrix.
-void polar_rotation(const float* L, float* Rout) {
-    double X[9]; for (int i = 0; i < 9; ++i) X[i] = L[i];
-    for (int it = 0; it < 32; ++it) {
-        const double c00 = X[4] * X[8] - X[5] * X[7], c01 = X[5] * X[6] - X[3] * X[8], c02 = X[3] * X[7] - X[4] * X[6];
-        const double det = X[0] * c00 + X[1] * c01 + X[2] * c02;
-        double inv[9];
-        inv[0] = c00 / det; inv[1] = (X[2] * X[7] - X[1] * X[8]) / det; inv[2] = (X[1] * X[5] - X[2] * X[4]) / det;
-        inv[3] = c01 / det; inv[4] = (X[0] * X[8] - X[2] * X[6]) / det; inv[5] = (X[2] * X[3] - X[0] * X[5]) / det;
-        inv[6] = c02 / det; inv[7] = (X[1] * X[6] - X[0] * X[7]) / det; inv[8] = (X[0] * X[4] - X[1] * X[3]) / det;
-        double delta = 0, Y[9];
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
-            Y[r * 3 + c] = 0.5 * (X[r * 3 + c] + inv[c * 3 + r]);
-            delta = std::max(delta, std::fabs(Y[r * 3 + c] - X[r * 3 + c]));
-        }
-        std::memcpy(X, Y, sizeof(X));
-        if (delta < 1e-15) break;
-    }
-    for (int i = 0; i < 9; ++i) Rout[i] = (float)X[i];
-}
+// (the arithmetic is stated once, in cvo_math.hpp: the device evaluates reset_initial too, cvo_track_link_kernel)
+Aff aff_mul(const Aff& a, const Aff& b) { Aff c; aff_mul12(a.m, b.m, c.m); return c; }   // Affine3f * Affine3f
 
 void sym_eig6(const double* Hin, double* ev) {   // cyclic Jacobi
     double A[36]; std::memcpy(A, Hin, sizeof(A));
@@ -1472,7 +1435,7 @@ struct cvo_batch_s {
     cvo_params prm;
     Engine eng;
     int max_pairs = 0;
-    std::vector<std::unique_ptr<Cloud>> fixed, moving;
+    std::vector<std::shared_ptr<Cloud>> fixed, moving;        // (shared: a tracker stream's frame is held by its odometry and its keyframe object at once, cvo_tracks_s)
     BatchImages img;
     std::vector<PairState> init_states;     // what set_pair / set_state last gave
     std::vector<unsigned char> dirty;       // per slot: the plain pair's device state differs from init_states (set for every slot by any set_*, as one flag was)
@@ -2006,12 +1969,9 @@ int cvo_reset_keyframe(cvo_handle h, const float odometry[12]) {
 }
 int cvo_reset_initial(cvo_handle h, const float odometry[12], float init_inverse_out[12]) {
     if (!h || !odometry) return fail(CVO_ERR_INVALID, "null argument");
-    Aff od; std::memcpy(od.m, odometry, sizeof(od.m));
-    const Aff init = aff_inverse(aff_mul(h->transform, od));          // cvo.cpp:613
-    float L[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) L[r * 3 + c] = init.m[r * 4 + c];
-    polar_rotation(L, h->R);                                         // cvo.cpp:614
-    h->T[0] = init.m[3]; h->T[1] = init.m[7]; h->T[2] = init.m[11];   // cvo.cpp:615
-    if (init_inverse_out) { const Aff back = aff_inverse(init); std::memcpy(init_inverse_out, back.m, sizeof(back.m)); }   // cvo.cpp:617
+    float back[12];
+    reset_initial_eval(h->transform.m, odometry, h->R, h->T, back);   // cvo.cpp:613-617 (cvo_math.hpp)
+    if (init_inverse_out) std::memcpy(init_inverse_out, back, sizeof(back));
     return CVO_OK;
 }
 
@@ -2067,7 +2027,8 @@ int selftest(int device, int kind, int n, const float* in, int in_w, float* out,
     DevBuf din, dout;
     if ((rc = din.ensure(sizeof(float) * (size_t)n * in_w)) || (rc = dout.ensure(sizeof(float) * (size_t)n * out_w))) { din.release(); dout.release(); return rc; }
     hipError_t e = hipMemcpy(din.p, in, sizeof(float) * (size_t)n * in_w, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_selftest(kind, static_cast<const float*>(din.p), static_cast<float*>(dout.p), n, nullptr);
+    if (e == hipSuccess) e = kind == 6 ? launch_selftest_reset_initial(static_cast<const float*>(din.p), static_cast<float*>(dout.p), n, nullptr)
+                                       : launch_selftest(kind, static_cast<const float*>(din.p), static_cast<float*>(dout.p), n, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, dout.p, sizeof(float) * (size_t)n * out_w, hipMemcpyDeviceToHost);
     din.release(); dout.release();
@@ -2149,6 +2110,7 @@ int cvo_selftest_dist_se3(int device, int n, const float* dR_dT, float* dist_out
 int cvo_selftest_libm(int device, int n, const float* x, float* out6) { return selftest(device, 3, n, x, 1, out6, 6); }
 int cvo_selftest_cubic_step_f32eig(int device, int n, const float* coef_minstep, float* step_out) { return selftest(device, 4, n, coef_minstep, 5, step_out, 1); }
 int cvo_selftest_dist_se3_f32logm(int device, int n, const float* dR_dT, float* dist_out) { return selftest(device, 5, n, dR_dT, 12, dist_out, 1); }
+int cvo_selftest_reset_initial(int device, int n, const float* transform_odometry, float* out) { return selftest(device, 6, n, transform_odometry, 24, out, 24); }
 int cvo_selftest_pair_values(int device, const cvo_params* params, float ell, int n, const float* y_g, float* a_out, float* d2_d2c_out) {
     int rc = check_device(device, nullptr); if (rc) return rc;
     if (n <= 0 || !y_g || !a_out || !(ell > 0.f)) return fail(CVO_ERR_INVALID, "bad self-test arguments");
@@ -2786,6 +2748,15 @@ int collect_tail_scores(cvo_batch b, int n, double* r /* n x 5 x 24 */) {
     return CVO_OK;
 }
 }  // namespace
+namespace {
+// the sums of one pair's score block (5 requests x 24 doubles) -> cvo_track_scores
+void finish_track_scores(const double (*ri)[24], cvo_track_scores& o) {
+    finish_inn_p(ri[0], &o.inn_pre); finish_inn_p(ri[1], &o.inn_post); finish_inn_p(ri[2], &o.inn_fixed_pcd); finish_inn_p(ri[3], &o.inn_moving_pcd);
+    o.cos_angle = o.inn_post.value / (sqrtf(o.inn_fixed_pcd.value) * sqrtf(o.inn_moving_pcd.value));           // cvo.cpp:498
+    o.inliers = (int)ri[4][1];                                   // cvo.cpp:708 with the caller's counter starting at 0 (local_tracker.cpp:240)
+    finish_hessian(ri[4] + 2, o.inliers, o.post_hessian);
+}
+}  // namespace
 int cvo_batch_last_tail_answers(cvo_batch b, int n, int* masks) {
     if (!b || !masks || n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "bad argument");
     int rc = b->eng.wait(); if (rc) return rc;
@@ -2798,14 +2769,7 @@ int cvo_batch_innerproduct_results(cvo_batch b, int n, cvo_track_scores* out) {
     int rc = (b->eng.last_tail && b->eng.score_pending == 0) ? collect_tail_scores(b, n, r.data())
                                                              : b->eng.score_collect(n * 5, reinterpret_cast<double (*)[24]>(r.data()));
     if (rc) return rc;
-    for (int i = 0; i < n; ++i) {
-        const double (*ri)[24] = reinterpret_cast<const double (*)[24]>(r.data() + (size_t)i * 5 * 24);
-        cvo_track_scores& o = out[i];
-        finish_inn_p(ri[0], &o.inn_pre); finish_inn_p(ri[1], &o.inn_post); finish_inn_p(ri[2], &o.inn_fixed_pcd); finish_inn_p(ri[3], &o.inn_moving_pcd);
-        o.cos_angle = o.inn_post.value / (sqrtf(o.inn_fixed_pcd.value) * sqrtf(o.inn_moving_pcd.value));           // cvo.cpp:498
-        o.inliers = (int)ri[4][1];                                   // cvo.cpp:708 with the caller's counter starting at 0 (local_tracker.cpp:240)
-        finish_hessian(ri[4] + 2, o.inliers, o.post_hessian);
-    }
+    for (int i = 0; i < n; ++i) finish_track_scores(reinterpret_cast<const double (*)[24]>(r.data() + (size_t)i * 5 * 24), out[i]);
     return CVO_OK;
 }
 int cvo_batch_compute_innerproduct(cvo_batch b, int n, cvo_track_scores* out) {
@@ -2824,6 +2788,333 @@ int cvo_batch_result_records(cvo_batch b, const void** records_device) {
     if (!b || !records_device) return fail(CVO_ERR_INVALID, "null argument");
     if (!b->eng.launched) return fail(CVO_ERR_INVALID, "no launch yet");
     *records_device = b->eng.d_records.p;
+    return CVO_OK;
+}
+
+// ======================= K-stream tracker steps (cvo_tracks_*): the two cvo::cvo objects of local_tracker, K streams per call ===========
+// A stream is the pair of objects local_tracker owns (local_tracker.cpp:228-251, 330-338, 356-431, 506): slot s of the batch `odo` is its
+// cvo_odometry (a stream slot, as cvo_batch_advance_images keeps it), slot s of the batch `key` holds the fixed and moving cloud of its
+// cvo_keyframe and that object's device state; what a keyframe object carries between frames lives in KeyObject on the host, as a handle
+// carries it.  A frame is generated once into a cloud object of its own; the slots that hold it share ownership (up to four at once: the
+// odometry moving / fixed cloud, the keyframe moving / previous / fixed cloud), and a cloud object is only written again when nobody holds it.
+struct KeyObject {
+    bool pre_pc_init = false, first_frame = true;
+    float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[3] = {0, 0, 0}, ell = 0.f;
+    int iter = 0, A_nonzero = 0;
+    Aff transform = aff_identity(), prev_transform = aff_identity(), accum_transform = aff_identity();
+    std::shared_ptr<Cloud> previous;        // ptr_previous_pcd (fixed and moving: the key batch's slot)
+};
+struct TrackStream {
+    int frames = 0;                         // frames seen: the next step's phase is min(frames, 2)
+    bool commit_pending = false;            // a phase-2 frame has been waited for and the caller's decision is not in yet
+    Aff t_odometry = aff_identity();        // the odometry transform of that frame (reset_keyframe's argument)
+    KeyObject key;
+};
+struct cvo_tracks_s {
+    cvo_params prm;
+    int max_streams = 0;
+    cvo_batch odo = nullptr, key = nullptr;
+    std::vector<TrackStream> st;
+    std::vector<std::shared_ptr<Cloud>> pool;   // every cloud object made so far; one that only the pool holds is free
+    PinBuf h_link_in, h_link_out;
+    // the step in flight
+    bool in_flight = false;
+    std::vector<int> list, phase, points, odo_pos, key_pos;   // per listed stream: its phase, points, and position in the two launches (-1: not in it)
+    std::vector<std::shared_ptr<Cloud>> moving_before;          // the keyframe object's moving cloud before the step (put back when the odometry alignment fails)
+    int n_odo = 0, n_key = 0;
+};
+
+namespace {
+void tracks_free_cloud(cvo_tracks_s* t, std::shared_ptr<Cloud>& out) {
+    for (std::shared_ptr<Cloud>& c : t->pool) if (c.use_count() == 1) { out = c; return; }
+    t->pool.push_back(std::make_shared<Cloud>());
+    out = t->pool.back();
+}
+void tracks_fresh_stream(cvo_tracks_s* t, int s) {
+    t->odo->fixed[s].reset(); t->odo->moving[s].reset(); t->key->fixed[s].reset(); t->key->moving[s].reset();
+    fresh_stream(t->odo, s);
+    t->st[s] = TrackStream();
+    t->st[s].key.ell = t->prm.ell;
+}
+void pair_result_from(const PairState& r, cvo_pair_result& o) {
+    std::memcpy(o.transform, r.transform, sizeof(float) * 12);
+    std::memcpy(o.R, r.R, sizeof(float) * 9); std::memcpy(o.T, r.T, sizeof(float) * 3);
+    o.ell = r.ell; o.iter = r.iter; o.A_nonzero = r.A_nonzero; o.iterations_run = r.iterations_run; o.status = r.status;
+    o.rebuilds = r.rebuilds; o.dense_fallbacks = r.dense_fallbacks;
+}
+// The score blocks of the positions of b's last launch marked in `want` (cvo.cpp:475-503, tran = the alignment's own result): what the launch
+// answered in its tail is taken from there, the rest goes to the score kernel in one launch (as cvo_batch_innerproduct_results has it).
+// out: one entry per position; positions not wanted are left alone.
+int tracks_scores(cvo_batch b, int n, const std::vector<unsigned char>& want, std::vector<cvo_track_scores>& out) {
+    std::vector<double> r((size_t)std::max(n, 1) * 5 * 24, 0.0);
+    if (b->eng.last_tail) std::memcpy(r.data(), b->eng.h_tail.p, sizeof(double) * (size_t)n * 5 * 24);
+    static const int bit_of[5] = {TAIL_PRE, TAIL_POST, TAIL_FIXED, TAIL_MOVING, TAIL_HESSIAN};
+    std::vector<Engine::ScoreReq> rq; std::vector<int> where;
+    for (int i = 0; i < n; ++i) {
+        if (!want[i]) continue;
+        const int mask = b->eng.last_tail ? (int)r[(size_t)i * 120 + 23] : 0;
+        const int p = b->last_slots[i];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
+        const Engine::ScoreReq all[5] = {{mv, nullptr, fx, false, 0.f, p, false}, {mv, nullptr, fx, false, 0.f, p, true}, {fx, nullptr, fx, false, 0.f, p, false},
+                                         {mv, nullptr, mv, false, 0.f, p, false}, {mv, nullptr, fx, true, 0.f, p, true}};   // cvo.cpp:489, 491, 496, 497, 500
+        for (int q = 0; q < 5; ++q) if (!(mask & bit_of[q])) { rq.push_back(all[q]); where.push_back(i * 5 + q); }
+    }
+    if (!rq.empty()) {
+        std::vector<double> extra(rq.size() * 24);
+        int rc = b->eng.score_many(rq.data(), (int)rq.size(), reinterpret_cast<double (*)[24]>(extra.data())); if (rc) return rc;
+        for (size_t k = 0; k < rq.size(); ++k) std::memcpy(r.data() + (size_t)where[k] * 24, extra.data() + k * 24, sizeof(double) * 24);
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!want[i]) continue;
+        r[(size_t)i * 120 + 23] = 0.0;
+        finish_track_scores(reinterpret_cast<const double (*)[24]>(r.data() + (size_t)i * 5 * 24), out[i]);
+    }
+    return CVO_OK;
+}
+int tracks_check_list(cvo_tracks_s* t, int count, const int* streams) {
+    if (!t || count <= 0 || count > t->max_streams) return fail(CVO_ERR_INVALID, "bad stream count");
+    if (!streams) return fail(CVO_ERR_INVALID, "null argument");
+    std::vector<unsigned char> seen(t->max_streams, 0);
+    for (int k = 0; k < count; ++k) {
+        if (streams[k] < 0 || streams[k] >= t->max_streams) return fail(CVO_ERR_INVALID, "stream index out of range");
+        if (seen[streams[k]]++) return fail(CVO_ERR_INVALID, "stream listed twice");
+    }
+    return CVO_OK;
+}
+}  // namespace
+
+int cvo_tracks_create(const cvo_params* p, int device, int max_streams, cvo_tracks* out) {
+    if (!out || max_streams <= 0) return fail(CVO_ERR_INVALID, "bad argument");
+    *out = nullptr;
+    std::unique_ptr<cvo_tracks_s> t(new cvo_tracks_s());
+    if (p) t->prm = *p; else cvo_default_params(&t->prm);
+    t->max_streams = max_streams;
+    int rc = cvo_batch_create(&t->prm, device, max_streams, &t->odo); if (rc) return rc;
+    rc = cvo_batch_create(&t->prm, device, max_streams, &t->key);
+    // the keyframe launch starts from device states the link kernel writes before that launch has sized the table: sized here, once
+    if (!rc) rc = t->key->eng.d_states.ensure(sizeof(PairState) * (size_t)max_streams);
+    if (rc) { cvo_batch_destroy(t->odo); cvo_batch_destroy(t->key); return rc; }
+    for (cvo_batch b : {t->odo, t->key}) { b->eng.tail_scores = true; b->eng.queue_behind = true; }
+    t->st.resize(max_streams);
+    for (int s = 0; s < max_streams; ++s) tracks_fresh_stream(t.get(), s);
+    *out = t.release();
+    return CVO_OK;
+}
+int cvo_tracks_destroy(cvo_tracks t) {
+    if (!t) return CVO_OK;
+    (void)hipSetDevice(t->odo->eng.device);
+    if (t->odo->eng.launched && t->odo->eng.last_stream) (void)hipStreamSynchronize(t->odo->eng.last_stream);
+    if (t->key->eng.launched && t->key->eng.last_stream) (void)hipStreamSynchronize(t->key->eng.last_stream);
+    for (TrackStream& s : t->st) s.key.previous.reset();
+    t->moving_before.clear();
+    cvo_batch_destroy(t->odo); cvo_batch_destroy(t->key);
+    t->pool.clear();
+    t->h_link_in.release(); t->h_link_out.release();
+    delete t;
+    return CVO_OK;
+}
+int cvo_tracks_set_num_want(cvo_tracks t, int num_want) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    return cvo_batch_set_num_want(t->odo, num_want);
+}
+int cvo_tracks_set_arith_mode(cvo_tracks t, int flags) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    int rc = cvo_batch_set_arith_mode(t->odo, flags); if (rc) return rc;
+    return cvo_batch_set_arith_mode(t->key, flags);
+}
+int cvo_tracks_reset(cvo_tracks t, int s) {
+    if (!t || s < 0 || s >= t->max_streams) return fail(CVO_ERR_INVALID, "bad stream index");
+    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    tracks_fresh_stream(t, s);
+    return CVO_OK;
+}
+int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                          const cvo_camera* cams, const int* cam_index, void* hip_stream) {
+    int rc = tracks_check_list(t, count, streams); if (rc) return rc;
+    if (!bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
+    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
+    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    for (int k = 0; k < count; ++k) {
+        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+        if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
+        if (t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " waits for the decision on its last frame (cvo_tracks_commit)");
+    }
+    cvo_batch bo = t->odo, bk = t->key;
+    if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
+    std::vector<cvo_camera> cam_of(count);
+    for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
+    const PcdImgRec* R = nullptr;
+    if ((rc = batch_generate(bo, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (the step's one host sync; fails before any stream changes)
+    // every frame into a cloud object nobody holds; the objects' slots take it (local_tracker.cpp:228-231, 233, 356, 415; update_fixed_pcd :403)
+    t->list.assign(streams, streams + count);
+    t->phase.assign(count, 0); t->points.assign(count, 0); t->odo_pos.assign(count, -1); t->key_pos.assign(count, -1);
+    t->moving_before.assign(count, nullptr);
+    std::vector<Cloud*> dst(count); std::vector<int> img(count), slots_odo, slots_key;
+    for (int k = 0; k < count; ++k) {
+        const int s = streams[k];
+        TrackStream& S = t->st[s]; StreamSlot& O = bo->streams[s];
+        std::shared_ptr<Cloud> c; tracks_free_cloud(t, c);
+        dst[k] = c.get(); img[k] = k;
+        const int ph = std::min(S.frames, 2);
+        t->phase[k] = ph; t->points[k] = R[k].npts;
+        if (ph == 0) {                                               // both objects' set_pcd of the first frame: their FIXED cloud (cvo.cpp:352-360)
+            bo->fixed[s] = c; bk->fixed[s] = c; O.init = true;
+        } else {
+            if (O.has_moving) bo->fixed[s] = bo->moving[s];          // update_fixed_pcd
+            bo->moving[s] = c; O.has_moving = true;
+            t->odo_pos[k] = (int)slots_odo.size(); slots_odo.push_back(s);
+            if (ph == 2) {                                           // the keyframe object's match_keyframe of the same frame
+                t->moving_before[k] = bk->moving[s]; bk->moving[s] = c;
+                t->key_pos[k] = (int)slots_key.size(); slots_key.push_back(s);
+            }
+        }
+        ++S.frames;
+    }
+    t->n_odo = (int)slots_odo.size(); t->n_key = (int)slots_key.size();
+    if ((rc = batch_scatter(bo, dst, img, R))) return rc;
+    if (t->n_odo == 0) { t->in_flight = true; return CVO_OK; }
+    // ONE odometry launch over the listed streams that align; its tail answers the score blocks
+    if ((rc = batch_launch(bo, slots_odo.data(), t->n_odo, static_cast<hipStream_t>(hip_stream), false))) return rc;
+    t->in_flight = true;                                             // (from here on there is something to wait for)
+    if (t->n_key == 0) return CVO_OK;
+    const hipStream_t hs = bo->eng.last_stream;
+    // the link: reset_initial on the device, from the odometry launch's device states into the keyframe launch's
+    if ((rc = t->h_link_in.ensure(sizeof(TrackLinkIn) * (size_t)t->max_streams)) || (rc = t->h_link_out.ensure(sizeof(TrackLinkOut) * (size_t)t->max_streams))) return rc;
+    TrackLinkIn* li = static_cast<TrackLinkIn*>(t->h_link_in.p);
+    for (int i = 0; i < t->n_key; ++i) {
+        const int s = slots_key[i]; const KeyObject& K = t->st[s].key;
+        std::memcpy(li[i].R, K.R, sizeof(K.R)); std::memcpy(li[i].T, K.T, sizeof(K.T)); li[i].ell = K.ell;
+        std::memcpy(li[i].transform, K.transform.m, sizeof(li[i].transform));
+        li[i].iter = K.iter; li[i].odo_state = s; li[i].key_state = s; li[i].pad_ = 0;
+        bk->streams[s] = StreamSlot(); bk->dirty[s] = 0;             // a plain pair that starts from its device state (Engine::launch: upload_each = 0)
+    }
+    const hipError_t e = launch_track_link(li, static_cast<const PairState*>(bo->eng.d_states.p), static_cast<PairState*>(bk->eng.d_states.p),
+                                           static_cast<TrackLinkOut*>(t->h_link_out.p), t->n_key, hs);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("track link kernel launch: ") + hipGetErrorString(e));
+    // ONE keyframe launch over the phase-2 streams, behind the link kernel on the same stream
+    return batch_launch(bk, slots_key.data(), t->n_key, hs, false);
+}
+int cvo_tracks_done(cvo_tracks t, int* done) {
+    if (!t || !done) return fail(CVO_ERR_INVALID, "null argument");
+    *done = 1;
+    if (!t->in_flight || t->n_odo == 0) return CVO_OK;
+    return cvo_batch_done(t->n_key > 0 && t->key->eng.launched ? t->key : t->odo, done);
+}
+int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out, int count) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    if (!t->in_flight) return fail(CVO_ERR_INVALID, "no step to wait for");
+    const int n = (int)t->list.size();
+    if (out && count != n) return fail(CVO_ERR_INVALID, "one result per stream of the step");
+    cvo_batch bo = t->odo, bk = t->key;
+    int rc;
+    if (t->n_odo > 0 && (rc = batch_settle(bo))) return rc;          // (the odometry objects take their results in, as after cvo_batch_wait)
+    if (t->n_key > 0 && (rc = bk->eng.wait())) return rc;
+    const PairState* ro = bo->eng.results(); const PairState* rk = bk->eng.results();
+    std::vector<unsigned char> want_o(std::max(t->n_odo, 1), 0), want_k(std::max(t->n_key, 1), 0);
+    for (int k = 0; k < n; ++k) {
+        if (t->odo_pos[k] >= 0) want_o[t->odo_pos[k]] = ro[t->odo_pos[k]].status == CVO_OK;
+        if (t->key_pos[k] >= 0) want_k[t->key_pos[k]] = ro[t->odo_pos[k]].status == CVO_OK && rk[t->key_pos[k]].status == CVO_OK;
+    }
+    std::vector<cvo_track_scores> so(std::max(t->n_odo, 1)), sk(std::max(t->n_key, 1));
+    std::memset(so.data(), 0, sizeof(cvo_track_scores) * so.size()); std::memset(sk.data(), 0, sizeof(cvo_track_scores) * sk.size());
+    if (t->n_odo > 0 && (rc = tracks_scores(bo, t->n_odo, want_o, so))) return rc;
+    if (t->n_key > 0 && (rc = tracks_scores(bk, t->n_key, want_k, sk))) return rc;
+    const TrackLinkOut* lo = static_cast<const TrackLinkOut*>(t->h_link_out.p);
+    for (int k = 0; k < n; ++k) {
+        const int s = t->list[k];
+        TrackStream& S = t->st[s]; KeyObject& K = S.key;
+        cvo_track_step step; std::memset(&step, 0, sizeof(step));
+        step.phase = t->phase[k]; step.points = t->points[k];
+        step.odometry.status = step.keyframe.status = CVO_ERR_NOT_INITIALIZED;
+        if (t->odo_pos[k] >= 0) {
+            const PairState& r = ro[t->odo_pos[k]];
+            pair_result_from(r, step.odometry); step.odometry_scores = so[t->odo_pos[k]];
+            const bool odo_ok = r.status == CVO_OK;
+            if (!odo_ok) {                                           // a failed alignment leaves the object as it was: report what it carries
+                const StreamSlot& O = bo->streams[s];
+                std::memcpy(step.odometry.R, O.R, sizeof(O.R)); std::memcpy(step.odometry.T, O.T, sizeof(O.T));
+                std::memcpy(step.odometry.transform, O.transform.m, sizeof(O.transform.m));
+                step.odometry.ell = O.ell; step.odometry.iter = O.iter;
+            }
+            if (t->phase[k] == 1 && odo_ok) {                        // local_tracker.cpp:330-333: first_frame = false; reset_transform(t_odometry)
+                K.first_frame = false; std::memcpy(K.transform.m, r.transform, sizeof(K.transform.m));
+            }
+            if (t->phase[k] == 2 && !odo_ok) bk->moving[s] = t->moving_before[k];   // the keyframe object does not see this frame
+            if (t->phase[k] == 2 && odo_ok) {
+                const int i = t->key_pos[k];
+                const PairState& q = rk[i];
+                std::memcpy(K.R, lo[i].R, sizeof(K.R)); std::memcpy(K.T, lo[i].T, sizeof(K.T));   // reset_initial, local_tracker.cpp:407
+                std::memcpy(step.initial_guess, lo[i].init_inverse, sizeof(step.initial_guess));
+                pair_result_from(q, step.keyframe); step.keyframe_scores = sk[i];
+                if (q.status == CVO_OK) {                            // what align() leaves behind (do_align)
+                    std::memcpy(K.R, q.R, sizeof(K.R)); std::memcpy(K.T, q.T, sizeof(K.T));
+                    K.ell = q.ell; K.iter = q.iter; K.A_nonzero = q.A_nonzero;
+                    Aff prev; std::memcpy(prev.m, q.prev_transform, sizeof(prev.m));
+                    K.prev_transform = prev; K.accum_transform = aff_mul(K.accum_transform, prev);
+                    std::memcpy(K.transform.m, q.transform, sizeof(K.transform.m));
+                } else {                                             // R, T stay as reset_initial set them, everything else as it was
+                    std::memcpy(step.keyframe.R, K.R, sizeof(K.R)); std::memcpy(step.keyframe.T, K.T, sizeof(K.T));
+                    std::memcpy(step.keyframe.transform, K.transform.m, sizeof(K.transform.m));
+                    step.keyframe.ell = K.ell; step.keyframe.iter = K.iter; step.keyframe.A_nonzero = K.A_nonzero;
+                }
+                S.commit_pending = true;
+                std::memcpy(S.t_odometry.m, r.transform, sizeof(S.t_odometry.m));
+            }
+        }
+        if (out) out[k] = step;
+    }
+    t->moving_before.clear();
+    t->in_flight = false;
+    return CVO_OK;
+}
+int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept) {
+    int rc = tracks_check_list(t, count, streams); if (rc) return rc;
+    if (!accept) return fail(CVO_ERR_INVALID, "null argument");
+    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    for (int k = 0; k < count; ++k)
+        if (!t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " expects no decision");
+    for (int k = 0; k < count; ++k) {
+        const int s = streams[k];
+        TrackStream& S = t->st[s]; KeyObject& K = S.key;
+        std::shared_ptr<Cloud>& fixed = t->key->fixed[s]; std::shared_ptr<Cloud>& moving = t->key->moving[s];
+        if (accept[k]) { K.previous = std::move(moving); K.pre_pc_init = true; }                        // update_previous_pcd, cvo.cpp:584-589
+        else {                                                                                          // reset_keyframe(t_odometry), cvo.cpp:591-604
+            if (!K.pre_pc_init) fixed = std::move(moving);
+            else { fixed = std::move(K.previous); K.previous = std::move(moving); K.pre_pc_init = true; }
+            K.transform = S.t_odometry;
+        }
+        moving.reset();
+        S.commit_pending = false;
+    }
+    return CVO_OK;
+}
+namespace {
+const Cloud* tracks_cloud(cvo_tracks_s* t, int s, int object, int slot) {
+    cvo_batch b = object == 0 ? t->odo : t->key;
+    if (slot == CVO_SLOT_FIXED) return b->fixed[s].get();
+    if (slot == CVO_SLOT_MOVING) return b->moving[s].get();
+    return object == 1 ? t->st[s].key.previous.get() : nullptr;
+}
+bool tracks_slot_ok(cvo_tracks_s* t, int s, int object, int slot) {
+    return t && s >= 0 && s < t->max_streams && (object == 0 || object == 1) && (slot == CVO_SLOT_FIXED || slot == CVO_SLOT_MOVING || slot == CVO_SLOT_PREVIOUS);
+}
+}  // namespace
+int cvo_tracks_get_cloud(cvo_tracks t, int s, int object, int slot, float* xyz, float* feat, int cap, int* n) {
+    if (!n || !tracks_slot_ok(t, s, object, slot)) return fail(CVO_ERR_INVALID, "bad argument");
+    return download_cloud(t->odo->eng, tracks_cloud(t, s, object, slot), xyz, feat, cap, n);
+}
+int cvo_tracks_get_selected_points(cvo_tracks t, int s, int object, int slot, unsigned short* px, int cap, int* n) {
+    if (!n || !tracks_slot_ok(t, s, object, slot)) return fail(CVO_ERR_INVALID, "bad argument");
+    return download_selected_points(t->odo->eng, tracks_cloud(t, s, object, slot), px, cap, n);
+}
+int cvo_tracks_get_state(cvo_tracks t, int s, int object, float R[9], float T[3], float* ell, float transform[12]) {
+    if (!t || s < 0 || s >= t->max_streams || (object != 0 && object != 1)) return fail(CVO_ERR_INVALID, "bad argument");
+    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    const StreamSlot& O = t->odo->streams[s]; const KeyObject& K = t->st[s].key;
+    if (R) std::memcpy(R, object == 0 ? O.R : K.R, sizeof(float) * 9);
+    if (T) std::memcpy(T, object == 0 ? O.T : K.T, sizeof(float) * 3);
+    if (ell) *ell = object == 0 ? O.ell : K.ell;
+    if (transform) std::memcpy(transform, object == 0 ? O.transform.m : K.transform.m, sizeof(float) * 12);
     return CVO_OK;
 }
 

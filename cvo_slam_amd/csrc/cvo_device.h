@@ -133,6 +133,23 @@ struct PairDesc {
                              // when it joins, at g + 1 members) instead of sharing one region cut into G parts -- see make_ctx
 };
 
+// K-stream tracker steps (cvo_tracks_step_async): between the odometry launch and the keyframe launch of a step, cvo_track_link_kernel evaluates
+// reset_initial (cvo.cpp:611-618) for every stream whose keyframe object aligns this frame, one lane per stream.  TrackLinkIn: what the keyframe
+// object carries, written by the host into pinned memory before the step is queued; TrackLinkOut: what the host takes in when the step is waited for.
+struct TrackLinkIn {
+    float R[9], T[3], ell;    // the keyframe object's R, T (kept when the odometry alignment failed) and ell
+    float transform[12];      // its cvo::transform
+    int iter;                 // its iter (Q4: stale unless an alignment breaks)
+    int odo_state, key_state; // index of the stream's odometry state (read) and keyframe state (written) in the two engines' state tables
+    int pad_;
+};
+struct TrackLinkOut {
+    float R[9], T[3];         // R, T after reset_initial
+    float init_inverse[12];   // what reset_initial returns (cvo.cpp:617)
+    int odo_status;           // the odometry alignment's status as the kernel read it (CVO_OK: reset_initial was evaluated)
+    int pad_[3];
+};
+
 // adaptive-ell variant (acvo::align, thirdparty/cvo/src/adaptive_cvo.cpp:490-555)
 struct AdaptiveRow { float omega[3], v[3], dl, ell, step; int nnz_xy, nnz_xx, nnz_yy; };   // == cvo_adaptive_row
 struct AdaptiveState {

@@ -117,4 +117,43 @@ public:
     void get_A_nonzero(int& nonzero) { cvo_get_A_nonzero(h_, &nonzero); }
 };
 
+// K tracker streams (cvo_tracks_* in include/cvo_hip.h): each stream is the pair of objects local_tracker owns, cvo_odometry (object 0) and
+// cvo_keyframe (object 1).  Not a class of the reference: there the two objects are stepped one frame, one sequence at a time.  Member names
+// follow the C entry points; errors throw, except the statuses a step reports per stream (cvo_track_step).
+class CvoTracks {
+    cvo_tracks t_ = nullptr;
+    static void check(int rc, const char* what) { if (rc != CVO_OK) throw std::runtime_error(std::string(what) + ": " + cvo_last_error()); }
+public:
+    enum { ODOMETRY = 0, KEYFRAME = 1 };
+    explicit CvoTracks(int max_streams, const cvo_params* params = nullptr, int device = 0) { check(cvo_tracks_create(params, device, max_streams, &t_), "cvo_tracks_create"); }
+    ~CvoTracks() { cvo_tracks_destroy(t_); }
+    CvoTracks(const CvoTracks&) = delete; CvoTracks& operator=(const CvoTracks&) = delete;
+
+    void set_num_want(int num_want) { check(cvo_tracks_set_num_want(t_, num_want), "set_num_want"); }
+    void set_arith_mode(int flags) { check(cvo_tracks_set_arith_mode(t_, flags), "set_arith_mode"); }
+    void reset(int s) { check(cvo_tracks_reset(t_, s), "reset"); }
+    // image k is the next frame of stream streams[k], generated with camera cams[cam_index[k]] (cam_index null: cams[0])
+    void step_async(int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                    const cvo_camera* cams, const int* cam_index = nullptr, void* hip_stream = nullptr) {
+        check(cvo_tracks_step_async(t_, count, streams, bgr8, depth16, width, height, cams, cam_index, hip_stream), "step_async");
+    }
+    bool done() { int d = 0; check(cvo_tracks_done(t_, &d), "done"); return d != 0; }
+    void wait(cvo_track_step* out, int count) { check(cvo_tracks_wait(t_, out, count), "wait"); }
+    void step(int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+              const cvo_camera* cams, const int* cam_index, cvo_track_step* out) {
+        step_async(count, streams, bgr8, depth16, width, height, cams, cam_index); wait(out, count);
+    }
+    // the caller's decision for the phase-2 frames just waited for: accept -> update_previous_pcd, else reset_keyframe(t_odometry)
+    void commit(int count, const int* streams, const int* accept) { check(cvo_tracks_commit(t_, count, streams, accept), "commit"); }
+    int get_cloud(int s, int object, int slot, float* xyz, float* feat, int cap) {
+        int n = 0; check(cvo_tracks_get_cloud(t_, s, object, slot, xyz, feat, cap, &n), "get_cloud"); return n;
+    }
+    int get_selected_points(int s, int object, int slot, unsigned short* px, int cap) {
+        int n = 0; check(cvo_tracks_get_selected_points(t_, s, object, slot, px, cap, &n), "get_selected_points"); return n;
+    }
+    void get_state(int s, int object, float R[9], float T[3], float& ell, Affine3f& transform) {
+        check(cvo_tracks_get_state(t_, s, object, R, T, &ell, transform.m), "get_state");
+    }
+};
+
 }  // namespace cvo_hip

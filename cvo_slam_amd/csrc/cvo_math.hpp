@@ -9,12 +9,21 @@
 // 3x3 matrices are row-major float[9].  Fixed-size 3-term reductions use Eigen's
 // unrolled order t0+(t1+t2); dynamic-size ones are sequential.
 #pragma once
+#if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
+#endif
 #include <math.h>
 
-namespace cvohip {
-
+// (a plain host compiler takes this header too: tests/test_tracks_host.py builds the reset_initial functions below with g++ -ffp-contract=off)
+#ifndef CVO_HD
+#if defined(__HIPCC__) || defined(__HIP__)
 #define CVO_HD __host__ __device__ __forceinline__
+#else
+#define CVO_HD inline
+#endif
+#endif
+
+namespace cvohip {
 
 CVO_HD float sum3f(float t0, float t1, float t2) { return t0 + (t1 + t2); }
 CVO_HD float dot3_seq(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
@@ -228,6 +237,62 @@ CVO_HD float dist_se3(const float* dR, const float* dT) {
     double u2 = 0;
     for (int k = 0; k < 3; ++k) { const double u = t[k] - 0.5 * pxt[k] + coef * ppxt[k]; u2 += u * u; }
     return (float)sqrt(2.0 * theta * theta + u2);
+}
+
+// ---- reset_initial, cvo.cpp:611-618: init = (transform * odometry).inverse(); R = init.rotation(); T = init.translation(); return init.inverse().
+// One statement of that arithmetic for the host's cvo_reset_initial and for the device (cvo_track_link_kernel, between the two align launches
+// of a tracker step): the same operations in the same order, every division correctly rounded on both sides, so the same bits.
+// Transforms are 3x4 row-major [R | t] (the top rows of an Affine3f).
+CVO_HD void aff_mul12(const float* a, const float* b, float* c) {   // Affine3f * Affine3f (the bottom row 0 0 0 1 takes part in the 4-term sums)
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k)
+            c[r * 4 + k] = (a[r * 4 + 0] * b[0 * 4 + k] + a[r * 4 + 1] * b[1 * 4 + k]) + (a[r * 4 + 2] * b[2 * 4 + k] + a[r * 4 + 3] * 0.f);
+        c[r * 4 + 3] = (a[r * 4 + 0] * b[0 * 4 + 3] + a[r * 4 + 1] * b[1 * 4 + 3]) + (a[r * 4 + 2] * b[2 * 4 + 3] + a[r * 4 + 3] * 1.f);
+    }
+}
+CVO_HD void aff_inverse12(const float* a, float* out) {             // Affine3f::inverse(), Affine mode: cofactor inverse of the linear part
+    float L[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) L[r * 3 + c] = a[r * 4 + c];
+    const float c00 = L[4] * L[8] - L[5] * L[7], c01 = L[5] * L[6] - L[3] * L[8], c02 = L[3] * L[7] - L[4] * L[6];
+    const float det = sum3f(L[0] * c00, L[1] * c01, L[2] * c02), id = 1.f / det;
+    float Li[9];
+    Li[0] = c00 * id; Li[1] = (L[2] * L[7] - L[1] * L[8]) * id; Li[2] = (L[1] * L[5] - L[2] * L[4]) * id;
+    Li[3] = c01 * id; Li[4] = (L[0] * L[8] - L[2] * L[6]) * id; Li[5] = (L[2] * L[3] - L[0] * L[5]) * id;
+    Li[6] = c02 * id; Li[7] = (L[1] * L[6] - L[0] * L[7]) * id; Li[8] = (L[0] * L[4] - L[1] * L[3]) * id;
+    const float t[3] = {a[3], a[7], a[11]}; float nt[3];
+    mat3_vec(Li, t, nt);
+    for (int i = 0; i < 3; ++i) { for (int k = 0; k < 3; ++k) out[i * 4 + k] = Li[i * 3 + k]; out[i * 4 + 3] = -nt[i]; }
+}
+// Affine3f::rotation(): orthogonal polar factor of the linear part (Eigen uses an SVD); Newton iteration X <- (X + X^-T)/2 in double
+// reaches the same matrix.
+CVO_HD void polar_rotation(const float* L, float* Rout) {
+    double X[9]; for (int i = 0; i < 9; ++i) X[i] = L[i];
+    for (int it = 0; it < 32; ++it) {
+        const double c00 = X[4] * X[8] - X[5] * X[7], c01 = X[5] * X[6] - X[3] * X[8], c02 = X[3] * X[7] - X[4] * X[6];
+        const double det = X[0] * c00 + X[1] * c01 + X[2] * c02;
+        double inv[9];
+        inv[0] = c00 / det; inv[1] = (X[2] * X[7] - X[1] * X[8]) / det; inv[2] = (X[1] * X[5] - X[2] * X[4]) / det;
+        inv[3] = c01 / det; inv[4] = (X[0] * X[8] - X[2] * X[6]) / det; inv[5] = (X[2] * X[3] - X[0] * X[5]) / det;
+        inv[6] = c02 / det; inv[7] = (X[1] * X[6] - X[0] * X[7]) / det; inv[8] = (X[0] * X[4] - X[1] * X[3]) / det;
+        double delta = 0, Y[9];
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) {
+            Y[r * 3 + c] = 0.5 * (X[r * 3 + c] + inv[c * 3 + r]);
+            const double d = fabs(Y[r * 3 + c] - X[r * 3 + c]);
+            if (delta < d) delta = d;
+        }
+        for (int i = 0; i < 9; ++i) X[i] = Y[i];
+        if (delta < 1e-15) break;
+    }
+    for (int i = 0; i < 9; ++i) Rout[i] = (float)X[i];
+}
+// reset_initial for an object whose cvo::transform is `transform`: R (row-major 3x3), T, and init.inverse() -- what the call returns (cvo.cpp:617)
+CVO_HD void reset_initial_eval(const float* transform, const float* odometry, float* R, float* T, float* init_inverse) {
+    float prod[12], init[12];
+    aff_mul12(transform, odometry, prod);
+    aff_inverse12(prod, init);                                       // cvo.cpp:613
+    float L[9]; for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) L[r * 3 + c] = init[r * 4 + c];
+    polar_rotation(L, R);                                            // cvo.cpp:614
+    T[0] = init[3]; T[1] = init[7]; T[2] = init[11];                 // cvo.cpp:615
+    aff_inverse12(init, init_inverse);                               // cvo.cpp:617
 }
 
 }  // namespace cvohip

@@ -10,6 +10,9 @@
 * replay            -- frame-to-frame CVO odometry through the C ABI (set_pcd / match_odometry from the images,
                        `update_fixed_pcd` after every frame, poses chained like `accum_transform`, `cvo.cpp:816`);
                        the reference's keyframe / loop-closure logic is control plane and stays out of scope.
+* tracker replay    -- the tracker's TWO alignments per frame (odometry object + keyframe object, local_tracker.cpp:228-251, 330-338,
+                       356-431, 506) with a caller-supplied accept rule: `replay_tracker` on two handles, `replay_tracker_many` on K tracker
+                       streams (cvo_tracks_*); poses chained without the reference's local pose-graph optimiser.
 """
 from __future__ import annotations
 
@@ -306,3 +309,167 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
     finally:
         B.close()
     return out
+
+
+# ----------------------------------------------------------------------------- the tracker's two objects (local_tracker.cpp:228-251, 330-338, 356-431, 506)
+def keyframe_roles(decisions):
+    """Which frame the KEYFRAME object holds as (fixed, moving, previous) cloud after every step of a stream: a pure function of the caller's
+    decisions, so that it can be checked without a GPU (tests/test_tracks_host.py holds it to the oracle's state machine).
+
+    decisions[j]: the decision on frame j + 2, the stream's j-th phase-2 frame -- True: accepted (update_previous_pcd, cvo.cpp:584-589), False:
+    rejected (reset_keyframe, cvo.cpp:591-604), None: the keyframe object did not see the frame (its odometry alignment failed).  Returns one
+    (fixed, moving, previous) per frame 0 .. len(decisions) + 1, frame indices or None, as the slots stand after the frame's step and decision:
+    frames 0 and 1 leave (0, None, None) -- the first frame is the fixed cloud (local_tracker.cpp:231), the second is not shown to the object --,
+    an accepted frame becomes the previous cloud, a rejected frame makes the previous cloud the fixed one and becomes the previous cloud itself --
+    or, while no frame has been accepted or rejected before (`!pre_pc_init`, cvo.cpp:593-596), becomes the fixed cloud."""
+    fixed, moving, previous, pre_pc_init = 0, None, None, False
+    out = [(fixed, moving, previous), (fixed, moving, previous)]
+    for j, d in enumerate(decisions):
+        f = j + 2
+        if d is not None:
+            moving = f                                              # match_keyframe: set_pcd fills the moving slot (cvo.cpp:362-366)
+            if d:
+                previous, moving, pre_pc_init = moving, None, True
+            elif not pre_pc_init:
+                fixed, moving = moving, None
+            else:
+                fixed, previous, moving = previous, moving, None
+        out.append((fixed, moving, previous))
+    return out
+
+
+def _tracker_poses(steps, decisions):
+    """Poses chained from a stream's steps WITHOUT an optimiser: frame 1 is pose 0 x odometry; an accepted frame whose keyframe alignment succeeded
+    is keyframe pose x keyframe transform; every other frame with a good odometry alignment is previous pose x odometry transform; a rejected frame
+    makes the previous frame the keyframe; a frame whose odometry alignment failed repeats the previous pose."""
+    poses, kf_pose = [], np.eye(4)
+    for k, (s, d) in enumerate(zip(steps, decisions)):
+        if k == 0:
+            poses.append(np.eye(4)); continue
+        prev = poses[-1]
+        if s["odometry"]["status"] != 0:
+            poses.append(prev.copy()); continue
+        if d is False:
+            kf_pose = prev
+        st = np.eye(4)
+        if d and s["keyframe"]["status"] == 0:
+            st[:3, :] = s["keyframe"]["transform"].astype(np.float64); poses.append(kf_pose @ st)
+        else:
+            st[:3, :] = s["odometry"]["transform"].astype(np.float64); poses.append(prev @ st)
+    return poses
+
+
+def _accept_args(step):
+    return (dict(step["odometry"], scores=step["odometry_scores"]),
+            dict(step["keyframe"], scores=step["keyframe_scores"], initial_guess=step["initial_guess"]))
+
+
+def replay_tracker(frames, camera, accept, params=None, device: int = 0, num_want: int = 3000, arith="base", sequence: int = 0):
+    """The tracker's loop on TWO HANDLES (a cvo_odometry and a cvo_keyframe object, local_tracker.cpp:228-251, 330-338, 356-431, 506), through the
+    entry points a single handle has: the reference the K-stream form (`replay_tracker_many`, cvo_tracks_*) is held to, bit for bit.
+
+    frames: a sequence of (bgr8, depth16); accept(sequence, frame, odometry_step, keyframe_step) -> bool is the CALLER's rule for every frame both
+    objects aligned (there is no built-in one: the reference's is control plane): odometry_step / keyframe_step are dicts of status, transform, R, T,
+    ell, iter, A_nonzero and `scores` (compute_innerproduct's fields), keyframe_step also `initial_guess`.  True: update_previous_pcd; False:
+    reset_keyframe(t_odometry).  A frame whose odometry alignment fails is not shown to the keyframe object (no decision is asked for).
+
+    Returns (poses, steps, decisions).  steps[k]: dict(phase, points, odometry, odometry_scores, keyframe, keyframe_scores, initial_guess), an
+    object that did not align the frame has status CVO_ERR_NOT_INITIALIZED; decisions[k]: True / False / None (none asked).  poses[k] (4, 4): the pose
+    of camera k in the frame of camera 0, chained WITHOUT an optimiser -- the reference optimises a local pose graph over these measurements instead
+    (local_map.cpp), which is out of scope here: an accepted frame is keyframe pose x keyframe transform, a rejected frame is previous pose x odometry
+    transform and makes the previous frame the keyframe."""
+    import ctypes as C
+    import cvo_slam_amd as ca
+    from .api import CVO_ERR_NOT_INITIALIZED, CvoError
+
+    def points(g, slot):
+        n = C.c_int(0); g.L.cvo_get_cloud(g.h, slot, None, None, 0, C.byref(n)); return n.value
+
+    def result(g, status):
+        st = g.get_state()
+        return dict(status=status, transform=g.transform, R=st["R"], T=st["T"], ell=st["ell"], iter=g.get_iteration_number(), A_nonzero=g.get_A_nonzero())
+
+    none = dict(status=CVO_ERR_NOT_INITIALIZED)
+    odo, kf = ca.Cvo(params, device=device), ca.Cvo(params, device=device)
+    steps, decisions = [], []
+    try:
+        for g in (odo, kf):
+            g.set_num_want(num_want); g.set_arith_mode(arith)
+        for k, (bgr, dep) in enumerate(frames):
+            step = dict(phase=min(k, 2), odometry=none, odometry_scores=None, keyframe=none, keyframe_scores=None, initial_guess=None)
+            decision = None
+            if k == 0:
+                odo.set_pcd_images(bgr, dep, camera); kf.set_pcd_images(bgr, dep, camera)          # :228, :231
+                step["points"] = points(odo, 0)
+            else:
+                try:
+                    odo.match_odometry_images(bgr, dep, camera); status = 0                          # :233, :356
+                except CvoError as e:
+                    status = e.code
+                step["points"] = points(odo, 1)
+                step["odometry"] = result(odo, status)
+                t = step["odometry"]["transform"]
+                if status == 0:
+                    step["odometry_scores"] = odo.compute_innerproduct(t)                            # :251, :375
+                odo.update_fixed_pcd()                                                               # :403
+                if status == 0 and k == 1:
+                    kf.first_frame = False; kf.reset_transform(t)                                    # :330-333
+                if status == 0 and k >= 2:
+                    step["initial_guess"] = kf.reset_initial(t)                                      # :407
+                    try:
+                        kf.match_keyframe_images(bgr, dep, camera); kstatus = 0                      # :415
+                    except CvoError as e:
+                        kstatus = e.code
+                    step["keyframe"] = result(kf, kstatus)
+                    if kstatus == 0:
+                        step["keyframe_scores"] = kf.compute_innerproduct(step["keyframe"]["transform"])   # :431
+                    decision = bool(accept(sequence, k, *_accept_args(step)))
+                    if decision:
+                        kf.update_previous_pcd()                                                     # :506
+                    else:
+                        kf.reset_keyframe(t)                                                         # :337 via :518
+            steps.append(step); decisions.append(decision)
+    finally:
+        odo.close(); kf.close()
+    return _tracker_poses(steps, decisions), steps, decisions
+
+
+def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None):
+    """`replay_tracker` for many sequences at once on one CvoTracks (cvo_tracks_*): each stream is the pair of objects of one sequence, every step
+    advances each running sequence by one frame -- one cvo_tracks_step per image size: generation, one odometry launch, reset_initial on the device,
+    one keyframe launch -- and hands the caller's decisions back with cvo_tracks_commit.  Scheduled by `plan_replay` (slots: the object's streams,
+    default one per sequence, fewer reuse streams through cvo_tracks_reset; starts: the step each sequence may start at).  sequences[i]: (bgr8,
+    depth16) frames (len() and indexing); cameras[i]: its (scaling_factor, fx, fy, cx, cy); accept: as for `replay_tracker`, called with the
+    sequence's index.  Returns [(poses, steps, decisions), ...], per sequence what `replay_tracker` returns for it alone: the same bits, poses
+    chained on the host the same way (no optimiser)."""
+    import cvo_slam_amd as ca
+    n_seq = len(sequences)
+    if len(cameras) != n_seq:
+        raise ValueError("one camera per sequence")
+    n_slots = n_seq if slots is None else int(slots)
+    plan = plan_replay([len(s) for s in sequences], max(1, n_slots), starts)
+    T = ca.CvoTracks(max(1, n_slots), params, device=device)
+    steps = [[] for _ in range(n_seq)]; decisions = [[] for _ in range(n_seq)]
+    try:
+        T.set_num_want(num_want)
+        T.set_arith_mode(arith)
+        for st in plan:
+            for p in st["resets"]:
+                T.reset(p)
+            frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
+            for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
+                cams = [tuple(cameras[i]) for _, i, _ in grp]
+                uniq = list(dict.fromkeys(cams))
+                res = T.step([p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams])
+                who, what = [], []
+                for (p, i, f), r in zip(grp, res):
+                    d = None
+                    if r["phase"] == 2 and r["odometry"]["status"] == 0:
+                        d = bool(accept(i, f, *_accept_args(r)))
+                        who.append(p); what.append(d)
+                    steps[i].append(r); decisions[i].append(d)
+                if who:
+                    T.commit(who, what)
+    finally:
+        T.close()
+    return [(_tracker_poses(steps[i], decisions[i]), steps[i], decisions[i]) for i in range(n_seq)]

@@ -268,6 +268,10 @@ int cvo_selftest_dist_se3_f32logm(int device, int n, const float* dR_dT, float* 
  *               polynomial's range), a by the branch-free 12-term chain, a by the degree-7 polynomial with its rounding guard (the steady walk)} --
  *               a = 0 for a pair that is not a member of A; d2_d2c_out (may be NULL): n x {d2, d2c} as the device formed them.
  *               tests/test_gpu_pair_values.py: all four bit-equal to the oracle's (float)(s2*exp(-d2/(2.0*l*l))) sequence on >= 1e7 samples. */
+/*   reset_initial: cvo::reset_initial (cvo.cpp:611-618) as the link kernel of the tracker streams evaluates it (cvo_tracks_step_async), with the very functions the
+ *               host's cvo_reset_initial calls      in: n x {the object's transform[12], odometry[12]}   out: n x {R[9] row-major, T[3], init.inverse()[12]}
+ *               tests/test_gpu_tracks.py: bit-equal to cvo_reset_initial on a handle and to the oracle */
+int cvo_selftest_reset_initial(int device, int n, const float* transform_odometry, float* out);
 int cvo_selftest_libm(int device, int n, const float* x, float* out6);
 int cvo_selftest_pair_values(int device, const cvo_params* params /* NULL = defaults */, float ell, int n, const float* y_g, float* a_out, float* d2_d2c_out);
 
@@ -539,6 +543,65 @@ int cvo_batch_set_tail_scores(cvo_batch b, int on);
 int cvo_batch_last_tail_answers(cvo_batch b, int n, int* masks);
 int cvo_batch_innerproduct_results(cvo_batch b, int n, cvo_track_scores* out);
 int cvo_batch_compute_innerproduct(cvo_batch b, int n, cvo_track_scores* out);
+
+
+/* ======================= K-stream tracker steps: the tracker's TWO objects per stream ===========
+ * local_tracker runs two cvo::cvo objects per frame (local_tracker.cpp:228-251, 330-338, 356-431, 506): cvo_odometry aligns the frame to the previous
+ * frame, cvo_keyframe aligns the same frame to the current keyframe, warm-started from the odometry result by reset_initial (cvo.cpp:611-618) and moved
+ * on, after the caller's accept decision, by update_previous_pcd or reset_keyframe (cvo.cpp:584-604).  A cvo_tracks object is K such pairs of objects.
+ * The accept rule stays with the caller; everything cvo::cvo does around it is done here, and every result is bit-identical to two handles driven
+ * through cvo_set_pcd_images, cvo_match_odometry_images, cvo_update_fixed_pcd, cvo_reset_initial, cvo_match_keyframe_images, cvo_update_previous_pcd /
+ * cvo_reset_keyframe (cvo_slam_amd/replay.py: replay_tracker is that loop).
+ *
+ * cvo_tracks_step_async: image k (as for cvo_batch_advance_images: one size per call, camera cams[cam_index[k]]) is the next frame of stream streams[k].
+ * The frame is generated ONCE; its cloud is the moving cloud of both objects and becomes the odometry object's fixed cloud at the stream's next step.
+ * By the frames a stream has seen:
+ *   phase 0 (first frame)   it becomes the FIXED cloud of both objects (local_tracker.cpp:228, 231); nothing is aligned.
+ *   phase 1 (second frame)  odometry: match_odometry and its score block (:233, :251).  When the step is waited for, the keyframe object gets
+ *                           first_frame = false; reset_transform(t_odometry) (:330-333); it does not see this frame.  No decision is expected.
+ *   phase 2 (later frames)  odometry alignment and score block (:356, :375); then on the keyframe object reset_initial(t_odometry) (:407),
+ *                           match_keyframe of the same frame (:415) and its score block (:431).  The stream's next step fails with CVO_ERR_INVALID
+ *                           until cvo_tracks_commit has been given the decision: accept != 0 update_previous_pcd (:506), accept == 0
+ *                           reset_keyframe(t_odometry) (:337 via :518; both branches of cvo.cpp:593-601).
+ * All of a step is queued without a host wait in between (the generator's one sync aside): ONE odometry launch over the listed streams, a link kernel
+ * that evaluates reset_initial on the device from the odometry launch's device-resident results, ONE keyframe launch over the phase-2 streams that
+ * starts from the states the link kernel wrote; both launches answer their score blocks in their tails (what a tail leaves open goes to the score
+ * kernel at cvo_tracks_wait).  hip_stream: a hipStream_t for the launches (NULL = the object's own).  One step is in flight at a time.
+ *
+ * A stream whose odometry alignment did not return CVO_OK (an empty frame: CVO_ERR_EMPTY_CLOUD, as a handle gives) leaves its keyframe object exactly
+ * as it was: keyframe.status is CVO_ERR_NOT_INITIALIZED, no decision is expected, a keyframe result computed anyway is dropped.  Its odometry object
+ * still moves on at the next step (update_fixed_pcd), as the two-handle loop does.  A keyframe alignment that itself fails is reported in
+ * keyframe.status; R and T stay as reset_initial set them, everything else is as it was, and a decision is expected as usual.  Argument errors -- a
+ * stream out of range or listed twice, a null pointer, the size limits of cvo_batch_advance_images, a step for a stream whose decision is pending, a
+ * decision for a stream that expects none -- fail with CVO_ERR_INVALID before any stream changes.
+ *
+ * cvo_tracks_wait: the results of the step in flight, one cvo_track_step per listed stream in list order (count = the step's count).  Entries of an
+ * object that did not align carry status CVO_ERR_NOT_INITIALIZED and zeros.  cvo_tracks_done never blocks.
+ * cvo_tracks_reset(t, s): stream s = two fresh objects.  cvo_tracks_get_cloud / _get_selected_points / _get_state: object 0 = odometry, 1 = keyframe;
+ * slot CVO_SLOT_FIXED / _MOVING / _PREVIOUS (the odometry object has no previous cloud: *n = 0). */
+typedef struct cvo_tracks_s* cvo_tracks;
+typedef struct cvo_track_step {
+    int phase;                          /* 0, 1, 2: see above */
+    int points;                         /* points of the frame's cloud */
+    cvo_pair_result  odometry;          /* match_odometry of the frame (phase >= 1) */
+    cvo_track_scores odometry_scores;   /* its compute_innerproduct (status CVO_OK only) */
+    cvo_pair_result  keyframe;          /* match_keyframe of the frame (phase 2, odometry CVO_OK) */
+    cvo_track_scores keyframe_scores;
+    float initial_guess[12];            /* what reset_initial returned, cvo.cpp:617 (phase 2, odometry CVO_OK) */
+} cvo_track_step;
+int cvo_tracks_create(const cvo_params* p /* NULL = defaults */, int device, int max_streams, cvo_tracks* out);
+int cvo_tracks_destroy(cvo_tracks t);
+int cvo_tracks_set_num_want(cvo_tracks t, int num_want);      /* as cvo_batch_set_num_want */
+int cvo_tracks_set_arith_mode(cvo_tracks t, int flags);       /* as cvo_batch_set_arith_mode, for both objects' launches */
+int cvo_tracks_reset(cvo_tracks t, int s);
+int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                          int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* hip_stream);
+int cvo_tracks_done(cvo_tracks t, int* done);
+int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out /* may be NULL */, int count);
+int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept);
+int cvo_tracks_get_cloud(cvo_tracks t, int s, int object, int slot, float* xyz, float* feat, int cap, int* n);
+int cvo_tracks_get_selected_points(cvo_tracks t, int s, int object, int slot, unsigned short* px, int cap, int* n);
+int cvo_tracks_get_state(cvo_tracks t, int s, int object, float R[9], float T[3], float* ell, float transform[12]);
 
 #ifdef __cplusplus
 }
