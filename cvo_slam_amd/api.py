@@ -121,6 +121,8 @@ ABI_SYMBOLS = [
     "cvo_selftest_reset_initial", "cvo_tracks_create", "cvo_tracks_destroy", "cvo_tracks_set_num_want", "cvo_tracks_set_arith_mode", "cvo_tracks_reset",
     "cvo_tracks_step_async", "cvo_tracks_done", "cvo_tracks_wait", "cvo_tracks_commit", "cvo_tracks_get_cloud", "cvo_tracks_get_selected_points",
     "cvo_tracks_get_state",
+    "cvo_batch_stage_images", "cvo_batch_advance_staged", "cvo_batch_staged_count",
+    "cvo_tracks_stage_async", "cvo_tracks_step_staged_async", "cvo_tracks_staged_count",
 ]
 
 _lib = None
@@ -282,6 +284,12 @@ def load_library():
     L.cvo_tracks_get_cloud.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, ip]
     L.cvo_tracks_get_selected_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, ip]
     L.cvo_tracks_get_state.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp]
+    L.cvo_batch_stage_images.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip]
+    L.cvo_batch_advance_staged.argtypes = [vp, ip]
+    L.cvo_batch_staged_count.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
+    L.cvo_tracks_stage_async.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip]
+    L.cvo_tracks_step_staged_async.argtypes = [vp, vp]
+    L.cvo_tracks_staged_count.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
     _lib = L
     return L
 
@@ -869,6 +877,27 @@ class CvoBatch:
                                                pts.ctypes.data_as(ip)))
         return pts
 
+    def stage_images(self, slots, images, cameras, cam_index=None):
+        """cvo_batch_stage_images: the arguments of advance_images, for the slots' NEXT frames.  Their clouds are generated on the stage's own
+        stream while a launch runs (call it between align_pairs_async and wait); the images may be reused as soon as the call returns.  One
+        stage per batch: a second call replaces the first.  Returns the number of images staged."""
+        args, keep = _image_list_args(slots, images, cameras, cam_index, "slot")
+        _check(self.L.cvo_batch_stage_images(self.h, *args))
+        return args[0]
+
+    def advance_staged(self):
+        """cvo_batch_advance_staged: advance_images of the staged list without generating anything; returns the points of each staged cloud"""
+        n = self.staged_count()[0]
+        pts = np.zeros(max(1, n), np.int32)
+        _check(self.L.cvo_batch_advance_staged(self.h, pts.ctypes.data_as(C.POINTER(C.c_int))))
+        return pts[:n]
+
+    def staged_count(self):
+        """cvo_batch_staged_count: (images in the stage now, clouds ever taken from a stage)"""
+        n = C.c_int(0); taken = C.c_longlong(0)
+        _check(self.L.cvo_batch_staged_count(self.h, C.byref(n), C.byref(taken)))
+        return n.value, taken.value
+
     def reset_stream(self, p: int):
         """cvo_batch_reset_stream: slot p becomes a fresh odometry object (no clouds, R = I, T = 0, ell = params.ell)"""
         _check(self.L.cvo_batch_reset_stream(self.h, int(p)))
@@ -1045,6 +1074,27 @@ class CvoBatch:
         _check(self.L.cvo_batch_results_to_device(self.h, C.c_void_p(dst_device_ptr), n, C.c_void_p(stream) if stream else None))
 
 
+def _image_list_args(ids, images, cameras, cam_index, what):
+    """the arguments the image-list entry points share (cvo_batch_advance_images, cvo_tracks_step_async and their stage calls): (n, ids, bgr
+    pointers, depth pointers, w, h, cameras, cam_index or None) plus the arrays that must stay alive during the call"""
+    ims = [Cvo._images(b, d) for b, d in images]
+    sl = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    if not ims or sl.shape[0] != len(ims):
+        raise ValueError(f"one {what} per image, at least one image")
+    w, h = ims[0][2], ims[0][3]
+    if any((q[2], q[3]) != (w, h) for q in ims):
+        raise ValueError("all images of one call must have the same size")
+    if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+        cameras = [cameras]
+    cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+    ci = None if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+    if ci is not None and (ci.shape[0] != len(ims) or ci.min() < 0 or ci.max() >= len(cameras)):
+        raise ValueError("cam_index: one index into cameras per image")
+    n = len(ims); ip = C.POINTER(C.c_int)
+    bgr = (C.c_void_p * n)(*[q[0].ctypes.data for q in ims]); dep = (C.c_void_p * n)(*[q[1].ctypes.data for q in ims])
+    return (n, sl.ctypes.data_as(ip), bgr, dep, w, h, cams, None if ci is None else ci.ctypes.data_as(ip)), (ims, sl, ci)
+
+
 def _pair_result_dict(r):
     return dict(transform=np.array(r.transform[:], np.float32).reshape(3, 4), R=np.array(r.R[:], np.float32).reshape(3, 3),
                 T=np.array(r.T[:], np.float32), ell=r.ell, iter=r.iter, A_nonzero=r.A_nonzero,
@@ -1114,6 +1164,30 @@ class CvoTracks:
                                             C.c_void_p(stream) if stream else None))
         self._n = n
         return n
+
+    def stage_async(self, streams, images, cameras, cam_index=None):
+        """cvo_tracks_stage_async: the arguments of step_async, for the streams' NEXT frames -- call it between step_async / step_staged_async
+        of the current step and its wait.  The images may be reused as soon as the call returns.  Returns the number of images staged."""
+        args, keep = _image_list_args(streams, images, cameras, cam_index, "stream")
+        _check(self.L.cvo_tracks_stage_async(self.h, *args))
+        return args[0]
+
+    def step_staged_async(self, stream: int | None = None):
+        """cvo_tracks_step_staged_async: step_async of the staged list, without generating anything"""
+        n = self.staged_count()[0]
+        _check(self.L.cvo_tracks_step_staged_async(self.h, C.c_void_p(stream) if stream else None))
+        self._n = n
+        return n
+
+    def step_staged(self):
+        self.step_staged_async()
+        return self.wait()
+
+    def staged_count(self):
+        """cvo_tracks_staged_count: (images in the stage now, clouds ever taken from a stage)"""
+        n = C.c_int(0); taken = C.c_longlong(0)
+        _check(self.L.cvo_tracks_staged_count(self.h, C.byref(n), C.byref(taken)))
+        return n.value, taken.value
 
     def done(self) -> bool:
         d = C.c_int(0)

@@ -91,6 +91,7 @@ int score_row_blocks(int na);
 int score_groups(int n);
 size_t score_box_bytes(int n);
 hipError_t launch_cloud_boxes(const float* rec, int n, float* gbox, hipStream_t stream);
+hipError_t launch_cloud_boxes_batch(const BoxDesc* descs, int n_clouds, int n_max, hipStream_t stream);
 hipError_t launch_adaptive(const AdaptiveArgs& A, int iterations, hipStream_t stream);
 int adaptive_partial_records(int nf, int nm);
 hipError_t launch_selftest(int kind, const float* in, float* out, int n, hipStream_t s);
@@ -1420,6 +1421,23 @@ struct BatchImages {
     }
 };
 
+// The frames of the NEXT step of a batch's or a tracker's streams, generated ahead of it (cvo_batch_stage_images, cvo_tracks_stage_async) on a stream
+// and in generator scratch of their own, while the launches of the current step run.  Three states: nothing staged; `pending`, the generator
+// queued (ev_gen behind its read-back of the point counts); `placed`, the counts read, every cloud copied into a cloud object that nothing
+// else holds and its group boxes made (one scatter and ONE box launch on the stage stream, ev_done behind them).  Placing needs the counts
+// on the host, so it happens where the host next looks and finds the generator finished: at the end of a wait, else in the consuming call.
+struct FrameStage {
+    hipStream_t s = nullptr; hipEvent_t ev_gen = nullptr, ev_done = nullptr;
+    BatchImages img;
+    PinBuf h_box;                                                   // the box launch's descriptor table (read by the kernel where it is)
+    bool pending = false, placed = false, gen_waited = true;
+    int rc = CVO_OK; std::string err;                               // what placing found: reported by the consuming call
+    std::vector<int> list, points;                                  // the slots / streams listed, in list order, and their clouds' points
+    std::vector<std::shared_ptr<Cloud>> clouds;
+    std::vector<std::shared_ptr<Cloud>>* pool = nullptr;            // where free cloud objects come from: one that only the pool holds is free
+    long long taken = 0;
+};
+
 // A pair slot run as one cvo::cvo odometry object (cvo_batch_advance_images): the fields a handle carries from one align() into the next
 // (cvo_handle_s, do_align), kept on the host and uploaded as the slot's start state by every launch that lists it.
 struct StreamSlot {
@@ -1445,6 +1463,8 @@ struct cvo_batch_s {
     std::vector<unsigned char> last_stream_pos, last_not_run;   // ... which were stream slots, which had no moving cloud (not run: CVO_ERR_NOT_INITIALIZED)
     bool settled = true;                    // the last launch's results have been taken in (batch_settle)
     bool clouds_changed = false;            // a slot of the last launch has new clouds since: answers computed from its clouds would be for others
+    FrameStage stage;                       // the next frames, staged ahead (cvo_batch_stage_images; a tracker's stage lives in its odometry batch)
+    std::vector<std::shared_ptr<Cloud>> pool;   // cloud objects for staged frames and the ones slots gave back to cvo_batch_advance_staged
 };
 
 namespace {
@@ -2163,9 +2183,10 @@ void fresh_stream(cvo_batch b, int p) {
     for (Cloud* c : {b->fixed[p].get(), b->moving[p].get()})
         if (c) { c->n = 0; c->n_px = 0; c->boxes_valid = false; c->raw = nullptr; c->raw_feat = nullptr; c->cost_hint = 0.f; }
 }
+void report_step_laps(const char* who); void stage_drop(cvo_batch b); void stage_drop_if_listed(cvo_batch b, int p); void stage_destroy(cvo_batch b); int stage_place(cvo_batch b, bool block);   // (the stage: below, behind the generator)
 // what every set_* did to the single flag it had: each plain pair starts its next launch from init_states again.  Slots set here stop being streams.
 void states_dirty(cvo_batch b) { std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)1); }
-void end_stream(cvo_batch b, int p) { if (b->streams[p].on) { b->streams[p] = StreamSlot(); fresh_state(b->init_states[p], b->prm.ell); } }
+void end_stream(cvo_batch b, int p) { stage_drop_if_listed(b, p); if (b->streams[p].on) { b->streams[p] = StreamSlot(); fresh_state(b->init_states[p], b->prm.ell); } }
 // A slot of the last launch got new clouds: answers held for them (score blocks computed from the slots' clouds) would be for others
 void slot_clouds_changed(cvo_batch b, int p) {
     for (int i = 0; i < b->last_n && !b->clouds_changed; ++i) b->clouds_changed = b->last_slots[i] == p;
@@ -2233,9 +2254,11 @@ int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* 
 int cvo_batch_destroy(cvo_batch b) {
     if (!b) return CVO_OK;
     (void)hipSetDevice(b->eng.device);
+    stage_destroy(b);                                               // (drains the stage stream first)
     if (b->eng.stream) (void)hipStreamSynchronize(b->eng.stream);
-    b->fixed.clear(); b->moving.clear();
+    b->fixed.clear(); b->moving.clear(); b->pool.clear();
     b->img.release();
+    report_step_laps("batch");
     b->eng.destroy();
     delete b;
     return CVO_OK;
@@ -2276,18 +2299,43 @@ int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* f
 // ---- clouds from RGB-D images: every image generated once by the batched generator (cvo_pcd_kernels.hip, a fixed list of launches over all
 // images, makeMaps decided on the device), ONE host sync for the point counts, then each destination cloud copied from its image's slot
 namespace {
-// The clouds of N images (all w x h) into the images' slots of b->img.cloud / px; *recs: their records on the host.  cam: one camera for all,
-// or cam_table (host, N cameras): a camera per image.  Nothing of the batch's pairs changes.
-int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height, const cvo_camera* cam,
-                   const cvo_camera* cam_table, const PcdImgRec** recs) {
-    Engine& E = b->eng; BatchImages& S = b->img;
-    HIP_TRY(hipSetDevice(E.device));
+// CVO_HIP_STEP_LAPS=1: host timers around the stages of a K-stream step, added up and printed (stderr, ms per step) when the object is destroyed.
+// A measuring mode: it waits for each host-to-device copy where it is queued, so that the copy's time is its own lap and not the generator's.
+struct StepLaps {
+    enum { COPY, H2D, GENERATE, SCATTER, LAUNCH, WAIT, COMMIT, STAGE, CONSUME, N };
+    bool on = false; double ms[N] = {}; long steps = 0;
+};
+StepLaps* step_laps() {
+    static StepLaps L = [] { StepLaps l; const char* e = std::getenv("CVO_HIP_STEP_LAPS"); l.on = e && std::atoi(e) != 0; return l; }();
+    return &L;
+}
+struct Lap {
+    int k; std::chrono::steady_clock::time_point t0;
+    explicit Lap(int k_) : k(k_) { if (step_laps()->on) t0 = std::chrono::steady_clock::now(); }
+    ~Lap() { if (step_laps()->on) step_laps()->ms[k] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+void report_step_laps(const char* who) {
+    StepLaps& L = *step_laps();
+    if (!L.on || L.steps <= 0) return;
+    static const char* name[StepLaps::N] = {"host_copy", "h2d_copy", "generate_to_sync", "scatter", "launches", "wait", "commit", "stage_call", "consume_call"};
+    std::fprintf(stderr, "[cvo_hip] %s step laps, ms per step over %ld steps:", who, L.steps);
+    for (int q = 0; q < StepLaps::N; ++q) std::fprintf(stderr, " %s %.3f", name[q], L.ms[q] / (double)L.steps);
+    std::fprintf(stderr, "\n");
+    L = StepLaps(); L.on = true;
+}
+// N images (all w x h) queued for generation on stream s into the images' slots of S.cloud / S.px: the images copied into S's pinned stage (by
+// `copy_parts` threads of the copy pool), their host-to-device copies, the generator's fixed list of launches, the read-back of the records into
+// S.h_rec.  Waits for nothing but a growing scratch; the caller's images are free when it returns.  cam: one camera for all, or cam_table
+// (host, N cameras): a camera per image.
+int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                     const cvo_camera* cam, const cvo_camera* cam_table, int copy_parts) {
     const int w = width, h = height, num_want = S.num_want;
     const size_t n = (size_t)w * h, n1 = (size_t)(w / 2) * (h / 2), n2 = (size_t)(w / 4) * (h / 4), nths = (size_t)(w / 32) * (h / 32) + 100;
     const int nt = pcd_tiles(w, h), cap = PCD_CLOUD_CAP;
+    const bool laps = step_laps()->on;
     int rc;
     if (N > S.n_cap || w != S.w || h != S.h) {
-        HIP_TRY(hipStreamSynchronize(E.stream));                       // the previous call's copies to the pairs may still read the slots
+        HIP_TRY(hipStreamSynchronize(s));                              // the previous call's copies out of the slots may still read them
         const size_t m = (size_t)std::max(N, S.n_cap);
         if ((rc = S.bgr.ensure(3 * n * m)) || (rc = S.depth.ensure(2 * n * m)) || (rc = S.map.ensure(n * m))) return rc;
         for (DevBuf* x : {&S.I0, &S.dx0, &S.dy0, &S.abs0}) if ((rc = x->ensure(sizeof(float) * n * m))) return rc;
@@ -2306,43 +2354,66 @@ int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const u
         S.n_cap = (int)m; S.w = w; S.h = h;
     }
     if (cam_table && ((rc = S.cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)) || (rc = S.h_cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)))) return rc;
-    hipStream_t s = E.stream;
     unsigned char* st = static_cast<unsigned char*>(S.stage.p);
+    // image k of `src` (bytes each) to dst + bytes * k, the images dealt to the copy threads in runs
+    auto copy_images = [&](unsigned char* dst, const void* const* src, size_t bytes) {
+        Lap lap(StepLaps::COPY);
+        const int parts = std::max(1, std::min(copy_parts, N));
+        CopyPool::get().run(parts, [&](int q) { for (int k = (int)((long long)N * q / parts); k < (int)((long long)N * (q + 1) / parts); ++k) std::memcpy(dst + bytes * k, src[k], bytes); });
+    };
+    // the colour images first: their copy and the pyramid / threshold / select kernels (which need nothing else) run while the host stages the depth images
+    copy_images(st, reinterpret_cast<const void* const*>(bgr8), 3 * n);
+    HIP_TRY(hipMemcpyAsync(S.bgr.p, st, 3 * n * N, hipMemcpyHostToDevice, s));
+    if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    HIP_TRY(hipMemsetAsync(S.ths.p, 0, sizeof(float) * nths * N, s));
+    HIP_TRY(hipMemsetAsync(S.thsS.p, 0, sizeof(float) * nths * N, s));
+    HIP_TRY(hipMemsetAsync(S.map.p, 0, n * N, s));
+    HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(PcdImgRec) * N, s));
+    float* abs0 = (float*)S.abs0.p; float* abs1 = (float*)S.abs1.p; float* abs2 = (float*)S.abs2.p; PcdImgRec* rec = (PcdImgRec*)S.rec.p;
+    hipError_t e = pcd_launch_pyramid((const uint8_t*)S.bgr.p, w, h, (float*)S.I0.p, (float*)S.I1.p, (float*)S.I2.p, (float*)S.dx0.p, (float*)S.dy0.p, abs0, abs1, abs2, N, s);
+    if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)S.ths.p, (float*)S.thsS.p, N, s);
+    if (e == hipSuccess) e = pcd_launch_select_batch(abs0, abs1, abs2, (const float*)S.thsS.p, w, h, (uint8_t*)S.map.p, rec, N, num_want, s);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
+    unsigned char* sd = st + 3 * n * N;
+    copy_images(sd, reinterpret_cast<const void* const*>(depth16), 2 * n);
+    if (laps) { Lap lap(StepLaps::GENERATE); HIP_TRY(hipStreamSynchronize(s)); }   // (the kernels queued so far: not part of the depth copy's lap)
+    HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
+    if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    const cvo_camera& c0 = cam ? *cam : cam_table[0];
+    const float camv[5] = {c0.scaling_factor, c0.fx, c0.fy, c0.cx, c0.cy};
+    if (cam_table) {
+        std::memcpy(S.h_cams.p, cam_table, sizeof(cvo_camera) * (size_t)N);
+        HIP_TRY(hipMemcpyAsync(S.cams.p, S.h_cams.p, sizeof(cvo_camera) * (size_t)N, hipMemcpyHostToDevice, s));
+    }
+    e = pcd_launch_subsample_batch((uint8_t*)S.map.p, (const uint8_t*)S.pattern.p, rec, num_want, (const uint16_t*)S.depth.p, w, h, (int*)S.tiles.p, N, s);
+    if (e == hipSuccess) e = pcd_launch_cloud_batch((const uint8_t*)S.map.p, (const uint16_t*)S.depth.p, (const uint8_t*)S.bgr.p, (const float*)S.dx0.p, (const float*)S.dy0.p,
+                                                    w, h, camv, cam_table ? (const float*)S.cams.p : nullptr, (const int*)S.tiles.p, rec, cap, (float*)S.cloud.p,
+                                                    (uint16_t*)S.px.p, N, s);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(S.h_rec.p, S.rec.p, sizeof(PcdImgRec) * N, hipMemcpyDeviceToHost, s));
+    return CVO_OK;
+}
+int check_cloud_caps(const PcdImgRec* R, int N) {
+    for (int k = 0; k < N; ++k)
+        if (R[k].npts > PCD_CLOUD_CAP) return fail(CVO_ERR_INVALID, "image " + std::to_string(k) + ": more than 65535 points per cloud is not supported (16-bit column indices)");
+    return CVO_OK;
+}
+// The clouds of N images (all w x h) into the images' slots of b->img.cloud / px; *recs: their records on the host.  Nothing of the batch's pairs changes.
+int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height, const cvo_camera* cam,
+                   const cvo_camera* cam_table, const PcdImgRec** recs) {
+    Engine& E = b->eng; BatchImages& S = b->img;
+    HIP_TRY(hipSetDevice(E.device));
+    hipStream_t s = E.stream;
     {
         // every return from here on leaves nothing of this call in flight: the next call overwrites the pinned stage the copies read from
         struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-        // the colour images first: their copy and the pyramid / threshold / select kernels (which need nothing else) run while the host stages the depth images
-        for (int k = 0; k < N; ++k) std::memcpy(st + 3 * n * k, bgr8[k], 3 * n);
-        HIP_TRY(hipMemcpyAsync(S.bgr.p, st, 3 * n * N, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(S.ths.p, 0, sizeof(float) * nths * N, s));
-        HIP_TRY(hipMemsetAsync(S.thsS.p, 0, sizeof(float) * nths * N, s));
-        HIP_TRY(hipMemsetAsync(S.map.p, 0, n * N, s));
-        HIP_TRY(hipMemsetAsync(S.rec.p, 0, sizeof(PcdImgRec) * N, s));
-        float* abs0 = (float*)S.abs0.p; float* abs1 = (float*)S.abs1.p; float* abs2 = (float*)S.abs2.p; PcdImgRec* rec = (PcdImgRec*)S.rec.p;
-        hipError_t e = pcd_launch_pyramid((const uint8_t*)S.bgr.p, w, h, (float*)S.I0.p, (float*)S.I1.p, (float*)S.I2.p, (float*)S.dx0.p, (float*)S.dy0.p, abs0, abs1, abs2, N, s);
-        if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)S.ths.p, (float*)S.thsS.p, N, s);
-        if (e == hipSuccess) e = pcd_launch_select_batch(abs0, abs1, abs2, (const float*)S.thsS.p, w, h, (uint8_t*)S.map.p, rec, N, num_want, s);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
-        unsigned char* sd = st + 3 * n * N;
-        for (int k = 0; k < N; ++k) std::memcpy(sd + 2 * n * k, depth16[k], 2 * n);
-        HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
-        const cvo_camera& c0 = cam ? *cam : cam_table[0];
-        const float camv[5] = {c0.scaling_factor, c0.fx, c0.fy, c0.cx, c0.cy};
-        if (cam_table) {
-            std::memcpy(S.h_cams.p, cam_table, sizeof(cvo_camera) * (size_t)N);
-            HIP_TRY(hipMemcpyAsync(S.cams.p, S.h_cams.p, sizeof(cvo_camera) * (size_t)N, hipMemcpyHostToDevice, s));
-        }
-        e = pcd_launch_subsample_batch((uint8_t*)S.map.p, (const uint8_t*)S.pattern.p, rec, num_want, (const uint16_t*)S.depth.p, w, h, (int*)S.tiles.p, N, s);
-        if (e == hipSuccess) e = pcd_launch_cloud_batch((const uint8_t*)S.map.p, (const uint16_t*)S.depth.p, (const uint8_t*)S.bgr.p, (const float*)S.dx0.p, (const float*)S.dy0.p,
-                                                        w, h, camv, cam_table ? (const float*)S.cams.p : nullptr, (const int*)S.tiles.p, rec, cap, (float*)S.cloud.p,
-                                                        (uint16_t*)S.px.p, N, s);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
-        HIP_TRY(hipMemcpyAsync(S.h_rec.p, S.rec.p, sizeof(PcdImgRec) * N, hipMemcpyDeviceToHost, s));
-    }                                                                 // (the one sync: Drain)
+        int rc = generate_enqueue(E, S, s, N, bgr8, depth16, width, height, cam, cam_table, 1); if (rc) return rc;
+        Lap lap(StepLaps::GENERATE);
+        (void)hipStreamSynchronize(s);
+    }                                                                 // (the one sync)
     HIP_TRY(hipStreamSynchronize(s));                                 // (reports an error of the queued work; nothing left to wait for)
     const PcdImgRec* R = static_cast<const PcdImgRec*>(S.h_rec.p);
-    for (int k = 0; k < N; ++k)
-        if (R[k].npts > cap) return fail(CVO_ERR_INVALID, "image " + std::to_string(k) + ": more than 65535 points per cloud is not supported (16-bit column indices)");
+    int rc = check_cloud_caps(R, N); if (rc) return rc;
     *recs = R;
     return CVO_OK;
 }
@@ -2379,6 +2450,141 @@ int batch_scatter(cvo_batch b, const std::vector<Cloud*>& dst, const std::vector
     return CVO_OK;
 }
 bool image_size_ok(int width, int height) { return width >= 64 && height >= 64 && (size_t)width * height <= (size_t)1 << 26; }
+
+// ---- the stage: the next step's frames generated ahead, on a stream of their own (FrameStage)
+void pool_free_cloud(std::vector<std::shared_ptr<Cloud>>& pool, std::shared_ptr<Cloud>& out) {
+    for (std::shared_ptr<Cloud>& c : pool) if (c.use_count() == 1) { out = c; return; }
+    pool.push_back(std::make_shared<Cloud>());
+    out = pool.back();
+}
+// The stage stream is made with the highest priority the device has.  HIP deals streams of one priority onto the process's few hardware queues in turn,
+// and a stream that lands on the queue of a persistent align launch makes no progress until that launch ends; priority streams take their queues
+// from a set of their own, so the generator's copies and kernels start while the launch runs (on the CUs it leaves free) instead of behind it.
+int stage_ready(cvo_batch b) {
+    FrameStage& F = b->stage;
+    if (F.s) return CVO_OK;
+    int least = 0, greatest = 0;
+    HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_TRY(hipStreamCreateWithPriority(&F.s, hipStreamNonBlocking, greatest));
+    HIP_TRY(hipEventCreateWithFlags(&F.ev_gen, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&F.ev_done, hipEventDisableTiming));
+    if (!F.pool) F.pool = &b->pool;
+    return CVO_OK;
+}
+// the staged list is given up: its cloud objects are free again (only the pool holds them).  Work of it that is still queued runs to its end on the
+// stage stream; the next stage call is ordered behind it there and waits for its copies before it writes the pinned stage again.
+void stage_drop(cvo_batch b) {
+    FrameStage& F = b->stage;
+    F.pending = F.placed = false; F.rc = CVO_OK; F.err.clear();
+    F.list.clear(); F.points.clear(); F.clouds.clear();
+}
+void stage_drop_if_listed(cvo_batch b, int p) {
+    FrameStage& F = b->stage;
+    if (F.pending && std::find(F.list.begin(), F.list.end(), p) != F.list.end()) stage_drop(b);
+}
+// `count` images staged for the slots / streams of `list` (the arguments are checked): returns with everything queued and every image byte copied
+int stage_begin(cvo_batch b, int count, const int* list, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                const cvo_camera* cams, const int* cam_index) {
+    Lap lap(StepLaps::STAGE);
+    Engine& E = b->eng; FrameStage& F = b->stage;
+    HIP_TRY(hipSetDevice(E.device));
+    int rc = stage_ready(b); if (rc) return rc;
+    F.img.num_want = b->img.num_want;
+    // an earlier stage's copies read the pinned stage this call writes, its read-back writes the records this call's placing reads
+    if (!F.gen_waited) { F.gen_waited = true; HIP_TRY(hipEventSynchronize(F.ev_gen)); }
+    stage_drop(b);                                                   // (a stage that was never consumed is replaced)
+    std::vector<cvo_camera> cam_of(count);
+    for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
+    rc = generate_enqueue(E, F.img, F.s, count, bgr8, depth16, width, height, nullptr, cam_of.data(), E.upload_threads);
+    if (rc) { (void)hipStreamSynchronize(F.s); return rc; }         // (nothing of a failed call stays in flight)
+    HIP_TRY(hipEventRecord(F.ev_gen, F.s));
+    F.gen_waited = false;
+    F.list.assign(list, list + count);
+    F.pending = true;
+    return CVO_OK;
+}
+// The staged clouds into cloud objects nobody holds, with their boxes: needs the point counts, so the generator must have finished.  block: wait
+// for it; else only when it already has.  What goes wrong here (a cloud above 65 535 points, a HIP error of the staged work) is kept for the
+// consuming call to report.  The objects are free ones of the pool: no queued or running launch reads them -- a launch only reads clouds that
+// slots held when it was set up, and a slot's object returns to the pool (commit, wait, the next step's hand-over) after its launch was waited for.
+int stage_place(cvo_batch b, bool block) {
+    Engine& E = b->eng; FrameStage& F = b->stage;
+    if (!F.pending || F.placed) return CVO_OK;
+    HIP_TRY(hipSetDevice(E.device));
+    if (!block) {
+        const hipError_t q = hipEventQuery(F.ev_gen);
+        if (q == hipErrorNotReady) { (void)hipGetLastError(); return CVO_OK; }
+    }
+    F.placed = true;
+    const hipError_t es = hipEventSynchronize(F.ev_gen);
+    F.gen_waited = true;
+    if (es != hipSuccess) { (void)hipGetLastError(); F.rc = CVO_ERR_HIP; F.err = std::string("staged frames: ") + hipGetErrorString(es); return CVO_OK; }
+    const int N = (int)F.list.size(), cap = PCD_CLOUD_CAP;
+    const PcdImgRec* R = static_cast<const PcdImgRec*>(F.img.h_rec.p);
+    if (check_cloud_caps(R, N) != CVO_OK) { F.rc = CVO_ERR_INVALID; F.err = g_err; return CVO_OK; }
+    auto bad = [&](int rc) { F.rc = rc; F.err = g_err; F.clouds.clear(); return CVO_OK; };
+    int rc;
+    if ((rc = F.h_box.ensure(sizeof(BoxDesc) * (size_t)N))) return bad(rc);
+    BoxDesc* bd = static_cast<BoxDesc*>(F.h_box.p);
+    F.clouds.assign(N, nullptr); F.points.assign(N, 0);
+    PcdScatter sc; std::memset(&sc, 0, sizeof(sc));
+    sc.src = (const float*)F.img.cloud.p; sc.src_px = (const uint16_t*)F.img.px.p; sc.rec = (const PcdImgRec*)F.img.rec.p; sc.cap = cap;
+    int n_max = 0, n_box = 0, box_max = 0;
+    auto flush = [&]() -> int {
+        const hipError_t e = pcd_launch_scatter(sc, n_max, F.s);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd scatter: ") + hipGetErrorString(e));
+        sc.n = 0; n_max = 0; return CVO_OK;
+    };
+    for (int k = 0; k < N; ++k) {
+        pool_free_cloud(*F.pool, F.clouds[k]);
+        Cloud& c = *F.clouds[k];
+        const PcdImgRec& r = R[k];
+        F.points[k] = r.npts;
+        c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr;
+        c.cost_hint = r.cost_n > 0 ? (float)(r.cost / r.cost_n) : 0.f;
+        if (c.n <= 0) continue;
+        if ((rc = c.buf.ensure((size_t)c.n * REC * sizeof(float))) || (rc = c.px.ensure((size_t)c.n * 2 * sizeof(uint16_t))) || (rc = c.boxes.ensure(score_box_bytes(c.n)))) return bad(rc);
+        sc.img[sc.n] = k; sc.dst[sc.n] = c.rec(); sc.dst_px[sc.n] = (uint16_t*)c.px.p; ++sc.n; n_max = std::max(n_max, c.n);
+        if (sc.n == PCD_SCATTER_MAX && (rc = flush())) return bad(rc);
+        BoxDesc& D = bd[n_box++];
+        D.rec = c.rec(); D.gbox = static_cast<float*>(c.boxes.p); D.self_cache = score_self_cache(D.gbox, c.n); D.n = c.n; D.ngroups = score_groups(c.n);
+        box_max = std::max(box_max, c.n);
+        c.boxes_valid = true; c.boxes_stream = E.stream;             // (the engine's stream is ordered behind ev_done before anything uses them: stage_take)
+    }
+    if (sc.n > 0 && (rc = flush())) return bad(rc);
+    const hipError_t e = launch_cloud_boxes_batch(bd, n_box, box_max, F.s);
+    if (e != hipSuccess) return bad(fail(CVO_ERR_HIP, std::string("cloud box kernel launch: ") + hipGetErrorString(e)));
+    const hipError_t er = hipEventRecord(F.ev_done, F.s);
+    if (er != hipSuccess) return bad(fail(CVO_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(er)));
+    return CVO_OK;
+}
+// The consuming call's first half: the staged clouds are placed (waiting for the generator if it has not finished), an error of the staged work
+// is reported and drops the stage.  On success F.clouds / F.points are the listed frames' clouds, and the engine's stream waits for them by an
+// event: launches on it follow without a host wait, a launch on another stream waits for the engine's stream once (Engine::settle_uploads).
+int stage_take(cvo_batch b) {
+    FrameStage& F = b->stage;
+    int rc = stage_place(b, true); if (rc) return rc;
+    if (F.rc != CVO_OK) { const int code = F.rc; const std::string msg = F.err; stage_drop(b); return fail(code, msg); }
+    HIP_TRY(hipStreamWaitEvent(b->eng.stream, F.ev_done, 0));
+    b->eng.uploads_pending = true;
+    return CVO_OK;
+}
+void stage_taken(cvo_batch b) { FrameStage& F = b->stage; F.taken += (long long)F.list.size(); stage_drop(b); }
+void stage_destroy(cvo_batch b) {
+    FrameStage& F = b->stage;
+    if (F.s) (void)hipStreamSynchronize(F.s);
+    stage_drop(b);
+    F.img.release(); F.h_box.release();
+    if (F.ev_gen) (void)hipEventDestroy(F.ev_gen);
+    if (F.ev_done) (void)hipEventDestroy(F.ev_done);
+    if (F.s) (void)hipStreamDestroy(F.s);
+    F.s = nullptr; F.ev_gen = F.ev_done = nullptr;
+}
+int stage_count(cvo_batch b, int* images, long long* taken) {
+    if (images) *images = b->stage.pending ? (int)b->stage.list.size() : 0;
+    if (taken) *taken = b->stage.taken;
+    return CVO_OK;
+}
 }  // namespace
 
 int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
@@ -2459,6 +2665,63 @@ int cvo_batch_reset_stream(cvo_batch b, int p) {
     fresh_stream(b, p);
     return CVO_OK;
 }
+namespace {
+int batch_check_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                       const cvo_camera* cams, const int* cam_index) {
+    if (!b || count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad image count");
+    if (!slots || !bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
+    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
+    std::vector<unsigned char> seen(b->max_pairs, 0);
+    for (int k = 0; k < count; ++k) {
+        if (slots[k] < 0 || slots[k] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
+        if (seen[slots[k]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
+        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+        if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
+    }
+    return CVO_OK;
+}
+}  // namespace
+// ---- the next frames of stream slots staged ahead: generated on a stream of the stage's own while a launch runs, taken by cvo_batch_advance_staged
+int cvo_batch_stage_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                           const cvo_camera* cams, const int* cam_index) {
+    int rc = batch_check_images(b, count, slots, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
+    return stage_begin(b, count, slots, bgr8, depth16, width, height, cams, cam_index);
+}
+int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    FrameStage& F = b->stage;
+    if (!F.pending) return fail(CVO_ERR_INVALID, "nothing staged (cvo_batch_stage_images)");
+    Lap lap(StepLaps::CONSUME);
+    int rc = batch_settle(b); if (rc) return rc;
+    if ((rc = stage_take(b))) return rc;                             // (fails before any slot changes)
+    // the cloud objects the slots give up go to the pool and are written by a later stage: no launch may still read them then
+    if (b->eng.launched && b->eng.last_stream) HIP_TRY(hipStreamSynchronize(b->eng.last_stream));
+    auto give_up = [&](std::shared_ptr<Cloud>& c) { if (c && c.use_count() == 1) b->pool.push_back(c); c.reset(); };   // (an object the pool knows is free once the slot lets go)
+    const int count = (int)F.list.size();
+    for (int k = 0; k < count; ++k) {                                // the commit of cvo_batch_advance_images, with cloud objects handed over instead of written
+        const int p = F.list[k];
+        if (!b->streams[p].on) fresh_stream(b, p);
+        StreamSlot& S = b->streams[p];
+        slot_clouds_changed(b, p);
+        if (!S.init) {                                                // cvo.cpp:352-360: the first frame only fills the fixed cloud
+            S.init = true;
+            give_up(b->fixed[p]); b->fixed[p] = F.clouds[k];
+            if (!b->moving[p]) b->moving[p].reset(new Cloud());
+        } else {
+            if (S.has_moving) { give_up(b->fixed[p]); b->fixed[p] = b->moving[p]; b->moving[p].reset(); }   // update_fixed_pcd, cvo.cpp:578-582
+            else give_up(b->moving[p]);
+            S.has_moving = true;
+            b->moving[p] = F.clouds[k];
+        }
+        if (points_out) points_out[k] = F.points[k];
+    }
+    stage_taken(b);
+    return CVO_OK;
+}
+int cvo_batch_staged_count(cvo_batch b, int* images, long long* taken) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    return stage_count(b, images, taken);
+}
 int cvo_batch_get_prev_accum_transform(cvo_batch b, int p, float prev_transform[12], float accum_transform[12]) {
     if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad slot index");
     int rc = batch_settle(b); if (rc) return rc;
@@ -2469,6 +2732,7 @@ int cvo_batch_get_prev_accum_transform(cvo_batch b, int p, float prev_transform[
 }
 int cvo_batch_set_num_want(cvo_batch b, int num_want) {
     if (!b || num_want <= 0) return fail(CVO_ERR_INVALID, "bad argument");
+    stage_drop(b);                                                  // (frames staged with the old count are not this object's next frames any more)
     b->img.num_want = num_want; return CVO_OK;
 }
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n) {
@@ -2571,6 +2835,7 @@ int cvo_batch_align_pairs_async(cvo_batch b, int count, const int* slots, void* 
 int cvo_batch_wait(cvo_batch b, cvo_pair_result* results, int n) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");
     int rc = b->settled ? b->eng.wait() : batch_settle(b); if (rc) return rc;
+    if ((rc = stage_place(b, false))) return rc;                     // (frames staged while the launch ran: placed now if their generator has finished too)
     if (results) {
         if (n > b->last_n) return fail(CVO_ERR_INVALID, "more results requested than pairs launched");
         const PairState* r = b->eng.results();
@@ -2825,11 +3090,7 @@ struct cvo_tracks_s {
 };
 
 namespace {
-void tracks_free_cloud(cvo_tracks_s* t, std::shared_ptr<Cloud>& out) {
-    for (std::shared_ptr<Cloud>& c : t->pool) if (c.use_count() == 1) { out = c; return; }
-    t->pool.push_back(std::make_shared<Cloud>());
-    out = t->pool.back();
-}
+void tracks_free_cloud(cvo_tracks_s* t, std::shared_ptr<Cloud>& out) { pool_free_cloud(t->pool, out); }
 void tracks_fresh_stream(cvo_tracks_s* t, int s) {
     t->odo->fixed[s].reset(); t->odo->moving[s].reset(); t->key->fixed[s].reset(); t->key->moving[s].reset();
     fresh_stream(t->odo, s);
@@ -2895,6 +3156,7 @@ int cvo_tracks_create(const cvo_params* p, int device, int max_streams, cvo_trac
     if (!rc) rc = t->key->eng.d_states.ensure(sizeof(PairState) * (size_t)max_streams);
     if (rc) { cvo_batch_destroy(t->odo); cvo_batch_destroy(t->key); return rc; }
     for (cvo_batch b : {t->odo, t->key}) { b->eng.tail_scores = true; b->eng.queue_behind = true; }
+    t->odo->stage.pool = &t->pool;                                   // staged frames (cvo_tracks_stage_async) go into cloud objects of the streams' pool
     t->st.resize(max_streams);
     for (int s = 0; s < max_streams; ++s) tracks_fresh_stream(t.get(), s);
     *out = t.release();
@@ -2905,8 +3167,10 @@ int cvo_tracks_destroy(cvo_tracks t) {
     (void)hipSetDevice(t->odo->eng.device);
     if (t->odo->eng.launched && t->odo->eng.last_stream) (void)hipStreamSynchronize(t->odo->eng.last_stream);
     if (t->key->eng.launched && t->key->eng.last_stream) (void)hipStreamSynchronize(t->key->eng.last_stream);
+    stage_destroy(t->odo);                                           // (drains the stage stream; its clouds return to the pool)
     for (TrackStream& s : t->st) s.key.previous.reset();
     t->moving_before.clear();
+    report_step_laps("tracks");
     cvo_batch_destroy(t->odo); cvo_batch_destroy(t->key);
     t->pool.clear();
     t->h_link_in.release(); t->h_link_out.release();
@@ -2928,23 +3192,31 @@ int cvo_tracks_reset(cvo_tracks t, int s) {
     tracks_fresh_stream(t, s);
     return CVO_OK;
 }
-int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
-                          const cvo_camera* cams, const int* cam_index, void* hip_stream) {
+namespace {
+// what a step checks about its arguments (a stage call checks the same)
+int tracks_check_images(cvo_tracks_s* t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                        const cvo_camera* cams, const int* cam_index) {
     int rc = tracks_check_list(t, count, streams); if (rc) return rc;
     if (!bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
     if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
-    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
     for (int k = 0; k < count; ++k) {
         if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
         if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
-        if (t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " waits for the decision on its last frame (cvo_tracks_commit)");
     }
+    return CVO_OK;
+}
+// ... and what depends on the streams' state
+int tracks_check_state(cvo_tracks_s* t, int count, const int* streams) {
+    if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    for (int k = 0; k < count; ++k)
+        if (t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " waits for the decision on its last frame (cvo_tracks_commit)");
+    return CVO_OK;
+}
+// The step once its frames' point counts are known.  staged (null: generated by this call, records R): the frames' finished cloud objects, handed to the
+// slots as they are; else every frame is scattered into a cloud object nobody holds.  Then the launches.
+int tracks_step_run(cvo_tracks_s* t, int count, const int* streams, const int* npts, const std::vector<std::shared_ptr<Cloud>>* staged, const PcdImgRec* R, void* hip_stream) {
     cvo_batch bo = t->odo, bk = t->key;
-    if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
-    std::vector<cvo_camera> cam_of(count);
-    for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
-    const PcdImgRec* R = nullptr;
-    if ((rc = batch_generate(bo, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (the step's one host sync; fails before any stream changes)
+    int rc;
     // every frame into a cloud object nobody holds; the objects' slots take it (local_tracker.cpp:228-231, 233, 356, 415; update_fixed_pcd :403)
     t->list.assign(streams, streams + count);
     t->phase.assign(count, 0); t->points.assign(count, 0); t->odo_pos.assign(count, -1); t->key_pos.assign(count, -1);
@@ -2953,10 +3225,11 @@ int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const uns
     for (int k = 0; k < count; ++k) {
         const int s = streams[k];
         TrackStream& S = t->st[s]; StreamSlot& O = bo->streams[s];
-        std::shared_ptr<Cloud> c; tracks_free_cloud(t, c);
+        std::shared_ptr<Cloud> c;
+        if (staged) c = (*staged)[k]; else tracks_free_cloud(t, c);
         dst[k] = c.get(); img[k] = k;
         const int ph = std::min(S.frames, 2);
-        t->phase[k] = ph; t->points[k] = R[k].npts;
+        t->phase[k] = ph; t->points[k] = npts[k];
         if (ph == 0) {                                               // both objects' set_pcd of the first frame: their FIXED cloud (cvo.cpp:352-360)
             bo->fixed[s] = c; bk->fixed[s] = c; O.init = true;
         } else {
@@ -2971,7 +3244,9 @@ int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const uns
         ++S.frames;
     }
     t->n_odo = (int)slots_odo.size(); t->n_key = (int)slots_key.size();
-    if ((rc = batch_scatter(bo, dst, img, R))) return rc;
+    if (!staged) { Lap lap(StepLaps::SCATTER); if ((rc = batch_scatter(bo, dst, img, R))) return rc; }
+    Lap lap(StepLaps::LAUNCH);
+    ++step_laps()->steps;
     if (t->n_odo == 0) { t->in_flight = true; return CVO_OK; }
     // ONE odometry launch over the listed streams that align; its tail answers the score blocks
     if ((rc = batch_launch(bo, slots_odo.data(), t->n_odo, static_cast<hipStream_t>(hip_stream), false))) return rc;
@@ -2994,6 +3269,46 @@ int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const uns
     // ONE keyframe launch over the phase-2 streams, behind the link kernel on the same stream
     return batch_launch(bk, slots_key.data(), t->n_key, hs, false);
 }
+}  // namespace
+int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                          const cvo_camera* cams, const int* cam_index, void* hip_stream) {
+    int rc = tracks_check_images(t, count, streams, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;
+    if ((rc = tracks_check_state(t, count, streams))) return rc;
+    cvo_batch bo = t->odo, bk = t->key;
+    if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
+    std::vector<cvo_camera> cam_of(count);
+    for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
+    const PcdImgRec* R = nullptr;
+    if ((rc = batch_generate(bo, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (the step's one host sync; fails before any stream changes)
+    std::vector<int> npts(count);
+    for (int k = 0; k < count; ++k) npts[k] = R[k].npts;
+    return tracks_step_run(t, count, streams, npts.data(), nullptr, R, hip_stream);
+}
+// ---- the next step's frames staged ahead: generated on the stage's own stream while the current step's launches run
+int cvo_tracks_stage_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                           const cvo_camera* cams, const int* cam_index) {
+    int rc = tracks_check_images(t, count, streams, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
+    return stage_begin(t->odo, count, streams, bgr8, depth16, width, height, cams, cam_index);
+}
+int cvo_tracks_step_staged_async(cvo_tracks t, void* hip_stream) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    FrameStage& F = t->odo->stage;
+    if (!F.pending) return fail(CVO_ERR_INVALID, "nothing staged (cvo_tracks_stage_async)");
+    Lap lap(StepLaps::CONSUME);
+    const int count = (int)F.list.size();
+    int rc = tracks_check_state(t, count, F.list.data()); if (rc) return rc;   // (the stage is kept: commit, then call again)
+    cvo_batch bo = t->odo, bk = t->key;
+    if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
+    if ((rc = stage_take(bo))) return rc;                            // (fails before any stream changes; the stage is dropped)
+    const std::vector<int> list = F.list, points = F.points;
+    const std::vector<std::shared_ptr<Cloud>> clouds = F.clouds;
+    stage_taken(bo);
+    return tracks_step_run(t, count, list.data(), points.data(), &clouds, nullptr, hip_stream);
+}
+int cvo_tracks_staged_count(cvo_tracks t, int* images, long long* taken) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    return stage_count(t->odo, images, taken);
+}
 int cvo_tracks_done(cvo_tracks t, int* done) {
     if (!t || !done) return fail(CVO_ERR_INVALID, "null argument");
     *done = 1;
@@ -3007,6 +3322,7 @@ int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out, int count) {
     if (out && count != n) return fail(CVO_ERR_INVALID, "one result per stream of the step");
     cvo_batch bo = t->odo, bk = t->key;
     int rc;
+    Lap lap(StepLaps::WAIT);
     if (t->n_odo > 0 && (rc = batch_settle(bo))) return rc;          // (the odometry objects take their results in, as after cvo_batch_wait)
     if (t->n_key > 0 && (rc = bk->eng.wait())) return rc;
     const PairState* ro = bo->eng.results(); const PairState* rk = bk->eng.results();
@@ -3065,12 +3381,13 @@ int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out, int count) {
     }
     t->moving_before.clear();
     t->in_flight = false;
-    return CVO_OK;
+    return stage_place(bo, false);                                   // (frames staged while the step ran: placed now if their generator has finished too)
 }
 int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept) {
     int rc = tracks_check_list(t, count, streams); if (rc) return rc;
     if (!accept) return fail(CVO_ERR_INVALID, "null argument");
     if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
+    Lap lap(StepLaps::COMMIT);
     for (int k = 0; k < count; ++k)
         if (!t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " expects no decision");
     for (int k = 0; k < count; ++k) {

@@ -223,6 +223,14 @@ struct PcdScatter {
     int img[PCD_SCATTER_MAX]; float* dst[PCD_SCATTER_MAX]; uint16_t* dst_px[PCD_SCATTER_MAX];
 };
 
+// the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
+struct BoxDesc {
+    const float* rec;        // the cloud's two planes of n float4
+    float* gbox;             // its boxes: 8 planes of ngroups floats
+    SelfCacheEntry* self_cache;   // the cloud's table of cached self inner products (behind the boxes: score_self_cache), emptied by the launch
+    int n, ngroups;
+};
+
 // a score block: up to 8 inner-product / Hessian requests evaluated by one launch
 constexpr int SCORE_MAXREQ = 8;
 struct ScoreBatch {

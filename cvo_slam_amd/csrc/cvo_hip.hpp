@@ -137,6 +137,14 @@ public:
                     const cvo_camera* cams, const int* cam_index = nullptr, void* hip_stream = nullptr) {
         check(cvo_tracks_step_async(t_, count, streams, bgr8, depth16, width, height, cams, cam_index, hip_stream), "step_async");
     }
+    // the NEXT step's frames, handed over while the current step is in flight (between step_async / step_staged_async and wait); the images are the
+    // caller's again when the call returns.  step_staged_async is step_async of the staged list, without generating anything
+    void stage_async(int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                     const cvo_camera* cams, const int* cam_index = nullptr) {
+        check(cvo_tracks_stage_async(t_, count, streams, bgr8, depth16, width, height, cams, cam_index), "stage_async");
+    }
+    void step_staged_async(void* hip_stream = nullptr) { check(cvo_tracks_step_staged_async(t_, hip_stream), "step_staged_async"); }
+    int staged_count(long long* taken = nullptr) { int n = 0; check(cvo_tracks_staged_count(t_, &n, taken), "staged_count"); return n; }
     bool done() { int d = 0; check(cvo_tracks_done(t_, &d), "done"); return d != 0; }
     void wait(cvo_track_step* out, int count) { check(cvo_tracks_wait(t_, out, count), "wait"); }
     void step(int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,

@@ -65,6 +65,34 @@ __global__ __launch_bounds__(64) void cvo_cloud_boxes_kernel(const float* __rest
     }
 }
 
+// The same boxes for MANY clouds in one launch (the frames staged ahead of a K-stream step: cvo_batch_stage_images, cvo_tracks_stage_async):
+// grid.y = cloud, grid.x = pairs of groups of the largest cloud; a workgroup (one wave) past its cloud's last group leaves at once.  Per
+// group the same 32-lane shuffle ladder over the same values in the same order as cvo_cloud_boxes_kernel: the same bytes.
+__global__ __launch_bounds__(64) void cvo_cloud_boxes_batch_kernel(const BoxDesc* __restrict__ descs) {
+    const BoxDesc D = descs[blockIdx.y];
+    const int n = D.n, ngroups = D.ngroups;
+    if ((int)blockIdx.x * 2 >= ngroups) return;                       // (uniform over the wave; ngroups >= 1, so block 0 of every cloud stays)
+    float* __restrict__ gbox = D.gbox;
+    const int lane = threadIdx.x, gi = blockIdx.x * 2 + (lane >> 5), j = gi * 32 + (lane & 31);
+    if (blockIdx.x == 0 && lane < SELF_CACHE_N) { SelfCacheEntry e; e.ell = 0.f; e.valid = 0; e.sum = 0.0; e.count = 0.0; D.self_cache[lane] = e; }
+    const float INF = __builtin_inff();
+    float lo[4] = {INF, INF, INF, INF}, hi[4] = {-INF, -INF, -INF, -INF};
+    if (j < n) {
+        const float4 p = ld4s(D.rec + lo_off(j));
+        lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z;
+        if (p.z > 1.0e-3f) { lo[3] = hi[3] = p.y / p.z; } else { lo[3] = -INF; hi[3] = INF; }
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { lo[q] = fminf(lo[q], __shfl_xor(lo[q], off, 64)); hi[q] = fmaxf(hi[q], __shfl_xor(hi[q], off, 64)); }
+    }
+    if ((lane & 31) == 0 && gi < ngroups) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { gbox[q * ngroups + gi] = lo[q]; gbox[(4 + q) * ngroups + gi] = hi[q]; }
+    }
+}
+
 __global__ __launch_bounds__(SCORE_BLOCK) void cvo_score_kernel(ScoreBatch B, const ScoreDesc* __restrict__ more, DevParams P, double* __restrict__ partials,
                                                                 unsigned* __restrict__ wgs_started) {
     // adoption's "is anything queued on the device?" (cvo_capi.hip, AdoptCounters): this workgroup has started
@@ -302,6 +330,12 @@ SelfCacheEntry* score_self_cache(float* gbox, int n) { return reinterpret_cast<S
 hipError_t launch_cloud_boxes(const float* rec, int n, float* gbox, hipStream_t stream) {
     const int ng = score_groups(n);
     hipLaunchKernelGGL(cvo_cloud_boxes_kernel, dim3((ng + 1) / 2), dim3(64), 0, stream, rec, n, gbox, ng, score_self_cache(gbox, n));
+    return hipGetLastError();
+}
+// descs: n_clouds descriptors the device can read (pinned host memory), every cloud with n > 0; n_max: the largest n among them
+hipError_t launch_cloud_boxes_batch(const BoxDesc* descs, int n_clouds, int n_max, hipStream_t stream) {
+    if (n_clouds <= 0 || n_max <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cvo_cloud_boxes_batch_kernel, dim3((score_groups(n_max) + 1) / 2, n_clouds), dim3(64), 0, stream, descs);
     return hipGetLastError();
 }
 int score_row_blocks(int na) { return (na + SCORE_BLOCK - 1) / SCORE_BLOCK; }

@@ -255,6 +255,14 @@ def plan_replay(lengths, n_slots: int, starts=None):
     return plan
 
 
+def stage_plan(plan):
+    """What `replay_odometry_many` / `replay_tracker_many` stage ahead (stage_ahead=True) while step j of `plan` (plan_replay's result) runs: a
+    pure function, so that it can be checked without a GPU.  Returns one list per step: the (slot, sequence, frame) entries step j + 1 will
+    advance, in its order -- frame t + 1 of a sequence depends on nothing step j computes, and a slot that step j + 1 resets for a new sequence
+    takes that sequence's first frame -- and an empty list for the last step."""
+    return [list(plan[j + 1]["advance"]) if j + 1 < len(plan) else [] for j in range(len(plan))]
+
+
 def group_by_size(items, size_of):
     """items grouped by size_of(item), in the order the sizes first occur: one advance call per image size (cvo_batch_advance_images takes one size)."""
     groups = {}
@@ -263,13 +271,16 @@ def group_by_size(items, size_of):
     return list(groups.values())
 
 
-def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None):
+def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None,
+                         stage_ahead: bool = False):
     """`replay_odometry` for many sequences at once on one CvoBatch: each slot is one odometry object (cvo_batch_advance_images), every step
     advances each running sequence by one frame -- one advance call per image size -- and aligns all of them in ONE launch
     (cvo_batch_align_pairs_async).  sequences[i]: a sequence of (bgr8, depth16) frames (len() and indexing; frames are read in order, once);
     cameras[i]: its (scaling_factor, fx, fy, cx, cy).  slots: the batch's slots (default: one per sequence; fewer reuse slots through
     cvo_batch_reset_stream); starts: the step each sequence may start at (plan_replay).  Returns [(poses, info), ...], per sequence what
-    `replay_odometry` returns for it alone (poses chained on the host the same way).  A failed alignment raises CvoError as it does there."""
+    `replay_odometry` returns for it alone (poses chained on the host the same way).  A failed alignment raises CvoError as it does there.
+    stage_ahead: the frames of step j + 1 (`stage_plan`) are handed over right after step j's launch is queued and generated while it runs
+    (cvo_batch_stage_images / cvo_batch_advance_staged) -- when they are of one image size; the results are the same bits."""
     import cvo_slam_amd as ca
     from .api import CVO_OK, CvoError
     n_seq = len(sequences)
@@ -283,22 +294,27 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
         B.set_arith_mode(arith)
         out = [([], []) for _ in range(n_seq)]
         pose = [np.eye(4) for _ in range(n_seq)]
-        for st in plan:
+        ahead = stage_plan(plan) if stage_ahead else [[] for _ in plan]
+        staged = None                                               # the list staged for the step to come
+        for j, st in enumerate(plan):
             for p in st["resets"]:
                 B.reset_stream(p)
-            frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
             points = {}
-            for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
-                cams = [tuple(cameras[i]) for _, i, _ in grp]
-                uniq = list(dict.fromkeys(cams))
-                pts = B.advance_images([p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams])
-                points.update({a: int(n) for a, n in zip(grp, pts)})
+            if staged is not None:
+                points.update({a: int(n) for a, n in zip(staged, B.advance_staged())})
+            else:
+                frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
+                for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
+                    pts = B.advance_images(*_image_call(grp, frames, cameras))
+                    points.update({a: int(n) for a, n in zip(grp, pts)})
             for a in st["advance"]:
                 if a[2] == 0:                                       # cvo.cpp:352-360: the first frame only fills the fixed cloud
                     out[a[1]][0].append(pose[a[1]].copy()); out[a[1]][1].append(dict(iterations=0, nnz=0, points=points[a]))
+            n_launched = B.align_pairs_async([p for p, _, _ in st["align"]]) if st["align"] else 0
+            staged = _stage_next(B.stage_images, ahead[j], sequences, cameras)   # generated while the launch runs
             if not st["align"]:
                 continue
-            res = B.align_pairs([p for p, _, _ in st["align"]])
+            res = B.wait(n_launched)
             for (p, i, f), r in zip(st["align"], res):
                 if r["status"] != CVO_OK:
                     raise CvoError(r["status"], f"sequence {i}, frame {f}: alignment failed")
@@ -309,6 +325,24 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
     finally:
         B.close()
     return out
+
+
+def _image_call(grp, frames, cameras):
+    """(ids, images, cameras, cam_index) of one advance / step / stage call over the (slot, sequence, frame) entries of grp"""
+    cams = [tuple(cameras[i]) for _, i, _ in grp]
+    uniq = list(dict.fromkeys(cams))
+    return [p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams]
+
+
+def _stage_next(stage, entries, sequences, cameras):
+    """stage(...) the frames of `entries` (a list of stage_plan) when there are any and they are of one image size; returns what was staged, or None"""
+    if not entries:
+        return None
+    frames = {(p, i, f): sequences[i][f] for p, i, f in entries}
+    if len(group_by_size(entries, lambda a: np.asarray(frames[a][1]).shape)) != 1:
+        return None                                                 # (one stage holds one image size: such a step is generated by its own calls)
+    stage(*_image_call(entries, frames, cameras))
+    return list(entries)
 
 
 # ----------------------------------------------------------------------------- the tracker's two objects (local_tracker.cpp:228-251, 330-338, 356-431, 506)
@@ -434,14 +468,17 @@ def replay_tracker(frames, camera, accept, params=None, device: int = 0, num_wan
     return _tracker_poses(steps, decisions), steps, decisions
 
 
-def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None):
+def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None,
+                        stage_ahead: bool = False):
     """`replay_tracker` for many sequences at once on one CvoTracks (cvo_tracks_*): each stream is the pair of objects of one sequence, every step
     advances each running sequence by one frame -- one cvo_tracks_step per image size: generation, one odometry launch, reset_initial on the device,
     one keyframe launch -- and hands the caller's decisions back with cvo_tracks_commit.  Scheduled by `plan_replay` (slots: the object's streams,
     default one per sequence, fewer reuse streams through cvo_tracks_reset; starts: the step each sequence may start at).  sequences[i]: (bgr8,
     depth16) frames (len() and indexing); cameras[i]: its (scaling_factor, fx, fy, cx, cy); accept: as for `replay_tracker`, called with the
     sequence's index.  Returns [(poses, steps, decisions), ...], per sequence what `replay_tracker` returns for it alone: the same bits, poses
-    chained on the host the same way (no optimiser)."""
+    chained on the host the same way (no optimiser).  stage_ahead: the frames of step j + 1 (`stage_plan`) are handed over right after step j is
+    queued and before it is waited for (cvo_tracks_stage_async), and step j + 1 starts its launches without generating anything
+    (cvo_tracks_step_staged_async) -- when they are of one image size; the results are the same bits."""
     import cvo_slam_amd as ca
     n_seq = len(sequences)
     if len(cameras) != n_seq:
@@ -453,14 +490,25 @@ def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0
     try:
         T.set_num_want(num_want)
         T.set_arith_mode(arith)
-        for st in plan:
+        ahead = stage_plan(plan) if stage_ahead else [[] for _ in plan]
+        staged = None                                               # the list staged for the step to come
+        for j, st in enumerate(plan):
             for p in st["resets"]:
                 T.reset(p)
-            frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
-            for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
-                cams = [tuple(cameras[i]) for _, i, _ in grp]
-                uniq = list(dict.fromkeys(cams))
-                res = T.step([p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams])
+            consume = staged is not None
+            if consume:
+                groups = [staged]
+            else:
+                frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
+                groups = group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape)
+            for g, grp in enumerate(groups):
+                if consume:
+                    T.step_staged_async()
+                else:
+                    T.step_async(*_image_call(grp, frames, cameras))
+                if g == len(groups) - 1:
+                    staged = _stage_next(T.stage_async, ahead[j], sequences, cameras)   # generated while the step runs
+                res = T.wait()
                 who, what = [], []
                 for (p, i, f), r in zip(grp, res):
                     d = None

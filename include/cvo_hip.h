@@ -322,7 +322,8 @@ int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* f
  * align result of its pairs carries CVO_ERR_EMPTY_CLOUD).  Pairs outside the range keep their clouds. */
 int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
                                int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out);
-/* pcd_generator::num_want (3000, pcd_generator.cpp:22) of this batch's later cvo_batch_set_pairs_images / cvo_batch_advance_images calls */
+/* pcd_generator::num_want (3000, pcd_generator.cpp:22) of this batch's later cvo_batch_set_pairs_images / cvo_batch_advance_images /
+ * cvo_batch_stage_images calls; frames staged before (cvo_batch_stage_images) are dropped */
 int cvo_batch_set_num_want(cvo_batch b, int num_want);
 
 /* ---- K-stream frame-to-frame odometry: a pair slot as one cvo::cvo odometry object (the cvo_main loop: set_pcd, match_odometry,
@@ -360,6 +361,34 @@ int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const uns
 int cvo_batch_reset_stream(cvo_batch b, int p);
 int cvo_batch_align_pairs_async(cvo_batch b, int count, const int* slots, void* stream);
 int cvo_batch_get_prev_accum_transform(cvo_batch b, int p, float prev_transform[12], float accum_transform[12]);
+
+/* ---- The next frames of stream slots, staged ahead.  Frame t + 1's cloud depends on nothing that frame t's alignment produces, so it can be
+ * generated while that alignment runs: stage the next frames right after cvo_batch_align_pairs_async, before cvo_batch_wait.
+ *
+ * cvo_batch_stage_images: the arguments of cvo_batch_advance_images.  The clouds of the `count` images are generated with the camera of
+ * each and the batch's current num_want, on a stream of the stage's own (made with the device's highest stream priority, so that it does
+ * not share a hardware queue with a running align launch) and in generator scratch of its own, into cloud objects that nothing else holds.
+ * The call touches no slot, no stream state, no device state and no launch, and neither waits for nor disturbs a launch in flight.  It
+ * returns without waiting for the device; every image byte has been copied to pinned memory by then (by the engine's copy threads), so the
+ * caller may reuse the images at once.  It checks what cvo_batch_advance_images checks about its arguments (the list, null pointers, the
+ * size limits, the camera index) and fails with CVO_ERR_INVALID before anything is staged: an earlier stage survives such a call.  There is
+ * ONE stage per batch: a successful call replaces a stage that was never consumed, whose cloud objects return to the pool.
+ * cvo_batch_set_num_want drops the stage, and so does a plain-pair call (cvo_batch_set_pair, _set_pairs, _set_pairs_images, _set_state) on
+ * a staged slot.  cvo_batch_reset_stream keeps it: the staged frame is that slot's next frame, whatever the slot is by then.
+ *
+ * cvo_batch_advance_staged: cvo_batch_advance_images of the staged list, without generating anything -- it waits on the host only if the
+ * staged generation has not finished (it needs the point counts), gives the staged cloud objects to the slots (the objects the slots let
+ * go of are kept for later stages), and orders the launches that follow behind the stage's stream by an event.  The staged clouds arrive
+ * with the boxes of their 32-point groups made, all of them by one launch.  Every result is bit-identical to cvo_batch_advance_images on
+ * the same frames.  With nothing staged it returns CVO_ERR_INVALID.  A staged cloud above 65535 points (CVO_ERR_INVALID) or a HIP error of
+ * the staged work (CVO_ERR_HIP) is reported here: no slot changes and the stage is dropped.  points_out: as for cvo_batch_advance_images.
+ *
+ * cvo_batch_staged_count: *images = images in the stage now (0 = none), *taken = clouds ever taken from a stage.  cvo_batch_destroy drains
+ * the stage's stream first. */
+int cvo_batch_stage_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                           int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */);
+int cvo_batch_advance_staged(cvo_batch b, int* points_out /* may be NULL, one int per staged image */);
+int cvo_batch_staged_count(cvo_batch b, int* images /* may be NULL */, long long* taken /* may be NULL */);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
@@ -578,7 +607,23 @@ int cvo_batch_compute_innerproduct(cvo_batch b, int n, cvo_track_scores* out);
  * cvo_tracks_wait: the results of the step in flight, one cvo_track_step per listed stream in list order (count = the step's count).  Entries of an
  * object that did not align carry status CVO_ERR_NOT_INITIALIZED and zeros.  cvo_tracks_done never blocks.
  * cvo_tracks_reset(t, s): stream s = two fresh objects.  cvo_tracks_get_cloud / _get_selected_points / _get_state: object 0 = odometry, 1 = keyframe;
- * slot CVO_SLOT_FIXED / _MOVING / _PREVIOUS (the odometry object has no previous cloud: *n = 0). */
+ * slot CVO_SLOT_FIXED / _MOVING / _PREVIOUS (the odometry object has no previous cloud: *n = 0).
+ *
+ * The next step's frames, staged ahead (the stage of cvo_batch_stage_images, for streams): call cvo_tracks_stage_async for step f + 1 between
+ * cvo_tracks_step_async / cvo_tracks_step_staged_async of step f and its cvo_tracks_wait -- staging while a step is in flight is the intended use.
+ * cvo_tracks_stage_async takes cvo_tracks_step_async's arguments but the stream handle, checks what that call checks about them (the list, null
+ * pointers, the size limits, the camera index: CVO_ERR_INVALID before anything is staged, an earlier stage survives), copies the images to pinned
+ * memory (they are the caller's again when it returns), queues their generation with the object's current num_want on the stage's own
+ * high-priority stream and scratch, into cloud objects nothing else holds, and returns without waiting for the device.  It touches no stream's
+ * state and no launch.  One stage per object: a successful call replaces a stage never consumed; cvo_tracks_set_num_want drops the stage;
+ * cvo_tracks_reset keeps it (the staged frame is the stream's next frame, whatever its phase then is).
+ * cvo_tracks_step_staged_async is cvo_tracks_step_async of the staged list: what depends on the streams' state is checked here.  With nothing
+ * staged: CVO_ERR_INVALID.  A step in flight or a listed stream that awaits its decision: CVO_ERR_INVALID, no stream changes and THE STAGE IS KEPT
+ * -- commit, then call again.  A staged cloud above 65535 points or a HIP error of the staged work is reported with the code
+ * cvo_tracks_step_async returns: no stream changes, the stage is dropped.  Otherwise the call waits on the host only if the staged generation has
+ * not finished, hands the staged cloud objects (group boxes made, one launch for all) to the objects' slots, orders its launches behind the
+ * stage's stream by an event and queues them: every result is bit-identical to cvo_tracks_step_async on the same frames.
+ * cvo_tracks_staged_count: as cvo_batch_staged_count.  cvo_tracks_destroy drains the stage's stream first. */
 typedef struct cvo_tracks_s* cvo_tracks;
 typedef struct cvo_track_step {
     int phase;                          /* 0, 1, 2: see above */
@@ -591,11 +636,15 @@ typedef struct cvo_track_step {
 } cvo_track_step;
 int cvo_tracks_create(const cvo_params* p /* NULL = defaults */, int device, int max_streams, cvo_tracks* out);
 int cvo_tracks_destroy(cvo_tracks t);
-int cvo_tracks_set_num_want(cvo_tracks t, int num_want);      /* as cvo_batch_set_num_want */
+int cvo_tracks_set_num_want(cvo_tracks t, int num_want);      /* as cvo_batch_set_num_want (drops staged frames) */
 int cvo_tracks_set_arith_mode(cvo_tracks t, int flags);       /* as cvo_batch_set_arith_mode, for both objects' launches */
 int cvo_tracks_reset(cvo_tracks t, int s);
 int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16,
                           int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* hip_stream);
+int cvo_tracks_stage_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                           int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */);
+int cvo_tracks_step_staged_async(cvo_tracks t, void* hip_stream);
+int cvo_tracks_staged_count(cvo_tracks t, int* images /* may be NULL */, long long* taken /* may be NULL */);
 int cvo_tracks_done(cvo_tracks t, int* done);
 int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out /* may be NULL */, int count);
 int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept);

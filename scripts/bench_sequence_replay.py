@@ -2,10 +2,12 @@
 """Frames per second of frame-to-frame odometry over K sequences at once (one CvoBatch, a slot per sequence: cvo_batch_advance_images +
 ONE cvo_batch_align_pairs_async per step) against the same K sequences replayed one after the other by a handle each (set_pcd_images,
 match_odometry_images, update_fixed_pcd per frame: the replay_odometry loop), in one process, on in-memory synthetic 640 x 480 frames.
-Every configuration is warmed up once, then timed `--runs` times (each run ends with a device synchronise); the median and the spread
-(min .. max) are printed per K, and one JSON line at the end.
+Beside the batch there is a staged row: the same steps with the frames of step f + 1 handed over while step f's launch runs
+(cvo_batch_stage_images / cvo_batch_advance_staged), on the same object.  Every configuration is warmed up once, then timed `--runs` times
+(each run ends with a device synchronise), the runs of the configurations interleaved; the median and the spread (min .. max) are printed
+per K, one JSON line at the end, and with --out the table is written to that file.
 
-    python scripts/bench_sequence_replay.py [--streams 1,8,64] [--frames 6] [--runs 3] [--pool 4]
+    python scripts/bench_sequence_replay.py [--streams 1,8,64] [--frames 6] [--runs 3] [--pool 4] [--out profiles/sequence_streams_staged.txt]
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ def main(argv=None):
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic sequences; stream s replays sequence s mod pool")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     import torch
     import cvo_slam_amd as ca
@@ -46,6 +49,20 @@ def main(argv=None):
                 r = B.align_pairs(range(K))
                 assert all(x["status"] == 0 for x in r)
 
+    def staged(K, B):
+        seq = [pool[s % a.pool] for s in range(K)]
+        for s in range(K):
+            B.reset_stream(s)
+        B.advance_images(range(K), [q[0] for q in seq], [cam])
+        for f in range(a.frames):
+            n = B.align_pairs_async(range(K)) if f else 0
+            if f + 1 < a.frames:
+                B.stage_images(range(K), [q[f + 1] for q in seq], [cam])   # generated while the launch runs
+            if f:
+                assert all(x["status"] == 0 for x in B.wait(n))
+            if f + 1 < a.frames:
+                B.advance_staged()
+
     def handles(K, _):
         for s in range(K):
             g = ca.Cvo(device=a.device)
@@ -55,24 +72,32 @@ def main(argv=None):
                 g.match_odometry_images(*fr[f], cam); g.update_fixed_pcd()
             g.close()
 
-    res = {}
+    res, lines = {}, [f"sequence streams: {a.frames} frames per sequence, 640 x 480, {a.runs} runs interleaved (median, min .. max)"]
     for K in ks:
         B = ca.CvoBatch(K, device=a.device)
-        row = {}
-        for name, fn in (("batch", batched), ("handles", handles)):
+        fns = (("batch", batched), ("staged", staged), ("handles", handles))
+        t = {name: [] for name, _ in fns}
+        for name, fn in fns:
             fn(K, B); sync()                                          # warm-up
-            t = []
-            for _ in range(a.runs):
-                t0 = time.perf_counter(); fn(K, B); sync(); t.append(time.perf_counter() - t0)
-            fps = sorted(K * (a.frames - 1) / x for x in t)             # aligned frames per second
-            row[name] = dict(fps_median=fps[len(fps) // 2], fps_min=fps[0], fps_max=fps[-1])
+        for _ in range(a.runs):
+            for name, fn in fns:
+                t0 = time.perf_counter(); fn(K, B); sync(); t[name].append(time.perf_counter() - t0)
         B.close()
+        row = {}
+        for name, _ in fns:
+            fps = sorted(K * (a.frames - 1) / x for x in t[name])       # aligned frames per second
+            row[name] = dict(fps_median=fps[len(fps) // 2], fps_min=fps[0], fps_max=fps[-1])
         row["speedup"] = row["batch"]["fps_median"] / row["handles"]["fps_median"]
         res[K] = row
-        print(f"K={K:3d}: batch {row['batch']['fps_median']:8.1f} frames/s ({row['batch']['fps_min']:.1f} .. {row['batch']['fps_max']:.1f}), "
-              f"handles {row['handles']['fps_median']:8.1f} ({row['handles']['fps_min']:.1f} .. {row['handles']['fps_max']:.1f}), x{row['speedup']:.2f}",
-              flush=True)
+        cell = lambda r: f"{r['fps_median']:8.1f} frames/s ({r['fps_min']:.1f} .. {r['fps_max']:.1f})"
+        lines.append(f"K={K:3d}: batch {cell(row['batch'])}, staged {cell(row['staged'])} x{row['staged']['fps_median'] / row['batch']['fps_median']:.3f}, "
+                     f"handles {cell(row['handles'])}, batch x{row['speedup']:.2f} the handles")
+        print(lines[-1], flush=True)
     print(json.dumps(dict(bench="sequence_replay", frames=a.frames, runs=a.runs, results=res)))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -2,8 +2,10 @@
 """Frames per second of the tracker's two alignments per frame over K sequences at once (one CvoTracks, a stream per sequence: ONE
 cvo_tracks_step_async + cvo_tracks_wait + cvo_tracks_commit per frame) against the same K sequences replayed one after the other on two handles
 each (replay.replay_tracker: the loop on the entry points a handle has), in one process and one call, on in-memory synthetic 640 x 480 frames.
-Every phase-2 frame but each `--keyframe-every`-th is accepted.  Every configuration is warmed up once, then timed `--runs` times;
-the median and the spread (min .. max) are printed per K, one JSON line at the end, and with --out the table is written to that file.
+Every phase-2 frame but each `--keyframe-every`-th is accepted.  Beside every K's row there is a staged row: the same steps with the frames of
+step f + 1 handed over while step f runs (cvo_tracks_stage_async / cvo_tracks_step_staged_async), on the same object, the timed runs of the two
+interleaved (plain, staged, plain, ...).  Every configuration is warmed up once, then timed `--runs` times; the median and the spread
+(min .. max) are printed per K, one JSON line at the end, and with --out the table is written to that file.
 
     python scripts/bench_tracker_replay.py [--streams 1,8,64] [--frames 8] [--runs 3] [--pool 4] [--out profiles/tracker_streams.txt]
 """
@@ -26,6 +28,7 @@ def main(argv=None):
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic sequences; stream s replays sequence s mod pool")
     ap.add_argument("--keyframe-every", type=int, default=4)
     ap.add_argument("--handle-streams", type=int, default=8, help="sequences the two-handle path replays per timed run (its rate does not depend on K)")
+    ap.add_argument("--variant", default="both", choices=("both", "plain", "staged"), help="time only one of the two rows (under a profiler, or with CVO_HIP_STEP_LAPS=1)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
@@ -51,17 +54,44 @@ def main(argv=None):
                 assert all(res[s].keyframe.status == 0 for s in every)
                 T.commit(every, [accept(s, f, None, None)] * K)
 
+    def streams_staged(K, T):
+        for s in range(K):
+            T.reset(s)
+        seq = [pool[s % a.pool] for s in range(K)]
+        every = list(range(K))
+        for f in range(a.frames):
+            if f == 0:
+                T.step_async(every, [q[f] for q in seq], cam)
+            else:
+                T.step_staged_async()
+            if f + 1 < a.frames:
+                T.stage_async(every, [q[f + 1] for q in seq], cam)      # generated while step f runs
+            res = T.wait_raw()
+            assert all(res[s].odometry.status == 0 for s in every) if f else True
+            if f >= 2:
+                assert all(res[s].keyframe.status == 0 for s in every)
+                T.commit(every, [accept(s, f, None, None)] * K)
+
     def handles(K, _):
         for s in range(K):
             replay.replay_tracker(pool[s % a.pool], cam, accept, device=a.device, sequence=s)
 
-    def timed(fn, K, T):
-        fn(K, T); sync()                                                # warm-up
-        t = []
+    def timed_all(fns, K, T):
+        """every function warmed up once, then their timed runs interleaved: run 1 of each, run 2 of each, ..."""
+        for fn in fns:
+            fn(K, T); sync()                                            # warm-up
+        t = [[] for _ in fns]
         for _ in range(a.runs):
-            t0 = time.perf_counter(); fn(K, T); sync(); t.append(time.perf_counter() - t0)
-        fps = sorted(K * (a.frames - 1) / x for x in t)                   # tracked frames per second (a frame = odometry + keyframe alignment)
-        return dict(fps_median=fps[len(fps) // 2], fps_min=fps[0], fps_max=fps[-1])
+            for q, fn in enumerate(fns):
+                t0 = time.perf_counter(); fn(K, T); sync(); t[q].append(time.perf_counter() - t0)
+        rows = []
+        for tq in t:
+            fps = sorted(K * (a.frames - 1) / x for x in tq)              # tracked frames per second (a frame = odometry + keyframe alignment)
+            rows.append(dict(fps_median=fps[len(fps) // 2], fps_min=fps[0], fps_max=fps[-1]))
+        return rows
+
+    def timed(fn, K, T):
+        return timed_all([fn], K, T)[0]
 
     lines = [f"tracker streams: {a.frames} frames per sequence, 640 x 480, keyframe replaced every {a.keyframe_every} frames, {a.runs} runs (median, min .. max)"]
     res, h = {}, None
@@ -71,13 +101,21 @@ def main(argv=None):
         print(lines[-1], flush=True)
     for K in ks:
         T = ca.CvoTracks(K, device=a.device)
-        row = timed(streams, K, T)
+        fns = {"both": [streams, streams_staged], "plain": [streams], "staged": [streams_staged]}[a.variant]
+        rows = timed_all(fns, K, T)
         T.close()
-        res[K] = row
-        lines.append(f"K={K:3d} streams: {row['fps_median']:8.1f} frames/s ({row['fps_min']:.1f} .. {row['fps_max']:.1f})")
+        row = res[K] = rows[0] if a.variant != "staged" else dict(rows[0], variant="staged")
+        staged = rows[-1] if a.variant == "both" else None
+        if staged:
+            row["staged"] = staged
+        lines.append(f"K={K:3d} {'staged ' if a.variant == 'staged' else 'streams'}: {row['fps_median']:8.1f} frames/s ({row['fps_min']:.1f} .. {row['fps_max']:.1f})")
         if h:
             row["speedup"] = row["fps_median"] / h["fps_median"]
             lines[-1] += f", x{row['speedup']:.2f} the two-handle path"
+        print(lines[-1], flush=True)
+        if not staged:
+            continue
+        lines.append(f"K={K:3d} staged : {staged['fps_median']:8.1f} frames/s ({staged['fps_min']:.1f} .. {staged['fps_max']:.1f}), x{staged['fps_median'] / row['fps_median']:.3f} the row above")
         print(lines[-1], flush=True)
     print(json.dumps(dict(bench="tracker_replay", frames=a.frames, runs=a.runs, results=res)))
     if a.out:

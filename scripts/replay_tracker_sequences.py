@@ -42,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--arith", default="base", help="arithmetic mode of the alignments: base or eigen337 (cvo_hip.h: cvo_set_arith_mode)")
     ap.add_argument("--max-frames", type=int, default=0, help="replay at most this many frames of every sequence (0 = all)")
     ap.add_argument("--out-dir", default=None, help="where trajectories without an `out` column go (default: beside the list file)")
+    ap.add_argument("--stage-ahead", action="store_true", help="hand the frames of step f + 1 over while step f runs (the same results)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.keyframe_every < 2:
@@ -54,7 +55,7 @@ def main(argv=None):
         if a.max_frames > 0:
             ent = ent[:a.max_frames]
         frames.append(Frames(folder, ent)); cams.append(replay.read_calibration(calib)); stamps.append([e[0] for e in ent])
-    out = replay.replay_tracker_many(frames, cams, keyframe_every(a.keyframe_every), device=a.device, arith=a.arith, slots=a.slots or None)
+    out = replay.replay_tracker_many(frames, cams, keyframe_every(a.keyframe_every), device=a.device, arith=a.arith, slots=a.slots or None, stage_ahead=a.stage_ahead)
     for (_, _, _, path), ts, (poses, steps, decisions) in zip(seqs, stamps, out):
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
         replay.write_trajectory(path, ts, poses)
