@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +65,11 @@ class PairResult(C.Structure):
 class Camera(C.Structure):
     """cvo::camera_info (data_type.h:33-39)."""
     _fields_ = [("scaling_factor", C.c_float), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+
+class DeviceImage(C.Structure):         # cvo_device_image: a frame in caller-owned device memory
+    _fields_ = [("bgr8", C.c_void_p), ("depth16", C.c_void_p), ("bgr_pitch", C.c_longlong), ("depth_pitch", C.c_longlong),
+                ("pixel_bytes", C.c_int), ("swap_rb", C.c_int)]
 
 
 class LcScores(C.Structure):
@@ -123,6 +129,8 @@ ABI_SYMBOLS = [
     "cvo_tracks_get_state",
     "cvo_batch_stage_images", "cvo_batch_advance_staged", "cvo_batch_staged_count",
     "cvo_tracks_stage_async", "cvo_tracks_step_staged_async", "cvo_tracks_staged_count",
+    "cvo_check_device_images", "cvo_selftest_ingest_images", "cvo_batch_set_pairs_device_images", "cvo_batch_advance_device_images",
+    "cvo_batch_stage_device_images", "cvo_tracks_step_device_async", "cvo_tracks_stage_device_async",
 ]
 
 _lib = None
@@ -290,6 +298,14 @@ def load_library():
     L.cvo_tracks_stage_async.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(Camera), ip]
     L.cvo_tracks_step_staged_async.argtypes = [vp, vp]
     L.cvo_tracks_staged_count.argtypes = [vp, ip, C.POINTER(C.c_longlong)]
+    dip = C.POINTER(DeviceImage)
+    L.cvo_check_device_images.argtypes = [C.c_int, C.c_int, dip, C.c_int, C.c_int]
+    L.cvo_selftest_ingest_images.argtypes = [C.c_int, C.c_int, dip, C.c_int, C.c_int, vp, vp, ip]
+    L.cvo_batch_set_pairs_device_images.argtypes = [vp, C.c_int, C.c_int, C.c_int, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, ip, ip, vp]
+    L.cvo_batch_advance_device_images.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, ip, vp]
+    L.cvo_batch_stage_device_images.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp]
+    L.cvo_tracks_step_device_async.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp, vp]
+    L.cvo_tracks_stage_device_async.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp]
     _lib = L
     return L
 
@@ -410,6 +426,127 @@ def _cloud_args(xyz, feat):
     if x.ndim != 2 or x.shape[1] != 3 or f.shape != (5, x.shape[0]):
         raise ValueError("cloud must be xyz (n,3) and feat (5,n)")
     return x, xp, f, fpt
+
+
+# ---- frames in device memory: anything that carries __cuda_array_interface__ (torch ROCm tensors do; torch itself is not needed here)
+def is_device_image(a) -> bool:
+    return hasattr(a, "__cuda_array_interface__")
+
+
+def _strides_of(cai, itemsize):
+    shape = tuple(int(v) for v in cai["shape"])
+    st = cai.get("strides")
+    if st is None:                                   # C-contiguous
+        st, acc = [], itemsize
+        for d in reversed(shape):
+            st.append(acc); acc *= d
+        st = tuple(reversed(st))
+    return shape, tuple(int(v) for v in st)
+
+
+def device_image(bgr, depth, swap_rb: bool = False):
+    """(DeviceImage, width, height) of a frame in device memory, from the shape and strides of its two __cuda_array_interface__ carriers.
+    bgr: uint8 (h, w, 3) or (h, w, 4), channel stride 1, pixel stride 3 or 4 bytes, any row stride >= the row's bytes (so a crop of a larger
+    tensor, or the first three channels of a BGRA tensor, is fine as it is).  depth: uint16 or int16 (reinterpreted) (h, w), element stride 2.
+    swap_rb: the colour bytes are R, G, B.  Anything else raises ValueError."""
+    if not is_device_image(bgr) or not is_device_image(depth):
+        raise ValueError("a device image is a pair of objects with __cuda_array_interface__")
+    cb, cd = bgr.__cuda_array_interface__, depth.__cuda_array_interface__
+    if cb["typestr"] != "|u1":
+        raise ValueError(f"bgr: uint8 expected, got typestr {cb['typestr']!r}")
+    if cd["typestr"] not in ("<u2", "<i2"):
+        raise ValueError(f"depth: little-endian uint16 or int16 expected, got typestr {cd['typestr']!r}")
+    sb, tb = _strides_of(cb, 1)
+    sd, td = _strides_of(cd, 2)
+    if len(sb) != 3 or sb[2] not in (3, 4):
+        raise ValueError(f"bgr: shape (h, w, 3) or (h, w, 4) expected, got {sb}")
+    h, w = sb[0], sb[1]
+    if tb[2] != 1:
+        raise ValueError(f"bgr: channel stride 1 expected, got {tb[2]}")
+    if tb[1] not in (3, 4) or tb[1] < sb[2]:
+        raise ValueError(f"bgr: pixel stride 3 or 4 bytes expected, got {tb[1]} for {sb[2]} channels")
+    if tb[0] < w * tb[1]:
+        raise ValueError(f"bgr: row stride {tb[0]} is below the row's {w * tb[1]} bytes")
+    if len(sd) != 2 or sd != (h, w):
+        raise ValueError(f"depth: shape {(h, w)} expected, got {sd}")
+    if td[1] != 2:
+        raise ValueError(f"depth: element stride 2 bytes expected, got {td[1]}")
+    if td[0] < 2 * w:
+        raise ValueError(f"depth: row stride {td[0]} is below the row's {2 * w} bytes")
+    pb, pd = cb["data"][0], cd["data"][0]
+    if not pb or not pd:
+        raise ValueError("null device pointer")
+    return DeviceImage(pb, pd, tb[0], td[0], tb[1], 1 if swap_rb else 0), w, h
+
+
+def _images_on_device(images) -> bool:
+    """True: every image of the list is a device image; False: none is.  A mixed list raises ValueError."""
+    kinds = {bool(is_device_image(b)) and bool(is_device_image(d)) for b, d in images}
+    if len(kinds) > 1 or any(is_device_image(b) != is_device_image(d) for b, d in images):
+        raise ValueError("host and device images mixed in one call")
+    return bool(kinds) and kinds.pop()
+
+
+def _device_images(images, swap_rb):
+    """[(DeviceImage, w, h)] of a list of (bgr, depth) device images; swap_rb: one flag for all, or one per image"""
+    sw = list(swap_rb) if hasattr(swap_rb, "__len__") else [swap_rb] * len(images)
+    if len(sw) != len(images):
+        raise ValueError("swap_rb: one flag, or one per image")
+    return [device_image(b, d, bool(f)) for (b, d), f in zip(images, sw)]
+
+
+def _stream_arg(image_stream):
+    h = getattr(image_stream, "cuda_stream", image_stream)   # a torch.cuda.Stream, or a raw hipStream_t value
+    return C.c_void_p(int(h)) if h else None
+
+
+def _settle_writer(images, image_stream):
+    """image_stream None: the entry point takes the images as already written.  torch tensors are written on torch's current stream, so that
+    stream is synchronised first (torch is only looked at when the caller has loaded it)."""
+    if image_stream is not None or "torch" not in sys.modules:
+        return
+    torch = sys.modules["torch"]
+    t = images[0][0]
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        torch.cuda.current_stream(t.device).synchronize()
+
+
+def _device_list_args(ids, images, cameras, cam_index, what, swap_rb):
+    """_image_list_args for device images: (n, ids, descriptors, w, h, cameras, cam_index or None) plus what must stay alive"""
+    ims = _device_images(images, swap_rb)
+    sl = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    if not ims or sl.shape[0] != len(ims):
+        raise ValueError(f"one {what} per image, at least one image")
+    w, h = ims[0][1], ims[0][2]
+    if any((q[1], q[2]) != (w, h) for q in ims):
+        raise ValueError("all images of one call must have the same size")
+    if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+        cameras = [cameras]
+    cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+    ci = None if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+    if ci is not None and (ci.shape[0] != len(ims) or ci.min() < 0 or ci.max() >= len(cameras)):
+        raise ValueError("cam_index: one index into cameras per image")
+    n = len(ims); ip = C.POINTER(C.c_int)
+    descs = (DeviceImage * n)(*[q[0] for q in ims])
+    return (n, sl.ctypes.data_as(ip), descs, w, h, cams, None if ci is None else ci.ctypes.data_as(ip)), (sl, ci, images)
+
+
+def check_device_images(images, swap_rb: bool = False, device: int = 0):
+    """cvo_check_device_images: the validation every device entry point runs first, alone (nothing is launched).  images: a list of
+    (bgr, depth) device images of one size.  Raises CvoError (code 4, the message names image and field) for what the device cannot read."""
+    ims = _device_images(images, swap_rb)
+    descs = (DeviceImage * len(ims))(*[q[0] for q in ims])
+    _check(load_library().cvo_check_device_images(device, len(ims), descs, ims[0][1], ims[0][2]))
+
+
+def selftest_ingest_images(descs, width: int, height: int, device: int = 0):
+    """cvo_selftest_ingest_images: the ingest kernel alone on a list of DeviceImage; returns (bgr stack (count, h, w, 3) uint8,
+    depth stack (count, h, w) uint16, guards intact)"""
+    n = len(descs)
+    arr = (DeviceImage * n)(*descs)
+    bgr = np.zeros((n, height, width, 3), np.uint8); dep = np.zeros((n, height, width), np.uint16); ok = C.c_int(0)
+    _check(load_library().cvo_selftest_ingest_images(device, n, arr, int(width), int(height), bgr.ctypes.data, dep.ctypes.data, C.byref(ok)))
+    return bgr, dep, bool(ok.value)
 
 
 class Cvo:
@@ -831,16 +968,29 @@ class CvoBatch:
         pr = prepared if isinstance(prepared, dict) else self.prepare_pairs(prepared)
         _check(self.L.cvo_batch_set_pairs(self.h, first, pr["n"], pr["fx"], pr["ff"], pr["nf"], pr["mx"], pr["mf"], pr["nm"]))
 
-    def set_pairs_images(self, images, fixed_image, moving_image, camera, first: int = 0):
+    def set_pairs_images(self, images, fixed_image, moving_image, camera, first: int = 0, swap_rb: bool = False, image_stream=None):
         """cvo_batch_set_pairs_images: pairs first .. first+len(fixed_image)-1 from RGB-D images.  images: list of (bgr8, depth16), all of one
         size, each generated once on the GPU; pair k takes images[fixed_image[k]] as its fixed cloud and images[moving_image[k]] as its moving
-        one.  camera = (scaling_factor, fx, fy, cx, cy).  Returns the points of each image's cloud."""
-        ims = [Cvo._images(b, d) for b, d in images]
-        if not ims:
-            raise ValueError("no images")
+        one.  camera = (scaling_factor, fx, fy, cx, cy).  Returns the points of each image's cloud.
+        Device images (objects with __cuda_array_interface__, see device_image) are read where they are: swap_rb (one flag, or one per image) for R, G, B colour bytes,
+        image_stream for the stream that wrote them (None: torch's current stream is synchronised first when the images are torch tensors)."""
         fi = np.ascontiguousarray(fixed_image, np.int32).reshape(-1); mi = np.ascontiguousarray(moving_image, np.int32).reshape(-1)
         if fi.shape != mi.shape:
             raise ValueError("fixed_image and moving_image must have one entry per pair")
+        if _images_on_device(images):
+            dm = _device_images(images, swap_rb)
+            w, h = dm[0][1], dm[0][2]
+            if any((q[1], q[2]) != (w, h) for q in dm):
+                raise ValueError("all images of one call must have the same size")
+            n = len(dm); cam = Camera(*[float(v) for v in camera]); descs = (DeviceImage * n)(*[q[0] for q in dm])
+            pts = np.zeros(n, np.int32); ip = C.POINTER(C.c_int)
+            _settle_writer(images, image_stream)
+            _check(self.L.cvo_batch_set_pairs_device_images(self.h, int(first), int(fi.shape[0]), n, descs, w, h, C.byref(cam), fi.ctypes.data_as(ip),
+                                                            mi.ctypes.data_as(ip), pts.ctypes.data_as(ip), _stream_arg(image_stream)))
+            return pts
+        ims = [Cvo._images(b, d) for b, d in images]
+        if not ims:
+            raise ValueError("no images")
         w, h = ims[0][2], ims[0][3]
         if any((q[2], q[3]) != (w, h) for q in ims):
             raise ValueError("all images of one call must have the same size")
@@ -852,11 +1002,17 @@ class CvoBatch:
         return pts
 
     # -- K-stream frame-to-frame odometry (cvo_hip.h: cvo_batch_advance_images & co): slot p is one cvo::cvo odometry object
-    def advance_images(self, slots, images, cameras, cam_index=None):
+    def advance_images(self, slots, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
         """cvo_batch_advance_images: images[k] = (bgr8, depth16), all of one size, is the next frame of slot slots[k], generated with camera
         cameras[cam_index[k]] (cam_index None: cameras[0] for all).  cameras: a list of (scaling_factor, fx, fy, cx, cy), or one such tuple.
         A slot's first frame becomes its fixed cloud; after that the moving cloud moves to fixed and the frame becomes the moving cloud.
-        Returns the points of each image's cloud."""
+        Returns the points of each image's cloud.  Device images: as for set_pairs_images."""
+        if _images_on_device(images):
+            args, keep = _device_list_args(slots, images, cameras, cam_index, "slot", swap_rb)
+            pts = np.zeros(args[0], np.int32)
+            _settle_writer(images, image_stream)
+            _check(self.L.cvo_batch_advance_device_images(self.h, *args, pts.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(image_stream)))
+            return pts
         ims = [Cvo._images(b, d) for b, d in images]
         sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
         if not ims or sl.shape[0] != len(ims):
@@ -877,10 +1033,16 @@ class CvoBatch:
                                                pts.ctypes.data_as(ip)))
         return pts
 
-    def stage_images(self, slots, images, cameras, cam_index=None):
+    def stage_images(self, slots, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
         """cvo_batch_stage_images: the arguments of advance_images, for the slots' NEXT frames.  Their clouds are generated on the stage's own
         stream while a launch runs (call it between align_pairs_async and wait); the images may be reused as soon as the call returns.  One
-        stage per batch: a second call replaces the first.  Returns the number of images staged."""
+        stage per batch: a second call replaces the first.  Returns the number of images staged.  Device images: as for set_pairs_images; with
+        an image_stream the call does not wait on the host at all."""
+        if _images_on_device(images):
+            args, keep = _device_list_args(slots, images, cameras, cam_index, "slot", swap_rb)
+            _settle_writer(images, image_stream)
+            _check(self.L.cvo_batch_stage_device_images(self.h, *args, _stream_arg(image_stream)))
+            return args[0]
         args, keep = _image_list_args(slots, images, cameras, cam_index, "slot")
         _check(self.L.cvo_batch_stage_images(self.h, *args))
         return args[0]
@@ -1142,9 +1304,17 @@ class CvoTracks:
         """stream s = two fresh objects"""
         _check(self.L.cvo_tracks_reset(self.h, int(s)))
 
-    def step_async(self, streams, images, cameras, cam_index=None, stream: int | None = None):
+    def step_async(self, streams, images, cameras, cam_index=None, stream: int | None = None, swap_rb: bool = False, image_stream=None):
         """cvo_tracks_step_async: images[k] = (bgr8, depth16), all of one size, is the next frame of stream streams[k], generated with camera
-        cameras[cam_index[k]] (cam_index None: cameras[0] for all; cameras: a list of (scaling_factor, fx, fy, cx, cy), or one such tuple)."""
+        cameras[cam_index[k]] (cam_index None: cameras[0] for all; cameras: a list of (scaling_factor, fx, fy, cx, cy), or one such tuple).
+        Device images (objects with __cuda_array_interface__, see device_image) go to cvo_tracks_step_device_async: swap_rb for R, G, B colour
+        bytes, image_stream for the stream that wrote them (None: torch's current stream is synchronised first for torch tensors)."""
+        if _images_on_device(images):
+            args, keep = _device_list_args(streams, images, cameras, cam_index, "stream", swap_rb)
+            _settle_writer(images, image_stream)
+            _check(self.L.cvo_tracks_step_device_async(self.h, *args, C.c_void_p(stream) if stream else None, _stream_arg(image_stream)))
+            self._n = args[0]
+            return args[0]
         ims = [Cvo._images(b, d) for b, d in images]
         sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
         if not ims or sl.shape[0] != len(ims):
@@ -1165,9 +1335,15 @@ class CvoTracks:
         self._n = n
         return n
 
-    def stage_async(self, streams, images, cameras, cam_index=None):
+    def stage_async(self, streams, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
         """cvo_tracks_stage_async: the arguments of step_async, for the streams' NEXT frames -- call it between step_async / step_staged_async
-        of the current step and its wait.  The images may be reused as soon as the call returns.  Returns the number of images staged."""
+        of the current step and its wait.  The images may be reused as soon as the call returns.  Returns the number of images staged.  Device images: as for
+        step_async; with an image_stream the call does not wait on the host, and the images are free for work queued on that stream."""
+        if _images_on_device(images):
+            args, keep = _device_list_args(streams, images, cameras, cam_index, "stream", swap_rb)
+            _settle_writer(images, image_stream)
+            _check(self.L.cvo_tracks_stage_device_async(self.h, *args, _stream_arg(image_stream)))
+            return args[0]
         args, keep = _image_list_args(streams, images, cameras, cam_index, "stream")
         _check(self.L.cvo_tracks_stage_async(self.h, *args))
         return args[0]
@@ -1208,8 +1384,8 @@ class CvoTracks:
                      keyframe=_pair_result_dict(o.keyframe), keyframe_scores=_track_scores_dict(o.keyframe_scores),
                      initial_guess=np.array(o.initial_guess[:], np.float32).reshape(3, 4)) for o in self.wait_raw()[:n]]
 
-    def step(self, streams, images, cameras, cam_index=None):
-        self.step_async(streams, images, cameras, cam_index)
+    def step(self, streams, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
+        self.step_async(streams, images, cameras, cam_index, swap_rb=swap_rb, image_stream=image_stream)
         return self.wait()
 
     def commit(self, streams, accept):

@@ -86,6 +86,7 @@ hipError_t pcd_launch_subsample_batch(uint8_t* map, const uint8_t* pattern, cons
 hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, const uint8_t* bgr, const float* dx0, const float* dy0, int w, int h, const float cam[5],
                                   const float* cam_table, const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s);
 hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s);
+hipError_t pcd_launch_ingest(const PcdIngestDesc* descs, uint8_t* bgr_stack, uint8_t* depth_stack, int w, int h, int n_img, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -1412,11 +1413,16 @@ constexpr int PCD_CLOUD_CAP = 65535;
 struct BatchImages {
     DevBuf bgr, depth, I0, I1, I2, dx0, dy0, abs0, abs1, abs2, ths, thsS, map, pattern, tiles, rec, cloud, px, cams;
     PinBuf stage, h_rec, h_cams;
+    PinBuf h_ingest;                                                // device images: the ingest kernel's descriptor table (read by the kernel where it is)
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;                   // ... and the two edges between the caller's image_stream and the stream of the ingest
     int n_cap = 0, w = 0, h = 0;
     int num_want = 3000;                                            // pcd_generator::num_want (pcd_generator.cpp:22)
     void release() {
         for (DevBuf* b : {&bgr, &depth, &I0, &I1, &I2, &dx0, &dy0, &abs0, &abs1, &abs2, &ths, &thsS, &map, &pattern, &tiles, &rec, &cloud, &px, &cams}) b->release();
-        stage.release(); h_rec.release(); h_cams.release();
+        stage.release(); h_rec.release(); h_cams.release(); h_ingest.release();
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_out) (void)hipEventDestroy(ev_out);
+        ev_in = ev_out = nullptr;
         n_cap = w = h = 0;
     }
 };
@@ -2302,7 +2308,7 @@ namespace {
 // CVO_HIP_STEP_LAPS=1: host timers around the stages of a K-stream step, added up and printed (stderr, ms per step) when the object is destroyed.
 // A measuring mode: it waits for each host-to-device copy where it is queued, so that the copy's time is its own lap and not the generator's.
 struct StepLaps {
-    enum { COPY, H2D, GENERATE, SCATTER, LAUNCH, WAIT, COMMIT, STAGE, CONSUME, N };
+    enum { COPY, H2D, GENERATE, SCATTER, LAUNCH, WAIT, COMMIT, STAGE, CONSUME, INGEST, N };
     bool on = false; double ms[N] = {}; long steps = 0;
 };
 StepLaps* step_laps() {
@@ -2317,18 +2323,60 @@ struct Lap {
 void report_step_laps(const char* who) {
     StepLaps& L = *step_laps();
     if (!L.on || L.steps <= 0) return;
-    static const char* name[StepLaps::N] = {"host_copy", "h2d_copy", "generate_to_sync", "scatter", "launches", "wait", "commit", "stage_call", "consume_call"};
+    static const char* name[StepLaps::N] = {"host_copy", "h2d_copy", "generate_to_sync", "scatter", "launches", "wait", "commit", "stage_call", "consume_call", "ingest"};
     std::fprintf(stderr, "[cvo_hip] %s step laps, ms per step over %ld steps:", who, L.steps);
     for (int q = 0; q < StepLaps::N; ++q) std::fprintf(stderr, " %s %.3f", name[q], L.ms[q] / (double)L.steps);
     std::fprintf(stderr, "\n");
     L = StepLaps(); L.on = true;
 }
-// N images (all w x h) queued for generation on stream s into the images' slots of S.cloud / S.px: the images copied into S's pinned stage (by
-// `copy_parts` threads of the copy pool), their host-to-device copies, the generator's fixed list of launches, the read-back of the records into
-// S.h_rec.  Waits for nothing but a growing scratch; the caller's images are free when it returns.  cam: one camera for all, or cam_table
-// (host, N cameras): a camera per image.
-int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+// The images of a call: host images (bgr8 / depth16, one pointer per image) or caller-owned device images (dev, checked by check_device_images)
+// with the stream their writer ran on (image_stream; null = the caller has synchronised it).
+struct ImageSrc {
+    const unsigned char* const* bgr8 = nullptr; const unsigned short* const* depth16 = nullptr;
+    const cvo_device_image* dev = nullptr; hipStream_t image_stream = nullptr;
+    static ImageSrc host(const unsigned char* const* bgr8, const unsigned short* const* depth16) { ImageSrc s; s.bgr8 = bgr8; s.depth16 = depth16; return s; }
+    static ImageSrc device(const cvo_device_image* images, void* image_stream) { ImageSrc s; s.dev = images; s.image_stream = static_cast<hipStream_t>(image_stream); return s; }
+};
+// The fill of the stacks from device images: ONE ingest launch on s, which is always a stream of the library's own -- a caller's stream may share
+// the hardware queue of a persistent align launch and would not start before that launch ends.  With an image_stream: s waits for what is queued
+// there by an event, and the image_stream waits for the ingest by a second one (no host wait); without: the host waits for the ingest alone.
+int ingest_enqueue(BatchImages& S, hipStream_t s, int N, const ImageSrc& src, int w, int h) {
+    int rc;
+    if ((rc = S.h_ingest.ensure(sizeof(PcdIngestDesc) * (size_t)S.n_cap))) return rc;
+    if (!S.ev_in) HIP_TRY(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
+    if (!S.ev_out) HIP_TRY(hipEventCreateWithFlags(&S.ev_out, hipEventDisableTiming));
+    PcdIngestDesc* d = static_cast<PcdIngestDesc*>(S.h_ingest.p);
+    for (int k = 0; k < N; ++k) {
+        const cvo_device_image& im = src.dev[k];
+        d[k].bgr = static_cast<const uint8_t*>(im.bgr8); d[k].depth = static_cast<const uint8_t*>(im.depth16);
+        d[k].bgr_pitch = im.bgr_pitch ? im.bgr_pitch : (long long)w * im.pixel_bytes;
+        d[k].depth_pitch = im.depth_pitch ? im.depth_pitch : 2ll * w;
+        d[k].pixel_bytes = im.pixel_bytes; d[k].swap_rb = im.swap_rb;
+        d[k].bgr_dwords = ((reinterpret_cast<uintptr_t>(im.bgr8) | (uintptr_t)d[k].bgr_pitch) & 3u) == 0;
+        d[k].depth_dwords = ((reinterpret_cast<uintptr_t>(im.depth16) | (uintptr_t)d[k].depth_pitch) & 3u) == 0;
+    }
+    if (src.image_stream) {
+        HIP_TRY(hipEventRecord(S.ev_in, src.image_stream));
+        HIP_TRY(hipStreamWaitEvent(s, S.ev_in, 0));
+    }
+    const hipError_t e = pcd_launch_ingest(d, (uint8_t*)S.bgr.p, (uint8_t*)S.depth.p, w, h, N, s);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd ingest kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(S.ev_out, s));
+    Lap lap(StepLaps::INGEST);
+    if (src.image_stream) HIP_TRY(hipStreamWaitEvent(src.image_stream, S.ev_out, 0));
+    else HIP_TRY(hipEventSynchronize(S.ev_out));
+    if (step_laps()->on) HIP_TRY(hipStreamSynchronize(s));
+    return CVO_OK;
+}
+// N images (all w x h) queued for generation on stream s into the images' slots of S.cloud / S.px: the stacks filled, the generator's fixed list
+// of launches, the read-back of the records into S.h_rec.  The fill: host images are copied into S's pinned stage (by `copy_parts` threads of
+// the copy pool) and from there to the device, the colour images first so that the kernels that need nothing else run while the host stages
+// the depth images; device images are gathered by the ingest launch (no pinned image stage, no copy threads).  Waits for nothing but a growing
+// scratch (and a device call without image_stream for its ingest); the caller's images are free when it returns, device images given with an
+// image_stream for work queued on that stream.  cam: one camera for all, or cam_table (host, N cameras): a camera per image.
+int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const ImageSrc& src, int width, int height,
                      const cvo_camera* cam, const cvo_camera* cam_table, int copy_parts) {
+    const unsigned char* const* bgr8 = src.bgr8; const unsigned short* const* depth16 = src.depth16;
     const int w = width, h = height, num_want = S.num_want;
     const size_t n = (size_t)w * h, n1 = (size_t)(w / 2) * (h / 2), n2 = (size_t)(w / 4) * (h / 4), nths = (size_t)(w / 32) * (h / 32) + 100;
     const int nt = pcd_tiles(w, h), cap = PCD_CLOUD_CAP;
@@ -2344,7 +2392,7 @@ int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsi
         for (DevBuf* x : {&S.ths, &S.thsS}) if ((rc = x->ensure(sizeof(float) * nths * m))) return rc;
         if ((rc = S.tiles.ensure(sizeof(int) * 3 * (size_t)nt * m)) || (rc = S.rec.ensure(sizeof(PcdImgRec) * m))) return rc;
         if ((rc = S.cloud.ensure(sizeof(float) * REC * (size_t)cap * m)) || (rc = S.px.ensure(sizeof(uint16_t) * 2 * (size_t)cap * m))) return rc;
-        if ((rc = S.stage.ensure(5 * n * m)) || (rc = S.h_rec.ensure(sizeof(PcdImgRec) * m))) return rc;
+        if ((rc = S.h_rec.ensure(sizeof(PcdImgRec) * m))) return rc;
         if (w != S.w || h != S.h) {                                   // the byte pattern only depends on w*h: made once per size, shared by every image
             if ((rc = S.pattern.ensure(n))) return rc;
             std::vector<unsigned char> pat(n);
@@ -2354,6 +2402,7 @@ int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsi
         S.n_cap = (int)m; S.w = w; S.h = h;
     }
     if (cam_table && ((rc = S.cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)) || (rc = S.h_cams.ensure(sizeof(cvo_camera) * (size_t)S.n_cap)))) return rc;
+    if (!src.dev && (rc = S.stage.ensure(5 * n * (size_t)S.n_cap))) return rc;
     unsigned char* st = static_cast<unsigned char*>(S.stage.p);
     // image k of `src` (bytes each) to dst + bytes * k, the images dealt to the copy threads in runs
     auto copy_images = [&](unsigned char* dst, const void* const* src, size_t bytes) {
@@ -2362,9 +2411,13 @@ int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsi
         CopyPool::get().run(parts, [&](int q) { for (int k = (int)((long long)N * q / parts); k < (int)((long long)N * (q + 1) / parts); ++k) std::memcpy(dst + bytes * k, src[k], bytes); });
     };
     // the colour images first: their copy and the pyramid / threshold / select kernels (which need nothing else) run while the host stages the depth images
-    copy_images(st, reinterpret_cast<const void* const*>(bgr8), 3 * n);
-    HIP_TRY(hipMemcpyAsync(S.bgr.p, st, 3 * n * N, hipMemcpyHostToDevice, s));
-    if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    if (src.dev) {
+        if ((rc = ingest_enqueue(S, s, N, src, w, h))) return rc;
+    } else {
+        copy_images(st, reinterpret_cast<const void* const*>(bgr8), 3 * n);
+        HIP_TRY(hipMemcpyAsync(S.bgr.p, st, 3 * n * N, hipMemcpyHostToDevice, s));
+        if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    }
     HIP_TRY(hipMemsetAsync(S.ths.p, 0, sizeof(float) * nths * N, s));
     HIP_TRY(hipMemsetAsync(S.thsS.p, 0, sizeof(float) * nths * N, s));
     HIP_TRY(hipMemsetAsync(S.map.p, 0, n * N, s));
@@ -2374,11 +2427,13 @@ int generate_enqueue(Engine& E, BatchImages& S, hipStream_t s, int N, const unsi
     if (e == hipSuccess) e = pcd_launch_thresholds(abs0, w, h, (float*)S.ths.p, (float*)S.thsS.p, N, s);
     if (e == hipSuccess) e = pcd_launch_select_batch(abs0, abs1, abs2, (const float*)S.thsS.p, w, h, (uint8_t*)S.map.p, rec, N, num_want, s);
     if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pcd kernels: ") + hipGetErrorString(e));
-    unsigned char* sd = st + 3 * n * N;
-    copy_images(sd, reinterpret_cast<const void* const*>(depth16), 2 * n);
-    if (laps) { Lap lap(StepLaps::GENERATE); HIP_TRY(hipStreamSynchronize(s)); }   // (the kernels queued so far: not part of the depth copy's lap)
-    HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
-    if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    if (!src.dev) {
+        unsigned char* sd = st + 3 * n * N;
+        copy_images(sd, reinterpret_cast<const void* const*>(depth16), 2 * n);
+        if (laps) { Lap lap(StepLaps::GENERATE); HIP_TRY(hipStreamSynchronize(s)); }   // (the kernels queued so far: not part of the depth copy's lap)
+        HIP_TRY(hipMemcpyAsync(S.depth.p, sd, 2 * n * N, hipMemcpyHostToDevice, s));
+        if (laps) { Lap lap(StepLaps::H2D); HIP_TRY(hipStreamSynchronize(s)); }
+    }
     const cvo_camera& c0 = cam ? *cam : cam_table[0];
     const float camv[5] = {c0.scaling_factor, c0.fx, c0.fy, c0.cx, c0.cy};
     if (cam_table) {
@@ -2399,7 +2454,7 @@ int check_cloud_caps(const PcdImgRec* R, int N) {
     return CVO_OK;
 }
 // The clouds of N images (all w x h) into the images' slots of b->img.cloud / px; *recs: their records on the host.  Nothing of the batch's pairs changes.
-int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height, const cvo_camera* cam,
+int batch_generate(cvo_batch b, int N, const ImageSrc& src, int width, int height, const cvo_camera* cam,
                    const cvo_camera* cam_table, const PcdImgRec** recs) {
     Engine& E = b->eng; BatchImages& S = b->img;
     HIP_TRY(hipSetDevice(E.device));
@@ -2407,7 +2462,7 @@ int batch_generate(cvo_batch b, int N, const unsigned char* const* bgr8, const u
     {
         // every return from here on leaves nothing of this call in flight: the next call overwrites the pinned stage the copies read from
         struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{s};
-        int rc = generate_enqueue(E, S, s, N, bgr8, depth16, width, height, cam, cam_table, 1); if (rc) return rc;
+        int rc = generate_enqueue(E, S, s, N, src, width, height, cam, cam_table, 1); if (rc) return rc;
         Lap lap(StepLaps::GENERATE);
         (void)hipStreamSynchronize(s);
     }                                                                 // (the one sync)
@@ -2450,6 +2505,53 @@ int batch_scatter(cvo_batch b, const std::vector<Cloud*>& dst, const std::vector
     return CVO_OK;
 }
 bool image_size_ok(int width, int height) { return width >= 64 && height >= 64 && (size_t)width * height <= (size_t)1 << 26; }
+// One plane of a device image: rows of row_bytes bytes, `pitch` apart (resolved), `height` of them from ptr.  The device must be able to read
+// every byte: device memory of `device` (the rows inside the allocation), managed memory, or pinned / registered host memory.  Anything else --
+// pageable host memory, another device's memory -- is refused here, it must never reach a kernel.
+int check_device_plane(int device, const void* ptr, long long pitch, long long row_bytes, int height, const std::string& what) {
+    hipPointerAttribute_t at; std::memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, ptr);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CVO_ERR_INVALID, what + ": not a pointer the device can read (" + hipGetErrorString(e) + ")"); }
+    if (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) return CVO_OK;
+    if (at.type != hipMemoryTypeDevice) return fail(CVO_ERR_INVALID, what + ": unregistered host memory, the device cannot read it");
+    if (at.device != device) return fail(CVO_ERR_INVALID, what + ": memory of device " + std::to_string(at.device) + ", the object runs on device " + std::to_string(device));
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    const hipError_t er = hipMemGetAddressRange(&base, &size, const_cast<void*>(ptr));
+    if (er != hipSuccess) { (void)hipGetLastError(); return fail(CVO_ERR_INVALID, what + ": no allocation found around the pointer (" + hipGetErrorString(er) + ")"); }
+    const unsigned long long lo = reinterpret_cast<uintptr_t>(ptr), a0 = reinterpret_cast<uintptr_t>(base);
+    const unsigned long long need = (unsigned long long)(height - 1) * (unsigned long long)pitch + (unsigned long long)row_bytes;
+    if (lo < a0 || lo - a0 > size || need > size - (lo - a0)) return fail(CVO_ERR_INVALID, what + ": the image ends outside its allocation (" + std::to_string(need) + " bytes from the pointer)");
+    return CVO_OK;
+}
+// What every device entry point checks first, before any stream changes and before anything is queued (cvo_check_device_images runs it alone).
+int check_device_images(int device, int count, const cvo_device_image* images, int width, int height) {
+    if (count <= 0 || count > 65535) return fail(CVO_ERR_INVALID, "bad image count");
+    if (!images) return fail(CVO_ERR_INVALID, "null argument: images");
+    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
+    for (int k = 0; k < count; ++k) {
+        const cvo_device_image& im = images[k];
+        const std::string who = "image " + std::to_string(k) + ": ";
+        if (!im.bgr8) return fail(CVO_ERR_INVALID, who + "bgr8 is null");
+        if (!im.depth16) return fail(CVO_ERR_INVALID, who + "depth16 is null");
+        if (im.pixel_bytes != 3 && im.pixel_bytes != 4) return fail(CVO_ERR_INVALID, who + "pixel_bytes must be 3 or 4, got " + std::to_string(im.pixel_bytes));
+        if (im.swap_rb != 0 && im.swap_rb != 1) return fail(CVO_ERR_INVALID, who + "swap_rb must be 0 or 1, got " + std::to_string(im.swap_rb));
+        const long long row = (long long)width * im.pixel_bytes, drow = 2ll * width;
+        if (im.bgr_pitch < 0 || (im.bgr_pitch != 0 && im.bgr_pitch < row)) return fail(CVO_ERR_INVALID, who + "bgr_pitch " + std::to_string(im.bgr_pitch) + " is below the row's " + std::to_string(row) + " bytes");
+        if (im.depth_pitch < 0 || (im.depth_pitch != 0 && im.depth_pitch < drow)) return fail(CVO_ERR_INVALID, who + "depth_pitch " + std::to_string(im.depth_pitch) + " is below the row's " + std::to_string(drow) + " bytes");
+        if (reinterpret_cast<uintptr_t>(im.depth16) & 1u) return fail(CVO_ERR_INVALID, who + "depth16 is not 2-byte aligned");
+        if (im.depth_pitch & 1) return fail(CVO_ERR_INVALID, who + "depth_pitch is not a multiple of 2");
+    }
+    HIP_TRY(hipSetDevice(device));
+    for (int k = 0; k < count; ++k) {
+        const cvo_device_image& im = images[k];
+        const std::string who = "image " + std::to_string(k) + ": ";
+        const long long row = (long long)width * im.pixel_bytes, drow = 2ll * width;
+        int rc;
+        if ((rc = check_device_plane(device, im.bgr8, im.bgr_pitch ? im.bgr_pitch : row, row, height, who + "bgr8"))) return rc;
+        if ((rc = check_device_plane(device, im.depth16, im.depth_pitch ? im.depth_pitch : drow, drow, height, who + "depth16"))) return rc;
+    }
+    return CVO_OK;
+}
 
 // ---- the stage: the next step's frames generated ahead, on a stream of their own (FrameStage)
 void pool_free_cloud(std::vector<std::shared_ptr<Cloud>>& pool, std::shared_ptr<Cloud>& out) {
@@ -2483,7 +2585,7 @@ void stage_drop_if_listed(cvo_batch b, int p) {
     if (F.pending && std::find(F.list.begin(), F.list.end(), p) != F.list.end()) stage_drop(b);
 }
 // `count` images staged for the slots / streams of `list` (the arguments are checked): returns with everything queued and every image byte copied
-int stage_begin(cvo_batch b, int count, const int* list, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+int stage_begin(cvo_batch b, int count, const int* list, const ImageSrc& src, int width, int height,
                 const cvo_camera* cams, const int* cam_index) {
     Lap lap(StepLaps::STAGE);
     Engine& E = b->eng; FrameStage& F = b->stage;
@@ -2495,7 +2597,7 @@ int stage_begin(cvo_batch b, int count, const int* list, const unsigned char* co
     stage_drop(b);                                                   // (a stage that was never consumed is replaced)
     std::vector<cvo_camera> cam_of(count);
     for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
-    rc = generate_enqueue(E, F.img, F.s, count, bgr8, depth16, width, height, nullptr, cam_of.data(), E.upload_threads);
+    rc = generate_enqueue(E, F.img, F.s, count, src, width, height, nullptr, cam_of.data(), E.upload_threads);
     if (rc) { (void)hipStreamSynchronize(F.s); return rc; }         // (nothing of a failed call stays in flight)
     HIP_TRY(hipEventRecord(F.ev_gen, F.s));
     F.gen_waited = false;
@@ -2587,18 +2689,19 @@ int stage_count(cvo_batch b, int* images, long long* taken) {
 }
 }  // namespace
 
-int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
-                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
+namespace {
+int batch_set_pairs_from(cvo_batch b, int first, int count, int n_images, const ImageSrc& src,
+                         int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
     if (!b || first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
-    if (!bgr8 || !depth16 || !cam || !fixed_image || !moving_image) return fail(CVO_ERR_INVALID, "null argument");
+    if ((!src.dev && (!src.bgr8 || !src.depth16)) || !cam || !fixed_image || !moving_image) return fail(CVO_ERR_INVALID, "null argument");
     if (n_images <= 0 || n_images > 65535) return fail(CVO_ERR_INVALID, "bad image count");
     if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
-    for (int k = 0; k < n_images; ++k) if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+    if (!src.dev) for (int k = 0; k < n_images; ++k) if (!src.bgr8[k] || !src.depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
     for (int k = 0; k < count; ++k)
         if (fixed_image[k] < 0 || fixed_image[k] >= n_images || moving_image[k] < 0 || moving_image[k] >= n_images) return fail(CVO_ERR_INVALID, "image index out of range");
     int rc = batch_settle(b); if (rc) return rc;
     const PcdImgRec* R = nullptr;
-    if ((rc = batch_generate(b, n_images, bgr8, depth16, width, height, cam, nullptr, &R))) return rc;
+    if ((rc = batch_generate(b, n_images, src, width, height, cam, nullptr, &R))) return rc;
     // commit: the pairs take their clouds
     std::vector<Cloud*> dst; std::vector<int> img;
     for (int k = 0; k < count; ++k) {
@@ -2615,24 +2718,28 @@ int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, 
     if (points_out) for (int k = 0; k < n_images; ++k) points_out[k] = R[k].npts;
     return CVO_OK;
 }
-// ---- K-stream odometry: slot p is one cvo::cvo object that takes a frame per call (cvo_main's loop, cvo.cpp:352-386 + 461-473 + 578-582)
-int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
-                             const cvo_camera* cams, const int* cam_index, int* points_out) {
+int batch_check_images(cvo_batch b, int count, const int* slots, const ImageSrc& src, int width, int height, const cvo_camera* cams, const int* cam_index) {
     if (!b || count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad image count");
-    if (!slots || !bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
+    if (!slots || (!src.dev && (!src.bgr8 || !src.depth16)) || !cams) return fail(CVO_ERR_INVALID, "null argument");
     if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
     std::vector<unsigned char> seen(b->max_pairs, 0);
     for (int k = 0; k < count; ++k) {
         if (slots[k] < 0 || slots[k] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
         if (seen[slots[k]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
-        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+        if (!src.dev && (!src.bgr8[k] || !src.depth16[k])) return fail(CVO_ERR_INVALID, "null image pointer");
         if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
     }
-    int rc = batch_settle(b); if (rc) return rc;
+    return CVO_OK;
+}
+// ---- K-stream odometry: slot p is one cvo::cvo object that takes a frame per call (cvo_main's loop, cvo.cpp:352-386 + 461-473 + 578-582)
+int batch_advance_from(cvo_batch b, int count, const int* slots, const ImageSrc& src, int width, int height,
+                       const cvo_camera* cams, const int* cam_index, int* points_out) {
+    int rc = batch_check_images(b, count, slots, src, width, height, cams, cam_index); if (rc) return rc;
+    if ((rc = batch_settle(b))) return rc;
     std::vector<cvo_camera> cam_of(count);
     for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
     const PcdImgRec* R = nullptr;
-    if ((rc = batch_generate(b, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (fails before any slot changes)
+    if ((rc = batch_generate(b, count, src, width, height, nullptr, cam_of.data(), &R))) return rc;   // (fails before any slot changes)
     // commit.  A started slot's moving cloud becomes its fixed cloud by a move of ownership (update_fixed_pcd, cvo.cpp:578-582); the cloud object it
     // held as the fixed one is taken for the new moving cloud, whose points the scatter overwrites (its boxes and cached self products are dropped)
     std::vector<Cloud*> dst; std::vector<int> img;
@@ -2657,6 +2764,27 @@ int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const uns
     if (points_out) for (int k = 0; k < count; ++k) points_out[k] = R[k].npts;
     return CVO_OK;
 }
+}  // namespace
+int cvo_batch_set_pairs_images(cvo_batch b, int first, int count, int n_images, const unsigned char* const* bgr8, const unsigned short* const* depth16,
+                               int width, int height, const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out) {
+    return batch_set_pairs_from(b, first, count, n_images, ImageSrc::host(bgr8, depth16), width, height, cam, fixed_image, moving_image, points_out);
+}
+int cvo_batch_set_pairs_device_images(cvo_batch b, int first, int count, int n_images, const cvo_device_image* images, int width, int height,
+                                      const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out, void* image_stream) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    int rc = check_device_images(b->eng.device, n_images, images, width, height); if (rc) return rc;
+    return batch_set_pairs_from(b, first, count, n_images, ImageSrc::device(images, image_stream), width, height, cam, fixed_image, moving_image, points_out);
+}
+int cvo_batch_advance_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                             const cvo_camera* cams, const int* cam_index, int* points_out) {
+    return batch_advance_from(b, count, slots, ImageSrc::host(bgr8, depth16), width, height, cams, cam_index, points_out);
+}
+int cvo_batch_advance_device_images(cvo_batch b, int count, const int* slots, const cvo_device_image* images, int width, int height,
+                                    const cvo_camera* cams, const int* cam_index, int* points_out, void* image_stream) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    int rc = check_device_images(b->eng.device, count, images, width, height); if (rc) return rc;
+    return batch_advance_from(b, count, slots, ImageSrc::device(images, image_stream), width, height, cams, cam_index, points_out);
+}
 int cvo_batch_reset_stream(cvo_batch b, int p) {
     if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad slot index");
     int rc = batch_settle(b); if (rc) return rc;
@@ -2665,27 +2793,56 @@ int cvo_batch_reset_stream(cvo_batch b, int p) {
     fresh_stream(b, p);
     return CVO_OK;
 }
-namespace {
-int batch_check_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
-                       const cvo_camera* cams, const int* cam_index) {
-    if (!b || count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad image count");
-    if (!slots || !bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
-    if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
-    std::vector<unsigned char> seen(b->max_pairs, 0);
-    for (int k = 0; k < count; ++k) {
-        if (slots[k] < 0 || slots[k] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
-        if (seen[slots[k]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
-        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
-        if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
-    }
-    return CVO_OK;
-}
-}  // namespace
 // ---- the next frames of stream slots staged ahead: generated on a stream of the stage's own while a launch runs, taken by cvo_batch_advance_staged
 int cvo_batch_stage_images(cvo_batch b, int count, const int* slots, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
                            const cvo_camera* cams, const int* cam_index) {
-    int rc = batch_check_images(b, count, slots, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
-    return stage_begin(b, count, slots, bgr8, depth16, width, height, cams, cam_index);
+    const ImageSrc src = ImageSrc::host(bgr8, depth16);
+    int rc = batch_check_images(b, count, slots, src, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
+    return stage_begin(b, count, slots, src, width, height, cams, cam_index);
+}
+int cvo_batch_stage_device_images(cvo_batch b, int count, const int* slots, const cvo_device_image* images, int width, int height,
+                                  const cvo_camera* cams, const int* cam_index, void* image_stream) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    int rc = check_device_images(b->eng.device, count, images, width, height); if (rc) return rc;
+    const ImageSrc src = ImageSrc::device(images, image_stream);
+    if ((rc = batch_check_images(b, count, slots, src, width, height, cams, cam_index))) return rc;
+    return stage_begin(b, count, slots, src, width, height, cams, cam_index);
+}
+int cvo_check_device_images(int device, int count, const cvo_device_image* images, int width, int height) {
+    return check_device_images(device, count, images, width, height);
+}
+// The ingest kernel alone (tests): `count` images into packed stacks that lie between guard bytes; the stacks and the guards' state come back.
+int cvo_selftest_ingest_images(int device, int count, const cvo_device_image* images, int width, int height, unsigned char* bgr_out, unsigned short* depth_out,
+                               int* guards_intact) {
+    if (!bgr_out || !depth_out || !guards_intact) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = check_device_images(device, count, images, width, height); if (rc) return rc;
+    constexpr size_t G = 64;
+    const size_t n = (size_t)width * height, nb = 3 * n * count, nd = 2 * n * count;
+    DevBuf bb, db;
+    BatchImages T; T.n_cap = count;                                   // (only the ingest's table and events; the stacks start behind the front guards)
+    struct Release { DevBuf& bb; DevBuf& db; BatchImages& T; ~Release() { T.bgr.p = nullptr; T.depth.p = nullptr; T.release(); bb.release(); db.release(); } } release{bb, db, T};
+    if ((rc = bb.ensure(nb + 2 * G)) || (rc = db.ensure(nd + 2 * G))) return rc;
+    HIP_TRY(hipMemset(bb.p, 0xA5, nb + 2 * G));
+    HIP_TRY(hipMemset(db.p, 0xA5, nd + 2 * G));
+    HIP_TRY(hipDeviceSynchronize());
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    struct Close { hipStream_t s; ~Close() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } close_{s};
+    unsigned char* b0 = static_cast<unsigned char*>(bb.p); unsigned char* d0 = static_cast<unsigned char*>(db.p);
+    T.bgr.p = b0 + G; T.depth.p = d0 + G;
+    ImageSrc src; src.dev = images;
+    if ((rc = ingest_enqueue(T, s, count, src, width, height))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<unsigned char> gb(2 * G), gd(2 * G);
+    HIP_TRY(hipMemcpy(bgr_out, b0 + G, nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(depth_out, d0 + G, nd, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(gb.data(), b0, G, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(gb.data() + G, b0 + G + nb, G, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(gd.data(), d0, G, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(gd.data() + G, d0 + G + nd, G, hipMemcpyDeviceToHost));
+    int ok = 1;
+    for (unsigned char v : gb) ok &= v == 0xA5;
+    for (unsigned char v : gd) ok &= v == 0xA5;
+    *guards_intact = ok;
+    return CVO_OK;
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");
@@ -3194,13 +3351,13 @@ int cvo_tracks_reset(cvo_tracks t, int s) {
 }
 namespace {
 // what a step checks about its arguments (a stage call checks the same)
-int tracks_check_images(cvo_tracks_s* t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+int tracks_check_images(cvo_tracks_s* t, int count, const int* streams, const ImageSrc& src, int width, int height,
                         const cvo_camera* cams, const int* cam_index) {
     int rc = tracks_check_list(t, count, streams); if (rc) return rc;
-    if (!bgr8 || !depth16 || !cams) return fail(CVO_ERR_INVALID, "null argument");
+    if ((!src.dev && (!src.bgr8 || !src.depth16)) || !cams) return fail(CVO_ERR_INVALID, "null argument");
     if (!image_size_ok(width, height)) return fail(CVO_ERR_INVALID, "image size out of range");
     for (int k = 0; k < count; ++k) {
-        if (!bgr8[k] || !depth16[k]) return fail(CVO_ERR_INVALID, "null image pointer");
+        if (!src.dev && (!src.bgr8[k] || !src.depth16[k])) return fail(CVO_ERR_INVALID, "null image pointer");
         if (cam_index && cam_index[k] < 0) return fail(CVO_ERR_INVALID, "camera index out of range");
     }
     return CVO_OK;
@@ -3269,26 +3426,45 @@ int tracks_step_run(cvo_tracks_s* t, int count, const int* streams, const int* n
     // ONE keyframe launch over the phase-2 streams, behind the link kernel on the same stream
     return batch_launch(bk, slots_key.data(), t->n_key, hs, false);
 }
-}  // namespace
-int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
-                          const cvo_camera* cams, const int* cam_index, void* hip_stream) {
-    int rc = tracks_check_images(t, count, streams, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;
+int tracks_step_from(cvo_tracks_s* t, int count, const int* streams, const ImageSrc& src, int width, int height,
+                     const cvo_camera* cams, const int* cam_index, void* hip_stream) {
+    int rc = tracks_check_images(t, count, streams, src, width, height, cams, cam_index); if (rc) return rc;
     if ((rc = tracks_check_state(t, count, streams))) return rc;
     cvo_batch bo = t->odo, bk = t->key;
     if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
     std::vector<cvo_camera> cam_of(count);
     for (int k = 0; k < count; ++k) cam_of[k] = cams[cam_index ? cam_index[k] : 0];
     const PcdImgRec* R = nullptr;
-    if ((rc = batch_generate(bo, count, bgr8, depth16, width, height, nullptr, cam_of.data(), &R))) return rc;   // (the step's one host sync; fails before any stream changes)
+    if ((rc = batch_generate(bo, count, src, width, height, nullptr, cam_of.data(), &R))) return rc;   // (the step's one host sync; fails before any stream changes)
     std::vector<int> npts(count);
     for (int k = 0; k < count; ++k) npts[k] = R[k].npts;
     return tracks_step_run(t, count, streams, npts.data(), nullptr, R, hip_stream);
 }
+}  // namespace
+int cvo_tracks_step_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
+                          const cvo_camera* cams, const int* cam_index, void* hip_stream) {
+    return tracks_step_from(t, count, streams, ImageSrc::host(bgr8, depth16), width, height, cams, cam_index, hip_stream);
+}
+int cvo_tracks_step_device_async(cvo_tracks t, int count, const int* streams, const cvo_device_image* images, int width, int height,
+                                 const cvo_camera* cams, const int* cam_index, void* hip_stream, void* image_stream) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    int rc = check_device_images(t->odo->eng.device, count, images, width, height); if (rc) return rc;
+    return tracks_step_from(t, count, streams, ImageSrc::device(images, image_stream), width, height, cams, cam_index, hip_stream);
+}
 // ---- the next step's frames staged ahead: generated on the stage's own stream while the current step's launches run
 int cvo_tracks_stage_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,
                            const cvo_camera* cams, const int* cam_index) {
-    int rc = tracks_check_images(t, count, streams, bgr8, depth16, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
-    return stage_begin(t->odo, count, streams, bgr8, depth16, width, height, cams, cam_index);
+    const ImageSrc src = ImageSrc::host(bgr8, depth16);
+    int rc = tracks_check_images(t, count, streams, src, width, height, cams, cam_index); if (rc) return rc;   // (an earlier stage survives a refused call)
+    return stage_begin(t->odo, count, streams, src, width, height, cams, cam_index);
+}
+int cvo_tracks_stage_device_async(cvo_tracks t, int count, const int* streams, const cvo_device_image* images, int width, int height,
+                                  const cvo_camera* cams, const int* cam_index, void* image_stream) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    int rc = check_device_images(t->odo->eng.device, count, images, width, height); if (rc) return rc;
+    const ImageSrc src = ImageSrc::device(images, image_stream);
+    if ((rc = tracks_check_images(t, count, streams, src, width, height, cams, cam_index))) return rc;
+    return stage_begin(t->odo, count, streams, src, width, height, cams, cam_index);
 }
 int cvo_tracks_step_staged_async(cvo_tracks t, void* hip_stream) {
     if (!t) return fail(CVO_ERR_INVALID, "null tracks");

@@ -223,6 +223,17 @@ struct PcdScatter {
     int img[PCD_SCATTER_MAX]; float* dst[PCD_SCATTER_MAX]; uint16_t* dst_px[PCD_SCATTER_MAX];
 };
 
+// a caller-owned device image gathered into the generator's packed stacks (pcd_ingest_images_kernel): one descriptor per image, the
+// pitches resolved (never 0) and the two read paths decided on the host from these fields alone
+struct PcdIngestDesc {
+    const uint8_t* bgr;      // pixel (x, y) at bgr + y * bgr_pitch + x * pixel_bytes
+    const uint8_t* depth;    // uint16 (x, y) at depth + y * depth_pitch + 2 * x
+    long long bgr_pitch, depth_pitch;
+    int pixel_bytes, swap_rb;
+    int bgr_dwords, depth_dwords;   // base and pitch are multiples of 4: the plane's rows are read as whole dwords (their last, partial dword as bytes)
+};
+static_assert(sizeof(PcdIngestDesc) == 48, "PcdIngestDesc layout");
+
 // the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
 struct BoxDesc {
     const float* rec;        // the cloud's two planes of n float4

@@ -143,6 +143,20 @@ public:
                      const cvo_camera* cams, const int* cam_index = nullptr) {
         check(cvo_tracks_stage_async(t_, count, streams, bgr8, depth16, width, height, cams, cam_index), "stage_async");
     }
+    // the same three for frames in caller-owned device memory (cvo_device_image in include/cvo_hip.h: what is checked, and how image_stream orders
+    // the images' writer against the library's ingest; null = already synchronised, the call waits on the host for the ingest alone)
+    void step_async(int count, const int* streams, const cvo_device_image* images, int width, int height, const cvo_camera* cams,
+                    const int* cam_index = nullptr, void* hip_stream = nullptr, void* image_stream = nullptr) {
+        check(cvo_tracks_step_device_async(t_, count, streams, images, width, height, cams, cam_index, hip_stream, image_stream), "step_async");
+    }
+    void stage_async(int count, const int* streams, const cvo_device_image* images, int width, int height, const cvo_camera* cams,
+                     const int* cam_index = nullptr, void* image_stream = nullptr) {
+        check(cvo_tracks_stage_device_async(t_, count, streams, images, width, height, cams, cam_index, image_stream), "stage_async");
+    }
+    void step(int count, const int* streams, const cvo_device_image* images, int width, int height, const cvo_camera* cams, const int* cam_index,
+              cvo_track_step* out, void* image_stream = nullptr) {
+        step_async(count, streams, images, width, height, cams, cam_index, nullptr, image_stream); wait(out, count);
+    }
     void step_staged_async(void* hip_stream = nullptr) { check(cvo_tracks_step_staged_async(t_, hip_stream), "step_staged_async"); }
     int staged_count(long long* taken = nullptr) { int n = 0; check(cvo_tracks_staged_count(t_, &n, taken), "staged_count"); return n; }
     bool done() { int d = 0; check(cvo_tracks_done(t_, &d), "done"); return d != 0; }

@@ -355,6 +355,74 @@ __global__ __launch_bounds__(256) void pcd_scatter_kernel(PcdScatter S) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < np; i += gridDim.x * 256) dpx[i] = spx[i];
 }
 
+// ---- caller-owned device images into the generator's packed stacks (cvo_*_device_images, cvo_tracks_*_device_async): image k's colour plane
+// to bgr_stack + 3 n k (B, G, R per pixel), its depth plane to depth_stack + 2 n k bytes, n = w * h.  Both planes are one gather of bytes:
+// output byte j of a plane with `ob` output bytes per pixel (3 / 2) comes from pixel p = j / ob, (x, y) = (p % w, p / w), source byte
+// y * pitch + x * pb + c (pb source bytes per pixel, c = j % ob, mirrored for swap_rb).  A lane owns one 16-byte-aligned piece of the output,
+// consecutive lanes consecutive pieces: a piece that lies wholly inside the image's plane is one 16-byte store, the plane's head and tail
+// pieces (3 n k is a multiple of 16 for few k) are stored byte by byte.  A source whose base and pitch are multiples of 4 is read as whole
+// dwords, each fetched once per lane; the last dword of a row, when the row's bytes end inside it, and every other source is read as bytes:
+// nothing outside [row start, row start + w * pb) is touched.  Which path an image takes follows from its descriptor alone (wave-uniform).
+__device__ __forceinline__ unsigned ingest_byte(const uint8_t* row, unsigned off, unsigned row_bytes, bool dwords, unsigned& at, unsigned& v) {
+    if (!dwords) return row[off];
+    const unsigned o4 = off & ~3u;
+    if (o4 != at) {
+        at = o4;
+        if (o4 + 4 <= row_bytes) v = *reinterpret_cast<const unsigned*>(row + o4);
+        else { v = 0; for (unsigned q = 0; o4 + q < row_bytes; ++q) v |= (unsigned)row[o4 + q] << (8 * q); }
+    }
+    return (v >> (8 * (off & 3u))) & 0xffu;
+}
+// grid: (pieces of the colour plane + pieces of the depth plane, images); pieces_* = the plane's bytes / 16 rounded up, + 1 for a plane that
+// starts inside a piece
+__global__ __launch_bounds__(256) void pcd_ingest_images_kernel(const PcdIngestDesc* __restrict__ descs, uint8_t* __restrict__ bgr_stack,
+                                                                uint8_t* __restrict__ depth_stack, int w, unsigned n, unsigned pieces_bgr, unsigned pieces_depth) {
+    const unsigned k = blockIdx.y;
+    unsigned t = blockIdx.x * 256u + threadIdx.x;
+    const bool is_depth = t >= pieces_bgr;
+    if (is_depth) { t -= pieces_bgr; if (t >= pieces_depth) return; }
+    const PcdIngestDesc D = descs[k];
+    const unsigned ob = is_depth ? 2u : 3u, pb = is_depth ? 2u : (unsigned)D.pixel_bytes;
+    const bool swap = !is_depth && D.swap_rb != 0, dwords = (is_depth ? D.depth_dwords : D.bgr_dwords) != 0;
+    const long long pitch = is_depth ? D.depth_pitch : D.bgr_pitch;
+    const uint8_t* src = is_depth ? D.depth : D.bgr;
+    uint8_t* out = (is_depth ? depth_stack : bgr_stack) + (size_t)ob * n * k;
+    const unsigned len = ob * n, row_bytes = pb * (unsigned)w;
+    // the piece: 16 bytes at a 16-byte-aligned address, [lo, hi) of it inside the plane (byte offsets from the plane's start; lo0 may lie before it)
+    const long long lo0 = 16ll * t - (long long)(reinterpret_cast<uintptr_t>(out) & 15u);
+    if (lo0 >= (long long)len) return;
+    const unsigned lo = lo0 < 0 ? 0u : (unsigned)lo0, hi = lo0 + 16 > (long long)len ? len : (unsigned)(lo0 + 16);
+    const unsigned p = lo / ob;
+    unsigned c = lo - p * ob, y = p / (unsigned)w, x = p - y * (unsigned)w;
+    const uint8_t* row = src + (long long)y * pitch;
+    unsigned at = 0xffffffffu, v = 0, word[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const long long j = lo0 + q;
+        if (j >= (long long)lo && j < (long long)hi) {
+            const unsigned byte = ingest_byte(row, x * pb + (swap ? 2u - c : c), row_bytes, dwords, at, v);
+            word[q >> 2] |= byte << (8 * (q & 3));
+            if (++c == ob) { c = 0; if (++x == (unsigned)w) { x = 0; row += pitch; at = 0xffffffffu; } }
+        }
+    }
+    if (hi - lo == 16u) {
+        *reinterpret_cast<uint4*>(out + lo) = make_uint4(word[0], word[1], word[2], word[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const long long j = lo0 + q;
+            if (j >= (long long)lo && j < (long long)hi) out[j] = (uint8_t)(word[q >> 2] >> (8 * (q & 3)));
+        }
+    }
+}
+hipError_t pcd_launch_ingest(const PcdIngestDesc* descs, uint8_t* bgr_stack, uint8_t* depth_stack, int w, int h, int n_img, hipStream_t s) {
+    const unsigned n = (unsigned)w * (unsigned)h;
+    const unsigned pieces_bgr = (3u * n + 15u) / 16u + 1u, pieces_depth = (2u * n + 15u) / 16u + 1u;
+    hipLaunchKernelGGL(pcd_ingest_images_kernel, dim3((pieces_bgr + pieces_depth + 255u) / 256u, n_img), dim3(256), 0, s, descs, bgr_stack, depth_stack, w, n,
+                       pieces_bgr, pieces_depth);
+    return hipGetLastError();
+}
+
 // cloud planes back to the reference layout (tests, get_*_selected_points callers)
 __global__ void pcd_unpack_kernel(const float* __restrict__ cloud, int n, float* __restrict__ xyz, float* __restrict__ feat) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -263,16 +263,37 @@ def stage_plan(plan):
     return [list(plan[j + 1]["advance"]) if j + 1 < len(plan) else [] for j in range(len(plan))]
 
 
-def group_by_size(items, size_of):
-    """items grouped by size_of(item), in the order the sizes first occur: one advance call per image size (cvo_batch_advance_images takes one size)."""
+def frame_size(frame):
+    """(h, w) of a (bgr8, depth16) frame from its depth image's .shape: numpy arrays and device tensors alike, nothing is converted or copied"""
+    d = frame[1]
+    return tuple(int(v) for v in (d.shape if hasattr(d, "shape") else np.asarray(d).shape))
+
+
+def group_by_size(items, size_of=None):
+    """items grouped by size_of(item) (default: the item's own .shape), in the order the sizes first occur: one advance call per image size
+    (cvo_batch_advance_images takes one size)."""
+    if size_of is None:
+        size_of = lambda it: tuple(int(v) for v in it.shape)
     groups = {}
     for it in items:
         groups.setdefault(size_of(it), []).append(it)
     return list(groups.values())
 
 
+def frames_to_device(sequences, device: int = 0):
+    """Every frame of every sequence uploaded ONCE, as torch tensors on GPU `device` (torch is imported here, not by the package): the same
+    nesting as `sequences`, each frame a (uint8 (h, w, 3), int16 (h, w)) pair of tensors -- the depth bits reinterpreted, which the device entry
+    points take as they are.  What `replay_odometry_many` / `replay_tracker_many` are given then never passes through host memory again."""
+    import torch
+    dev = torch.device("cuda", device)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt).copy()).to(dev)
+    out = [[(up(b, np.uint8), up(d, np.int16)) for b, d in seq] for seq in sequences]
+    torch.cuda.synchronize(dev)
+    return out
+
+
 def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None,
-                         stage_ahead: bool = False):
+                         stage_ahead: bool = False, swap_rb: bool = False, image_stream=None):
     """`replay_odometry` for many sequences at once on one CvoBatch: each slot is one odometry object (cvo_batch_advance_images), every step
     advances each running sequence by one frame -- one advance call per image size -- and aligns all of them in ONE launch
     (cvo_batch_align_pairs_async).  sequences[i]: a sequence of (bgr8, depth16) frames (len() and indexing; frames are read in order, once);
@@ -280,7 +301,9 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
     cvo_batch_reset_stream); starts: the step each sequence may start at (plan_replay).  Returns [(poses, info), ...], per sequence what
     `replay_odometry` returns for it alone (poses chained on the host the same way).  A failed alignment raises CvoError as it does there.
     stage_ahead: the frames of step j + 1 (`stage_plan`) are handed over right after step j's launch is queued and generated while it runs
-    (cvo_batch_stage_images / cvo_batch_advance_staged) -- when they are of one image size; the results are the same bits."""
+    (cvo_batch_stage_images / cvo_batch_advance_staged) -- when they are of one image size; the results are the same bits.
+    Frames in device memory (`frames_to_device`, or anything with __cuda_array_interface__) are read where they are: swap_rb and image_stream
+    go to every image call as CvoBatch.advance_images documents them."""
     import cvo_slam_amd as ca
     from .api import CVO_OK, CvoError
     n_seq = len(sequences)
@@ -296,6 +319,7 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
         pose = [np.eye(4) for _ in range(n_seq)]
         ahead = stage_plan(plan) if stage_ahead else [[] for _ in plan]
         staged = None                                               # the list staged for the step to come
+        how = dict(swap_rb=swap_rb, image_stream=image_stream)
         for j, st in enumerate(plan):
             for p in st["resets"]:
                 B.reset_stream(p)
@@ -304,14 +328,14 @@ def replay_odometry_many(sequences, cameras, params=None, device: int = 0, num_w
                 points.update({a: int(n) for a, n in zip(staged, B.advance_staged())})
             else:
                 frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
-                for grp in group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape):
-                    pts = B.advance_images(*_image_call(grp, frames, cameras))
+                for grp in group_by_size(st["advance"], lambda a: frame_size(frames[a])):
+                    pts = B.advance_images(*_image_call(grp, frames, cameras), **how)
                     points.update({a: int(n) for a, n in zip(grp, pts)})
             for a in st["advance"]:
                 if a[2] == 0:                                       # cvo.cpp:352-360: the first frame only fills the fixed cloud
                     out[a[1]][0].append(pose[a[1]].copy()); out[a[1]][1].append(dict(iterations=0, nnz=0, points=points[a]))
             n_launched = B.align_pairs_async([p for p, _, _ in st["align"]]) if st["align"] else 0
-            staged = _stage_next(B.stage_images, ahead[j], sequences, cameras)   # generated while the launch runs
+            staged = _stage_next(B.stage_images, ahead[j], sequences, cameras, how)   # generated while the launch runs
             if not st["align"]:
                 continue
             res = B.wait(n_launched)
@@ -334,14 +358,14 @@ def _image_call(grp, frames, cameras):
     return [p for p, _, _ in grp], [frames[a] for a in grp], uniq, [uniq.index(c) for c in cams]
 
 
-def _stage_next(stage, entries, sequences, cameras):
+def _stage_next(stage, entries, sequences, cameras, how):
     """stage(...) the frames of `entries` (a list of stage_plan) when there are any and they are of one image size; returns what was staged, or None"""
     if not entries:
         return None
     frames = {(p, i, f): sequences[i][f] for p, i, f in entries}
-    if len(group_by_size(entries, lambda a: np.asarray(frames[a][1]).shape)) != 1:
+    if len(group_by_size(entries, lambda a: frame_size(frames[a]))) != 1:
         return None                                                 # (one stage holds one image size: such a step is generated by its own calls)
-    stage(*_image_call(entries, frames, cameras))
+    stage(*_image_call(entries, frames, cameras), **how)
     return list(entries)
 
 
@@ -469,7 +493,7 @@ def replay_tracker(frames, camera, accept, params=None, device: int = 0, num_wan
 
 
 def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0, num_want: int = 3000, arith="base", slots=None, starts=None,
-                        stage_ahead: bool = False):
+                        stage_ahead: bool = False, swap_rb: bool = False, image_stream=None):
     """`replay_tracker` for many sequences at once on one CvoTracks (cvo_tracks_*): each stream is the pair of objects of one sequence, every step
     advances each running sequence by one frame -- one cvo_tracks_step per image size: generation, one odometry launch, reset_initial on the device,
     one keyframe launch -- and hands the caller's decisions back with cvo_tracks_commit.  Scheduled by `plan_replay` (slots: the object's streams,
@@ -478,7 +502,8 @@ def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0
     sequence's index.  Returns [(poses, steps, decisions), ...], per sequence what `replay_tracker` returns for it alone: the same bits, poses
     chained on the host the same way (no optimiser).  stage_ahead: the frames of step j + 1 (`stage_plan`) are handed over right after step j is
     queued and before it is waited for (cvo_tracks_stage_async), and step j + 1 starts its launches without generating anything
-    (cvo_tracks_step_staged_async) -- when they are of one image size; the results are the same bits."""
+    (cvo_tracks_step_staged_async) -- when they are of one image size; the results are the same bits.  Frames in device memory
+    (`frames_to_device`) are read where they are; swap_rb and image_stream go to every image call as CvoTracks.step_async documents them."""
     import cvo_slam_amd as ca
     n_seq = len(sequences)
     if len(cameras) != n_seq:
@@ -492,6 +517,7 @@ def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0
         T.set_arith_mode(arith)
         ahead = stage_plan(plan) if stage_ahead else [[] for _ in plan]
         staged = None                                               # the list staged for the step to come
+        how = dict(swap_rb=swap_rb, image_stream=image_stream)
         for j, st in enumerate(plan):
             for p in st["resets"]:
                 T.reset(p)
@@ -500,14 +526,14 @@ def replay_tracker_many(sequences, cameras, accept, params=None, device: int = 0
                 groups = [staged]
             else:
                 frames = {(p, i, f): sequences[i][f] for p, i, f in st["advance"]}
-                groups = group_by_size(st["advance"], lambda a: np.asarray(frames[a][1]).shape)
+                groups = group_by_size(st["advance"], lambda a: frame_size(frames[a]))
             for g, grp in enumerate(groups):
                 if consume:
                     T.step_staged_async()
                 else:
-                    T.step_async(*_image_call(grp, frames, cameras))
+                    T.step_async(*_image_call(grp, frames, cameras), **how)
                 if g == len(groups) - 1:
-                    staged = _stage_next(T.stage_async, ahead[j], sequences, cameras)   # generated while the step runs
+                    staged = _stage_next(T.stage_async, ahead[j], sequences, cameras, how)   # generated while the step runs
                 res = T.wait()
                 who, what = [], []
                 for (p, i, f), r in zip(grp, res):

@@ -389,6 +389,54 @@ int cvo_batch_stage_images(cvo_batch b, int count, const int* slots, const unsig
                            int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */);
 int cvo_batch_advance_staged(cvo_batch b, int* points_out /* may be NULL, one int per staged image */);
 int cvo_batch_staged_count(cvo_batch b, int* images /* may be NULL */, long long* taken /* may be NULL */);
+
+/* ---- Frames that are already on the GPU (a decoder, a camera pipeline, a simulator, a torch tensor): the device twins of the image entry
+ * points read caller-owned device memory, so nothing is copied to the host and back.  A call takes `count` descriptors, one per image, in
+ * place of the two pointer arrays; everything else -- arguments, checks, results, the stage -- is its host twin's.  One kernel launch per
+ * call (pcd_ingest_images_kernel) gathers all images into the generator's packed stacks; from there on the host twin's code runs, and every
+ * result is bit-identical to the host twin given the same pixel values.
+ *
+ * Validation.  Every device entry point first runs the check that cvo_check_device_images runs alone, before any slot or stream changes
+ * and before anything is queued: CVO_ERR_INVALID, the message naming image and field, for a null pointer, pixel_bytes not 3 or 4, swap_rb
+ * not 0 or 1, a negative pitch or one below the row's bytes, depth16 or depth_pitch not 2-byte aligned, the size limits of the host twin,
+ * and a pointer the device cannot read: hipPointerGetAttributes must report device memory of the object's device (and the image's rows,
+ * [ptr, ptr + (height-1)*pitch + row bytes), must lie inside that allocation), managed memory, or pinned / registered host memory.  Pageable
+ * host memory and memory of another device are refused and never reach a kernel.  The kernel reads nothing outside the rows: a row may end
+ * where its allocation ends.
+ *
+ * Ordering.  The ingest ALWAYS runs on a stream of the library's own (the stage's high-priority stream for the stage calls, the object's
+ * stream otherwise), never on the caller's: HIP deals streams of equal priority onto a few hardware queues, and a caller's stream that
+ * shares the queue of a running align launch would not start before that launch ends.  image_stream says how the images' writer is ordered:
+ *   image_stream != NULL: the library records an event on image_stream and its stream waits for it; behind the ingest it records a second
+ *     event that image_stream waits for.  No host wait.  The images are the caller's again for any work queued on image_stream after the
+ *     call has returned (work on other streams must be ordered behind image_stream by the caller).
+ *   image_stream == NULL: the caller has already synchronised whatever wrote the images; the call waits on the host for the ingest alone
+ *     (not for the generator) before it returns, and the images are the caller's again then.
+ * The HIP null stream is handle 0, i.e. NULL: it cannot be named here and gets the host-waited form.  torch's default stream on ROCm is
+ * that stream, so frames written on torch's default stream are passed with image_stream NULL after a synchronize of that stream; a
+ * torch side stream (torch.cuda.Stream().cuda_stream) can be passed as image_stream. */
+typedef struct cvo_device_image {
+    const void* bgr8;        /* device-accessible; pixel (x, y) at bgr8 + y*bgr_pitch + x*pixel_bytes: bytes B, G, R (swap_rb: R, G, B); a 4th byte is ignored */
+    const void* depth16;     /* device-accessible; uint16 at depth16 + y*depth_pitch + 2*x */
+    long long bgr_pitch;     /* bytes per row; 0 = tight (width*pixel_bytes) */
+    long long depth_pitch;   /* bytes per row; 0 = tight (2*width) */
+    int pixel_bytes;         /* 3 or 4 */
+    int swap_rb;             /* 0 / 1 */
+} cvo_device_image;
+int cvo_check_device_images(int device, int count, const cvo_device_image* images, int width, int height);   /* the validation alone: launches nothing */
+int cvo_batch_set_pairs_device_images(cvo_batch b, int first, int count, int n_images, const cvo_device_image* images, int width, int height,
+                                      const cvo_camera* cam, const int* fixed_image, const int* moving_image, int* points_out /* may be NULL */,
+                                      void* image_stream);
+int cvo_batch_advance_device_images(cvo_batch b, int count, const int* slots, const cvo_device_image* images, int width, int height,
+                                    const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, int* points_out /* may be NULL */,
+                                    void* image_stream);
+/* the ONE stage of the batch: replaces an unconsumed stage of either kind; cvo_batch_advance_staged consumes either kind, cvo_batch_staged_count counts both */
+int cvo_batch_stage_device_images(cvo_batch b, int count, const int* slots, const cvo_device_image* images, int width, int height,
+                                  const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* image_stream);
+/* The ingest kernel alone (tests): `count` images gathered into packed stacks that lie between 64 guard bytes on either side, prefilled with
+ * 0xA5.  bgr_out: count*3*width*height bytes, depth_out: count*width*height uint16; *guards_intact = 1 when no guard byte changed. */
+int cvo_selftest_ingest_images(int device, int count, const cvo_device_image* images, int width, int height, unsigned char* bgr_out,
+                               unsigned short* depth_out, int* guards_intact);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
@@ -645,6 +693,12 @@ int cvo_tracks_stage_async(cvo_tracks t, int count, const int* streams, const un
                            int width, int height, const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */);
 int cvo_tracks_step_staged_async(cvo_tracks t, void* hip_stream);
 int cvo_tracks_staged_count(cvo_tracks t, int* images /* may be NULL */, long long* taken /* may be NULL */);
+/* The device twins (see cvo_device_image above for validation and ordering): the step's or the stage's frames read from caller-owned device memory.
+ * A refused call changes no stream and keeps the stage.  cvo_tracks_step_staged_async consumes a stage of either kind. */
+int cvo_tracks_step_device_async(cvo_tracks t, int count, const int* streams, const cvo_device_image* images, int width, int height,
+                                 const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* hip_stream, void* image_stream);
+int cvo_tracks_stage_device_async(cvo_tracks t, int count, const int* streams, const cvo_device_image* images, int width, int height,
+                                  const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* image_stream);
 int cvo_tracks_done(cvo_tracks t, int* done);
 int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out /* may be NULL */, int count);
 int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept);

@@ -3,7 +3,9 @@
 ONE cvo_batch_align_pairs_async per step) against the same K sequences replayed one after the other by a handle each (set_pcd_images,
 match_odometry_images, update_fixed_pcd per frame: the replay_odometry loop), in one process, on in-memory synthetic 640 x 480 frames.
 Beside the batch there is a staged row: the same steps with the frames of step f + 1 handed over while step f's launch runs
-(cvo_batch_stage_images / cvo_batch_advance_staged), on the same object.  Every configuration is warmed up once, then timed `--runs` times
+(cvo_batch_stage_images / cvo_batch_advance_staged), on the same object, and a `device` and a `device staged` row: the same two loops on
+frames that are already on the GPU (replay.frames_to_device: every frame uploaded ONCE, before anything is timed), handed to
+cvo_batch_advance_device_images / cvo_batch_stage_device_images with a side torch stream (high priority) as image_stream.  Every configuration is warmed up once, then timed `--runs` times
 (each run ends with a device synchronise), the runs of the configurations interleaved; the median and the spread (min .. max) are printed
 per K, one JSON line at the end, and with --out the table is written to that file.
 
@@ -28,40 +30,50 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=6, help="frames per sequence")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic sequences; stream s replays sequence s mod pool")
+    ap.add_argument("--host-only", action="store_true", help="leave the two device rows out (a library without the device entry points)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     import torch
     import cvo_slam_amd as ca
-    from cvo_slam_amd import synth
+    from cvo_slam_amd import replay, synth
     ks = [int(k) for k in a.streams.split(",")]
     pool = [synth.make_sequence(60 + i, n_frames=a.frames)[0] for i in range(a.pool)]
     cam = synth.camera_tuple(synth.TUM1)
     sync = lambda: torch.cuda.synchronize(a.device)
 
-    def batched(K, B):
-        seq = [pool[s % a.pool] for s in range(K)]
+    dpool = None if a.host_only else replay.frames_to_device(pool, a.device)   # uploaded once, outside every timed run
+    side = None if a.host_only else torch.cuda.Stream(a.device, priority=-1)
+
+    def batched(K, B, frames=None, how={}):
+        seq = [(frames or pool)[s % a.pool] for s in range(K)]
         for s in range(K):
             B.reset_stream(s)
         for f in range(a.frames):
-            B.advance_images(range(K), [q[f] for q in seq], [cam])
+            B.advance_images(range(K), [q[f] for q in seq], [cam], **how)
             if f:
                 r = B.align_pairs(range(K))
                 assert all(x["status"] == 0 for x in r)
 
-    def staged(K, B):
-        seq = [pool[s % a.pool] for s in range(K)]
+    def staged(K, B, frames=None, how={}):
+        seq = [(frames or pool)[s % a.pool] for s in range(K)]
         for s in range(K):
             B.reset_stream(s)
-        B.advance_images(range(K), [q[0] for q in seq], [cam])
+        B.advance_images(range(K), [q[0] for q in seq], [cam], **how)
         for f in range(a.frames):
             n = B.align_pairs_async(range(K)) if f else 0
             if f + 1 < a.frames:
-                B.stage_images(range(K), [q[f + 1] for q in seq], [cam])   # generated while the launch runs
+                B.stage_images(range(K), [q[f + 1] for q in seq], [cam], **how)   # generated while the launch runs
             if f:
                 assert all(x["status"] == 0 for x in B.wait(n))
             if f + 1 < a.frames:
                 B.advance_staged()
+
+    def device(K, B):
+        batched(K, B, dpool, dict(image_stream=side))
+
+    def device_staged(K, B):
+        staged(K, B, dpool, dict(image_stream=side))
 
     def handles(K, _):
         for s in range(K):
@@ -72,10 +84,11 @@ def main(argv=None):
                 g.match_odometry_images(*fr[f], cam); g.update_fixed_pcd()
             g.close()
 
-    res, lines = {}, [f"sequence streams: {a.frames} frames per sequence, 640 x 480, {a.runs} runs interleaved (median, min .. max)"]
+    res, lines = {}, [f"sequence streams: {a.frames} frames per sequence, 640 x 480, {a.runs} runs interleaved (median, min .. max)",
+                  "device rows: every frame uploaded once before the timed runs (no upload is timed); image_stream = a high-priority side torch stream"][:1 if a.host_only else 2]
     for K in ks:
         B = ca.CvoBatch(K, device=a.device)
-        fns = (("batch", batched), ("staged", staged), ("handles", handles))
+        fns = (("batch", batched), ("staged", staged)) + ((), (("device", device), ("device_staged", device_staged)))[not a.host_only] + (("handles", handles),)
         t = {name: [] for name, _ in fns}
         for name, fn in fns:
             fn(K, B); sync()                                          # warm-up
@@ -90,7 +103,9 @@ def main(argv=None):
         row["speedup"] = row["batch"]["fps_median"] / row["handles"]["fps_median"]
         res[K] = row
         cell = lambda r: f"{r['fps_median']:8.1f} frames/s ({r['fps_min']:.1f} .. {r['fps_max']:.1f})"
-        lines.append(f"K={K:3d}: batch {cell(row['batch'])}, staged {cell(row['staged'])} x{row['staged']['fps_median'] / row['batch']['fps_median']:.3f}, "
+        rel = lambda name: f"x{row[name]['fps_median'] / row['batch']['fps_median']:.3f}"
+        dev = "" if a.host_only else f"device {cell(row['device'])} {rel('device')}, device staged {cell(row['device_staged'])} {rel('device_staged')}, "
+        lines.append(f"K={K:3d}: batch {cell(row['batch'])}, staged {cell(row['staged'])} {rel('staged')}, {dev}"
                      f"handles {cell(row['handles'])}, batch x{row['speedup']:.2f} the handles")
         print(lines[-1], flush=True)
     print(json.dumps(dict(bench="sequence_replay", frames=a.frames, runs=a.runs, results=res)))

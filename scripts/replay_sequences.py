@@ -5,7 +5,7 @@ one trajectory per sequence in the format of scripts/replay_sequence.py (`timest
 The list file has one sequence per line, `folder assoc calib [out]` (whitespace-separated; `#` starts a comment); relative paths are taken from
 the list file's directory.  Without `out` the trajectory goes to <--out-dir or the list file's directory>/<folder name>.txt.
 
-    python scripts/replay_sequences.py sequences.txt --slots 16 [--arith eigen337] [--max-frames N] [--out-dir DIR]
+    python scripts/replay_sequences.py sequences.txt --slots 16 [--arith eigen337] [--max-frames N] [--out-dir DIR] [--stage-ahead] [--device-frames]
 """
 from __future__ import annotations
 
@@ -58,6 +58,8 @@ def main(argv=None):
     ap.add_argument("--max-frames", type=int, default=0, help="replay at most this many frames of every sequence (0 = all)")
     ap.add_argument("--out-dir", default=None, help="where trajectories without an `out` column go (default: beside the list file)")
     ap.add_argument("--stage-ahead", action="store_true", help="hand the frames of step f + 1 over while step f runs (the same results)")
+    ap.add_argument("--device-frames", action="store_true",
+                    help="upload every frame to the GPU first (torch) and replay from device memory: the same results, no host intake per step")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     from cvo_slam_amd import replay
@@ -68,6 +70,8 @@ def main(argv=None):
         if a.max_frames > 0:
             ent = ent[:a.max_frames]
         frames.append(Frames(folder, ent)); cams.append(replay.read_calibration(calib)); stamps.append([e[0] for e in ent])
+    if a.device_frames:                                               # every frame read and uploaded once; the replay reads device memory only
+        frames = replay.frames_to_device(frames, a.device)
     out = replay.replay_odometry_many(frames, cams, device=a.device, arith=a.arith, slots=a.slots or None, stage_ahead=a.stage_ahead)
     for (_, _, _, path), ts, (poses, info) in zip(seqs, stamps, out):
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)

@@ -7,7 +7,7 @@ The list file is that of scripts/replay_sequences.py: one sequence per line, `fo
 script's is the simplest there is: --keyframe-every N (required) accepts a frame while its keyframe is fewer than N frames behind it; a rejected
 frame makes the frame before it the new keyframe.  Poses are chained without an optimiser (replay.replay_tracker).
 
-    python scripts/replay_tracker_sequences.py sequences.txt --keyframe-every 5 [--slots 16] [--arith eigen337] [--max-frames N] [--out-dir DIR]
+    python scripts/replay_tracker_sequences.py sequences.txt --keyframe-every 5 [--slots 16] [--arith eigen337] [--max-frames N] [--out-dir DIR] [--stage-ahead] [--device-frames]
 """
 from __future__ import annotations
 
@@ -43,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--max-frames", type=int, default=0, help="replay at most this many frames of every sequence (0 = all)")
     ap.add_argument("--out-dir", default=None, help="where trajectories without an `out` column go (default: beside the list file)")
     ap.add_argument("--stage-ahead", action="store_true", help="hand the frames of step f + 1 over while step f runs (the same results)")
+    ap.add_argument("--device-frames", action="store_true",
+                    help="upload every frame to the GPU first (torch) and replay from device memory: the same results, no host intake per step")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.keyframe_every < 2:
@@ -55,6 +57,8 @@ def main(argv=None):
         if a.max_frames > 0:
             ent = ent[:a.max_frames]
         frames.append(Frames(folder, ent)); cams.append(replay.read_calibration(calib)); stamps.append([e[0] for e in ent])
+    if a.device_frames:                                               # every frame read and uploaded once; the replay reads device memory only
+        frames = replay.frames_to_device(frames, a.device)
     out = replay.replay_tracker_many(frames, cams, keyframe_every(a.keyframe_every), device=a.device, arith=a.arith, slots=a.slots or None, stage_ahead=a.stage_ahead)
     for (_, _, _, path), ts, (poses, steps, decisions) in zip(seqs, stamps, out):
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
