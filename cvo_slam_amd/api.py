@@ -72,6 +72,11 @@ class DeviceImage(C.Structure):         # cvo_device_image: a frame in caller-ow
                 ("pixel_bytes", C.c_int), ("swap_rb", C.c_int)]
 
 
+class DeviceCloud(C.Structure):         # cvo_device_cloud: a point cloud in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p), ("xyz_stride", C.c_longlong), ("feat_point_stride", C.c_longlong),
+                ("feat_channel_stride", C.c_longlong), ("n", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -131,6 +136,8 @@ ABI_SYMBOLS = [
     "cvo_tracks_stage_async", "cvo_tracks_step_staged_async", "cvo_tracks_staged_count",
     "cvo_check_device_images", "cvo_selftest_ingest_images", "cvo_batch_set_pairs_device_images", "cvo_batch_advance_device_images",
     "cvo_batch_stage_device_images", "cvo_tracks_step_device_async", "cvo_tracks_stage_device_async",
+    "cvo_check_device_clouds", "cvo_selftest_ingest_clouds", "cvo_batch_set_pairs_device_clouds", "cvo_batch_advance_device_clouds",
+    "cvo_tracks_step_device_clouds_async",
 ]
 
 _lib = None
@@ -306,6 +313,12 @@ def load_library():
     L.cvo_batch_stage_device_images.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp]
     L.cvo_tracks_step_device_async.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp, vp]
     L.cvo_tracks_stage_device_async.argtypes = [vp, C.c_int, ip, dip, C.c_int, C.c_int, C.POINTER(Camera), ip, vp]
+    dcp = C.POINTER(DeviceCloud)
+    L.cvo_check_device_clouds.argtypes = [C.c_int, C.c_int, dcp]
+    L.cvo_selftest_ingest_clouds.argtypes = [C.c_int, C.c_int, dcp, vp, vp, vp, ip]
+    L.cvo_batch_set_pairs_device_clouds.argtypes = [vp, C.c_int, C.c_int, C.c_int, dcp, ip, ip, vp]
+    L.cvo_batch_advance_device_clouds.argtypes = [vp, C.c_int, ip, dcp, vp]
+    L.cvo_tracks_step_device_clouds_async.argtypes = [vp, C.c_int, ip, dcp, vp, vp]
     _lib = L
     return L
 
@@ -547,6 +560,90 @@ def selftest_ingest_images(descs, width: int, height: int, device: int = 0):
     bgr = np.zeros((n, height, width, 3), np.uint8); dep = np.zeros((n, height, width), np.uint16); ok = C.c_int(0)
     _check(load_library().cvo_selftest_ingest_images(device, n, arr, int(width), int(height), bgr.ctypes.data, dep.ctypes.data, C.byref(ok)))
     return bgr, dep, bool(ok.value)
+
+
+# ---- clouds in device memory (cvo_hip.h: cvo_device_cloud): the same carriers
+def device_cloud(xyz, feat, feat_layout: str | None = None) -> DeviceCloud:
+    """DeviceCloud of a cloud in device memory, from the shape and strides of its two __cuda_array_interface__ carriers.
+    xyz: float32 (n, 3), inner stride 4 bytes, any row stride that is a multiple of 4 and at least 12 (a slice of a wider tensor, float4 points).
+    feat: float32 (5, n) (channels first) or (n, 5) (points first), told apart by the shape; a 5 x 5 tensor needs feat_layout = "channels_first"
+    or "points_first".  Strides must be positive multiples of 4.  Anything else -- a host array among it -- raises ValueError."""
+    if not hasattr(xyz, "__cuda_array_interface__") or not hasattr(feat, "__cuda_array_interface__"):
+        raise ValueError("a device cloud is a pair of objects with __cuda_array_interface__ (a host array is handed over with set_pairs / set_pcd)")
+    if feat_layout not in (None, "channels_first", "points_first"):
+        raise ValueError(f"feat_layout: 'channels_first' or 'points_first' expected, got {feat_layout!r}")
+    cx, cf = xyz.__cuda_array_interface__, feat.__cuda_array_interface__
+    for name, c in (("xyz", cx), ("feat", cf)):
+        if c["typestr"] != "<f4":
+            raise ValueError(f"{name}: little-endian float32 expected, got typestr {c['typestr']!r}")
+    sx, tx = _strides_of(cx, 4)
+    sf, tf = _strides_of(cf, 4)
+    if len(sx) != 2 or sx[1] != 3:
+        raise ValueError(f"xyz: shape (n, 3) expected, got {sx}")
+    n = sx[0]
+    if len(sf) != 2 or 5 not in sf:
+        raise ValueError(f"feat: shape (5, n) or (n, 5) expected, got {sf}")
+    if sf == (5, 5) and feat_layout is None:
+        raise ValueError("feat: a 5 x 5 tensor reads either way, say feat_layout = 'channels_first' or 'points_first'")
+    channels_first = (feat_layout == "channels_first") if feat_layout else sf[0] == 5
+    if sf !=((5, n) if channels_first else (n, 5)):
+        raise ValueError(f"feat: shape {(5, n) if channels_first else (n, 5)} expected for {n} points, got {sf}")
+    if n > 65535:
+        raise ValueError(f"{n} points: more than 65535 per cloud is not supported")
+    if n == 0:
+        return DeviceCloud(None, None, 0, 0, 0, 0, 0)
+    point_stride, channel_stride = (tf[1], tf[0]) if channels_first else (tf[0], tf[1])
+    if tx[1] != 4:
+        raise ValueError(f"xyz: inner stride 4 bytes expected, got {tx[1]}")
+    for name, v in (("xyz row", tx[0]), ("feat point", point_stride), ("feat channel", channel_stride)):
+        if v <= 0:
+            raise ValueError(f"{name} stride {v}: a positive stride expected")
+        if v % 4:
+            raise ValueError(f"{name} stride {v} is not a multiple of 4")
+    if tx[0] < 12:
+        raise ValueError(f"xyz row stride {tx[0]} is below a point's 12 bytes")
+    px, pf = cx["data"][0], cf["data"][0]
+    if not px or not pf:
+        raise ValueError("null device pointer")
+    if px % 4 or pf % 4:
+        raise ValueError("a base pointer is not 4-byte aligned")
+    return DeviceCloud(px, pf, tx[0], point_stride, channel_stride, n, 0)
+
+
+def _device_clouds(clouds):
+    """(ctypes array of DeviceCloud, n) of a list whose entries are DeviceCloud, (xyz, feat) or (xyz, feat, feat_layout)"""
+    ds = [c if isinstance(c, DeviceCloud) else device_cloud(*c) for c in clouds]
+    if not ds:
+        raise ValueError("no clouds")
+    return (DeviceCloud * len(ds))(*ds), len(ds)
+
+
+def _settle_cloud_writer(clouds, cloud_stream):
+    first = next((c for c in clouds if not isinstance(c, DeviceCloud)), None)
+    if first is not None:
+        _settle_writer([(first[0], None)], cloud_stream)
+
+
+def check_device_clouds(clouds, device: int = 0):
+    """cvo_check_device_clouds: the validation every device-cloud entry point runs first, alone (nothing is launched).  clouds: a list of
+    DeviceCloud, (xyz, feat) or (xyz, feat, feat_layout).  Raises CvoError (code 4, the message names cloud and field)."""
+    arr, n = _device_clouds(clouds)
+    _check(load_library().cvo_check_device_clouds(device, n, arr))
+
+
+def selftest_ingest_clouds(clouds, device: int = 0):
+    """cvo_selftest_ingest_clouds: the ingest kernel alone.  Returns ([(xyz (n, 3), feat (5, n)) per cloud], cost (count, 2) float64 {sum,
+    samples}, guards intact)."""
+    arr, n = _device_clouds(clouds)
+    ns = [int(arr[k].n) for k in range(n)]
+    tot = sum(ns)
+    xyz = np.zeros(max(1, 3 * tot), np.float32); feat = np.zeros(max(1, 5 * tot), np.float32); cost = np.zeros((n, 2), np.float64); ok = C.c_int(0)
+    _check(load_library().cvo_selftest_ingest_clouds(device, n, arr, xyz.ctypes.data, feat.ctypes.data, cost.ctypes.data, C.byref(ok)))
+    out, at = [], 0
+    for m in ns:
+        out.append((xyz[3 * at:3 * (at + m)].reshape(m, 3).copy(), feat[5 * at:5 * (at + m)].reshape(5, m).copy()))
+        at += m
+    return out, cost, bool(ok.value)
 
 
 class Cvo:
@@ -1001,6 +1098,28 @@ class CvoBatch:
                                                  fi.ctypes.data_as(ip), mi.ctypes.data_as(ip), pts.ctypes.data_as(ip)))
         return pts
 
+    def set_pairs_clouds(self, clouds, fixed_cloud, moving_cloud, first: int = 0, cloud_stream=None):
+        """cvo_batch_set_pairs_device_clouds: pairs first .. first+len(fixed_cloud)-1 from clouds in device memory.  clouds: a list of DeviceCloud,
+        (xyz, feat) or (xyz, feat, feat_layout) (see device_cloud), each ingested once; pair k takes clouds[fixed_cloud[k]] and
+        clouds[moving_cloud[k]].  cloud_stream: the stream that wrote them (None: torch's current stream is synchronised first for torch tensors)."""
+        fi = np.ascontiguousarray(fixed_cloud, np.int32).reshape(-1); mi = np.ascontiguousarray(moving_cloud, np.int32).reshape(-1)
+        if fi.shape != mi.shape:
+            raise ValueError("fixed_cloud and moving_cloud must have one entry per pair")
+        arr, n = _device_clouds(clouds); ip = C.POINTER(C.c_int)
+        _settle_cloud_writer(clouds, cloud_stream)
+        _check(self.L.cvo_batch_set_pairs_device_clouds(self.h, int(first), int(fi.shape[0]), n, arr, fi.ctypes.data_as(ip), mi.ctypes.data_as(ip),
+                                                        _stream_arg(cloud_stream)))
+
+    def advance_clouds(self, slots, clouds, cloud_stream=None):
+        """cvo_batch_advance_device_clouds: clouds[k] (as for set_pairs_clouds) is the next cloud of slot slots[k]: a slot's first cloud becomes its
+        fixed cloud; after that the moving cloud moves to fixed and the cloud becomes the moving one."""
+        sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        arr, n = _device_clouds(clouds)
+        if sl.shape[0] != n:
+            raise ValueError("one slot per cloud")
+        _settle_cloud_writer(clouds, cloud_stream)
+        _check(self.L.cvo_batch_advance_device_clouds(self.h, n, sl.ctypes.data_as(C.POINTER(C.c_int)), arr, _stream_arg(cloud_stream)))
+
     # -- K-stream frame-to-frame odometry (cvo_hip.h: cvo_batch_advance_images & co): slot p is one cvo::cvo odometry object
     def advance_images(self, slots, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
         """cvo_batch_advance_images: images[k] = (bgr8, depth16), all of one size, is the next frame of slot slots[k], generated with camera
@@ -1334,6 +1453,23 @@ class CvoTracks:
                                             C.c_void_p(stream) if stream else None))
         self._n = n
         return n
+
+    def step_clouds_async(self, streams, clouds, stream: int | None = None, cloud_stream=None):
+        """cvo_tracks_step_device_clouds_async: clouds[k] (a DeviceCloud, (xyz, feat) or (xyz, feat, feat_layout), see device_cloud) is the next
+        frame of stream streams[k], ingested once and held by both objects.  cloud_stream: as for CvoBatch.set_pairs_clouds."""
+        sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        arr, n = _device_clouds(clouds)
+        if sl.shape[0] != n:
+            raise ValueError("one stream per cloud")
+        _settle_cloud_writer(clouds, cloud_stream)
+        _check(self.L.cvo_tracks_step_device_clouds_async(self.h, n, sl.ctypes.data_as(C.POINTER(C.c_int)), arr, C.c_void_p(stream) if stream else None,
+                                                          _stream_arg(cloud_stream)))
+        self._n = n
+        return n
+
+    def step_clouds(self, streams, clouds, cloud_stream=None):
+        self.step_clouds_async(streams, clouds, cloud_stream=cloud_stream)
+        return self.wait()
 
     def stage_async(self, streams, images, cameras, cam_index=None, swap_rb: bool = False, image_stream=None):
         """cvo_tracks_stage_async: the arguments of step_async, for the streams' NEXT frames -- call it between step_async / step_staged_async

@@ -87,6 +87,7 @@ hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, con
                                   const float* cam_table, const int* tile_counts, PcdImgRec* rec, int cap, float* cloud, uint16_t* px, int n_img, hipStream_t s);
 hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s);
 hipError_t pcd_launch_ingest(const PcdIngestDesc* descs, uint8_t* bgr_stack, uint8_t* depth_stack, int w, int h, int n_img, hipStream_t s);
+hipError_t launch_ingest_clouds(const CloudIngestDesc* descs, int n_clouds, int n_max, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -170,6 +171,7 @@ struct Cloud {
     mutable const float* raw = nullptr;
     mutable const float* raw_feat = nullptr;   // with `raw`: the feature arrays when they do not lie right behind the positions (clouds handed over in caller-registered memory)
     float cost_hint = 0.f;          // mean 1/z^2 of a sample of the points (0 = unknown): what a pair costs per iteration follows the density of its clouds
+    bool multi = false;             // held by several slots of one batch (cvo_batch_set_pairs_device_clouds lists a cloud once for several pairs): never written or emptied through a slot
     float* rec() const { return static_cast<float*>(buf.p); }
     ~Cloud() { buf.release(); px.release(); boxes.release(); }
 };
@@ -1250,6 +1252,8 @@ struct Engine {
             // fip(cloud, cloud), untransformed: a function of the cloud and ell alone (cvo.cpp:496-497), kept with the cloud
             if (self_cache_on && rq[r].a == rq[r].b && !rq[r].hessian && !rq[r].tran && !rq[r].tran_from_state)
                 D.self_cache = score_self_cache(static_cast<float*>(rq[r].b->boxes.p), rq[r].b->n);
+            // (a cloud that several pairs hold is asked about once per pair, each with its own ell: one request of a launch keeps the table, two workgroups never fill one entry)
+            for (int q = 0; q < r && D.self_cache; ++q) if (descs[q].self_cache == D.self_cache) D.self_cache = nullptr;
             D.from = rq[r].from >= 0 ? static_cast<const PairState*>(d_states.p) + rq[r].from : nullptr;
             if (rq[r].tran_from_state && !D.from) return fail(CVO_ERR_INVALID, "score request: transform from a state that is not named");
             D.use_tran = rq[r].tran_from_state ? 2 : (rq[r].tran ? 1 : 0);
@@ -1427,6 +1431,20 @@ struct BatchImages {
     }
 };
 
+// What the hand-over of caller-owned device clouds needs (cvo_*_device_clouds): the ingest kernel's descriptor table and the table its blocks write
+// their cost samples to (pinned, free again once ev_out has been waited for), the two edges between the caller's cloud_stream and the engine's
+// stream, and the box launch's descriptor table -- two of them taken in turn, since the host waits for the ingest and not for the boxes behind it.
+struct CloudIntake {
+    PinBuf h_desc, h_cost, h_box[2];
+    hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_box[2] = {nullptr, nullptr};
+    bool box_queued[2] = {false, false}; int flip = 0;
+    void release() {
+        h_desc.release(); h_cost.release(); h_box[0].release(); h_box[1].release();
+        for (hipEvent_t* e : {&ev_in, &ev_out, &ev_box[0], &ev_box[1]}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
+        box_queued[0] = box_queued[1] = false;
+    }
+};
+
 // The frames of the NEXT step of a batch's or a tracker's streams, generated ahead of it (cvo_batch_stage_images, cvo_tracks_stage_async) on a stream
 // and in generator scratch of their own, while the launches of the current step run.  Three states: nothing staged; `pending`, the generator
 // queued (ev_gen behind its read-back of the point counts); `placed`, the counts read, every cloud copied into a cloud object that nothing
@@ -1461,6 +1479,7 @@ struct cvo_batch_s {
     int max_pairs = 0;
     std::vector<std::shared_ptr<Cloud>> fixed, moving;        // (shared: a tracker stream's frame is held by its odometry and its keyframe object at once, cvo_tracks_s)
     BatchImages img;
+    CloudIntake cin;
     std::vector<PairState> init_states;     // what set_pair / set_state last gave
     std::vector<unsigned char> dirty;       // per slot: the plain pair's device state differs from init_states (set for every slot by any set_*, as one flag was)
     std::vector<StreamSlot> streams;
@@ -2189,6 +2208,8 @@ void fresh_stream(cvo_batch b, int p) {
     for (Cloud* c : {b->fixed[p].get(), b->moving[p].get()})
         if (c) { c->n = 0; c->n_px = 0; c->boxes_valid = false; c->raw = nullptr; c->raw_feat = nullptr; c->cost_hint = 0.f; }
 }
+// A slot's cloud objects before they are written or emptied through the slot: one that other slots hold too is let go of (the pool keeps it)
+void own_slot_clouds(cvo_batch b, int p) { for (std::shared_ptr<Cloud>* c : {&b->fixed[p], &b->moving[p]}) if (*c && (*c)->multi) c->reset(); }
 void report_step_laps(const char* who); void stage_drop(cvo_batch b); void stage_drop_if_listed(cvo_batch b, int p); void stage_destroy(cvo_batch b); int stage_place(cvo_batch b, bool block);   // (the stage: below, behind the generator)
 // what every set_* did to the single flag it had: each plain pair starts its next launch from init_states again.  Slots set here stop being streams.
 void states_dirty(cvo_batch b) { std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)1); }
@@ -2263,7 +2284,7 @@ int cvo_batch_destroy(cvo_batch b) {
     stage_destroy(b);                                               // (drains the stage stream first)
     if (b->eng.stream) (void)hipStreamSynchronize(b->eng.stream);
     b->fixed.clear(); b->moving.clear(); b->pool.clear();
-    b->img.release();
+    b->img.release(); b->cin.release();
     report_step_laps("batch");
     b->eng.destroy();
     delete b;
@@ -2273,6 +2294,7 @@ int cvo_batch_set_pair(cvo_batch b, int p, const float* fixed_xyz, const float* 
                        const float* moving_xyz, const float* moving_feat, int n_moving) {
     if (!b || p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair index");
     int rc = batch_settle(b); if (rc) return rc;
+    own_slot_clouds(b, p);
     if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
     if (!b->moving[p]) b->moving[p].reset(new Cloud());
     end_stream(b, p);
@@ -2291,6 +2313,7 @@ int cvo_batch_set_pairs(cvo_batch b, int first, int count, const float* const* f
     for (int k = 0; k < count; ++k) {
         const int p = first + k;
         end_stream(b, p);
+        own_slot_clouds(b, p);
         if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
         if (!b->moving[p]) b->moving[p].reset(new Cloud());
         items.push_back(Engine::UploadItem{b->fixed[p].get(), fixed_xyz[k], fixed_feat[k], n_fixed[k]});
@@ -2508,7 +2531,7 @@ bool image_size_ok(int width, int height) { return width >= 64 && height >= 64 &
 // One plane of a device image: rows of row_bytes bytes, `pitch` apart (resolved), `height` of them from ptr.  The device must be able to read
 // every byte: device memory of `device` (the rows inside the allocation), managed memory, or pinned / registered host memory.  Anything else --
 // pageable host memory, another device's memory -- is refused here, it must never reach a kernel.
-int check_device_plane(int device, const void* ptr, long long pitch, long long row_bytes, int height, const std::string& what) {
+int check_device_plane(int device, const void* ptr, long long pitch, long long row_bytes, int height, const std::string& what, const char* thing = "image") {
     hipPointerAttribute_t at; std::memset(&at, 0, sizeof(at));
     const hipError_t e = hipPointerGetAttributes(&at, ptr);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(CVO_ERR_INVALID, what + ": not a pointer the device can read (" + hipGetErrorString(e) + ")"); }
@@ -2520,7 +2543,7 @@ int check_device_plane(int device, const void* ptr, long long pitch, long long r
     if (er != hipSuccess) { (void)hipGetLastError(); return fail(CVO_ERR_INVALID, what + ": no allocation found around the pointer (" + hipGetErrorString(er) + ")"); }
     const unsigned long long lo = reinterpret_cast<uintptr_t>(ptr), a0 = reinterpret_cast<uintptr_t>(base);
     const unsigned long long need = (unsigned long long)(height - 1) * (unsigned long long)pitch + (unsigned long long)row_bytes;
-    if (lo < a0 || lo - a0 > size || need > size - (lo - a0)) return fail(CVO_ERR_INVALID, what + ": the image ends outside its allocation (" + std::to_string(need) + " bytes from the pointer)");
+    if (lo < a0 || lo - a0 > size || need > size - (lo - a0)) return fail(CVO_ERR_INVALID, what + ": the " + thing + " ends outside its allocation (" + std::to_string(need) + " bytes from the pointer)");
     return CVO_OK;
 }
 // What every device entry point checks first, before any stream changes and before anything is queued (cvo_check_device_images runs it alone).
@@ -2642,7 +2665,7 @@ int stage_place(cvo_batch b, bool block) {
         Cloud& c = *F.clouds[k];
         const PcdImgRec& r = R[k];
         F.points[k] = r.npts;
-        c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr;
+        c.n = r.npts; c.n_px = r.npts; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr; c.multi = false;
         c.cost_hint = r.cost_n > 0 ? (float)(r.cost / r.cost_n) : 0.f;
         if (c.n <= 0) continue;
         if ((rc = c.buf.ensure((size_t)c.n * REC * sizeof(float))) || (rc = c.px.ensure((size_t)c.n * 2 * sizeof(uint16_t))) || (rc = c.boxes.ensure(score_box_bytes(c.n)))) return bad(rc);
@@ -2707,6 +2730,7 @@ int batch_set_pairs_from(cvo_batch b, int first, int count, int n_images, const 
     for (int k = 0; k < count; ++k) {
         const int p = first + k;
         end_stream(b, p);
+        own_slot_clouds(b, p);
         if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
         if (!b->moving[p]) b->moving[p].reset(new Cloud());
         dst.push_back(b->fixed[p].get()); img.push_back(fixed_image[k]);
@@ -2745,6 +2769,7 @@ int batch_advance_from(cvo_batch b, int count, const int* slots, const ImageSrc&
     std::vector<Cloud*> dst; std::vector<int> img;
     for (int k = 0; k < count; ++k) {
         const int p = slots[k];
+        own_slot_clouds(b, p);
         if (!b->fixed[p]) b->fixed[p].reset(new Cloud());
         if (!b->moving[p]) b->moving[p].reset(new Cloud());
         if (!b->streams[p].on) fresh_stream(b, p);
@@ -2790,6 +2815,7 @@ int cvo_batch_reset_stream(cvo_batch b, int p) {
     int rc = batch_settle(b); if (rc) return rc;
     if (b->eng.launched && b->eng.last_stream) HIP_TRY(hipStreamSynchronize(b->eng.last_stream));   // (a launch may still read the clouds; their memory is kept)
     slot_clouds_changed(b, p);
+    own_slot_clouds(b, p);
     fresh_stream(b, p);
     return CVO_OK;
 }
@@ -2844,6 +2870,243 @@ int cvo_selftest_ingest_images(int device, int count, const cvo_device_image* im
     *guards_intact = ok;
     return CVO_OK;
 }
+// ---- clouds that are already on the GPU (cvo_device_cloud): the device twin of the cloud hand-over.  Eager: one ingest launch per call copies
+// the caller's arrays into library-owned cloud objects, one box launch behind it makes their group boxes; from there on they are clouds like any other.
+namespace {
+void cloud_strides(const cvo_device_cloud& c, long long* xs, long long* ps, long long* cs) {
+    *xs = c.xyz_stride ? c.xyz_stride : 12;
+    const bool ref = c.feat_point_stride == 0 && c.feat_channel_stride == 0;         // the reference layout: 5 channel-major arrays of n (data_type.h:75)
+    *ps = ref ? 4 : c.feat_point_stride; *cs = ref ? 4ll * c.n : c.feat_channel_stride;
+}
+// What every device-cloud entry point checks first, before any slot or stream changes and before anything is queued (cvo_check_device_clouds runs it alone).
+int check_device_clouds(int device, int count, const cvo_device_cloud* clouds) {
+    if (count <= 0 || count > 65535) return fail(CVO_ERR_INVALID, "bad cloud count");
+    if (!clouds) return fail(CVO_ERR_INVALID, "null argument: clouds");
+    for (int k = 0; k < count; ++k) {
+        const cvo_device_cloud& c = clouds[k];
+        const std::string who = "cloud " + std::to_string(k) + ": ";
+        if (c.n < 0 || c.n > 65535) return fail(CVO_ERR_INVALID, who + "n " + std::to_string(c.n) + " is outside 0 .. 65535 (16-bit column indices)");
+        const struct { const char* name; long long v; } strides[3] = {{"xyz_stride", c.xyz_stride}, {"feat_point_stride", c.feat_point_stride}, {"feat_channel_stride", c.feat_channel_stride}};
+        for (const auto& st : strides) {
+            if (st.v < 0) return fail(CVO_ERR_INVALID, who + st.name + " " + std::to_string(st.v) + " is negative");
+            if (st.v & 3) return fail(CVO_ERR_INVALID, who + st.name + " " + std::to_string(st.v) + " is not a multiple of 4");
+            if (st.v > (1ll << 40)) return fail(CVO_ERR_INVALID, who + st.name + " " + std::to_string(st.v) + " is out of range");
+        }
+        if (c.xyz_stride != 0 && c.xyz_stride < 12) return fail(CVO_ERR_INVALID, who + "xyz_stride " + std::to_string(c.xyz_stride) + " is below a point's 12 bytes");
+        if ((c.feat_point_stride == 0) != (c.feat_channel_stride == 0)) return fail(CVO_ERR_INVALID, who + "exactly one of feat_point_stride and feat_channel_stride is 0");
+        if (c.n == 0) continue;                                       // (an empty cloud needs no pointers)
+        if (!c.xyz) return fail(CVO_ERR_INVALID, who + "xyz is null");
+        if (!c.feat) return fail(CVO_ERR_INVALID, who + "feat is null");
+        if (reinterpret_cast<uintptr_t>(c.xyz) & 3u) return fail(CVO_ERR_INVALID, who + "xyz is not 4-byte aligned");
+        if (reinterpret_cast<uintptr_t>(c.feat) & 3u) return fail(CVO_ERR_INVALID, who + "feat is not 4-byte aligned");
+    }
+    HIP_TRY(hipSetDevice(device));
+    for (int k = 0; k < count; ++k) {
+        const cvo_device_cloud& c = clouds[k];
+        if (c.n == 0) continue;
+        const std::string who = "cloud " + std::to_string(k) + ": ";
+        long long xs, ps, cs; cloud_strides(c, &xs, &ps, &cs);
+        int rc;
+        if ((rc = check_device_plane(device, c.xyz, xs, 12, c.n, who + "xyz", "cloud"))) return rc;              // [xyz, xyz + (n-1)*xyz_stride + 12)
+        if ((rc = check_device_plane(device, c.feat, ps, 4 * cs + 4, c.n, who + "feat", "cloud"))) return rc;    // [feat, feat + (n-1)*point_stride + 4*channel_stride + 4)
+    }
+    return CVO_OK;
+}
+// One cloud of an ingest launch (n > 0): where it goes, where its boxes go (null: none are made), and what its cost samples came to.
+struct IngestItem { const cvo_device_cloud* src; float* dst; float* gbox; double cost_sum; int cost_n; };
+// ONE ingest launch for all items on s, a stream of the library's own (see ingest_enqueue: a caller's stream may sit behind a persistent launch),
+// and ONE box launch behind it.  With a cloud_stream: s waits for what is queued there by an event, and the cloud_stream waits for the ingest by a
+// second one.  The host waits for the ingest alone, always: the cost samples its blocks wrote to pinned memory are added up here, in block order.
+int ingest_clouds_run(CloudIntake& C, hipStream_t s, hipStream_t cloud_stream, std::vector<IngestItem>& items) {
+    const int live = (int)items.size();
+    if (live == 0) return CVO_OK;
+    int rc;
+    for (hipEvent_t* e : {&C.ev_in, &C.ev_out, &C.ev_box[0], &C.ev_box[1]}) if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    size_t blocks = 0; int n_max = 0;
+    for (const IngestItem& it : items) { blocks += (size_t)(it.src->n + 255) / 256; n_max = std::max(n_max, it.src->n); }
+    const int f = C.flip; C.flip ^= 1;
+    if (C.box_queued[f]) { HIP_TRY(hipEventSynchronize(C.ev_box[f])); C.box_queued[f] = false; }   // (the box launch before the last one: long over)
+    if ((rc = C.h_desc.ensure(sizeof(CloudIngestDesc) * (size_t)live)) || (rc = C.h_cost.ensure(sizeof(double) * 2 * blocks)) || (rc = C.h_box[f].ensure(sizeof(BoxDesc) * (size_t)live))) return rc;
+    CloudIngestDesc* d = static_cast<CloudIngestDesc*>(C.h_desc.p);
+    BoxDesc* bd = static_cast<BoxDesc*>(C.h_box[f].p);
+    double* cost = static_cast<double*>(C.h_cost.p);
+    size_t at = 0; int n_box = 0;
+    for (int q = 0; q < live; ++q) {
+        const cvo_device_cloud& c = *items[q].src;
+        long long xs, ps, cs; cloud_strides(c, &xs, &ps, &cs);
+        d[q].xyz = static_cast<const float*>(c.xyz); d[q].feat = static_cast<const float*>(c.feat); d[q].dst = items[q].dst; d[q].cost = cost + 2 * at;
+        d[q].xyz_stride = xs; d[q].feat_point_stride = ps; d[q].feat_channel_stride = cs; d[q].n = c.n; d[q].xyz_tight = xs == 12;
+        at += (size_t)(c.n + 255) / 256;
+        if (items[q].gbox) {
+            BoxDesc& D = bd[n_box++];
+            D.rec = items[q].dst; D.gbox = items[q].gbox; D.self_cache = score_self_cache(D.gbox, c.n); D.n = c.n; D.ngroups = score_groups(c.n);
+        }
+    }
+    if (cloud_stream) {
+        HIP_TRY(hipEventRecord(C.ev_in, cloud_stream));
+        HIP_TRY(hipStreamWaitEvent(s, C.ev_in, 0));
+    }
+    hipError_t e = launch_ingest_clouds(d, live, n_max, s);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("cloud ingest kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(C.ev_out, s));
+    if (n_box > 0) {
+        e = launch_cloud_boxes_batch(bd, n_box, n_max, s);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("cloud box kernel launch: ") + hipGetErrorString(e));
+        HIP_TRY(hipEventRecord(C.ev_box[f], s));
+        C.box_queued[f] = true;
+    }
+    if (cloud_stream) HIP_TRY(hipStreamWaitEvent(cloud_stream, C.ev_out, 0));
+    {
+        Lap lap(StepLaps::INGEST);
+        HIP_TRY(hipEventSynchronize(C.ev_out));                       // (the call's one host wait)
+    }
+    at = 0;
+    for (int q = 0; q < live; ++q) {
+        const size_t nb = (size_t)(items[q].src->n + 255) / 256;
+        double sum = 0.0, m = 0.0;
+        for (size_t k = 0; k < nb; ++k) { sum += cost[2 * (at + k)]; m += cost[2 * (at + k) + 1]; }
+        items[q].cost_sum = sum; items[q].cost_n = (int)m;
+        at += nb;
+    }
+    return CVO_OK;
+}
+// `count` checked clouds into cloud objects of `pool` that nothing else holds (out[k]; an empty cloud gets an empty object), on b's stream.  No slot
+// changes.  A free object is read by no launch that is queued behind this call's work: the launches of b run on its stream, or are waited for here.
+int clouds_ingest(cvo_batch b, std::vector<std::shared_ptr<Cloud>>& pool, int count, const cvo_device_cloud* clouds, void* cloud_stream,
+                  std::vector<std::shared_ptr<Cloud>>& out) {
+    Engine& E = b->eng;
+    HIP_TRY(hipSetDevice(E.device));
+    if (E.launched && E.last_stream && E.last_stream != E.stream) HIP_TRY(hipStreamSynchronize(E.last_stream));
+    out.assign(count, nullptr);
+    std::vector<IngestItem> items; std::vector<int> of; items.reserve(count); of.reserve(count);
+    int rc;
+    for (int k = 0; k < count; ++k) {
+        pool_free_cloud(pool, out[k]);
+        Cloud& c = *out[k];
+        c.n = clouds[k].n; c.n_px = 0; c.boxes_valid = false; c.raw = nullptr; c.raw_feat = nullptr; c.cost_hint = 0.f; c.multi = false;
+        if (c.n <= 0) continue;
+        if ((rc = c.buf.ensure((size_t)c.n * REC * sizeof(float))) || (rc = c.boxes.ensure(score_box_bytes(c.n)))) return rc;
+        items.push_back(IngestItem{&clouds[k], c.rec(), static_cast<float*>(c.boxes.p), 0.0, 0}); of.push_back(k);
+    }
+    if ((rc = ingest_clouds_run(b->cin, E.stream, static_cast<hipStream_t>(cloud_stream), items))) return rc;
+    for (size_t q = 0; q < items.size(); ++q) {
+        Cloud& c = *out[of[q]];
+        c.cost_hint = items[q].cost_n > 0 ? (float)(items[q].cost_sum / items[q].cost_n) : 0.f;
+        c.boxes_valid = true; c.boxes_stream = E.stream;
+    }
+    E.uploads_pending = true;                                         // (a launch on another stream waits for the engine's stream once: settle_uploads)
+    return CVO_OK;
+}
+}  // namespace
+int cvo_check_device_clouds(int device, int count, const cvo_device_cloud* clouds) { return check_device_clouds(device, count, clouds); }
+int cvo_batch_set_pairs_device_clouds(cvo_batch b, int first, int count, int n_clouds, const cvo_device_cloud* clouds, const int* fixed_cloud, const int* moving_cloud,
+                                      void* cloud_stream) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    if (first < 0 || count <= 0 || first + count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad pair range");
+    if (!fixed_cloud || !moving_cloud) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = check_device_clouds(b->eng.device, n_clouds, clouds); if (rc) return rc;
+    for (int k = 0; k < count; ++k)
+        if (fixed_cloud[k] < 0 || fixed_cloud[k] >= n_clouds || moving_cloud[k] < 0 || moving_cloud[k] >= n_clouds) return fail(CVO_ERR_INVALID, "cloud index out of range");
+    if ((rc = batch_settle(b))) return rc;
+    std::vector<std::shared_ptr<Cloud>> in;
+    if ((rc = clouds_ingest(b, b->pool, n_clouds, clouds, cloud_stream, in))) return rc;   // (fails before any pair changes)
+    // commit: the pairs take the cloud objects; one listed for several pairs is held by all of them
+    if (b->eng.launched && b->eng.last_stream) HIP_TRY(hipStreamSynchronize(b->eng.last_stream));   // (objects the pairs give up are written by later hand-overs)
+    std::vector<int> uses(n_clouds, 0);
+    for (int k = 0; k < count; ++k) { ++uses[fixed_cloud[k]]; ++uses[moving_cloud[k]]; }
+    for (int j = 0; j < n_clouds; ++j) in[j]->multi = uses[j] > 1;
+    auto give_up = [&](std::shared_ptr<Cloud>& c) { if (c && c.use_count() == 1) b->pool.push_back(c); c.reset(); };
+    for (int k = 0; k < count; ++k) {
+        const int p = first + k;
+        end_stream(b, p);
+        give_up(b->fixed[p]); give_up(b->moving[p]);
+        b->fixed[p] = in[fixed_cloud[k]]; b->moving[p] = in[moving_cloud[k]];
+        fresh_state(b->init_states[p], b->prm.ell);
+    }
+    states_dirty(b);
+    return CVO_OK;
+}
+int cvo_batch_advance_device_clouds(cvo_batch b, int count, const int* slots, const cvo_device_cloud* clouds, void* cloud_stream) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    if (count <= 0 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "bad cloud count");
+    if (!slots) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = check_device_clouds(b->eng.device, count, clouds); if (rc) return rc;
+    std::vector<unsigned char> seen(b->max_pairs, 0);
+    for (int k = 0; k < count; ++k) {
+        if (slots[k] < 0 || slots[k] >= b->max_pairs) return fail(CVO_ERR_INVALID, "slot index out of range");
+        if (seen[slots[k]]++) return fail(CVO_ERR_INVALID, "slot listed twice");
+    }
+    if ((rc = batch_settle(b))) return rc;
+    std::vector<std::shared_ptr<Cloud>> in;
+    if ((rc = clouds_ingest(b, b->pool, count, clouds, cloud_stream, in))) return rc;      // (fails before any slot changes)
+    if (b->eng.launched && b->eng.last_stream) HIP_TRY(hipStreamSynchronize(b->eng.last_stream));   // (as cvo_batch_advance_staged: objects the slots give up are written later)
+    auto give_up = [&](std::shared_ptr<Cloud>& c) { if (c && c.use_count() == 1) b->pool.push_back(c); c.reset(); };
+    for (int k = 0; k < count; ++k) {                                // the commit of cvo_batch_advance_staged
+        const int p = slots[k];
+        stage_drop_if_listed(b, p);
+        own_slot_clouds(b, p);
+        if (!b->streams[p].on) fresh_stream(b, p);
+        StreamSlot& S = b->streams[p];
+        slot_clouds_changed(b, p);
+        if (!S.init) {                                                // cvo.cpp:352-360: the first cloud only fills the fixed slot
+            S.init = true;
+            give_up(b->fixed[p]); b->fixed[p] = in[k];
+            if (!b->moving[p]) b->moving[p].reset(new Cloud());
+        } else {
+            if (S.has_moving) { give_up(b->fixed[p]); b->fixed[p] = b->moving[p]; b->moving[p].reset(); }   // update_fixed_pcd, cvo.cpp:578-582
+            else give_up(b->moving[p]);
+            S.has_moving = true;
+            b->moving[p] = in[k];
+        }
+    }
+    return CVO_OK;
+}
+// The ingest kernel alone (tests): every cloud's planes lie between 64 guard bytes on either side, prefilled with 0xA5
+int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* clouds, float* xyz_out, float* feat_out, double* cost_out, int* guards_intact) {
+    if (!xyz_out || !feat_out || !cost_out || !guards_intact) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = check_device_clouds(device, count, clouds); if (rc) return rc;
+    constexpr size_t G = 64;
+    size_t bytes = G;
+    for (int k = 0; k < count; ++k) bytes += (size_t)clouds[k].n * REC * sizeof(float) + G;
+    DevBuf buf; CloudIntake C;
+    struct Release { DevBuf& b; CloudIntake& C; ~Release() { C.release(); b.release(); } } release{buf, C};
+    if ((rc = buf.ensure(bytes))) return rc;
+    HIP_TRY(hipMemset(buf.p, 0xA5, bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    hipStream_t s = nullptr;
+    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    struct Close { hipStream_t s; ~Close() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } close_{s};
+    unsigned char* base = static_cast<unsigned char*>(buf.p);
+    std::vector<IngestItem> items; std::vector<int> of;
+    size_t at = G;
+    for (int k = 0; k < count; ++k) {
+        if (clouds[k].n > 0) { items.push_back(IngestItem{&clouds[k], reinterpret_cast<float*>(base + at), nullptr, 0.0, 0}); of.push_back(k); }
+        at += (size_t)clouds[k].n * REC * sizeof(float) + G;
+    }
+    if ((rc = ingest_clouds_run(C, s, nullptr, items))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    std::vector<unsigned char> host(bytes);
+    HIP_TRY(hipMemcpy(host.data(), buf.p, bytes, hipMemcpyDeviceToHost));
+    for (int k = 0; k < count; ++k) { cost_out[2 * k] = 0.0; cost_out[2 * k + 1] = 0.0; }
+    for (size_t q = 0; q < items.size(); ++q) { cost_out[2 * of[q]] = items[q].cost_sum; cost_out[2 * of[q] + 1] = (double)items[q].cost_n; }
+    int ok = 1;
+    auto guard = [&](size_t from) { for (size_t i = 0; i < G; ++i) ok &= host[from + i] == 0xA5; };
+    at = 0; guard(at); at += G;
+    for (int k = 0; k < count; ++k) {                                // the planes back to the reference layout: n x 3 positions, 5 channel-major arrays of n
+        const int n = clouds[k].n;
+        const float* rec = reinterpret_cast<const float*>(host.data() + at);
+        for (int i = 0; i < n; ++i) {
+            const float* lo = rec + lo_off(i); const float* hi = rec + hi_off(n, i);
+            xyz_out[3 * (size_t)i] = lo[0]; xyz_out[3 * (size_t)i + 1] = lo[1]; xyz_out[3 * (size_t)i + 2] = lo[2];
+            feat_out[i] = lo[3]; feat_out[(size_t)n + i] = hi[0]; feat_out[2 * (size_t)n + i] = hi[1]; feat_out[3 * (size_t)n + i] = hi[2]; feat_out[4 * (size_t)n + i] = hi[3];
+        }
+        xyz_out += 3 * (size_t)n; feat_out += 5 * (size_t)n;
+        at += (size_t)n * REC * sizeof(float);
+        guard(at); at += G;
+    }
+    *guards_intact = ok;
+    return CVO_OK;
+}
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");
     FrameStage& F = b->stage;
@@ -2857,6 +3120,7 @@ int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     const int count = (int)F.list.size();
     for (int k = 0; k < count; ++k) {                                // the commit of cvo_batch_advance_images, with cloud objects handed over instead of written
         const int p = F.list[k];
+        own_slot_clouds(b, p);
         if (!b->streams[p].on) fresh_stream(b, p);
         StreamSlot& S = b->streams[p];
         slot_clouds_changed(b, p);
@@ -3450,6 +3714,21 @@ int cvo_tracks_step_device_async(cvo_tracks t, int count, const int* streams, co
     if (!t) return fail(CVO_ERR_INVALID, "null tracks");
     int rc = check_device_images(t->odo->eng.device, count, images, width, height); if (rc) return rc;
     return tracks_step_from(t, count, streams, ImageSrc::device(images, image_stream), width, height, cams, cam_index, hip_stream);
+}
+// The cloud twin (see cvo_device_cloud): the step's frames as clouds in caller-owned device memory, each ingested once into a cloud object both of the
+// stream's objects hold; phases, commit protocol and stage are cvo_tracks_step_async's.  A refused call changes no stream and keeps the stage.
+int cvo_tracks_step_device_clouds_async(cvo_tracks t, int count, const int* streams, const cvo_device_cloud* clouds, void* hip_stream, void* cloud_stream) {
+    if (!t) return fail(CVO_ERR_INVALID, "null tracks");
+    int rc = check_device_clouds(t->odo->eng.device, count, clouds); if (rc) return rc;
+    if ((rc = tracks_check_list(t, count, streams))) return rc;
+    if ((rc = tracks_check_state(t, count, streams))) return rc;
+    cvo_batch bo = t->odo, bk = t->key;
+    if ((rc = batch_settle(bo)) || (rc = batch_settle(bk))) return rc;
+    std::vector<std::shared_ptr<Cloud>> in;
+    if ((rc = clouds_ingest(bo, t->pool, count, clouds, cloud_stream, in))) return rc;     // (the step's one host wait; fails before any stream changes)
+    std::vector<int> npts(count);
+    for (int k = 0; k < count; ++k) npts[k] = clouds[k].n;
+    return tracks_step_run(t, count, streams, npts.data(), &in, nullptr, hip_stream);
 }
 // ---- the next step's frames staged ahead: generated on the stage's own stream while the current step's launches run
 int cvo_tracks_stage_async(cvo_tracks t, int count, const int* streams, const unsigned char* const* bgr8, const unsigned short* const* depth16, int width, int height,

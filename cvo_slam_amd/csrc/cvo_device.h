@@ -234,6 +234,19 @@ struct PcdIngestDesc {
 };
 static_assert(sizeof(PcdIngestDesc) == 48, "PcdIngestDesc layout");
 
+// a caller-owned device cloud copied into a cloud's two float4 planes (cvo_ingest_clouds_kernel): one descriptor per cloud, n > 0, the
+// strides resolved (never 0) and the read path of the positions decided on the host from these fields alone
+struct CloudIngestDesc {
+    const float* xyz;        // point i at (const char*)xyz + i * xyz_stride: x, y, z
+    const float* feat;       // feature c (0..4) of point i at (const char*)feat + i * feat_point_stride + c * feat_channel_stride
+    float* dst;              // two planes of n float4
+    double* cost;            // {sum of 1/z^2, samples} per 256-point block of the cloud, in block order (pinned host memory)
+    long long xyz_stride, feat_point_stride, feat_channel_stride;   // bytes, multiples of 4
+    int n;
+    int xyz_tight;           // xyz_stride == 12: a block's positions are consecutive floats, fetched through LDS
+};
+static_assert(sizeof(CloudIngestDesc) == 64, "CloudIngestDesc layout");
+
 // the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
 struct BoxDesc {
     const float* rec;        // the cloud's two planes of n float4

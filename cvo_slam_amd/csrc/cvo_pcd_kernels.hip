@@ -458,6 +458,76 @@ hipError_t launch_pack_clouds(const float* raw, const PackDesc* descs, int n_clo
     return hipGetLastError();
 }
 
+// caller-owned device clouds (cvo_*_device_clouds) into the clouds' two float4 planes: one launch for all clouds of a call, grid.y = cloud,
+// a block per 256 consecutive points, the descriptor table read where it lies (pinned host memory).  Each lane assembles its point's two
+// float4 and writes them with two 16-byte stores.
+//   positions, xyz_stride 12 (xyz_tight): the block's m = 3 * cnt floats are consecutive, src[0, m).  They are split into a head of
+//     min(m, floats up to the next 16-byte boundary), a body of whole 16-byte pieces and a tail of (m - head) % 4 floats: head + body + tail
+//     = m, the 16-byte loads cover src[head, head + body) only, head and tail are taken float by float.  Through LDS to the lanes.
+//   positions, any other stride: lane i reads its three floats at xyz + i * xyz_stride.
+//   features: feature c of point i at feat + i * point_stride + c * channel_stride, one float per lane and channel: with a point stride
+//     of 4 the lanes of a wave read consecutive floats of a channel array.
+// Bounds: a lane reads for a point i < n only, so the bytes read are inside [xyz, xyz + (n - 1) * xyz_stride + 12) and [feat, feat + (n - 1) *
+// point_stride + 4 * channel_stride + 4) -- the extents the host has checked against the allocations -- by construction: in the tight path the
+// block reads floats [3 i0, 3 i0 + 3 cnt) of the position array and 3 (i0 + cnt) <= 3 n; no load is wider than what is left of its range.
+// Cost samples (Engine::upload_many's: points i % 16 == 0 with z > 1e-3f, 1.0 / ((double)z * z)): a block starts at a multiple of 256, so its
+// samples are its lanes 0, 16, ..., 240; each forms its term, lane 0 adds the sixteen in lane order and writes {sum, samples} to the block's
+// place in the cloud's table.  The host adds the blocks in block order: no atomics, the same bytes on every run.
+__global__ __launch_bounds__(256) void cvo_ingest_clouds_kernel(const CloudIngestDesc* __restrict__ descs) {
+    __shared__ __align__(16) float pos[768];
+    __shared__ double term[16];
+    __shared__ int sampled[16];
+    const CloudIngestDesc D = descs[blockIdx.y];
+    const int i0 = blockIdx.x * 256, tid = threadIdx.x;
+    if (i0 >= D.n) return;                                            // (uniform over the block)
+    const int cnt = min(256, D.n - i0), i = i0 + tid;
+    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+    if (D.xyz_tight) {
+        const float* src = D.xyz + 3 * (size_t)i0;
+        const int m = 3 * cnt;
+        const int head = min(m, (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(src) & 15u)) & 15u) >> 2));
+        const int body = (m - head) & ~3, tail0 = head + body;
+        if (tid < head) pos[tid] = src[tid];
+        if (4 * tid < body) {
+            const float4 v = *reinterpret_cast<const float4*>(src + head + 4 * tid);
+            float* o = pos + head + 4 * tid;
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+        }
+        if (tid < m - tail0) pos[tail0 + tid] = src[tail0 + tid];
+        __syncthreads();
+        if (tid < cnt) { lo.x = pos[3 * tid]; lo.y = pos[3 * tid + 1]; lo.z = pos[3 * tid + 2]; }
+    } else if (tid < cnt) {
+        const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.xyz) + (long long)i * D.xyz_stride);
+        lo.x = p[0]; lo.y = p[1]; lo.z = p[2];
+    }
+    if (tid < cnt) {
+        const char* f = reinterpret_cast<const char*>(D.feat) + (long long)i * D.feat_point_stride;
+        const long long cs = D.feat_channel_stride;
+        lo.w = *reinterpret_cast<const float*>(f);
+        hi.x = *reinterpret_cast<const float*>(f + cs); hi.y = *reinterpret_cast<const float*>(f + 2 * cs);
+        hi.z = *reinterpret_cast<const float*>(f + 3 * cs); hi.w = *reinterpret_cast<const float*>(f + 4 * cs);
+        *reinterpret_cast<float4*>(D.dst + lo_off(i)) = lo;
+        *reinterpret_cast<float4*>(D.dst + hi_off(D.n, i)) = hi;
+    }
+    if ((tid & 15) == 0) {
+        const bool ok = tid < cnt && lo.z > 1e-3f;
+        term[tid >> 4] = ok ? 1.0 / ((double)lo.z * (double)lo.z) : 0.0;
+        sampled[tid >> 4] = ok ? 1 : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0; int k = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) { if (sampled[q]) s += term[q]; k += sampled[q]; }
+        D.cost[2 * blockIdx.x] = s; D.cost[2 * blockIdx.x + 1] = (double)k;
+    }
+}
+// descs: n_clouds descriptors the device can read (pinned host memory), every cloud with n > 0; n_max: the largest n among them
+hipError_t launch_ingest_clouds(const CloudIngestDesc* descs, int n_clouds, int n_max, hipStream_t s) {
+    if (n_clouds > 0 && n_max > 0) hipLaunchKernelGGL(cvo_ingest_clouds_kernel, dim3((n_max + 255) / 256, n_clouds), dim3(256), 0, s, descs);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ host-side launchers
 #define PCD_LAUNCH_1D(kernel, n, stream, ...) hipLaunchKernelGGL(kernel, dim3(((n) + 255) / 256), dim3(256), 0, stream, __VA_ARGS__)
 

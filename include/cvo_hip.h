@@ -437,6 +437,53 @@ int cvo_batch_stage_device_images(cvo_batch b, int count, const int* slots, cons
  * 0xA5.  bgr_out: count*3*width*height bytes, depth_out: count*width*height uint16; *guards_intact = 1 when no guard byte changed. */
 int cvo_selftest_ingest_images(int device, int count, const cvo_device_image* images, int width, int height, unsigned char* bgr_out,
                                unsigned short* depth_out, int* guards_intact);
+/* ---- Clouds that are already on the GPU (the caller's own point selector, a learned feature extractor in torch, a lidar or stereo front end, a
+ * simulator): the device twins of the cloud hand-over (cvo_batch_set_pair(s), and the K-stream steps, which have no host cloud form).  A call takes
+ * `count` descriptors, one per cloud.  Validation, ordering and "a refused call changes nothing" are cvo_device_image's, rule for rule, with
+ * cloud_stream in the place of image_stream; what differs is said here.
+ *
+ * Ingest is eager.  One kernel launch per call (cvo_ingest_clouds_kernel) copies all clouds of the call into cloud objects the library owns -- stream
+ * slots and tracker objects hold a cloud for several steps -- and one more launch makes the boxes of their 32-point groups.  Both run on the object's
+ * own stream, never on the caller's.  The caller's memory is the caller's again under image_stream's rule: with a cloud_stream an event edge in and an
+ * event edge out; with NULL when the call has returned.  The host waits once per call, for the ingest launch alone, in either form: the launch leaves
+ * each cloud's cost sample (cvo_batch_set_pairs' mean of 1/z^2 over every 16th point) in pinned memory, as the image path waits for its point
+ * counts.  Every result is bit-identical to the same floats handed over from the host (cvo_batch_set_pairs; handles driven through cvo_set_pcd,
+ * cvo_match_odometry, cvo_update_fixed_pcd).
+ *
+ * Validation: CVO_ERR_INVALID, the message naming cloud and field, for n outside 0 .. 65535; a stride that is negative or no multiple of 4;
+ * xyz_stride in 1 .. 11; exactly one of the two feature strides 0; and, for n > 0, a null pointer, a base pointer that is not 4-byte aligned, and a
+ * pointer the device cannot read, by the hipPointerGetAttributes rule of cvo_device_image with the extents
+ *   [xyz, xyz + (n-1)*xyz_stride + 12)   and   [feat, feat + (n-1)*feat_point_stride + 4*feat_channel_stride + 4)
+ * which must lie inside the allocation, and outside which the kernel reads nothing.  Pinned or registered host memory and managed memory are
+ * accepted (a route for host callers); pageable host memory and another device's memory are refused.  n == 0 is valid and needs no pointers.
+ *
+ * cvo_batch_set_pairs_device_clouds: cvo_batch_set_pairs_images with clouds in place of generated images: n_clouds distinct clouds, pair k takes
+ *   fixed_cloud[k] / moving_cloud[k]; a cloud listed for several pairs is ingested once and held by all of them; fresh-object state.
+ * cvo_batch_advance_device_clouds: cvo_batch_advance_images per slot: a slot that has not started takes the cloud as its FIXED cloud, a started one
+ *   does update_fixed_pcd by a move of ownership and takes the cloud as its MOVING cloud.  An unconsumed stage for a listed slot is dropped.
+ * cvo_tracks_step_device_clouds_async (declared with the tracker steps below): cvo_tracks_step_async, the frame's cloud ingested once and held by
+ *   both objects; cvo_track_step::points is n; n == 0 is an empty frame (CVO_ERR_EMPTY_CLOUD, the keyframe object left alone).
+ * A slot or stream may receive images in one step and clouds in another.  For clouds handed over this way cvo_*_get_selected_points gives *n = 0
+ * and cvo_*_get_cloud returns the floats that were handed over.  Reading the caller's device memory in place, without the copy, is not offered: it
+ * would need cvo_host_register's lifetime contract. */
+typedef struct cvo_device_cloud {
+    const void* xyz;               /* float32, device-accessible; point i at xyz + i*xyz_stride: x, y, z */
+    const void* feat;              /* float32; feature c (0..4) of point i at feat + i*feat_point_stride + c*feat_channel_stride */
+    long long xyz_stride;          /* bytes; 0 = 12 (data_type.h:30) */
+    long long feat_point_stride;   /* bytes; both feature strides 0 = the reference layout: 4 and 4*n (data_type.h:75) */
+    long long feat_channel_stride;
+    int n;                         /* 0 .. 65535 */
+    int pad_;
+} cvo_device_cloud;               /* 48 bytes */
+int cvo_check_device_clouds(int device, int count, const cvo_device_cloud* clouds);      /* the validation alone: launches nothing */
+int cvo_batch_set_pairs_device_clouds(cvo_batch b, int first, int count, int n_clouds, const cvo_device_cloud* clouds,
+                                      const int* fixed_cloud, const int* moving_cloud, void* cloud_stream);
+int cvo_batch_advance_device_clouds(cvo_batch b, int count, const int* slots, const cvo_device_cloud* clouds, void* cloud_stream);
+/* The ingest kernel alone (tests): every cloud's planes lie between 64 guard bytes on either side, prefilled with 0xA5.  xyz_out: the clouds' n x 3
+ * positions one cloud behind the other, feat_out: their 5 channel-major arrays of n likewise (the reference layout); cost_out: count x {sum of the
+ * cost sample's terms, samples}; *guards_intact = 1 when no guard byte changed. */
+int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* clouds, float* xyz_out, float* feat_out,
+                               double* cost_out /* count x {sum, samples} */, int* guards_intact);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
@@ -699,6 +746,9 @@ int cvo_tracks_step_device_async(cvo_tracks t, int count, const int* streams, co
                                  const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* hip_stream, void* image_stream);
 int cvo_tracks_stage_device_async(cvo_tracks t, int count, const int* streams, const cvo_device_image* images, int width, int height,
                                   const cvo_camera* cams, const int* cam_index /* NULL: cams[0] for every image */, void* image_stream);
+/* The cloud twin (see cvo_device_cloud above): the step's frames as clouds in caller-owned device memory. */
+int cvo_tracks_step_device_clouds_async(cvo_tracks t, int count, const int* streams, const cvo_device_cloud* clouds,
+                                        void* hip_stream, void* cloud_stream);
 int cvo_tracks_done(cvo_tracks t, int* done);
 int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out /* may be NULL */, int count);
 int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept);
