@@ -119,7 +119,7 @@ ABI_SYMBOLS = [
     "cvo_set_pcd_images", "cvo_shared_cloud_count", "cvo_stage_next_frame", "cvo_staged_frame_count", "cvo_queued_score_count", "cvo_set_num_want", "cvo_match_odometry_images", "cvo_match_keyframe_images", "cvo_get_cloud", "cvo_get_selected_points",
     "cvo_batch_enqueue_innerproduct", "cvo_batch_innerproduct_results", "cvo_batch_compute_innerproduct",
     "cvo_selftest_cubic_step", "cvo_selftest_exp_sek3", "cvo_selftest_dist_se3", "cvo_selftest_libm", "cvo_selftest_pair_values",
-    "cvo_function_inner_product_clouds", "cvo_se3_hessian_clouds", "cvo_batch_set_max_workgroups", "cvo_batch_set_adoption", "cvo_batch_last_adoptions", "cvo_batch_last_adoption_retractions", "cvo_batch_last_launch_shape",
+    "cvo_function_inner_product_clouds", "cvo_se3_hessian_clouds", "cvo_batch_set_max_workgroups", "cvo_batch_set_adoption", "cvo_batch_last_adoptions", "cvo_batch_last_adoption_retractions", "cvo_batch_last_launch_shape", "cvo_batch_queue_class",
     "cvo_adaptive_default_params", "cvo_adaptive_align",
     "cvo_shard_range", "cvo_comm_unique_id", "cvo_comm_create", "cvo_comm_create_all", "cvo_host_register", "cvo_host_unregister", "cvo_comm_destroy", "cvo_comm_info", "cvo_comm_set_gather_stream", "cvo_comm_library_path", "cvo_batch_gather_results",
     "cvo_gather_results", "cvo_multi_create", "cvo_multi_destroy", "cvo_multi_batch", "cvo_multi_align_async", "cvo_multi_wait",
@@ -250,6 +250,7 @@ def load_library():
     L.cvo_batch_last_adoptions.argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_batch_last_adoption_retractions.argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_batch_last_launch_shape.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.cvo_batch_queue_class.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.cvo_adaptive_default_params.argtypes = [C.POINTER(AdaptiveParams)]
     L.cvo_adaptive_align.argtypes = [C.c_int, C.POINTER(AdaptiveParams), fp, fp, C.c_int, fp, fp, C.c_int, fp, fp, fp, fp, ip, C.POINTER(AdaptiveRow), C.c_int, ip]
     L.cvo_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
@@ -1310,6 +1311,12 @@ class CvoBatch:
         _check(self.L.cvo_batch_last_launch_shape(self.h, C.byref(grid), C.byref(helpers), C.byref(conc)))
         return dict(kernel_ms=ms.value, iterations_total=it.value, candidates_total=ca.value, nonzeros_total=nz.value,
                     grid=grid.value, helpers=helpers.value, concurrent=conc.value)
+
+    def queue_class(self):
+        """cvo_batch_queue_class: (class of the batch's own stream: 0 = normal priority, 1 = the second class; hardware queues per class)."""
+        cls = C.c_int(0); lim = C.c_int(0)
+        _check(self.L.cvo_batch_queue_class(self.h, C.byref(cls), C.byref(lim)))
+        return cls.value, lim.value
 
     def last_phase_seconds(self):
         out = np.zeros(10); _check(self.L.cvo_batch_last_phase_seconds(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))

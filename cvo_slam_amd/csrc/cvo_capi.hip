@@ -11,6 +11,7 @@
 #include <functional>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -28,6 +29,12 @@
 #include "../../include/cvo_hip.h"
 #include "cvo_device.h"
 #include "cvo_math.hpp"
+#include "cvo_queue_classes.hpp"
+
+// what CVO_HIP_QUEUE_CLASSES defaults to (queue_classes(); measured in profiles/hw_queue_classes_ab.txt)
+#ifndef CVO_QUEUE_CLASSES_DEFAULT
+#define CVO_QUEUE_CLASSES_DEFAULT 1
+#endif
 
 // the align kernel's translation unit is in the library four times (cvo_kernels.hip, head comment): cvohip = two waves per SIMD, cvohip_w3 = three;
 // cvohip_e337 and cvohip_e337_w3 = the same two with the arithmetic modes (CVO_ARITH_*; the default builds refuse any mode bit)
@@ -385,6 +392,23 @@ int hw_queue_count() {
     static const int q = [] { const char* e = std::getenv("GPU_MAX_HW_QUEUES"); const int v = e ? std::atoi(e) : 0; return v > 0 ? v : 4; }();
     return q;
 }
+// Queue classes (cvo_queue_classes.hpp; DESIGN.md section 4.1, "Queue classes"): the runtime's limit of Q hardware queues holds per stream PRIORITY, so the
+// streams of batch objects are dealt over two priorities -- class 0 normal, class 1 the least -- and 2 Q of them have a hardware queue each.  The greatest
+// priority stays with the stage streams (stage_ready).  CVO_HIP_QUEUE_CLASSES, read once: 0 = every stream normal, 1 = normal then least,
+// 2 = normal then greatest (for one measurement: such launches take the queues the staged frames count on).
+struct QueueClasses { int mode = 0; std::vector<std::array<int, cvo_qc::CLASSES>> live; };   // live[device][c]: library-made engine streams alive in class c (guarded by adopt_submit_mutex)
+QueueClasses& queue_classes() {
+    static QueueClasses q = [] { QueueClasses v; const char* e = std::getenv("CVO_HIP_QUEUE_CLASSES"); v.mode = e ? std::max(0, std::min(2, std::atoi(e))) : CVO_QUEUE_CLASSES_DEFAULT; return v; }();
+    return q;
+}
+// the stream priority of class 1 on the current device; false when the device has no such level (or the dealer is off): everything is class 0 then
+bool second_class_priority(int* priority) {
+    const int mode = queue_classes().mode;
+    int least = 0, greatest = 0;
+    if (mode == 0 || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *priority = mode == 2 ? greatest : least;                       // (numerically greater = lower priority; normal is 0)
+    return mode == 2 ? greatest < 0 : least > 0;
+}
 
 // Launch machinery shared by single-object handles and batches.
 struct Engine {
@@ -425,6 +449,9 @@ struct Engine {
     bool adopt = false;          // finished workgroups help with the pairs of their launch that still run (one workgroup and one slot per pair; CVO_HIP_ADOPT)
     int last_grid = 0, last_helpers = 0, last_concurrent = 0;   // the last align launch: its workgroups, those of them launched as helpers, launch_share's estimate
     bool registered = false;     // in live_engines() (guarded by adopt_submit_mutex)
+    int queue_class = 0;         // the priority class of `stream` (queue_classes(); guarded by adopt_submit_mutex once other engines can see this one)
+    bool class_counted = false;  // ... and it holds a place in queue_classes().live
+    hipStream_t retired_stream = nullptr;   // the class-1 stream this engine left (leave_second_class): kept, idle, until destroy() for whoever still names it
     bool queue_behind = false;   // tracker streams (cvo_tracks_step_async): this engine's launches are queued on a stream that holds other work of the step, which the
                                  // host must not wait for; the engine's own previous launch is what its descriptor table has to be safe from, and that is ev1
 
@@ -432,28 +459,65 @@ struct Engine {
     // streams onto Q hardware queues (hw_queue_count) by a rule of its own; launches on one hardware queue run one after the other.
     // So with `inflight` align launches of this library on this device still running or queued (this engine's earlier launch is ahead of
     // this one on its stream and does not count), about concurrent = min(Q, inflight + 1) of them run side by side, each on a share of
-    // capacity / concurrent workgroup slots, and when inflight >= Q this one waits behind one of them: deferred.  It is an estimate -- the
+    // capacity / concurrent workgroup slots, and when inflight >= Q this one waits behind one of them: deferred.  The limit Q holds per
+    // queue class, so the launches are counted per class of their engines (cvo_qc::launch_share).  It is an estimate -- the
     // queue mapping is the runtime's, and launches of other processes are not seen.  When it is wrong, only speed suffers (helpers hold back,
     // or take a compute unit a later launch wanted); results do not depend on it.
     void launch_share(int* concurrent, bool* deferred) {
         std::vector<const Engine*>& live = live_engines();
         if (!registered) { live.push_back(this); registered = true; }
-        int inflight = 0;
+        int inflight[cvo_qc::CLASSES] = {0, 0};
         for (const Engine* o : live) {
             if (o == this || o->device != device || !o->launched) continue;
             const hipError_t e = hipEventQuery(o->ev1);
-            if (e == hipErrorNotReady) { ++inflight; (void)hipGetLastError(); }
+            if (e == hipErrorNotReady) { ++inflight[o->queue_class]; (void)hipGetLastError(); }
         }
-        const int Q = hw_queue_count();
-        *concurrent = std::min(Q, inflight + 1);
-        *deferred = inflight >= Q;
+        cvo_qc::launch_share(inflight, queue_class, hw_queue_count(), concurrent, deferred);
     }
     void forget() {
-        if (!registered) return;
         std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+        if (class_counted) { --queue_classes().live[device][queue_class]; class_counted = false; }   // the place in its queue class goes back to the dealer
+        if (!registered) return;
         std::vector<const Engine*>& live = live_engines();
         live.erase(std::remove(live.begin(), live.end(), this), live.end());
         registered = false;
+    }
+    // The engine's own stream, in the queue class the dealer gives it (dealt: a batch object of the public API; everything else is class 0 and counted there).
+    int make_stream(bool dealt) {
+        int prio = 0;
+        const bool second = second_class_priority(&prio);
+        {
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            auto& live = queue_classes().live;
+            if ((int)live.size() <= device) live.resize(device + 1, std::array<int, cvo_qc::CLASSES>{});
+            queue_class = cvo_qc::choose_class(live[device].data(), hw_queue_count(), dealt, second);
+            ++live[device][queue_class]; class_counted = true;
+        }
+        if (queue_class == 0) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        else HIP_TRY(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio));
+        return CVO_OK;
+    }
+    // Launches of cooperating workgroups never run below normal priority: the workgroups of a pair wait for each other, and beside a steady supply of normal
+    // launches a below-normal one could wait for siblings that never get a compute unit.  A class-1 engine that plans such a launch on its own stream moves
+    // to class 0 first, once: its stream drains, a normal stream takes its place wherever the engine names it, the dealer's counts follow.  The old stream
+    // stays alive and idle until destroy(): clouds shared with other objects may still name it (Cloud::boxes_stream), and waiting for an idle stream is free.
+    int leave_second_class() {
+        int prio = 0;
+        if (queue_class == 0 || !second_class_priority(&prio) || prio <= 0) return CVO_OK;   // (class 1 above normal, CVO_HIP_QUEUE_CLASSES=2: nothing to fear)
+        HIP_TRY(hipStreamSynchronize(stream));
+        hipStream_t fresh = nullptr;
+        HIP_TRY(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
+        {
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            auto& live = queue_classes().live[device];
+            if (class_counted) { --live[queue_class]; ++live[0]; }
+            queue_class = 0;
+        }
+        for (hipStream_t& r : ring_readers) if (r == stream) r = fresh;
+        if (packdesc_stream == stream) packdesc_stream = fresh;
+        if (last_stream == stream) last_stream = fresh;
+        retired_stream = stream; stream = fresh;
+        return CVO_OK;
     }
 
     void release_slots() {
@@ -483,11 +547,11 @@ struct Engine {
         return G;
     }
 
-    int init(int dev, const cvo_params& prm) {
+    int init(int dev, const cvo_params& prm, bool dealt = false) {
         device = dev;
         int rc = check_device(dev, &num_cus); if (rc) return rc;
         HIP_TRY(hipSetDevice(dev));
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if ((rc = make_stream(dealt))) return rc;
         HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1));
         P = to_dev(prm);
         if (const char* e = std::getenv("CVO_HIP_FLAT_CAP")) capf_request = std::atoi(e);
@@ -535,7 +599,8 @@ struct Engine {
         if (ev1) (void)hipEventDestroy(ev1);
         if (ev_ring) (void)hipEventDestroy(ev_ring);
         if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr; ev0 = ev1 = nullptr;
+        if (retired_stream) (void)hipStreamDestroy(retired_stream);
+        stream = retired_stream = nullptr; ev0 = ev1 = nullptr;
     }
 
     // Host arrays in the reference layout -> the clouds' float4 planes in HBM.  All clouds of one hand-over travel together: their
@@ -857,10 +922,11 @@ struct Engine {
         HIP_TRY(hipSetDevice(device));
         const int n = (int)pairs.size();
         if (n <= 0) return fail(CVO_ERR_INVALID, "no pairs to align");
-        hipStream_t s = on_stream ? on_stream : stream;
-        { int rcs = settle_uploads(s); if (rcs) return rcs; }
         int nf_max = 0, nm_max = 0;
         for (const PairIn& p : pairs) { nf_max = std::max(nf_max, p.fixed ? p.fixed->n : 0); nm_max = std::max(nm_max, p.moving ? p.moving->n : 0); }
+        if (queue_class != 0 && !on_stream && pick_workgroups(n, nf_max) > 1) { int rcq = leave_second_class(); if (rcq) return rcq; }   // (before the stream is named below)
+        hipStream_t s = on_stream ? on_stream : stream;
+        { int rcs = settle_uploads(s); if (rcs) return rcs; }
         const int g_floor = std::max(1, (((nf_max + 127) / 128) + (MAX_ROWS_PER_WG / 128) - 1) / (MAX_ROWS_PER_WG / 128));
         std::unique_lock<std::mutex> book_lock; std::vector<hipEvent_t> run_after;
         const int G = acquire_slots(pick_workgroups(n, nf_max), g_floor, n, book_lock, run_after);   // fewer workgroups per pair beside other handles' cooperative launches
@@ -2259,12 +2325,14 @@ int batch_launch(cvo_batch b, const int* slots, int n, hipStream_t stream, bool 
 }
 }  // namespace
 
-int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* out) {
+// dealt: the object's stream may take the second queue class (Engine::make_stream) -- the batch objects a caller makes; the two inside a tracker
+// object stay normal, their launches go on a stream that holds other work of the step (queue_behind)
+static int batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* out, bool dealt) {
     if (!out || max_pairs <= 0) return fail(CVO_ERR_INVALID, "bad argument");
     *out = nullptr;
     std::unique_ptr<cvo_batch_s> b(new cvo_batch_s());
     if (p) b->prm = *p; else cvo_default_params(&b->prm);
-    int rc = b->eng.init(device, b->prm); if (rc) { b->eng.destroy(); return rc; }
+    int rc = b->eng.init(device, b->prm, dealt); if (rc) { b->eng.destroy(); return rc; }
     b->max_pairs = max_pairs;
     b->eng.defer_pack = true;                                       // hand-overs are packed by the next align launch (Engine::upload_many)
     b->eng.rec_hint = max_pairs + 1;                                // room for the padding record of an uneven shard (cvo_shard_range)
@@ -2278,6 +2346,7 @@ int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* 
     *out = b.release();
     return CVO_OK;
 }
+int cvo_batch_create(const cvo_params* p, int device, int max_pairs, cvo_batch* out) { return batch_create(p, device, max_pairs, out, true); }
 int cvo_batch_destroy(cvo_batch b) {
     if (!b) return CVO_OK;
     (void)hipSetDevice(b->eng.device);
@@ -3297,6 +3366,13 @@ int cvo_batch_last_launch_shape(cvo_batch b, int* grid, int* helpers, int* concu
     if (concurrent) *concurrent = b->eng.last_concurrent;
     return CVO_OK;
 }
+int cvo_batch_queue_class(cvo_batch b, int* cls, int* per_class_limit) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+    if (cls) *cls = b->eng.queue_class;
+    if (per_class_limit) *per_class_limit = hw_queue_count();
+    return CVO_OK;
+}
 int cvo_batch_last_nonzeros(cvo_batch b, long long* nonzeros_total) {
     if (!b || !nonzeros_total) return fail(CVO_ERR_INVALID, "null argument");
     long long nz = 0;
@@ -3571,8 +3647,8 @@ int cvo_tracks_create(const cvo_params* p, int device, int max_streams, cvo_trac
     std::unique_ptr<cvo_tracks_s> t(new cvo_tracks_s());
     if (p) t->prm = *p; else cvo_default_params(&t->prm);
     t->max_streams = max_streams;
-    int rc = cvo_batch_create(&t->prm, device, max_streams, &t->odo); if (rc) return rc;
-    rc = cvo_batch_create(&t->prm, device, max_streams, &t->key);
+    int rc = batch_create(&t->prm, device, max_streams, &t->odo, false); if (rc) return rc;
+    rc = batch_create(&t->prm, device, max_streams, &t->key, false);
     // the keyframe launch starts from device states the link kernel writes before that launch has sized the table: sized here, once
     if (!rc) rc = t->key->eng.d_states.ensure(sizeof(PairState) * (size_t)max_streams);
     if (rc) { cvo_batch_destroy(t->odo); cvo_batch_destroy(t->key); return rc; }

@@ -528,6 +528,13 @@ int cvo_batch_last_launch(cvo_batch b, float* kernel_ms, long long* iterations_t
 /* the shape of the last launch: its workgroups, how many of them were launched as helpers (adoption), and the number of launches
  * (this one included) it was estimated to share the device with when it was submitted */
 int cvo_batch_last_launch_shape(cvo_batch b, int* grid, int* helpers, int* concurrent);
+/* The queue class of the batch's own stream, and how many hardware queues a class has (GPU_MAX_HW_QUEUES, read and never set; 4 when unset).
+ * The HIP runtime keeps that limit per stream priority, so the library deals the streams of batch objects over two priorities: class 0 = normal
+ * for the first `per_class_limit` objects alive on a device, class 1 = the least priority for the next as many, then whichever class has fewer.
+ * Launches of class 1 yield to normal-priority work where both wait for a compute unit.  A class-1 object that plans a launch with more than one
+ * workgroup per pair moves to class 0 first (cooperating workgroups never run below normal priority).  Handles, the batches inside a tracker
+ * object and streams the caller passes are left alone.  CVO_HIP_QUEUE_CLASSES=0 (read once): every stream normal. */
+int cvo_batch_queue_class(cvo_batch b, int* cls, int* per_class_limit);
 /* nonzeros of the kernel matrix A (cvo.cpp:166-175) summed over every executed iteration of every pair of the last launch: the work the
  * reference's arithmetic is defined on (bench.py prices the kernel's instructions per nonzero with it) */
 int cvo_batch_last_nonzeros(cvo_batch b, long long* nonzeros_total);
