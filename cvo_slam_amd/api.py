@@ -99,6 +99,10 @@ class TrackScores(C.Structure):
                 ("inliers", C.c_int), ("cos_angle", C.c_float)]
 
 
+class PointSupportDst(C.Structure):      # cvo_point_support_dst: one pair's four output arrays (host or device memory, by entry point)
+    _fields_ = [("sum_moving", C.c_void_p), ("count_moving", C.c_void_p), ("sum_fixed", C.c_void_p), ("count_fixed", C.c_void_p)]
+
+
 class TrackStep(C.Structure):
     """cvo_track_step: one stream's share of a tracker step (cvo_hip.h: cvo_tracks_wait)."""
     _fields_ = [("phase", C.c_int), ("points", C.c_int), ("odometry", PairResult), ("odometry_scores", TrackScores),
@@ -138,6 +142,7 @@ ABI_SYMBOLS = [
     "cvo_batch_stage_device_images", "cvo_tracks_step_device_async", "cvo_tracks_stage_device_async",
     "cvo_check_device_clouds", "cvo_selftest_ingest_clouds", "cvo_batch_set_pairs_device_clouds", "cvo_batch_advance_device_clouds",
     "cvo_tracks_step_device_clouds_async",
+    "cvo_point_support", "cvo_batch_point_support", "cvo_batch_point_support_device", "cvo_tracks_point_support", "cvo_tracks_point_support_device",
 ]
 
 _lib = None
@@ -320,6 +325,12 @@ def load_library():
     L.cvo_batch_set_pairs_device_clouds.argtypes = [vp, C.c_int, C.c_int, C.c_int, dcp, ip, ip, vp]
     L.cvo_batch_advance_device_clouds.argtypes = [vp, C.c_int, ip, dcp, vp]
     L.cvo_tracks_step_device_clouds_async.argtypes = [vp, C.c_int, ip, dcp, vp, vp]
+    psp = C.POINTER(PointSupportDst)
+    L.cvo_point_support.argtypes = [vp, C.c_int, fp, C.c_int, fp, ip, C.c_int, fp, ip, C.c_int]
+    L.cvo_batch_point_support.argtypes = [vp, C.c_int, ip, psp]
+    L.cvo_batch_point_support_device.argtypes = [vp, C.c_int, ip, psp, vp]
+    L.cvo_tracks_point_support.argtypes = [vp, C.c_int, C.c_int, ip, psp]
+    L.cvo_tracks_point_support_device.argtypes = [vp, C.c_int, C.c_int, ip, psp, vp]
     _lib = L
     return L
 
@@ -647,6 +658,60 @@ def selftest_ingest_clouds(clouds, device: int = 0):
     return out, cost, bool(ok.value)
 
 
+# ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms
+_SUPPORT_KEYS = (("sum_moving", "<f4"), ("count_moving", "<i4"), ("sum_fixed", "<f4"), ("count_fixed", "<i4"))
+
+
+def _support_host_records(sizes):
+    """numpy arrays for pairs of (n_moving, n_fixed) points, and the records that point at them"""
+    arrays = [dict(sum_moving=np.zeros(nm, np.float32), count_moving=np.zeros(nm, np.int32),
+                   sum_fixed=np.zeros(nf, np.float32), count_fixed=np.zeros(nf, np.int32)) for nm, nf in sizes]
+    recs = (PointSupportDst * max(1, len(arrays)))()
+    for r, a in zip(recs, arrays):
+        for key, _ in _SUPPORT_KEYS:
+            setattr(r, key, a[key].ctypes.data)
+    return arrays, recs
+
+
+def _support_device_records(out, sizes):
+    """records over caller-owned device arrays: out[k] is a dict with sum_moving / count_moving and / or sum_fixed / count_fixed, each anything
+    with __cuda_array_interface__ (torch ROCm tensors): float32 / int32, one-dimensional, contiguous, one entry per point of its cloud"""
+    if len(out) != len(sizes):
+        raise ValueError("out: one dict per pair")
+    recs = (PointSupportDst * max(1, len(out)))()
+    for r, o, (nm, nf) in zip(recs, out, sizes):
+        if set(o) - {k for k, _ in _SUPPORT_KEYS}:
+            raise ValueError(f"out: unknown keys {sorted(set(o) - {k for k, _ in _SUPPORT_KEYS})}")
+        for key, typestr in _SUPPORT_KEYS:
+            a = o.get(key)
+            if a is None:
+                continue
+            if not hasattr(a, "__cuda_array_interface__"):
+                raise ValueError(f"out[{key}]: device memory wanted, an object with __cuda_array_interface__ (host arrays: out=None)")
+            cai = a.__cuda_array_interface__
+            n = nm if key.endswith("moving") else nf
+            if cai["typestr"] != typestr:
+                raise ValueError(f"out[{key}]: dtype {cai['typestr']}, wanted {typestr}")
+            if tuple(cai["shape"]) != (n,):
+                raise ValueError(f"out[{key}]: shape {tuple(cai['shape'])}, the cloud has {n} points")
+            if cai.get("strides") not in (None, (4,)):
+                raise ValueError(f"out[{key}]: not contiguous")
+            setattr(r, key, int(cai["data"][0]))
+    return recs
+
+
+def _settle_support_writer(out, out_stream):
+    """out_stream None: the arrays are taken as ready to be written.  torch tensors are touched on torch's current stream, so that stream is
+    synchronised first (as _settle_writer does for images that are read)."""
+    if out_stream is not None or "torch" not in sys.modules or not out:
+        return
+    torch = sys.modules["torch"]
+    for a in out[0].values():
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            torch.cuda.current_stream(a.device).synchronize()
+            return
+
+
 class Cvo:
     """One `cvo::cvo` object (cvo.hpp:82-282) living on a gfx950 device."""
 
@@ -754,6 +819,18 @@ class Cvo:
         r = InnP(); t, tp = _tran(tran_a)
         _check(self.L.cvo_function_inner_product(self.h, slot_a, tp, slot_b, C.byref(r)))
         return (r.value, r.num, r.num_e)
+
+    # -- not in the reference: the terms of function_inner_product per point (cvo_hip.h, "per-point support")
+    def point_support(self, slot_a, tran_a, slot_b):
+        """(sum_a, count_a, sum_b, count_b): per point of the cloud in slot_a (moved by tran_a when given) the sum and number of its kernel
+        values against slot_b's points inside both gates, and the same per point of slot_b"""
+        na, nb = C.c_int(0), C.c_int(0)
+        _check(self.L.cvo_get_cloud(self.h, slot_a, None, None, 0, C.byref(na))); _check(self.L.cvo_get_cloud(self.h, slot_b, None, None, 0, C.byref(nb)))
+        sa = np.zeros(na.value, np.float32); ca = np.zeros(na.value, np.int32); sb = np.zeros(nb.value, np.float32); cb = np.zeros(nb.value, np.int32)
+        fp = C.POINTER(C.c_float); ip = C.POINTER(C.c_int); t, tp = _tran(tran_a)
+        _check(self.L.cvo_point_support(self.h, slot_a, tp, slot_b, sa.ctypes.data_as(fp), ca.ctypes.data_as(ip), na.value,
+                                        sb.ctypes.data_as(fp), cb.ctypes.data_as(ip), nb.value))
+        return sa, ca, sb, cb
 
     # -- cvo.cpp:620-759
     def se3_hessian(self, slot_a, tran_a, slot_b, inliers: int = 0):
@@ -1188,6 +1265,7 @@ class CvoBatch:
         """cvo_batch_align_pairs_async: one launch over the listed slots; results come back in list order"""
         sl = np.ascontiguousarray(slots, np.int32).reshape(-1)
         _check(self.L.cvo_batch_align_pairs_async(self.h, sl.shape[0], sl.ctypes.data_as(C.POINTER(C.c_int)), C.c_void_p(stream) if stream else None))
+        self._last_slots = sl.copy()
         return sl.shape[0]
 
     def align_pairs(self, slots):
@@ -1282,6 +1360,7 @@ class CvoBatch:
 
     def align_async(self, n_pairs: int, stream: int | None = None):
         _check(self.L.cvo_batch_align_async(self.h, n_pairs, C.c_void_p(stream) if stream else None))
+        self._last_slots = np.arange(n_pairs, dtype=np.int32)        # (position i of the launch is slot i)
 
     def wait(self, n: int = 0):
         if n <= 0:
@@ -1357,6 +1436,37 @@ class CvoBatch:
     def compute_innerproduct(self, n: int):
         self.enqueue_innerproduct(n)
         return self.innerproduct_results(n)
+
+    # -- not in the reference: per-point support of the last launch's pairs (cvo_hip.h, "per-point support")
+    def point_support(self, pairs=None, out=None, out_stream=None):
+        """For positions `pairs` of the last launch (None: all of an align(n) / align_pairs(slots) launch), the moving cloud under the pair's own
+        result transform and ell against its fixed cloud.  out None: one dict of numpy arrays per pair (sum_moving, count_moving, sum_fixed,
+        count_fixed).  Else out is one dict per pair of device arrays under those keys (a direction may be left out) and the kernel writes them
+        itself: with an out_stream (a torch.cuda.Stream or a raw hipStream_t) that stream waits for the launch and the host does not, with None
+        the call waits.  Returns out."""
+        last = getattr(self, "_last_slots", None)
+        if pairs is None:
+            if last is None and out is None:
+                raise ValueError("pairs: name the positions (the launch was not started through this object, its length is not known here)")
+            pairs = np.arange(len(last) if last is not None else len(out))
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1)
+        sizes = []
+        for i in pr:
+            slot = int(last[i]) if last is not None and 0 <= i < len(last) else int(i)
+            nm, nf = C.c_int(0), C.c_int(0)
+            if 0 <= slot < self.max_pairs:                           # (a bad index is the library's to refuse)
+                _check(self.L.cvo_batch_get_cloud(self.h, slot, SLOT_MOVING, None, None, 0, C.byref(nm)))
+                _check(self.L.cvo_batch_get_cloud(self.h, slot, SLOT_FIXED, None, None, 0, C.byref(nf)))
+            sizes.append((nm.value, nf.value))
+        ip = C.POINTER(C.c_int)
+        if out is None:
+            arrays, recs = _support_host_records(sizes)
+            _check(self.L.cvo_batch_point_support(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
+            return arrays
+        recs = _support_device_records(out, sizes)
+        _settle_support_writer(out, out_stream)
+        _check(self.L.cvo_batch_point_support_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
+        return out
 
     def results_to_device(self, dst_device_ptr: int, n: int, stream: int | None = None):
         _check(self.L.cvo_batch_results_to_device(self.h, C.c_void_p(dst_device_ptr), n, C.c_void_p(stream) if stream else None))
@@ -1538,6 +1648,28 @@ class CvoTracks:
             raise ValueError("one decision per stream")
         ip = C.POINTER(C.c_int)
         _check(self.L.cvo_tracks_commit(self.h, sl.shape[0], sl.ctypes.data_as(ip), ac.ctypes.data_as(ip)))
+
+    # -- not in the reference: per-point support of the step just waited for (cvo_hip.h, "per-point support")
+    def point_support(self, obj: int, streams, out=None, out_stream=None):
+        """Between wait() of a step and the next commit() or step: for the listed streams of that step whose object `obj` (ODOMETRY / KEYFRAME)
+        aligned, the step's frame at that object's result transform against the object's fixed cloud.  out / out_stream as CvoBatch.point_support."""
+        sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        sizes = []
+        for s in sl:
+            nm, nf = C.c_int(0), C.c_int(0)
+            if 0 <= s < self.max_streams and obj in (0, 1):          # (anything else is the library's to refuse)
+                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_MOVING, None, None, 0, C.byref(nm)))
+                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_FIXED, None, None, 0, C.byref(nf)))
+            sizes.append((nm.value, nf.value))
+        ip = C.POINTER(C.c_int)
+        if out is None:
+            arrays, recs = _support_host_records(sizes)
+            _check(self.L.cvo_tracks_point_support(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs))
+            return arrays
+        recs = _support_device_records(out, sizes)
+        _settle_support_writer(out, out_stream)
+        _check(self.L.cvo_tracks_point_support_device(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
+        return out
 
     def get_cloud(self, s: int, obj: int, slot: int):
         """the cloud of stream s, object ODOMETRY / KEYFRAME, slot SLOT_FIXED / SLOT_MOVING / SLOT_PREVIOUS: xyz (n, 3), feat (5, n)"""

@@ -109,6 +109,9 @@ hipError_t launch_track_link(const TrackLinkIn* in, const PairState* odo_states,
 hipError_t launch_selftest_pairs(const float* in, float* out, float* aux, int n, float ell, const DevParams& P, hipStream_t s);
 hipError_t launch_score(const ScoreBatch& B, const ScoreDesc* more, int nreq, int row_blocks, int chunks, const DevParams& P, double* partials,
                         double* out_pinned, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
+int support_row_blocks(int na);
+hipError_t launch_support(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, const SupportDesc* reqs, int n_reqs, int row_blocks,
+                          const DevParams& P, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
 }  // namespace cvohip
 
 using namespace cvohip;
@@ -592,6 +595,10 @@ struct Engine {
         if (last_stream && last_stream != stream) (void)hipStreamSynchronize(last_stream);
         release_slots();
         d_scoredescs.release(); h_scoredescs.release(); h_counts.release();
+        if (ev_support) { (void)hipEventSynchronize(ev_support); (void)hipEventDestroy(ev_support); ev_support = nullptr; }   // (a device-form call may sit on a caller's stream)
+        if (ev_support_in) { (void)hipEventDestroy(ev_support_in); ev_support_in = nullptr; }
+        support_queued = false;
+        d_support_tab.release(); d_support_moved.release(); d_support_out.release(); h_support_tab.release(); h_support_out.release();
         for (DevBuf* b : {&d_bgr, &d_depth, &d_I0, &d_I1, &d_I2, &d_dx0, &d_dy0, &d_abs0, &d_abs1, &d_abs2, &d_ths, &d_thsS, &d_map, &d_pattern, &d_counts, &d_tiles}) b->release();
         for (DevBuf* b : {&d_descs, &d_states, &d_ybuf, &d_jT, &d_ent, &d_surv, &d_xch, &d_queue, &d_trace, &d_tracelen, &d_partials, &d_raw, &d_ring, &d_records}) b->release();
         for (PinBuf* b : {&h_descs, &h_states, &h_states_in, &h_stage, &h_partials, &h_tail, &h_packdesc, &h_rawtab}) b->release();
@@ -1376,6 +1383,138 @@ struct Engine {
         int rc = score_enqueue(rq, n, stream); if (rc) return rc;
         return score_collect(n, out);
     }
+
+    // Per-point support (cvo_support_kernels.hip; include/cvo_hip.h: cvo_point_support): for every request the rows of a against the columns of b
+    // (sum_a / count_a, a->n entries) and the roles swapped (sum_b / count_b, b->n entries); a direction whose two arrays are null is not computed.
+    // ell and the transform as a ScoreReq names them.  to_host: the arrays are host memory, filled by support_collect; else device memory the
+    // caller owns (checked by the entry point), written by the kernel itself.
+    struct SupportReq {
+        const Cloud* a; const float* tran; const Cloud* b; float ell;
+        int from; bool tran_from_state;
+        float* sum_a; int* count_a; float* sum_b; int* count_b;
+    };
+    struct SupportCopy { void* dst; size_t off, bytes; };
+    // buffers of its own: nothing here is shared with a score block in flight.  One call at a time: the next one waits for ev_support first.
+    DevBuf d_support_tab, d_support_moved, d_support_out; PinBuf h_support_tab, h_support_out;
+    hipEvent_t ev_support = nullptr, ev_support_in = nullptr; bool support_queued = false;
+    std::vector<SupportCopy> support_copies; hipStream_t support_stream = nullptr;
+    int support_enqueue(const SupportReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
+        HIP_TRY(hipSetDevice(device));
+        if (n <= 0) return fail(CVO_ERR_INVALID, "bad support request count");
+        for (int r = 0; r < n; ++r) {
+            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
+            if (!rq[r].sum_a != !rq[r].count_a || !rq[r].sum_b != !rq[r].count_b) return fail(CVO_ERR_INVALID, "point support: a direction needs its sum and its count array");
+            if (!rq[r].sum_a && !rq[r].sum_b) return fail(CVO_ERR_INVALID, "point support: no output array");
+            if (rq[r].tran_from_state && rq[r].from < 0) return fail(CVO_ERR_INVALID, "point support: transform from a state that is not named");
+        }
+        if (!ev_support) HIP_TRY(hipEventCreateWithFlags(&ev_support, hipEventDisableTiming));
+        if (support_queued) { HIP_TRY(hipEventSynchronize(ev_support)); support_queued = false; }   // the last call's tables, moved planes and outputs are free
+        support_copies.clear();
+        { int rcs = flush_pending(s); if (rcs) return rcs; }
+        { int rcs = settle_uploads(s); if (rcs) return rcs; }
+        // what the call needs: a moved {x, y, z, f0} plane and its boxes per transformed cloud, the tables, and (to_host) a place per output array
+        int n_moves = 0, n_move_max = 0, n_dirs = 0, row_blocks = 1;
+        size_t moved_bytes = 0, out_bytes = 0;
+        for (int r = 0; r < n; ++r) {
+            const bool moved = rq[r].tran || rq[r].tran_from_state;
+            const int na = rq[r].a->n, nb = rq[r].b->n;
+            if (moved) { ++n_moves; n_move_max = std::max(n_move_max, na); moved_bytes += sizeof(float) * 4 * (size_t)na + score_box_bytes(na); }
+            if (rq[r].sum_a) { ++n_dirs; out_bytes += 8 * (size_t)na; row_blocks = std::max(row_blocks, support_row_blocks(na)); }
+            if (rq[r].sum_b) { ++n_dirs; out_bytes += 8 * (size_t)nb; row_blocks = std::max(row_blocks, support_row_blocks(nb)); }
+        }
+        const size_t off_box = sizeof(SupportMoveDesc) * (size_t)n_moves, off_req = off_box + sizeof(BoxDesc) * (size_t)n_moves;
+        const size_t tab_bytes = off_req + sizeof(SupportDesc) * (size_t)n_dirs;
+        int rc;
+        if ((rc = h_support_tab.ensure(tab_bytes)) || (rc = d_support_tab.ensure(tab_bytes)) || (rc = d_support_moved.ensure(std::max(moved_bytes, (size_t)16)))) return rc;
+        if (to_host && ((rc = d_support_out.ensure(out_bytes)) || (rc = h_support_out.ensure(out_bytes)))) return rc;
+        unsigned char* const tab = static_cast<unsigned char*>(h_support_tab.p);
+        SupportMoveDesc* const mv = reinterpret_cast<SupportMoveDesc*>(tab);
+        BoxDesc* const bx = reinterpret_cast<BoxDesc*>(tab + off_box);
+        SupportDesc* const sd = reinterpret_cast<SupportDesc*>(tab + off_req);
+        std::memset(tab, 0, tab_bytes);
+        size_t moved_at = 0, out_at = 0; int im = 0, id = 0;
+        auto place = [&](void* host_dst, size_t bytes) -> void* {     // an output array: the caller's device memory, or a place in d_support_out
+            if (!to_host) return host_dst;
+            support_copies.push_back(SupportCopy{host_dst, out_at, bytes});
+            void* p = static_cast<unsigned char*>(d_support_out.p) + out_at; out_at += bytes; return p;
+        };
+        for (int r = 0; r < n; ++r) {
+            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
+            const PairState* from = rq[r].from >= 0 ? static_cast<const PairState*>(d_states.p) + rq[r].from : nullptr;
+            const float* a_lo = a.rec(); const float* a_box = nullptr;
+            if (rq[r].tran || rq[r].tran_from_state) {
+                float* plane = reinterpret_cast<float*>(static_cast<unsigned char*>(d_support_moved.p) + moved_at);
+                float* gbox = plane + 4 * (size_t)a.n;
+                moved_at += sizeof(float) * 4 * (size_t)a.n + score_box_bytes(a.n);
+                SupportMoveDesc& M = mv[im]; BoxDesc& B = bx[im]; ++im;
+                M.src = a.rec(); M.dst = plane; M.n = a.n; M.from = rq[r].tran_from_state ? from : nullptr;
+                for (int i = 0; i < 12; ++i) M.tran[i] = rq[r].tran_from_state ? 0.f : rq[r].tran[i];
+                B.rec = plane; B.gbox = gbox; B.self_cache = score_self_cache(gbox, a.n); B.n = a.n; B.ngroups = score_groups(a.n);
+                a_lo = plane; a_box = gbox;
+            } else if (rq[r].sum_b) {
+                if ((rc = ensure_boxes(a, s))) return rc;
+                a_box = static_cast<const float*>(a.boxes.p);
+            }
+            if (rq[r].sum_a) {
+                if ((rc = ensure_boxes(b, s))) return rc;
+                SupportDesc& D = sd[id++];
+                D.a_lo = a_lo; D.a_hi = a.rec() + hi_off(a.n, 0); D.na = a.n;
+                D.b_lo = b.rec(); D.b_hi = b.rec() + hi_off(b.n, 0); D.nb = b.n;
+                D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
+                D.ell = rq[r].ell; D.from = from;
+                D.sum = static_cast<float*>(place(rq[r].sum_a, 4 * (size_t)a.n)); D.count = static_cast<int*>(place(rq[r].count_a, 4 * (size_t)a.n));
+            }
+            if (rq[r].sum_b) {
+                SupportDesc& D = sd[id++];
+                D.a_lo = b.rec(); D.a_hi = b.rec() + hi_off(b.n, 0); D.na = b.n;
+                D.b_lo = a_lo; D.b_hi = a.rec() + hi_off(a.n, 0); D.nb = a.n;
+                D.bbox = a_box; D.nbox = score_groups(a.n);
+                D.ell = rq[r].ell; D.from = from;
+                D.sum = static_cast<float*>(place(rq[r].sum_b, 4 * (size_t)b.n)); D.count = static_cast<int*>(place(rq[r].count_b, 4 * (size_t)b.n));
+            }
+        }
+        if (out_stream && out_stream != s) {                         // whatever out_stream still does to the arrays comes first
+            if (!ev_support_in) HIP_TRY(hipEventCreateWithFlags(&ev_support_in, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(ev_support_in, out_stream));
+            HIP_TRY(hipStreamWaitEvent(s, ev_support_in, 0));
+        }
+        HIP_TRY(hipMemcpyAsync(d_support_tab.p, h_support_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        const unsigned char* const dtab = static_cast<const unsigned char*>(d_support_tab.p);
+        const SupportMoveDesc* d_mv = reinterpret_cast<const SupportMoveDesc*>(dtab);
+        const BoxDesc* d_bx = reinterpret_cast<const BoxDesc*>(dtab + off_box);
+        const SupportDesc* d_sd = reinterpret_cast<const SupportDesc*>(dtab + off_req);
+        hipError_t e;
+        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            const unsigned wgs = (unsigned)row_blocks * (unsigned)n_dirs;
+            *qc->submitted_host += wgs;
+            bool sweep_submitted = false;
+            e = launch_support(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, P, s, qc->started_dev, &sweep_submitted);
+            if (!sweep_submitted) *qc->submitted_host -= wgs;
+            else if (e != hipSuccess) resync_adopt_counters(qc);
+        } else e = launch_support(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, P, s, nullptr, nullptr);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("support kernel launch: ") + hipGetErrorString(e));
+        if (to_host) HIP_TRY(hipMemcpyAsync(h_support_out.p, d_support_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(ev_support, s));
+        support_queued = true; support_stream = s;
+        return CVO_OK;
+    }
+    // waits for the call queued last; its host arrays (to_host) are filled here
+    int support_collect() {
+        HIP_TRY(hipSetDevice(device));
+        if (!support_queued) return fail(CVO_ERR_INVALID, "no queued point support");
+        HIP_TRY(hipEventSynchronize(ev_support));
+        support_queued = false;
+        for (const SupportCopy& c : support_copies) std::memcpy(c.dst, static_cast<const unsigned char*>(h_support_out.p) + c.off, c.bytes);
+        support_copies.clear();
+        return CVO_OK;
+    }
+    // the device form's ordering: with an out_stream that stream waits for the launch and the host does not; else the host waits
+    int support_publish(hipStream_t out_stream) {
+        if (!out_stream) return support_collect();
+        if (out_stream != support_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_support, 0));
+        return CVO_OK;
+    }
 };
 
 // ---- host-side pieces of the reference's state helpers ----------------------
@@ -1960,6 +2099,19 @@ int cvo_se3_hessian(cvo_handle h, int slot_a, const float* tran_a, int slot_b, d
     *inliers += (int)r[0][1];                                        // cvo.cpp:708 increments the caller's variable
     finish_hessian(r[0] + 2, *inliers, H);
     return CVO_OK;
+}
+
+// Not in the reference: the terms function_inner_product adds up, kept per point (include/cvo_hip.h, "per-point support")
+int cvo_point_support(cvo_handle h, int slot_a, const float* tran_a, int slot_b, float* sum_a, int* count_a, int cap_a, float* sum_b, int* count_b, int cap_b) {
+    if (!h) return fail(CVO_ERR_INVALID, "null argument");
+    if (!sum_a != !count_a || !sum_b != !count_b) return fail(CVO_ERR_INVALID, "point support: a direction needs its sum and its count array");
+    if (!sum_a && !sum_b) return fail(CVO_ERR_INVALID, "point support: no output array");
+    Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
+    if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point support: empty cloud slot");
+    if ((sum_a && cap_a < a->n) || (sum_b && cap_b < b->n)) return fail(CVO_ERR_INVALID, "point support: an output array is shorter than its cloud");
+    const Engine::SupportReq rq[1] = {{a, tran_a, b, h->ell, -1, false, sum_a, count_a, sum_b, count_b}};
+    int rc = h->eng.support_enqueue(rq, 1, h->eng.stream, true); if (rc) return rc;
+    return h->eng.support_collect();
 }
 
 namespace {
@@ -3538,6 +3690,55 @@ int cvo_batch_compute_innerproduct(cvo_batch b, int n, cvo_track_scores* out) {
     int rc = cvo_batch_enqueue_innerproduct(b, n); if (rc) return rc;
     return cvo_batch_innerproduct_results(b, n, out);
 }
+namespace {
+// One pair's record of a point-support call: both directions' arrays, each direction whole or absent; on_device: every array is n x 4 bytes the
+// device can write (the rule of cvo_device_cloud: check_device_plane), 4-byte aligned.  Nothing is queued here.
+int support_check_dst(int device, const cvo_point_support_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
+    if (!d.sum_moving != !d.count_moving || !d.sum_fixed != !d.count_fixed) return fail(CVO_ERR_INVALID, who + "a direction needs its sum and its count array");
+    if (!d.sum_moving && !d.sum_fixed) return fail(CVO_ERR_INVALID, who + "no output array");
+    if (!on_device) return CVO_OK;
+    const struct { const void* p; int n; const char* name; } arr[4] = {{d.sum_moving, n_moving, "sum_moving"}, {d.count_moving, n_moving, "count_moving"},
+                                                                       {d.sum_fixed, n_fixed, "sum_fixed"}, {d.count_fixed, n_fixed, "count_fixed"}};
+    for (const auto& x : arr) {
+        if (!x.p) continue;
+        if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
+        int rc = check_device_plane(device, x.p, 4ll * x.n, 4ll * x.n, 1, who + x.name, "array"); if (rc) return rc;
+    }
+    return CVO_OK;
+}
+// The requests of the listed slots of b (their device states name transform and ell), checked; then one launch on the stream of b's last launch.
+int batch_support_run(cvo_batch b, const std::vector<int>& slots, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+    Engine& E = b->eng;
+    if (on_device) HIP_TRY(hipSetDevice(E.device));
+    std::vector<Engine::SupportReq> rq(slots.size());
+    for (size_t k = 0; k < slots.size(); ++k) {
+        const int p = slots[k];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
+        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point support: empty cloud in the batch");
+        int rc = support_check_dst(E.device, dst[k], mv->n, fx->n, on_device, "point support, record " + std::to_string(k) + ": "); if (rc) return rc;
+        rq[k] = Engine::SupportReq{mv, nullptr, fx, 0.f, p, true, dst[k].sum_moving, dst[k].count_moving, dst[k].sum_fixed, dst[k].count_fixed};
+    }
+    int rc = E.support_enqueue(rq.data(), (int)rq.size(), E.last_stream, !on_device, on_device ? static_cast<hipStream_t>(out_stream) : nullptr); if (rc) return rc;
+    return on_device ? E.support_publish(static_cast<hipStream_t>(out_stream)) : E.support_collect();
+}
+int batch_support(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+    if (!b || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
+    int rc = check_last_clouds(b); if (rc) return rc;
+    std::vector<int> slots(count); std::vector<unsigned char> seen(b->last_n, 0);
+    for (int k = 0; k < count; ++k) {
+        const int i = pairs ? pairs[k] : k;
+        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "point support: pair " + std::to_string(i) + " is not a position of the last launch");
+        if (seen[i]++) return fail(CVO_ERR_INVALID, "point support: pair " + std::to_string(i) + " listed twice");
+        slots[k] = b->last_slots[i];
+    }
+    return batch_support_run(b, slots, dst, on_device, out_stream);
+}
+}  // namespace
+int cvo_batch_point_support(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst) { return batch_support(b, count, pairs, dst, false, nullptr); }
+int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, void* out_stream) {
+    return batch_support(b, count, pairs, dst, true, out_stream);
+}
 int cvo_batch_results_to_device(cvo_batch b, void* dst_device, int n, void* stream) {
     if (!b || !dst_device || n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(b->eng.device));
@@ -3584,6 +3785,9 @@ struct cvo_tracks_s {
     std::vector<int> list, phase, points, odo_pos, key_pos;   // per listed stream: its phase, points, and position in the two launches (-1: not in it)
     std::vector<std::shared_ptr<Cloud>> moving_before;          // the keyframe object's moving cloud before the step (put back when the odometry alignment fails)
     int n_odo = 0, n_key = 0;
+    // the step waited for last, until the next commit or step: which objects of its listed streams aligned with CVO_OK (cvo_tracks_point_support)
+    bool support_valid = false;
+    std::vector<unsigned char> odo_ok, key_ok;
 };
 
 namespace {
@@ -3687,6 +3891,7 @@ int cvo_tracks_reset(cvo_tracks t, int s) {
     if (!t || s < 0 || s >= t->max_streams) return fail(CVO_ERR_INVALID, "bad stream index");
     if (t->in_flight) return fail(CVO_ERR_INVALID, "a step is in flight (cvo_tracks_wait first)");
     tracks_fresh_stream(t, s);
+    t->support_valid = false;
     return CVO_OK;
 }
 namespace {
@@ -3715,6 +3920,7 @@ int tracks_step_run(cvo_tracks_s* t, int count, const int* streams, const int* n
     cvo_batch bo = t->odo, bk = t->key;
     int rc;
     // every frame into a cloud object nobody holds; the objects' slots take it (local_tracker.cpp:228-231, 233, 356, 415; update_fixed_pcd :403)
+    t->support_valid = false;
     t->list.assign(streams, streams + count);
     t->phase.assign(count, 0); t->points.assign(count, 0); t->odo_pos.assign(count, -1); t->key_pos.assign(count, -1);
     t->moving_before.assign(count, nullptr);
@@ -3867,6 +4073,11 @@ int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out, int count) {
     if (t->n_odo > 0 && (rc = tracks_scores(bo, t->n_odo, want_o, so))) return rc;
     if (t->n_key > 0 && (rc = tracks_scores(bk, t->n_key, want_k, sk))) return rc;
     const TrackLinkOut* lo = static_cast<const TrackLinkOut*>(t->h_link_out.p);
+    t->odo_ok.assign(n, 0); t->key_ok.assign(n, 0);
+    for (int k = 0; k < n; ++k) {
+        if (t->odo_pos[k] >= 0) t->odo_ok[k] = want_o[t->odo_pos[k]];
+        if (t->key_pos[k] >= 0) t->key_ok[k] = want_k[t->key_pos[k]];
+    }
     for (int k = 0; k < n; ++k) {
         const int s = t->list[k];
         TrackStream& S = t->st[s]; KeyObject& K = S.key;
@@ -3912,6 +4123,7 @@ int cvo_tracks_wait(cvo_tracks t, cvo_track_step* out, int count) {
     }
     t->moving_before.clear();
     t->in_flight = false;
+    t->support_valid = true;
     return stage_place(bo, false);                                   // (frames staged while the step ran: placed now if their generator has finished too)
 }
 int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* accept) {
@@ -3921,6 +4133,7 @@ int cvo_tracks_commit(cvo_tracks t, int count, const int* streams, const int* ac
     Lap lap(StepLaps::COMMIT);
     for (int k = 0; k < count; ++k)
         if (!t->st[streams[k]].commit_pending) return fail(CVO_ERR_INVALID, "stream " + std::to_string(streams[k]) + " expects no decision");
+    t->support_valid = false;                                        // (the keyframe objects' clouds move on below)
     for (int k = 0; k < count; ++k) {
         const int s = streams[k];
         TrackStream& S = t->st[s]; KeyObject& K = S.key;
@@ -3964,6 +4177,30 @@ int cvo_tracks_get_state(cvo_tracks t, int s, int object, float R[9], float T[3]
     if (ell) *ell = object == 0 ? O.ell : K.ell;
     if (transform) std::memcpy(transform, object == 0 ? O.transform.m : K.transform.m, sizeof(float) * 12);
     return CVO_OK;
+}
+namespace {
+int tracks_support(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+    int rc = tracks_check_list(t, count, streams); if (rc) return rc;
+    if (!dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (object != 0 && object != 1) return fail(CVO_ERR_INVALID, "object must be 0 (odometry) or 1 (keyframe)");
+    if (t->in_flight || !t->support_valid) return fail(CVO_ERR_INVALID, "point support: between cvo_tracks_wait of a step and the next cvo_tracks_commit or step only");
+    std::vector<int> slots(count);
+    for (int k = 0; k < count; ++k) {
+        const int s = streams[k];
+        int at = -1;
+        for (size_t q = 0; q < t->list.size(); ++q) if (t->list[q] == s) at = (int)q;
+        if (at < 0) return fail(CVO_ERR_INVALID, "point support: stream " + std::to_string(s) + " was not listed in the step");
+        if (!(object == 0 ? t->odo_ok[at] : t->key_ok[at])) return fail(CVO_ERR_INVALID, "point support: that object of stream " + std::to_string(s) + " did not align in the step");
+        slots[k] = s;                                                // (a stream's slot in both batches, and its device state's index)
+    }
+    return batch_support_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
+}
+}  // namespace
+int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst) {
+    return tracks_support(t, object, count, streams, dst, false, nullptr);
+}
+int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream) {
+    return tracks_support(t, object, count, streams, dst, true, out_stream);
 }
 
 // ---------------------------------------------------------------- multi-GPU: RCCL all-gather of the result records

@@ -255,6 +255,28 @@ struct BoxDesc {
     int n, ngroups;
 };
 
+// per-point support (cvo_support_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds -- a {sum, count}
+// per ROW over the columns inside both gates.  Rows and columns are given plane by plane, so the rows (or columns) of a transformed cloud are a
+// scratch copy of its {x, y, z, f0} plane beside the cloud's own {f1..f4} plane.  The table lives in pinned host memory and is read where it is.
+struct SupportDesc {
+    const float* a_lo; const float* a_hi;   // rows: na float4 {x, y, z, f0} and na float4 {f1, f2, f3, f4}
+    const float* b_lo; const float* b_hi;   // columns: nb float4 each
+    const float* bbox;                      // boxes of the columns' 32-point groups (of b_lo as it is: planes of nbox floats, as ScoreDesc::bbox)
+    int nbox, na, nb;
+    float ell;
+    const PairState* from;                  // non-null: ell comes from this device-resident state (ScoreDesc::from)
+    float* sum; int* count;                 // na each
+};
+static_assert(sizeof(SupportDesc) == 80, "SupportDesc layout");
+// the pre-pass of a transformed cloud (cvo_support_move_kernel): its {x, y, z, f0} plane with the positions moved, one descriptor per cloud
+struct SupportMoveDesc {
+    const float* src; float* dst;           // n float4 each
+    const PairState* from;                  // non-null: the transform is from->transform (the pair's own align() result), else tran
+    float tran[12];
+    int n, pad_;
+};
+static_assert(sizeof(SupportMoveDesc) == 80, "SupportMoveDesc layout");
+
 // a score block: up to 8 inner-product / Hessian requests evaluated by one launch
 constexpr int SCORE_MAXREQ = 8;
 struct ScoreBatch {

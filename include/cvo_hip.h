@@ -763,6 +763,53 @@ int cvo_tracks_get_cloud(cvo_tracks t, int s, int object, int slot, float* xyz, 
 int cvo_tracks_get_selected_points(cvo_tracks t, int s, int object, int slot, unsigned short* px, int cap, int* n);
 int cvo_tracks_get_state(cvo_tracks t, int s, int object, float R[9], float T[3], float* ell, float transform[12]);
 
+
+/* ======================= per-point support: which points of a frame an alignment agrees on (NOT in the reference) ===========
+ * function_inner_product (cvo.cpp:388-459) sums the kernel matrix of two clouds into one number; these calls keep it per point.  For clouds a (rows,
+ * moved by the 3 x 4 tran_a first when one is given, as cvo.cpp:485-487 does) and b (columns) and a length scale ell, pair (i, j) is INSIDE when
+ * d2 < d2_thres and d2_color < d2_c_thres (cvo.cpp:395-396, 423, 428), its value is a_ij = ck * k (cvo.cpp:429-431; no a > sp_thres test, as there), and
+ *   sum_a[i]   float  sum over j of a_ij of the inside pairs of row i, added in double in ascending j and rounded once;   count_a[i]  int  how many
+ *   sum_b[j]   float  the same over i for column j, ascending i;                                                           count_b[j]  int
+ * A point with no inside pair gets 0 and 0 (the "count 0 reads 1" rule of cvo.cpp:455-456 belongs to the cloud's total, not to a point).  The counts
+ * of either side add up to the num of cvo_function_inner_product for the same arguments (0 where that reads 1), the sums to its value.  The float
+ * sequence is that call's: un-fused d2 (nanoflann.hpp:403-406), double exp, float product; the moved point is computed once and used by both
+ * directions, so a_ij is one float on both sides.  Every bit of the four arrays is a function of the two clouds, tran_a, ell and the parameters
+ * alone: a row's columns are swept by one lane in ascending order whatever else shares the launch, and nothing is added atomically.  Index i of an
+ * array is point i of the cloud, the point cvo_*_get_selected_points maps to its pixel.
+ *
+ * cvo_point_support: the arguments of cvo_function_inner_product, the handle's ell; writes host arrays and waits.  sum_a and count_a (cap_a entries
+ * each) may both be NULL: that direction is not computed; the same for sum_b / count_b.  CVO_ERR_EMPTY_CLOUD for an empty slot, CVO_ERR_INVALID for a
+ * cap below the cloud's size, for one array of a direction without the other, and when both directions are NULL: nothing is written then.
+ *
+ * cvo_batch_point_support: for positions pairs[k] (k < count; NULL: 0 .. count-1) of the LAST launch's list -- the positions cvo_batch_wait reports --
+ * a is the pair's moving cloud under the transform, and with the ell, its alignment left in the pair's device-resident state, b its fixed cloud.
+ * dst[k] holds that pair's four host arrays (moving: n_moving entries, fixed: n_fixed; a direction's two pointers may both be NULL).  ONE launch for
+ * all pairs and both directions, queued behind the align launch on its stream like cvo_batch_enqueue_innerproduct, no transform crosses the host;
+ * the call then waits and copies.  It shares no buffer with a score block in flight.  CVO_ERR_INVALID (a position out of range or listed twice, a
+ * NULL dst, half a direction, no launch yet, clouds replaced since the launch) and CVO_ERR_EMPTY_CLOUD are found before anything is queued.
+ *
+ * cvo_batch_point_support_device: the same records pointing into caller-owned DEVICE memory, n x 4 bytes per array, nothing outside them is written.
+ * Every pointer is checked before anything is queued by the rule of cvo_device_cloud (device memory of the object's device with the extent inside its
+ * allocation, managed, or pinned / registered host memory; pageable host memory: CVO_ERR_INVALID) and must be 4-byte aligned.  Ordering is
+ * image_stream's rule with the direction reversed: with an out_stream (a hipStream_t) that stream waits for an event recorded behind the launch and
+ * the call returns without a host wait -- work queued on out_stream afterwards sees the arrays, and what out_stream held before the call (a fill of
+ * the arrays, their last reader) is waited for by the launch; with NULL the arrays must be idle and the call waits on the host.
+ *
+ * cvo_tracks_point_support(_device): valid between cvo_tracks_wait of a step and the next cvo_tracks_commit or step.  streams[k] must have been listed
+ * in that step, and its `object` (0 odometry, 1 keyframe) must have aligned there with CVO_OK (so: not a phase-0 stream, and object 1 only in phase
+ * 2); a is the step's frame at that object's result transform and ell, b that object's fixed cloud.  Anything else: CVO_ERR_INVALID before anything
+ * is queued, no stream is touched. */
+typedef struct cvo_point_support_dst {
+    float* sum_moving; int* count_moving;     /* one entry per point of a (the moving cloud / the step's frame) */
+    float* sum_fixed;  int* count_fixed;      /* one entry per point of b (the fixed cloud) */
+} cvo_point_support_dst;
+int cvo_point_support(cvo_handle h, int slot_a, const float* tran_a /* 3x4 row-major or NULL */, int slot_b,
+                      float* sum_a, int* count_a, int cap_a, float* sum_b, int* count_b, int cap_b);
+int cvo_batch_point_support(cvo_batch b, int count, const int* pairs /* NULL: 0 .. count-1 */, const cvo_point_support_dst* dst);
+int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, void* out_stream);
+int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst);
+int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream);
+
 #ifdef __cplusplus
 }
 #endif
