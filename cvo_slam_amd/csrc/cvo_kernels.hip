@@ -39,6 +39,7 @@
 #include <stdint.h>
 #include "cvo_device.h"
 #include "cvo_math.hpp"
+#include "cvo_sweep.hpp"
 #include <algorithm>
 #include <type_traits>
 
@@ -2421,41 +2422,18 @@ static __device__ __noinline__ void phase_iteration(const PairDesc* Dp_in, int g
 // within the radius at the ell the alignment left behind (Q1) -- a subset of the candidate lists, once the cloud has been transformed
 // with the FINAL transform (cvo.cpp:485-487, 817) and the lists are still valid for it; no a > sp_thres test here (Q6).  inn_pre =
 // fip(moving, fixed) (cvo.cpp:489) takes one cull of the untransformed cloud at that radius.  fip(fixed, fixed), fip(moving, moving)
-// (cvo.cpp:496-497) come from the clouds' tables when they are there.  The pair arithmetic is the score kernel's (cvo_score_kernels.hip:
-// un-fused d2, double exp with the division as written).  Whatever cannot be answered here (lists stale, a helped pair, a cloud not
+// (cvo.cpp:496-497) come from the clouds' tables when they are there.  The pair arithmetic is the score kernel's (cvo_sweep.hpp, pair_*; the
+// un-fused d2 is written out at the two call sites).  Whatever cannot be answered here (lists stale, a helped pair, a cloud not
 // resident in LDS as float4, a cold table) is left to the host, which runs the score kernel for it.  A pair run by several workgroups
 // (cooperative launch, helped pair) adds its members' sums up through the pair's exchange area.
 __device__ __forceinline__ void score_pair_terms(const float (&pa)[3], const float (&fa)[5], const float (&pb)[3], const float (&fb)[5], float d2, float d2c_thres,
                                                  float sig2, float csig2, double den_l, double den_c, float il2, double& sumA, int& count, float (&H)[21], int& hcount) {
-    float t[5];
-#pragma unroll
-    for (int cc = 0; cc < 5; ++cc) { const float e = fa[cc] - fb[cc]; t[cc] = e * e; }
-    const float d2c = (t[0] + t[1]) + (t[2] + (t[3] + t[4]));
+    const float d2c = pair_d2c(fa, fb);
     if (!(d2c < d2c_thres)) return;                                                     // cvo.cpp:428 / 659
-    const float k = (float)((double)sig2 * exp((double)(-d2) / den_l));                // cvo.cpp:429 / 661
-    const float ck = (float)((double)csig2 * exp((double)(-d2c) / den_c));             // cvo.cpp:430
-    sumA += ck * k; count += 1;                                                        // cvo.cpp:432-435
-#pragma unroll
-    for (int cc = 0; cc < 5; ++cc) t[cc] = fa[cc] * fb[cc];
-    const float cdot = (t[0] + t[1]) + (t[2] + (t[3] + t[4]));                          // cvo.cpp:662
-    float cr[3]; cross3(pa, pb, cr);
-    const float dot1 = pa[1] * pb[1] + pa[2] * pb[2], dot2 = pa[0] * pb[0] + pa[2] * pb[2], dot3 = pa[0] * pb[0] + pa[1] * pb[1];
-    const float db[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
-    float Bq[21];
-    Bq[0] = il2 * cr[0] * cr[0] - dot1;                                                // block A, cvo.cpp:670-675
-    Bq[1] = (float)(il2 * cr[0] * cr[1] + 0.5 * (pa[0] * pb[1] + pa[1] * pb[0]));
-    Bq[2] = (float)(il2 * cr[0] * cr[2] + 0.5 * (pa[0] * pb[2] + pa[2] * pb[0]));
-    Bq[3] = il2 * cr[1] * cr[1] - dot2;
-    Bq[4] = (float)(il2 * cr[1] * cr[2] + 0.5 * (pa[1] * pb[2] + pa[2] * pb[1]));
-    Bq[5] = il2 * cr[2] * cr[2] - dot3;
-    Bq[6] = il2 * cr[0] * db[0];          Bq[7] = -pa[2] + il2 * db[0] * cr[1];  Bq[8] = pa[1] + il2 * db[0] * cr[2];    // block C, cvo.cpp:680-688
-    Bq[9] = pa[2] + il2 * db[1] * cr[0];  Bq[10] = il2 * cr[1] * db[1];          Bq[11] = -pa[0] + il2 * db[1] * cr[2];
-    Bq[12] = -pa[1] + il2 * db[2] * cr[0]; Bq[13] = pa[0] + il2 * db[2] * cr[1]; Bq[14] = il2 * cr[2] * db[2];
-    Bq[15] = il2 * db[0] * db[0] - 1; Bq[16] = il2 * db[0] * db[1]; Bq[17] = il2 * db[0] * db[2];                        // block D, cvo.cpp:692-697
-    Bq[18] = il2 * db[1] * db[1] - 1; Bq[19] = il2 * db[1] * db[2]; Bq[20] = il2 * db[2] * db[2] - 1;
-    const float wgt = il2 * cdot * k;                                                  // cvo.cpp:707
-#pragma unroll
-    for (int q2 = 0; q2 < 21; ++q2) H[q2] += wgt * Bq[q2];
+    const float k = pair_k(d2, sig2, den_l);                                            // cvo.cpp:429 / 661
+    const float ck = pair_ck(d2c, csig2, den_c);                                        // cvo.cpp:430
+    sumA += ck * k; count += 1;                                                         // cvo.cpp:432-435
+    pair_hessian_add(pa, fa, pb, fb, il2, k, H);
     hcount += 1;
 }
 // eight partial sums over the workgroup and, for a pair run by several workgroups (a cooperative launch, a helped pair), over its members

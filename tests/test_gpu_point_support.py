@@ -144,6 +144,34 @@ def test_support_row_counts_around_a_wave(hiplib, pairs, rows):
     g.close()
 
 
+def test_support_past_one_ballot_round(hiplib):
+    """2049 columns are 65 groups: a wave tests 64 group boxes per ballot, so the 65th -- one point -- is reached only in the sweep's second round.
+    65 rows (a wave and one row) sit on columns 1984..2048; then the roles swapped, 2049 rows against 65 columns.  The same arguments through
+    function_inner_product: two row blocks make the host deal 16 column chunks of 5 groups, so the score kernel runs ranges that end before, at
+    and after group 65, empty ones included."""
+    from cvo_slam_amd import synth
+    p = synth.make_small_pair(31, 2100)
+    bx, bf = np.ascontiguousarray(p.fixed.xyz[:2049]), np.ascontiguousarray(p.fixed.feat[:, :2049])
+    ax = np.ascontiguousarray(p.fixed.xyz[1984:2049] + np.float32(0.003)); af = np.ascontiguousarray(p.moving.feat[:, 1984:2049])
+    assert bx.shape[0] == 2049 and ax.shape[0] == 65
+    ell = 0.15
+    g = handle_for(hiplib, (bx, bf), (ax, af), ell)
+    for t in (None, small_tf()):
+        # the precondition, on the reading: the 65th group's only column is hit, and so is a column of every other group
+        want = support_reading.point_support(ax, af, bx, bf, ell, t)
+        assert want[3][2048] >= 1
+        assert all(want[3][32 * k:32 * k + 32].any() for k in range(65))
+        for (sa, a, sb, b) in ((MOVING, (ax, af), FIXED, (bx, bf)), (FIXED, (bx, bf), MOVING, (ax, af))):
+            got = g.point_support(sa, t, sb)
+            check_against_reading(got, a, b, ell, t, ("second round", sa, t is not None))
+            value, num, _ = g.function_inner_product(sa, t, sb)
+            total_a, total_b = int(got[1].sum(dtype=np.int64)), int(got[3].sum(dtype=np.int64))
+            assert total_a > 0 and total_a == total_b == num
+            assert float(got[0].sum(dtype=np.float64)) == pytest.approx(value, rel=1e-6)
+            assert float(got[2].sum(dtype=np.float64)) == pytest.approx(value, rel=1e-6)
+    g.close()
+
+
 # ---- 4. a cloud against itself
 def test_a_cloud_against_itself_is_symmetric(hiplib, pairs):
     p = pairs[(77, 800)]
