@@ -143,7 +143,9 @@ ABI_SYMBOLS = [
     "cvo_check_device_clouds", "cvo_selftest_ingest_clouds", "cvo_batch_set_pairs_device_clouds", "cvo_batch_advance_device_clouds",
     "cvo_tracks_step_device_clouds_async",
     "cvo_point_support", "cvo_batch_point_support", "cvo_batch_point_support_device", "cvo_tracks_point_support", "cvo_tracks_point_support_device",
+    "cvo_score_hypotheses", "cvo_batch_score_hypotheses", "cvo_batch_seed_hypotheses_async", "cvo_batch_hypothesis_results",
 ]
+MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 
 _lib = None
 
@@ -331,6 +333,11 @@ def load_library():
     L.cvo_batch_point_support_device.argtypes = [vp, C.c_int, ip, psp, vp]
     L.cvo_tracks_point_support.argtypes = [vp, C.c_int, C.c_int, ip, psp]
     L.cvo_tracks_point_support_device.argtypes = [vp, C.c_int, C.c_int, ip, psp, vp]
+    inp = C.POINTER(InnP)
+    L.cvo_score_hypotheses.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, C.c_float, inp, ip]
+    L.cvo_batch_score_hypotheses.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float, inp, ip]
+    L.cvo_batch_seed_hypotheses_async.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float]
+    L.cvo_batch_hypothesis_results.argtypes = [vp, C.c_int, inp, ip]
     _lib = L
     return L
 
@@ -436,6 +443,23 @@ def _tran(t):
     if t is None:
         return None, None
     return _f(np.asarray(t, dtype=np.float32).reshape(12))
+
+
+def _inn_arrays(recs, shape):
+    """an array of cvo_inn_p as (values float32, nums int32) of `shape`"""
+    raw = np.frombuffer(recs, dtype=np.dtype([("value", np.float32), ("num", np.int32), ("num_e", np.int32)]))
+    return raw["value"].reshape(shape).copy(), raw["num"].reshape(shape).copy()
+
+
+def _hyp_trans(trans, count):
+    """count x K x 3 x 4 transforms (a single pair may leave the first axis out) as one contiguous float32 array and K"""
+    t = np.ascontiguousarray(trans, dtype=np.float32)
+    if count is None:
+        t = t.reshape((1,) + t.shape) if t.ndim == 3 else t
+        count = t.shape[0]
+    if t.ndim < 2 or t.size == 0 or t.size % (12 * count) != 0:
+        raise ValueError("trans: count x K transforms of 3 x 4 expected")
+    return t.reshape(count, -1, 12), t.size // (12 * count)
 
 
 def default_params() -> Params:
@@ -831,6 +855,18 @@ class Cvo:
         _check(self.L.cvo_point_support(self.h, slot_a, tp, slot_b, sa.ctypes.data_as(fp), ca.ctypes.data_as(ip), na.value,
                                         sb.ctypes.data_as(fp), cb.ctypes.data_as(ip), nb.value))
         return sa, ca, sb, cb
+
+    # -- not in the reference: K start transforms scored before an alignment (cvo_hip.h, "pose hypotheses")
+    def score_hypotheses(self, slot_a, slot_b, trans, ell=None):
+        """(values float32[K], nums int32[K], best): function_inner_product of slot_a's cloud under each of the K transforms `trans` (K x 3 x 4, moving ->
+        fixed) against slot_b's cloud at length scale ell (None: params.ell), in one launch; best = the lowest index of the largest value.  The object's
+        state is untouched."""
+        t, k = _hyp_trans(np.asarray(trans, np.float32).reshape(1, -1, 12), 1)
+        recs = (InnP * max(k, 1))(); best = C.c_int(-1)
+        _check(self.L.cvo_score_hypotheses(self.h, int(slot_a), int(slot_b), k, t.ctypes.data_as(C.POINTER(C.c_float)),
+                                           float(self.params.ell if ell is None else ell), recs, C.byref(best)))
+        v, n = _inn_arrays(recs, (k,))
+        return v, n, int(best.value)
 
     # -- cvo.cpp:620-759
     def se3_hessian(self, slot_a, tran_a, slot_b, inliers: int = 0):
@@ -1467,6 +1503,39 @@ class CvoBatch:
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_batch_point_support_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out
+
+    # -- not in the reference: K start transforms per pair, scored in one launch; the next alignment can start from the best (cvo_hip.h, "pose hypotheses")
+    def _hyp_args(self, trans, pairs):
+        pr = None if pairs is None else np.ascontiguousarray(pairs, np.int32).reshape(-1)
+        t, k = _hyp_trans(trans, None if pr is None else pr.shape[0])
+        return t, k, t.shape[0], pr, (None if pr is None else pr.ctypes.data_as(C.POINTER(C.c_int)))
+
+    def score_hypotheses(self, trans, pairs=None, ell=None):
+        """(values float32[count, K], nums int32[count, K], best int32[count]) for slots `pairs` (None: 0 .. count-1): each slot's moving cloud under its K
+        transforms trans[i] (count x K x 3 x 4, moving -> fixed) against its fixed cloud at ell (None: params.ell).  Scores only: no state changes."""
+        t, k, count, pr, prp = self._hyp_args(trans, pairs)
+        recs = (InnP * max(count * k, 1))(); best = np.full(count, -1, np.int32)
+        _check(self.L.cvo_batch_score_hypotheses(self.h, count, prp, k, t.ctypes.data_as(C.POINTER(C.c_float)), float(self.params.ell if ell is None else ell),
+                                                 recs, best.ctypes.data_as(C.POINTER(C.c_int))))
+        v, n = _inn_arrays(recs, (count, k))
+        return v, n, best
+
+    def seed_hypotheses(self, trans, pairs=None, ell=None):
+        """The same launches without a host wait, and each listed slot's next alignment starts from reset_initial(its best hypothesis) on the device;
+        set_state, reset_states and the set_pair* calls drop the seed.  hypothesis_results(count) returns the scores and choices."""
+        t, k, count, pr, prp = self._hyp_args(trans, pairs)
+        _check(self.L.cvo_batch_seed_hypotheses_async(self.h, count, prp, k, t.ctypes.data_as(C.POINTER(C.c_float)), float(self.params.ell if ell is None else ell)))
+        self._seed_k = k
+
+    def hypothesis_results(self, count: int):
+        """(values[count, K], nums[count, K], best[count]) of the last seed_hypotheses call; waits for that call's kernels alone"""
+        k = int(getattr(self, "_seed_k", 0))
+        if k < 1:
+            raise CvoError(4, "hypothesis_results: no seed_hypotheses call yet")
+        recs = (InnP * max(int(count) * k, 1))(); best = np.full(max(int(count), 0), -1, np.int32)
+        _check(self.L.cvo_batch_hypothesis_results(self.h, int(count), recs, best.ctypes.data_as(C.POINTER(C.c_int))))
+        v, n = _inn_arrays(recs, (int(count), k))
+        return v, n, best
 
     def results_to_device(self, dst_device_ptr: int, n: int, stream: int | None = None):
         _check(self.L.cvo_batch_results_to_device(self.h, C.c_void_p(dst_device_ptr), n, C.c_void_p(stream) if stream else None))

@@ -112,12 +112,17 @@ hipError_t launch_score(const ScoreBatch& B, const ScoreDesc* more, int nreq, in
 int support_row_blocks(int na);
 hipError_t launch_support(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, const SupportDesc* reqs, int n_reqs, int row_blocks,
                           const DevParams& P, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
+int hyp_row_blocks(int na);
+int hyp_max();
+hipError_t launch_hypotheses(const HypDesc* descs, int n_pairs, int k, int row_blocks, const DevParams& P, double* partials, HypScore* scores, int* best,
+                             int seed, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
 }  // namespace cvohip
 
 using namespace cvohip;
 
 static_assert(sizeof(cvo_trace_row) == sizeof(TraceRow), "trace row layout");
 static_assert(sizeof(cvo_adaptive_row) == sizeof(AdaptiveRow), "adaptive trace row layout");
+static_assert(sizeof(cvo_inn_p) == sizeof(HypScore), "inn_p record layout");
 
 namespace {
 
@@ -599,6 +604,9 @@ struct Engine {
         if (ev_support_in) { (void)hipEventDestroy(ev_support_in); ev_support_in = nullptr; }
         support_queued = false;
         d_support_tab.release(); d_support_moved.release(); d_support_out.release(); h_support_tab.release(); h_support_out.release();
+        if (ev_hyp) { (void)hipEventSynchronize(ev_hyp); (void)hipEventDestroy(ev_hyp); ev_hyp = nullptr; }
+        hyp_queued = false;
+        d_hyp_tab.release(); d_hyp_partials.release(); h_hyp_tab.release(); h_hyp_out.release();
         for (DevBuf* b : {&d_bgr, &d_depth, &d_I0, &d_I1, &d_I2, &d_dx0, &d_dy0, &d_abs0, &d_abs1, &d_abs2, &d_ths, &d_thsS, &d_map, &d_pattern, &d_counts, &d_tiles}) b->release();
         for (DevBuf* b : {&d_descs, &d_states, &d_ybuf, &d_jT, &d_ent, &d_surv, &d_xch, &d_queue, &d_trace, &d_tracelen, &d_partials, &d_raw, &d_ring, &d_records}) b->release();
         for (PinBuf* b : {&h_descs, &h_states, &h_states_in, &h_stage, &h_partials, &h_tail, &h_packdesc, &h_rawtab}) b->release();
@@ -1513,6 +1521,94 @@ struct Engine {
     int support_publish(hipStream_t out_stream) {
         if (!out_stream) return support_collect();
         if (out_stream != support_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_support, 0));
+        return CVO_OK;
+    }
+
+    // Pose hypotheses (cvo_hypothesis_kernels.hip; include/cvo_hip.h: cvo_score_hypotheses): for every request the moving cloud a under each of the k
+    // transforms trans[r][0 .. k) against the fixed cloud b at `ell`, all in ONE sweep launch, and the reduce / select launch behind it.  seed: the
+    // select step also writes d_states[rq[r].state] -- R, T from reset_initial(best hypothesis), ell, transform and iter from rq[r].start.  The
+    // caller's trans array is copied into the pinned table before the call returns; nothing waits for the device here but the call before
+    // (one at a time, buffers of its own: the next one waits for ev_hyp first, as the support calls do for theirs).
+    struct HypReq { const Cloud* a; const Cloud* b; int state; const PairState* start; };
+    DevBuf d_hyp_tab, d_hyp_partials; PinBuf h_hyp_tab, h_hyp_out;
+    hipEvent_t ev_hyp = nullptr; bool hyp_queued = false; int hyp_n = 0, hyp_k = 0;
+    bool hyp_seed = false;                  // the call in flight is a seeding call: its answers are kept for cvo_batch_hypothesis_results (hyp_keep)
+    std::vector<cvo_inn_p> seed_scores; std::vector<int> seed_best; int seed_n = 0, seed_k = 0;   // the last seeding call's answers, once it has been waited for
+    // the call in flight has finished: a seeding call's answers move out of the pinned block the next call writes over
+    int hyp_keep() {
+        if (!hyp_queued) return CVO_OK;
+        HIP_TRY(hipEventSynchronize(ev_hyp));
+        hyp_queued = false;
+        if (hyp_seed) {
+            const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(h_hyp_out.p);
+            const int* bs = reinterpret_cast<const int*>(sc + (size_t)hyp_n * hyp_k);
+            seed_scores.assign(sc, sc + (size_t)hyp_n * hyp_k); seed_best.assign(bs, bs + hyp_n);
+            seed_n = hyp_n; seed_k = hyp_k; hyp_seed = false;
+        }
+        return CVO_OK;
+    }
+    int hyp_enqueue(const HypReq* rq, int n, int k, const float* trans, float ell, hipStream_t s, bool seed) {
+        HIP_TRY(hipSetDevice(device));
+        if (n <= 0 || k < 1 || k > hyp_max()) return fail(CVO_ERR_INVALID, "bad hypothesis request");
+        for (int r = 0; r < n; ++r) if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
+        if (!ev_hyp) HIP_TRY(hipEventCreateWithFlags(&ev_hyp, hipEventDisableTiming));
+        int rc = hyp_keep(); if (rc) return rc;                       // the last call's table, records and answers are free
+        if ((rc = flush_pending(s)) || (rc = settle_uploads(s))) return rc;
+        if (launched && last_stream && last_stream != s) HIP_TRY(hipStreamWaitEvent(s, ev1, 0));   // an align launch on a caller's stream packs clouds and writes states
+        int row_blocks = 1;
+        for (int r = 0; r < n; ++r) row_blocks = std::max(row_blocks, hyp_row_blocks(rq[r].a->n));
+        const size_t off_tran = sizeof(HypDesc) * (size_t)n, tab_bytes = off_tran + sizeof(float) * 12 * (size_t)n * k;
+        const size_t out_bytes = sizeof(cvo_inn_p) * (size_t)n * k + sizeof(int) * (size_t)n;
+        if ((rc = h_hyp_tab.ensure(tab_bytes)) || (rc = d_hyp_tab.ensure(tab_bytes)) || (rc = h_hyp_out.ensure(out_bytes)) ||
+            (rc = d_hyp_partials.ensure(sizeof(double) * 2 * (size_t)n * k * row_blocks))) return rc;
+        if (seed && (rc = d_states.ensure(sizeof(PairState) * (size_t)std::max(1, state_slots)))) return rc;   // (the size every launch asks for: it stays where it is)
+        unsigned char* const tab = static_cast<unsigned char*>(h_hyp_tab.p);
+        HypDesc* const hd = reinterpret_cast<HypDesc*>(tab);
+        std::memset(tab, 0, off_tran);
+        std::memcpy(tab + off_tran, trans, sizeof(float) * 12 * (size_t)n * k);
+        const float* const d_tran = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d_hyp_tab.p) + off_tran);
+        for (int r = 0; r < n; ++r) {
+            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
+            if ((rc = ensure_boxes(b, s))) return rc;
+            HypDesc& D = hd[r];
+            D.a = a.rec(); D.na = a.n; D.b = b.rec(); D.nb = b.n;
+            D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
+            D.trans = d_tran + 12 * (size_t)r * k; D.ell = ell;
+            if (seed) {
+                if (rq[r].state < 0 || rq[r].state >= state_slots || !rq[r].start) return fail(CVO_ERR_INVALID, "hypothesis seed: no device state for the pair");
+                D.state = static_cast<PairState*>(d_states.p) + rq[r].state;
+                D.seed_ell = rq[r].start->ell; D.seed_iter = rq[r].start->iter;
+                std::memcpy(D.seed_transform, rq[r].start->transform, sizeof(D.seed_transform));
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(d_hyp_tab.p, h_hyp_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        cvo_inn_p* const sc = static_cast<cvo_inn_p*>(h_hyp_out.p);
+        HypScore* const d_sc = reinterpret_cast<HypScore*>(sc); int* const d_best = reinterpret_cast<int*>(sc + (size_t)n * k);
+        const HypDesc* const d_hd = static_cast<const HypDesc*>(d_hyp_tab.p);
+        hipError_t e;
+        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            const unsigned wgs = (unsigned)row_blocks * (unsigned)k * (unsigned)n;
+            *qc->submitted_host += wgs;
+            bool sweep_submitted = false;
+            e = launch_hypotheses(d_hd, n, k, row_blocks, P, static_cast<double*>(d_hyp_partials.p), d_sc, d_best, seed ? 1 : 0, s, qc->started_dev, &sweep_submitted);
+            if (!sweep_submitted) *qc->submitted_host -= wgs;
+            else if (e != hipSuccess) resync_adopt_counters(qc);
+        } else e = launch_hypotheses(d_hd, n, k, row_blocks, P, static_cast<double*>(d_hyp_partials.p), d_sc, d_best, seed ? 1 : 0, s, nullptr, nullptr);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("hypothesis kernel launch: ") + hipGetErrorString(e));
+        HIP_TRY(hipEventRecord(ev_hyp, s));
+        hyp_queued = true; hyp_seed = seed; hyp_n = n; hyp_k = k;
+        return CVO_OK;
+    }
+    // waits for the scores-only call queued last and hands out its answers (best may be null)
+    int hyp_collect(cvo_inn_p* scores, int* best) {
+        HIP_TRY(hipSetDevice(device));
+        if (!hyp_queued || hyp_seed) return fail(CVO_ERR_INVALID, "no queued hypothesis scores");
+        HIP_TRY(hipEventSynchronize(ev_hyp));
+        hyp_queued = false;
+        const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(h_hyp_out.p);
+        std::memcpy(scores, sc, sizeof(cvo_inn_p) * (size_t)hyp_n * hyp_k);
+        if (best) std::memcpy(best, sc + (size_t)hyp_n * hyp_k, sizeof(int) * (size_t)hyp_n);
         return CVO_OK;
     }
 };
@@ -2461,6 +2557,8 @@ int batch_launch(cvo_batch b, const int* slots, int n, hipStream_t stream, bool 
             up[i] = b->dirty[p]; st[i] = b->init_states[p];
         }
     }
+    // a seed queued on the object's stream (cvo_batch_seed_hypotheses_async) comes before a launch on a caller's stream: it writes the start states
+    if (stream && stream != b->eng.stream && b->eng.hyp_queued) HIP_TRY(hipStreamWaitEvent(stream, b->eng.ev_hyp, 0));
     rc = b->eng.launch(pairs, st.data(), false, stream, false, 0, slots, up.data());
     if (rc) return rc;
     if (clean_all) std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)0);   // device states now evolve launch to launch (warm start) until reset
@@ -4196,6 +4294,76 @@ int tracks_support(cvo_tracks_s* t, int object, int count, const int* streams, c
     return batch_support_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
 }
 }  // namespace
+// ---- pose hypotheses (include/cvo_hip.h, "pose hypotheses"; cvo_hypothesis_kernels.hip)
+namespace {
+// what every hypothesis call checks about k, ell and the transforms before anything else happens
+int hyp_check_args(int k, const float* trans, size_t n_trans, float ell) {
+    if (!trans) return fail(CVO_ERR_INVALID, "hypotheses: null transform array");
+    if (k < 1 || k > CVO_MAX_HYPOTHESES) return fail(CVO_ERR_INVALID, "hypotheses: k must be 1 .. CVO_MAX_HYPOTHESES");
+    if (!std::isfinite(ell) || !(ell > 0.f)) return fail(CVO_ERR_INVALID, "hypotheses: ell must be finite and positive");
+    for (size_t i = 0; i < 12 * n_trans; ++i) if (!std::isfinite(trans[i])) return fail(CVO_ERR_INVALID, "hypotheses: non-finite entry in transform " + std::to_string(i / 12));
+    return CVO_OK;
+}
+// the listed slots of a batch call as requests; every argument error is found here, before anything is queued or changed
+int batch_hyp_requests(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell, std::vector<int>& slots, std::vector<Engine::HypReq>& rq) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    if (count < 1 || count > b->max_pairs) return fail(CVO_ERR_INVALID, "hypotheses: bad pair count");
+    int rc = hyp_check_args(k, trans, (size_t)count * (size_t)std::max(k, 0), ell); if (rc) return rc;
+    std::vector<unsigned char> seen(b->max_pairs, 0);
+    slots.resize(count); rq.resize(count);
+    for (int i = 0; i < count; ++i) {
+        const int p = pairs ? pairs[i] : i;
+        if (p < 0 || p >= b->max_pairs) return fail(CVO_ERR_INVALID, "hypotheses: slot " + std::to_string(p) + " out of range");
+        if (seen[p]++) return fail(CVO_ERR_INVALID, "hypotheses: slot " + std::to_string(p) + " listed twice");
+        if (b->streams[p].on) return fail(CVO_ERR_INVALID, "hypotheses: slot " + std::to_string(p) + " is a stream slot (it carries its own state)");
+        slots[i] = p;
+    }
+    for (int i = 0; i < count; ++i) {
+        const Cloud* fx = b->fixed[slots[i]].get(); const Cloud* mv = b->moving[slots[i]].get();
+        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "hypotheses: empty cloud in slot " + std::to_string(slots[i]));
+        rq[i] = Engine::HypReq{mv, fx, slots[i], &b->init_states[slots[i]]};
+    }
+    return CVO_OK;
+}
+}  // namespace
+
+int cvo_score_hypotheses(cvo_handle h, int slot_a, int slot_b, int k, const float* trans, float ell, cvo_inn_p* scores, int* best) {
+    if (!h || !scores) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = hyp_check_args(k, trans, (size_t)std::max(k, 0), ell); if (rc) return rc;
+    Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
+    if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "hypotheses: empty cloud slot");
+    const Engine::HypReq rq[1] = {{a, b, -1, nullptr}};
+    if ((rc = h->eng.hyp_enqueue(rq, 1, k, trans, ell, h->eng.stream, false))) return rc;
+    return h->eng.hyp_collect(scores, best);
+}
+int cvo_batch_score_hypotheses(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell, cvo_inn_p* scores, int* best) {
+    if (!scores) return fail(CVO_ERR_INVALID, "null argument");
+    std::vector<int> slots; std::vector<Engine::HypReq> rq;
+    int rc = batch_hyp_requests(b, count, pairs, k, trans, ell, slots, rq); if (rc) return rc;
+    if ((rc = batch_settle(b))) return rc;
+    if ((rc = b->eng.hyp_enqueue(rq.data(), count, k, trans, ell, b->eng.stream, false))) return rc;
+    return b->eng.hyp_collect(scores, best);
+}
+int cvo_batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell) {
+    std::vector<int> slots; std::vector<Engine::HypReq> rq;
+    int rc = batch_hyp_requests(b, count, pairs, k, trans, ell, slots, rq); if (rc) return rc;
+    if ((rc = batch_settle(b))) return rc;
+    if ((rc = b->eng.hyp_enqueue(rq.data(), count, k, trans, ell, b->eng.stream, true))) return rc;
+    for (int p : slots) b->dirty[p] = 0;                             // the next launch that lists them starts from what the select step wrote (Engine::launch: upload_each == 0)
+    return CVO_OK;
+}
+int cvo_batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores, int* best) {
+    if (!b) return fail(CVO_ERR_INVALID, "null batch");
+    Engine& E = b->eng;
+    const bool pending = E.hyp_queued && E.hyp_seed;
+    if (count < 1 || count > (pending ? E.hyp_n : E.seed_n)) return fail(CVO_ERR_INVALID, "hypothesis results: no seeding call of that many pairs");
+    HIP_TRY(hipSetDevice(E.device));
+    int rc = E.hyp_keep(); if (rc) return rc;                        // (waits for the seeding call's two kernels alone: their own event)
+    if (scores) std::memcpy(scores, E.seed_scores.data(), sizeof(cvo_inn_p) * (size_t)count * E.seed_k);
+    if (best) std::memcpy(best, E.seed_best.data(), sizeof(int) * (size_t)count);
+    return CVO_OK;
+}
+
 int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst) {
     return tracks_support(t, object, count, streams, dst, false, nullptr);
 }

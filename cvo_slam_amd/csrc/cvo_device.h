@@ -277,6 +277,22 @@ struct SupportMoveDesc {
 };
 static_assert(sizeof(SupportMoveDesc) == 80, "SupportMoveDesc layout");
 
+// pose hypotheses (cvo_hypothesis_kernels.hip; not in the reference): one pair of a launch -- its moving cloud under each of the launch's K transforms
+// against its fixed cloud, function_inner_product's sum per transform.  The table and the transforms are copied to device memory by the call.
+struct HypDesc {
+    const float* a;                         // moving cloud: two planes of na float4 (lo_off / hi_off)
+    const float* b;                         // fixed cloud: two planes of nb float4
+    const float* bbox;                      // boxes of b's 32-point groups (planes of nbox floats, as ScoreDesc::bbox)
+    const float* trans;                     // this pair's K transforms, 12 floats each (moving -> fixed, 3x4 row-major)
+    PairState* state;                       // seeding: the pair's device-resident state, written by the select step; null = scores only
+    int nbox, na, nb;
+    float ell;
+    float seed_ell; int seed_iter;          // seeding: what the state takes from the pair's start state besides R, T (cvo_track_link_kernel's TrackLinkIn)
+    float seed_transform[12];
+};
+static_assert(sizeof(HypDesc) == 112, "HypDesc layout");
+struct HypScore { float value; int num; int num_e; };   // == cvo_inn_p (include/cvo_hip.h)
+
 // a score block: up to 8 inner-product / Hessian requests evaluated by one launch
 constexpr int SCORE_MAXREQ = 8;
 struct ScoreBatch {

@@ -87,6 +87,16 @@ public:
         if (rc != CVO_OK) throw std::runtime_error(std::string("match_odometry: ") + cvo_last_error());
         sync();
     }
+    // not in the reference: k candidate transforms (moving -> fixed) scored before an alignment, function_inner_product(slot_a moved, slot_b) of each at
+    // `ell`; returns the index of the best (cvo_score_hypotheses in include/cvo_hip.h).  The object's R, T, ell and transform are untouched.
+    int score_hypotheses(int slot_a, int slot_b, int k, const Affine3f* trans, float ell, inn_p* scores) {
+        if (k < 1 || k > CVO_MAX_HYPOTHESES || !trans || !scores) throw std::runtime_error("score_hypotheses: bad argument");
+        cvo_inn_p r[CVO_MAX_HYPOTHESES]; float t[CVO_MAX_HYPOTHESES][12]; int best = 0;
+        for (int i = 0; i < k; ++i) std::memcpy(t[i], trans[i].m, sizeof(t[i]));
+        if (cvo_score_hypotheses(h_, slot_a, slot_b, k, &t[0][0], ell, r, &best) != CVO_OK) throw std::runtime_error(std::string("score_hypotheses: ") + cvo_last_error());
+        for (int i = 0; i < k; ++i) to(r[i], scores[i]);
+        return best;
+    }
     void align() { if (cvo_align(h_) != CVO_OK) throw std::runtime_error(std::string("align: ") + cvo_last_error()); sync(); }
 
     void compute_innerproduct(inn_p& inn_pre, inn_p& inn_post, Matrix6d& post_hessian, Affine3f& tran, int& inliers,
@@ -116,6 +126,20 @@ public:
     void get_iteration_number(int& iteration) { cvo_get_iteration_number(h_, &iteration); }
     void get_A_nonzero(int& nonzero) { cvo_get_A_nonzero(h_, &nonzero); }
 };
+
+// Pose hypotheses for the pairs of a batch (cvo_batch_*_hypotheses in include/cvo_hip.h; not in the reference): k transforms per listed slot, count x k x 12
+// floats in list order.  The reference has no batch class, so these are free functions over the C handle; errors throw.
+inline void batch_score_hypotheses(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell, cvo_inn_p* scores, int* best = nullptr) {
+    if (cvo_batch_score_hypotheses(b, count, pairs, k, trans, ell, scores, best) != CVO_OK) throw std::runtime_error(std::string("batch_score_hypotheses: ") + cvo_last_error());
+}
+// the same launches, and every listed slot's next alignment starts from its best hypothesis (reset_initial on a fresh object); no host wait
+inline void batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell) {
+    if (cvo_batch_seed_hypotheses_async(b, count, pairs, k, trans, ell) != CVO_OK) throw std::runtime_error(std::string("batch_seed_hypotheses_async: ") + cvo_last_error());
+}
+// the last seeding call's scores and choices; waits for that call's kernels alone
+inline void batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores, int* best) {
+    if (cvo_batch_hypothesis_results(b, count, scores, best) != CVO_OK) throw std::runtime_error(std::string("batch_hypothesis_results: ") + cvo_last_error());
+}
 
 // K tracker streams (cvo_tracks_* in include/cvo_hip.h): each stream is the pair of objects local_tracker owns, cvo_odometry (object 0) and
 // cvo_keyframe (object 1).  Not a class of the reference: there the two objects are stepped one frame, one sequence at a time.  Member names

@@ -810,6 +810,49 @@ int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, con
 int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst);
 int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream);
 
+
+/* ======================= pose hypotheses: score K start transforms per pair, align from the best (NOT in the reference) ===========
+ * The alignment converges from a start that is already close (the radius gate is 10 cm at ell = 0.15).  A loop-closure candidate or a re-localisation
+ * has several guesses instead -- detectLoopClousure_top10 holds lc_prior and lc_prior_2 per candidate, aligns from the first and scores both afterwards
+ * (keyframe_graph.cpp:649-714; inn_prior, inn_lc_prior in cvo.cpp:539-551).  These calls score the guesses BEFORE the alignment: for each listed pair,
+ * k candidate transforms (moving -> fixed, 3x4 row-major, the convention of tran_a in cvo_function_inner_product) and a length scale ell; the score of a
+ * hypothesis is cvo_function_inner_product(moving, that transform, fixed) at that ell -- both gates, no a > sp_thres test (cvo.cpp:388-459): value
+ * the float of the double sum, num the pair count (1 where it is 0, cvo.cpp:455-456), num_e 0.  All pairs and all hypotheses of a call are ONE launch,
+ * a second small one adds up and selects: best = the LOWEST index among the hypotheses with the largest value, compared as floats.
+ * The bits of value and num of a (pair, hypothesis) depend on the two clouds, that transform, ell and the parameters alone -- not on k, on the
+ * hypothesis' place in the list, on the other pairs of the call or on the launch's shape: a row's columns are swept by one lane in ascending order,
+ * the sums are added in a fixed order, nothing atomically.  They agree with cvo_function_inner_product's to the last few bits of a double sum (that
+ * kernel cuts the columns into chunks), i.e. to 1e-6 relative in value and exactly in num.
+ *
+ * cvo_score_hypotheses: scores only, clouds from the handle's slots (a = moving side, b = fixed side), explicit ell; the call waits.  The handle's
+ *   R, T, ell and transform are untouched.  best may be NULL.
+ * cvo_batch_score_hypotheses: scores only, for batch slots pairs[i] (slot indices as cvo_batch_align_pairs_async takes them; NULL: 0 .. count-1);
+ *   a = the slot's moving cloud, b = its fixed cloud; trans holds k transforms per listed slot, in list order.  Takes in a launch in flight first
+ *   (as every batch call does), waits and copies.  No state and no start flag of any slot changes: an align launch that follows gives the bits it
+ *   would have given without the call.
+ * cvo_batch_seed_hypotheses_async: the same two launches on the object's stream, and the select step also writes each listed slot's device-resident
+ *   start state: R, T = what cvo_reset_initial(fresh handle, hypothesis[best]) leaves in cvo_get_state (reset_initial with transform = I, cvo.cpp:611-618,
+ *   keyframe_graph.cpp:696), ell, transform and iter as cvo_batch_set_pair / cvo_batch_set_state last left them for the slot, everything else zero.
+ *   Returns without a host wait; trans has been copied and is the caller's again.  The next align launch that lists a seeded slot starts from that
+ *   state -- also on a caller's stream, which is ordered behind the seed by an event -- and its cvo_pair_result is bit-identical to
+ *   cvo_batch_set_state(p, R*, T*, ell_p) followed by the same launch, ell_p the slot's own start ell and R*, T* as above.  No score crosses the host.
+ *   The seed is DROPPED by anything that makes the slot start from its host-side state again: cvo_batch_set_state (of any slot),
+ *   cvo_batch_reset_states, cvo_batch_set_pair, _set_pairs and the other set_pairs_* calls.
+ * cvo_batch_hypothesis_results: waits for the last seeding call's two kernels alone (an event of their own, not an align launch queued behind them)
+ *   and returns that call's scores (count x k, k that call's) and choices, in its list order.  count above that call's count, or no seeding call
+ *   yet: CVO_ERR_INVALID.  Either output may be NULL.
+ *
+ * Errors, all found before anything is queued, with no output written and no state changed -- CVO_ERR_INVALID: a null pointer (pairs and best aside),
+ * k < 1 or k > CVO_MAX_HYPOTHESES, ell not finite or <= 0, a non-finite entry in trans, count < 1 or above the batch's pairs, a slot out of range or
+ * listed twice, a stream slot (cvo_batch_advance_*: these carry their own state); CVO_ERR_EMPTY_CLOUD: an empty cloud. */
+#define CVO_MAX_HYPOTHESES 64
+int cvo_score_hypotheses(cvo_handle h, int slot_a, int slot_b, int k, const float* trans /* k x 12 */, float ell,
+                         cvo_inn_p* scores /* k */, int* best /* may be NULL */);
+int cvo_batch_score_hypotheses(cvo_batch b, int count, const int* pairs /* slots; NULL: 0 .. count-1 */, int k,
+                               const float* trans /* count x k x 12 */, float ell, cvo_inn_p* scores /* count x k */, int* best /* count, may be NULL */);
+int cvo_batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell);
+int cvo_batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores /* count x k, may be NULL */, int* best /* count, may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
