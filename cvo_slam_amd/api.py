@@ -103,6 +103,10 @@ class PointSupportDst(C.Structure):      # cvo_point_support_dst: one pair's fou
     _fields_ = [("sum_moving", C.c_void_p), ("count_moving", C.c_void_p), ("sum_fixed", C.c_void_p), ("count_fixed", C.c_void_p)]
 
 
+class PoseModel(C.Structure):            # cvo_pose_model: value, se(3) gradient and Hessian of the inner product at one pose
+    _fields_ = [("value", C.c_float), ("num", C.c_int), ("grad", C.c_double * 6), ("hess", C.c_double * 36)]
+
+
 class TrackStep(C.Structure):
     """cvo_track_step: one stream's share of a tracker step (cvo_hip.h: cvo_tracks_wait)."""
     _fields_ = [("phase", C.c_int), ("points", C.c_int), ("odometry", PairResult), ("odometry_scores", TrackScores),
@@ -144,6 +148,7 @@ ABI_SYMBOLS = [
     "cvo_tracks_step_device_clouds_async",
     "cvo_point_support", "cvo_batch_point_support", "cvo_batch_point_support_device", "cvo_tracks_point_support", "cvo_tracks_point_support_device",
     "cvo_score_hypotheses", "cvo_batch_score_hypotheses", "cvo_batch_seed_hypotheses_async", "cvo_batch_hypothesis_results",
+    "cvo_pose_models", "cvo_batch_pose_models", "cvo_batch_result_models",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 
@@ -338,6 +343,10 @@ def load_library():
     L.cvo_batch_score_hypotheses.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float, inp, ip]
     L.cvo_batch_seed_hypotheses_async.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float]
     L.cvo_batch_hypothesis_results.argtypes = [vp, C.c_int, inp, ip]
+    pmp = C.POINTER(PoseModel)
+    L.cvo_pose_models.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, C.c_float, pmp]
+    L.cvo_batch_pose_models.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float, pmp]
+    L.cvo_batch_result_models.argtypes = [vp, C.c_int, ip, pmp]
     _lib = L
     return L
 
@@ -449,6 +458,13 @@ def _inn_arrays(recs, shape):
     """an array of cvo_inn_p as (values float32, nums int32) of `shape`"""
     raw = np.frombuffer(recs, dtype=np.dtype([("value", np.float32), ("num", np.int32), ("num_e", np.int32)]))
     return raw["value"].reshape(shape).copy(), raw["num"].reshape(shape).copy()
+
+
+def _model_arrays(recs, shape):
+    """an array of cvo_pose_model as (values float32, nums int32, grads float64[.., 6], hess float64[.., 6, 6]) of `shape`"""
+    raw = np.frombuffer(recs, dtype=np.dtype([("value", np.float32), ("num", np.int32), ("grad", np.float64, (6,)), ("hess", np.float64, (6, 6))]))
+    return (raw["value"].reshape(shape).copy(), raw["num"].reshape(shape).copy(), raw["grad"].reshape(shape + (6,)).copy(),
+            raw["hess"].reshape(shape + (6, 6)).copy())
 
 
 def _hyp_trans(trans, count):
@@ -867,6 +883,17 @@ class Cvo:
                                            float(self.params.ell if ell is None else ell), recs, C.byref(best)))
         v, n = _inn_arrays(recs, (k,))
         return v, n, int(best.value)
+
+    # -- not in the reference: how the inner product changes with the pose (cvo_hip.h, "pose models")
+    def pose_models(self, slot_a, slot_b, trans, ell=None):
+        """(values float32[K], nums int32[K], grads float64[K, 6], hess float64[K, 6, 6]): value, se(3) gradient and Hessian (twist [omega; v] in the
+        fixed frame, applied on the left) of function_inner_product of slot_a's cloud under each of the K transforms `trans` against slot_b's cloud at
+        length scale ell (None: params.ell), in one launch.  The object's state is untouched."""
+        t, k = _hyp_trans(np.asarray(trans, np.float32).reshape(1, -1, 12), 1)
+        recs = (PoseModel * max(k, 1))()
+        _check(self.L.cvo_pose_models(self.h, int(slot_a), int(slot_b), k, t.ctypes.data_as(C.POINTER(C.c_float)),
+                                      float(self.params.ell if ell is None else ell), recs))
+        return _model_arrays(recs, (k,))
 
     # -- cvo.cpp:620-759
     def se3_hessian(self, slot_a, tran_a, slot_b, inliers: int = 0):
@@ -1536,6 +1563,30 @@ class CvoBatch:
         _check(self.L.cvo_batch_hypothesis_results(self.h, int(count), recs, best.ctypes.data_as(C.POINTER(C.c_int))))
         v, n = _inn_arrays(recs, (int(count), k))
         return v, n, best
+
+    # -- not in the reference: value, se(3) gradient and Hessian of the inner product (cvo_hip.h, "pose models")
+    def pose_models(self, trans, pairs=None, ell=None):
+        """(values float32[count, K], nums int32[count, K], grads float64[count, K, 6], hess float64[count, K, 6, 6]) for slots `pairs` (None: 0 .. count-1):
+        each slot's moving cloud under its K transforms trans[i] (count x K x 3 x 4, moving -> fixed) against its fixed cloud at ell (None: params.ell).
+        No state changes."""
+        t, k, count, pr, prp = self._hyp_args(trans, pairs)
+        recs = (PoseModel * max(count * k, 1))()
+        _check(self.L.cvo_batch_pose_models(self.h, count, prp, k, t.ctypes.data_as(C.POINTER(C.c_float)), float(self.params.ell if ell is None else ell), recs))
+        return _model_arrays(recs, (count, k))
+
+    def result_models(self, pairs=None):
+        """(values float32[count], nums int32[count], grads float64[count, 6], hess float64[count, 6, 6]) for positions `pairs` of the last launch (None: all of
+        an align(n) / align_pairs(slots) launch): each pair's model at its own result transform and ell, read from its device-resident state behind the
+        align launch."""
+        if pairs is None:
+            last = getattr(self, "_last_slots", None)
+            if last is None:
+                raise ValueError("pairs: name the positions (the launch was not started through this object, its length is not known here)")
+            pairs = np.arange(len(last))
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1)
+        recs = (PoseModel * max(pr.shape[0], 1))()
+        _check(self.L.cvo_batch_result_models(self.h, pr.shape[0], pr.ctypes.data_as(C.POINTER(C.c_int)), recs))
+        return _model_arrays(recs, (pr.shape[0],))
 
     def results_to_device(self, dst_device_ptr: int, n: int, stream: int | None = None):
         _check(self.L.cvo_batch_results_to_device(self.h, C.c_void_p(dst_device_ptr), n, C.c_void_p(stream) if stream else None))

@@ -116,6 +116,9 @@ int hyp_row_blocks(int na);
 int hyp_max();
 hipError_t launch_hypotheses(const HypDesc* descs, int n_pairs, int k, int row_blocks, const DevParams& P, double* partials, HypScore* scores, int* best,
                              int seed, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
+int pose_model_row_blocks(int na);
+hipError_t launch_pose_models(const PoseModelDesc* descs, int n_pairs, int k, int row_blocks, const DevParams& P, double* partials, PoseModel* out,
+                              hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
 }  // namespace cvohip
 
 using namespace cvohip;
@@ -123,6 +126,8 @@ using namespace cvohip;
 static_assert(sizeof(cvo_trace_row) == sizeof(TraceRow), "trace row layout");
 static_assert(sizeof(cvo_adaptive_row) == sizeof(AdaptiveRow), "adaptive trace row layout");
 static_assert(sizeof(cvo_inn_p) == sizeof(HypScore), "inn_p record layout");
+static_assert(sizeof(cvo_pose_model) == sizeof(PoseModel) && offsetof(cvo_pose_model, grad) == offsetof(PoseModel, grad) &&
+              offsetof(cvo_pose_model, hess) == offsetof(PoseModel, hess), "pose model record layout");
 
 namespace {
 
@@ -1609,6 +1614,74 @@ struct Engine {
         const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(h_hyp_out.p);
         std::memcpy(scores, sc, sizeof(cvo_inn_p) * (size_t)hyp_n * hyp_k);
         if (best) std::memcpy(best, sc + (size_t)hyp_n * hyp_k, sizeof(int) * (size_t)hyp_n);
+        return CVO_OK;
+    }
+
+    // Pose models (cvo_pose_model_kernels.hip; include/cvo_hip.h: cvo_pose_models): for every request value, gradient and Hessian of the moving cloud a
+    // against the fixed cloud b at each of the k transforms trans[r][0 .. k) and `ell` -- or, from >= 0 (k = 1, trans null), at the transform and ell
+    // of d_states[from], so that the call can be queued behind the align launch that writes them.  ONE sweep launch and the reduce launch behind it.
+    // Buffers of its own (nothing is shared with a score block, a support call or a hypothesis call in flight); one call at a time, and every
+    // call is collected before its entry point returns.
+    struct PoseModelReq { const Cloud* a; const Cloud* b; int from; };
+    DevBuf d_pm_tab, d_pm_partials; PinBuf h_pm_tab, h_pm_out;
+    hipEvent_t ev_pm = nullptr; bool pm_queued = false; int pm_n = 0, pm_k = 0;
+    int pm_enqueue(const PoseModelReq* rq, int n, int k, const float* trans, float ell, hipStream_t s) {
+        HIP_TRY(hipSetDevice(device));
+        if (n <= 0 || k < 1 || k > hyp_max()) return fail(CVO_ERR_INVALID, "bad pose model request");
+        for (int r = 0; r < n; ++r) {
+            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
+            if (rq[r].from >= 0 ? (k != 1 || rq[r].from >= state_slots) : !trans) return fail(CVO_ERR_INVALID, "pose models: no transform for a pair");
+        }
+        if (!ev_pm) HIP_TRY(hipEventCreateWithFlags(&ev_pm, hipEventDisableTiming));
+        if (pm_queued) { HIP_TRY(hipEventSynchronize(ev_pm)); pm_queued = false; }   // the last call's table, records and answers are free
+        int rc;
+        if ((rc = flush_pending(s)) || (rc = settle_uploads(s))) return rc;
+        if (launched && last_stream && last_stream != s) HIP_TRY(hipStreamWaitEvent(s, ev1, 0));   // an align launch on a caller's stream packs clouds and writes states
+        int row_blocks = 1;
+        for (int r = 0; r < n; ++r) row_blocks = std::max(row_blocks, pose_model_row_blocks(rq[r].a->n));
+        const size_t off_tran = sizeof(PoseModelDesc) * (size_t)n, tab_bytes = off_tran + (trans ? sizeof(float) * 12 * (size_t)n * k : 0);
+        if ((rc = h_pm_tab.ensure(tab_bytes)) || (rc = d_pm_tab.ensure(tab_bytes)) || (rc = h_pm_out.ensure(sizeof(PoseModel) * (size_t)n * k)) ||
+            (rc = d_pm_partials.ensure(sizeof(double) * POSE_MODEL_TERMS * (size_t)n * k * row_blocks))) return rc;
+        unsigned char* const tab = static_cast<unsigned char*>(h_pm_tab.p);
+        PoseModelDesc* const pd = reinterpret_cast<PoseModelDesc*>(tab);
+        std::memset(tab, 0, off_tran);
+        if (trans) std::memcpy(tab + off_tran, trans, sizeof(float) * 12 * (size_t)n * k);
+        const float* const d_tran = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d_pm_tab.p) + off_tran);
+        for (int r = 0; r < n; ++r) {
+            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
+            if ((rc = ensure_boxes(b, s))) return rc;
+            PoseModelDesc& D = pd[r];
+            D.a = a.rec(); D.na = a.n; D.b = b.rec(); D.nb = b.n;
+            D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
+            D.ell = ell;
+            if (rq[r].from >= 0) D.from = static_cast<const PairState*>(d_states.p) + rq[r].from;
+            else D.trans = d_tran + 12 * (size_t)r * k;
+        }
+        HIP_TRY(hipMemcpyAsync(d_pm_tab.p, h_pm_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        const PoseModelDesc* const d_pd = static_cast<const PoseModelDesc*>(d_pm_tab.p);
+        PoseModel* const d_out = static_cast<PoseModel*>(h_pm_out.p);
+        hipError_t e;
+        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            const unsigned wgs = (unsigned)row_blocks * (unsigned)k * (unsigned)n;
+            *qc->submitted_host += wgs;
+            bool sweep_submitted = false;
+            e = launch_pose_models(d_pd, n, k, row_blocks, P, static_cast<double*>(d_pm_partials.p), d_out, s, qc->started_dev, &sweep_submitted);
+            if (!sweep_submitted) *qc->submitted_host -= wgs;
+            else if (e != hipSuccess) resync_adopt_counters(qc);
+        } else e = launch_pose_models(d_pd, n, k, row_blocks, P, static_cast<double*>(d_pm_partials.p), d_out, s, nullptr, nullptr);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pose model kernel launch: ") + hipGetErrorString(e));
+        HIP_TRY(hipEventRecord(ev_pm, s));
+        pm_queued = true; pm_n = n; pm_k = k;
+        return CVO_OK;
+    }
+    // waits for the call queued last and hands out its models
+    int pm_collect(cvo_pose_model* out) {
+        HIP_TRY(hipSetDevice(device));
+        if (!pm_queued) return fail(CVO_ERR_INVALID, "no queued pose models");
+        HIP_TRY(hipEventSynchronize(ev_pm));
+        pm_queued = false;
+        std::memcpy(out, h_pm_out.p, sizeof(cvo_pose_model) * (size_t)pm_n * pm_k);
         return CVO_OK;
     }
 };
@@ -4362,6 +4435,44 @@ int cvo_batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores, int*
     if (scores) std::memcpy(scores, E.seed_scores.data(), sizeof(cvo_inn_p) * (size_t)count * E.seed_k);
     if (best) std::memcpy(best, E.seed_best.data(), sizeof(int) * (size_t)count);
     return CVO_OK;
+}
+
+// ---- pose models (include/cvo_hip.h, "pose models"; cvo_pose_model_kernels.hip)
+int cvo_pose_models(cvo_handle h, int slot_a, int slot_b, int k, const float* trans, float ell, cvo_pose_model* out) {
+    if (!h || !out) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = hyp_check_args(k, trans, (size_t)std::max(k, 0), ell); if (rc) return rc;
+    Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
+    if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "pose models: empty cloud slot");
+    const Engine::PoseModelReq rq[1] = {{a, b, -1}};
+    if ((rc = h->eng.pm_enqueue(rq, 1, k, trans, ell, h->eng.stream))) return rc;
+    return h->eng.pm_collect(out);
+}
+int cvo_batch_pose_models(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell, cvo_pose_model* out) {
+    if (!out) return fail(CVO_ERR_INVALID, "null argument");
+    std::vector<int> slots; std::vector<Engine::HypReq> hq;
+    int rc = batch_hyp_requests(b, count, pairs, k, trans, ell, slots, hq); if (rc) return rc;   // the rules and errors of cvo_batch_score_hypotheses
+    std::vector<Engine::PoseModelReq> rq(count);
+    for (int i = 0; i < count; ++i) rq[i] = Engine::PoseModelReq{hq[i].a, hq[i].b, -1};
+    if ((rc = batch_settle(b))) return rc;
+    if ((rc = b->eng.pm_enqueue(rq.data(), count, k, trans, ell, b->eng.stream))) return rc;
+    return b->eng.pm_collect(out);
+}
+int cvo_batch_result_models(cvo_batch b, int count, const int* pairs, cvo_pose_model* out) {
+    if (!b || !out) return fail(CVO_ERR_INVALID, "null argument");
+    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
+    int rc = check_last_clouds(b); if (rc) return rc;
+    std::vector<Engine::PoseModelReq> rq(count); std::vector<unsigned char> seen(b->last_n, 0);
+    for (int k = 0; k < count; ++k) {
+        const int i = pairs ? pairs[k] : k;
+        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "result models: pair " + std::to_string(i) + " is not a position of the last launch");
+        if (seen[i]++) return fail(CVO_ERR_INVALID, "result models: pair " + std::to_string(i) + " listed twice");
+        const int p = b->last_slots[i];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
+        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "result models: empty cloud in the batch");
+        rq[k] = Engine::PoseModelReq{mv, fx, p};                     // transform and ell: the pair's device-resident state, as cvo_batch_point_support reads it
+    }
+    if ((rc = b->eng.pm_enqueue(rq.data(), count, 1, nullptr, 0.f, b->eng.last_stream))) return rc;   // behind the align launch on its stream
+    return b->eng.pm_collect(out);
 }
 
 int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst) {

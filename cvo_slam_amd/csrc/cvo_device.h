@@ -293,6 +293,22 @@ struct HypDesc {
 static_assert(sizeof(HypDesc) == 112, "HypDesc layout");
 struct HypScore { float value; int num; int num_e; };   // == cvo_inn_p (include/cvo_hip.h)
 
+// pose models (cvo_pose_model_kernels.hip; not in the reference): one pair of a launch -- value, se(3) gradient and Hessian of that sum at each of the
+// launch's K transforms.  HypDesc without the seeding fields, and with the state a result call reads its one transform and its ell from.
+struct PoseModelDesc {
+    const float* a;                         // moving cloud: two planes of na float4 (lo_off / hi_off)
+    const float* b;                         // fixed cloud: two planes of nb float4
+    const float* bbox;                      // boxes of b's 32-point groups (planes of nbox floats, as ScoreDesc::bbox)
+    const float* trans;                     // this pair's K transforms, 12 floats each (moving -> fixed, 3x4 row-major); unused with `from`
+    const PairState* from;                  // non-null (K = 1): the transform is from->transform and ell is from->ell (the pair's own align() result)
+    int nbox, na, nb;
+    float ell;
+};
+static_assert(sizeof(PoseModelDesc) == 56, "PoseModelDesc layout");
+constexpr int POSE_MODEL_TERMS = 29;        // a block's record of doubles: sum, count, 6 gradient sums, the 21 sums of pair_hessian_add_weighted
+struct PoseModel { float value; int num; double grad[6]; double hess[36]; };   // == cvo_pose_model (include/cvo_hip.h)
+static_assert(sizeof(PoseModel) == 344, "PoseModel layout");
+
 // a score block: up to 8 inner-product / Hessian requests evaluated by one launch
 constexpr int SCORE_MAXREQ = 8;
 struct ScoreBatch {

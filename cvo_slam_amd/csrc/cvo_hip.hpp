@@ -97,6 +97,13 @@ public:
         for (int i = 0; i < k; ++i) to(r[i], scores[i]);
         return best;
     }
+    // not in the reference: value, se(3) gradient and Hessian of that inner product at each of k transforms (cvo_pose_models in include/cvo_hip.h)
+    void pose_models(int slot_a, int slot_b, int k, const Affine3f* trans, float ell, cvo_pose_model* out) {
+        if (k < 1 || k > CVO_MAX_HYPOTHESES || !trans || !out) throw std::runtime_error("pose_models: bad argument");
+        float t[CVO_MAX_HYPOTHESES][12];
+        for (int i = 0; i < k; ++i) std::memcpy(t[i], trans[i].m, sizeof(t[i]));
+        if (cvo_pose_models(h_, slot_a, slot_b, k, &t[0][0], ell, out) != CVO_OK) throw std::runtime_error(std::string("pose_models: ") + cvo_last_error());
+    }
     void align() { if (cvo_align(h_) != CVO_OK) throw std::runtime_error(std::string("align: ") + cvo_last_error()); sync(); }
 
     void compute_innerproduct(inn_p& inn_pre, inn_p& inn_post, Matrix6d& post_hessian, Affine3f& tran, int& inliers,
@@ -139,6 +146,15 @@ inline void batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs
 // the last seeding call's scores and choices; waits for that call's kernels alone
 inline void batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores, int* best) {
     if (cvo_batch_hypothesis_results(b, count, scores, best) != CVO_OK) throw std::runtime_error(std::string("batch_hypothesis_results: ") + cvo_last_error());
+}
+
+// Pose models for the pairs of a batch (include/cvo_hip.h, "pose models"): k transforms per listed slot, out count x k
+inline void batch_pose_models(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell, cvo_pose_model* out) {
+    if (cvo_batch_pose_models(b, count, pairs, k, trans, ell, out) != CVO_OK) throw std::runtime_error(std::string("batch_pose_models: ") + cvo_last_error());
+}
+// one model per listed position of the last launch, at the pair's own result transform and ell
+inline void batch_result_models(cvo_batch b, int count, const int* pairs, cvo_pose_model* out) {
+    if (cvo_batch_result_models(b, count, pairs, out) != CVO_OK) throw std::runtime_error(std::string("batch_result_models: ") + cvo_last_error());
 }
 
 // K tracker streams (cvo_tracks_* in include/cvo_hip.h): each stream is the pair of objects local_tracker owns, cvo_odometry (object 0) and

@@ -1,6 +1,7 @@
 // cvo_sweep.hpp -- what cvo_score_kernel (cvo_score_kernels.hip), cvo_support_kernel (cvo_support_kernels.hip) and the align launch's
 // tail scores (cvo_kernels.hip, score_pair_terms) have in common, written once: the group boxes of a cloud, the box-culled radius sweep
 // of 64 rows over a cloud's columns, and the reference's arithmetic of one pair.  The tests hold these three places to the same bits.
+// cvo_hyp_score_kernel (cvo_hypothesis_kernels.hip) and cvo_pose_model_sweep_kernel (cvo_pose_model_kernels.hip) are built on the same pieces.
 //
 // The sweep.  The radius search the reference runs per point (KD-tree, nanoflann) is restated as a box cull: clouds come in image scan
 // order, so 32 consecutive points span the image width but only a few image rows -- every cloud carries the bounding boxes of its
@@ -167,15 +168,14 @@ __device__ __forceinline__ float pair_d2c(const float (&fa)[5], const float (&fb
 // sig2 = sigma^2, den_l = 2 ell^2 (cvo.cpp:429 / 661); csig2 = c_sigma^2, den_c = 2 c_ell^2 (cvo.cpp:430): double exp, the division as written
 __device__ __forceinline__ float pair_k(float d2, float sig2, double den_l) { return (float)((double)sig2 * exp((double)(-d2) / den_l)); }
 __device__ __forceinline__ float pair_ck(float d2c, float csig2, double den_c) { return (float)((double)csig2 * exp((double)(-d2c) / den_c)); }
-// se3_Hessian's 21 terms of the pair, added to H (f32, as the reference keeps its Hessian: cvo.cpp:622, 707); il2 = 1 / ell^2
-__device__ __forceinline__ void pair_hessian_add(const float (&pa)[3], const float (&fa)[5], const float (&pb)[3], const float (&fb)[5], float il2, float k, float (&H)[21]) {
-    float t[5];
-#pragma unroll
-    for (int c = 0; c < 5; ++c) t[c] = fa[c] * fb[c];
-    const float cdot = (t[0] + t[1]) + (t[2] + (t[3] + t[4]));       // cvo.cpp:662
-    float cr[3]; cross3(pa, pb, cr);
+// se3_Hessian's 21 terms of the pair (cvo.cpp:665-704), each a float, times the float weight wgt, each product a float, added to H; il2 = 1 / ell^2.
+// Acc: float as the reference keeps its Hessian (cvo.cpp:622, 707), or double (cvo_pose_model_kernels.hip).  cr = pa x pb and db = pb - pa are
+// handed back: the gradient's terms are made of them.
+template <class Acc>
+__device__ __forceinline__ void pair_hessian_add_weighted(const float (&pa)[3], const float (&pb)[3], float il2, float wgt, Acc (&H)[21], float (&cr)[3], float (&db)[3]) {
+    cross3(pa, pb, cr);
     const float dot1 = pa[1] * pb[1] + pa[2] * pb[2], dot2 = pa[0] * pb[0] + pa[2] * pb[2], dot3 = pa[0] * pb[0] + pa[1] * pb[1];
-    const float db[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
+    db[0] = pb[0] - pa[0]; db[1] = pb[1] - pa[1]; db[2] = pb[2] - pa[2];
     float Bq[21];
     // block A (symmetric): 00 01 02 11 12 22                          cvo.cpp:670-675
     Bq[0] = il2 * cr[0] * cr[0] - dot1;
@@ -191,9 +191,17 @@ __device__ __forceinline__ void pair_hessian_add(const float (&pa)[3], const flo
     // block D (symmetric): 00 01 02 11 12 22                          cvo.cpp:692-697
     Bq[15] = il2 * db[0] * db[0] - 1; Bq[16] = il2 * db[0] * db[1]; Bq[17] = il2 * db[0] * db[2];
     Bq[18] = il2 * db[1] * db[1] - 1; Bq[19] = il2 * db[1] * db[2]; Bq[20] = il2 * db[2] * db[2] - 1;
-    const float wgt = il2 * cdot * k;                                // cvo.cpp:707
 #pragma unroll
     for (int q2 = 0; q2 < 21; ++q2) H[q2] += wgt * Bq[q2];
+}
+// the reference's weight: the features' dot product where the energy has ck (cvo.cpp:662, 707)
+__device__ __forceinline__ void pair_hessian_add(const float (&pa)[3], const float (&fa)[5], const float (&pb)[3], const float (&fb)[5], float il2, float k, float (&H)[21]) {
+    float t[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) t[c] = fa[c] * fb[c];
+    const float cdot = (t[0] + t[1]) + (t[2] + (t[3] + t[4]));       // cvo.cpp:662
+    float cr[3], db[3];
+    pair_hessian_add_weighted(pa, pb, il2, il2 * cdot * k, H, cr, db);   // cvo.cpp:707
 }
 
 }  // namespace cvohip

@@ -853,6 +853,57 @@ int cvo_batch_score_hypotheses(cvo_batch b, int count, const int* pairs /* slots
 int cvo_batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs, int k, const float* trans, float ell);
 int cvo_batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores /* count x k, may be NULL */, int* best /* count, may be NULL */);
 
+
+/* ======================= pose models: value, se(3) gradient and Hessian of the inner product at a pose (NOT in the reference) ===========
+ * The calls above report the alignment energy at a pose as one number; these say how it changes with the pose.  a is the moving side (rows), b the
+ * fixed side (columns), T a 3x4 row-major transform moving -> fixed (the convention of tran_a), ell a length scale.  pa_i = T a_i, computed as the
+ * hypotheses' score computes it; pair (i, j) is INSIDE by the two gates of function_inner_product (cvo.cpp:395-396, 423, 428), its value is
+ * a_ij = ck * k (cvo.cpp:429-431), no a > sp_thres test: all as in "pose hypotheses".  Define
+ *   f(xi) = sum over the inside pairs of a_ij with the moving cloud under Exp(xi^) o T,
+ * xi = [omega; v] a twist in the FIXED frame, rotation first, Exp the SE(3) exponential, the inside set held at what it is at xi = 0.  A model:
+ *   value   f(0): the float of the double sum              num   the inside pairs, 1 where that is 0 (cvo.cpp:455-456)
+ *   grad    df/dxi at 0                                    hess  d2f/dxi2 at 0, 6 x 6 row-major, symmetric bit for bit
+ * With il2 = 1 / ell^2 and w_ij = il2 * a_ij (floats), pb = b_j, cr = pa x pb, db = pb - pa:
+ *   grad[0..2] = sum w_ij cr      grad[3..5] = sum w_ij db      hess = sum w_ij Blocks_ij + S
+ * Blocks: the 21 terms se3_Hessian builds per pair (cvo.cpp:665-704) -- A at (omega, omega), D at (v, v), C at (v, omega), C^T at (omega, v) -- under
+ * the weight il2 * ck * k of the energy itself, NOT the reference's il2 * cdot * k (cvo.cpp:662, 707).  S holds 1/2 hat(grad[3..5]) in the (v, omega)
+ * block and its transpose in the (omega, v) block, hat(g) = [[0, -g2, g1], [g2, 0, -g0], [-g1, g0, 0]]: the 1/2 omega x v term of Exp.  It vanishes
+ * at a stationary pose; with it hess is the exact second derivative (against central differences: 1e-5 of the largest entry, 2e-3 to 1e-2 without).
+ * value is MAXIMISED by the alignment: hess is negative definite near a good pose, -hess at a result is an information matrix in the energy's own
+ * units, and (-hess) delta = grad is a Newton step, to be applied as Exp(delta^) o T.  cvo_se3_hessian is something else: the reference's matrix
+ * (cdot weight, scaled by -1/100000, shifted until every |eigenvalue| >= 1, cvo.cpp:662, 707, 726-748), not the curvature of this energy.
+ *
+ * Float sequence: a pair's terms are floats, products and sums as written; a row adds its terms to double accumulators in ascending column order, a
+ * wave adds its lanes with a fixed butterfly, a second step adds the row blocks in ascending order and then adds S; nothing is added atomically.
+ * Every bit of a model depends on the two clouds, T, ell and the parameters alone -- not on k, on the model's place in the call, on the other pairs
+ * or on the launch's shape.  value and num are the bytes cvo_score_hypotheses gives for the same arguments.  No inside pair: value 0, num 1, zeros.
+ *
+ * cvo_pose_models: clouds from the handle's slots (a = moving side, b = fixed side), k transforms, explicit ell; the call waits.  The handle's
+ *   state is untouched.
+ * cvo_batch_pose_models: for batch slots pairs[i] with the rules of cvo_batch_score_hypotheses (slot indices; NULL: 0 .. count-1; trans holds k
+ *   transforms per listed slot, in list order; out count x k).  Takes in a launch in flight first, waits and copies.  No state, seed or start flag
+ *   changes: an align launch that follows gives the bytes it would have given without the call.
+ * cvo_batch_result_models: for positions pairs[k] (NULL: 0 .. count-1) of the LAST launch's list, with the rules of cvo_batch_point_support: one
+ *   model per pair at the transform and ell its alignment left in the pair's device-resident state.  Queued behind the align launch on its stream,
+ *   no transform crosses the host; the call then waits and copies.  It shares no buffer with a score block, a support call or a seeding call in
+ *   flight.
+ *
+ * Errors, all found before anything is queued, with nothing written -- cvo_pose_models and cvo_batch_pose_models: those of the hypothesis calls
+ * (a null pointer, pairs aside; k < 1 or k > CVO_MAX_HYPOTHESES; ell not finite or <= 0; a non-finite entry in trans; count < 1 or above the batch's
+ * pairs; a slot out of range or listed twice; a stream slot: CVO_ERR_INVALID; an empty cloud: CVO_ERR_EMPTY_CLOUD).  cvo_batch_result_models: those
+ * of cvo_batch_point_support (a NULL out, no launch yet, count < 1 or above the last launch's, a position out of range or listed twice, clouds
+ * replaced since the launch: CVO_ERR_INVALID; CVO_ERR_EMPTY_CLOUD). */
+typedef struct cvo_pose_model {
+    float  value;     /* f(0): the float of the double sum                                     */
+    int    num;       /* inside pairs; 1 where that is 0 (cvo.cpp:455-456)                     */
+    double grad[6];   /* df/dxi at 0                                                           */
+    double hess[36];  /* d2f/dxi2 at 0, 6 x 6 row-major, symmetric                             */
+} cvo_pose_model;
+int cvo_pose_models(cvo_handle h, int slot_a, int slot_b, int k, const float* trans /* k x 12 */, float ell, cvo_pose_model* out /* k */);
+int cvo_batch_pose_models(cvo_batch b, int count, const int* pairs /* slots; NULL: 0 .. count-1 */, int k,
+                          const float* trans /* count x k x 12 */, float ell, cvo_pose_model* out /* count x k */);
+int cvo_batch_result_models(cvo_batch b, int count, const int* pairs /* NULL: 0 .. count-1 */, cvo_pose_model* out /* count */);
+
 #ifdef __cplusplus
 }
 #endif
