@@ -103,6 +103,16 @@ class PointSupportDst(C.Structure):      # cvo_point_support_dst: one pair's fou
     _fields_ = [("sum_moving", C.c_void_p), ("count_moving", C.c_void_p), ("sum_fixed", C.c_void_p), ("count_fixed", C.c_void_p)]
 
 
+class MatchFit(C.Structure):             # cvo_match_fit: one direction's fit record of a point-matches call
+    _fields_ = [("rows", C.c_int), ("matched", C.c_int), ("sum_w", C.c_double), ("sum_w_res2", C.c_double)]
+
+
+class PointMatchesDst(C.Structure):      # cvo_point_matches_dst: one pair's ten output arrays and its two fit records (host or device memory, by entry point)
+    _fields_ = [("best_moving", C.c_void_p), ("best_value_moving", C.c_void_p), ("mean_moving", C.c_void_p), ("sum_moving", C.c_void_p), ("count_moving", C.c_void_p),
+                ("best_fixed", C.c_void_p), ("best_value_fixed", C.c_void_p), ("mean_fixed", C.c_void_p), ("sum_fixed", C.c_void_p), ("count_fixed", C.c_void_p),
+                ("fit", C.c_void_p)]
+
+
 class PoseModel(C.Structure):            # cvo_pose_model: value, se(3) gradient and Hessian of the inner product at one pose
     _fields_ = [("value", C.c_float), ("num", C.c_int), ("grad", C.c_double * 6), ("hess", C.c_double * 36)]
 
@@ -147,6 +157,7 @@ ABI_SYMBOLS = [
     "cvo_check_device_clouds", "cvo_selftest_ingest_clouds", "cvo_batch_set_pairs_device_clouds", "cvo_batch_advance_device_clouds",
     "cvo_tracks_step_device_clouds_async",
     "cvo_point_support", "cvo_batch_point_support", "cvo_batch_point_support_device", "cvo_tracks_point_support", "cvo_tracks_point_support_device",
+    "cvo_point_matches", "cvo_batch_point_matches", "cvo_batch_point_matches_device", "cvo_tracks_point_matches", "cvo_tracks_point_matches_device",
     "cvo_score_hypotheses", "cvo_batch_score_hypotheses", "cvo_batch_seed_hypotheses_async", "cvo_batch_hypothesis_results",
     "cvo_pose_models", "cvo_batch_pose_models", "cvo_batch_result_models",
 ]
@@ -338,6 +349,12 @@ def load_library():
     L.cvo_batch_point_support_device.argtypes = [vp, C.c_int, ip, psp, vp]
     L.cvo_tracks_point_support.argtypes = [vp, C.c_int, C.c_int, ip, psp]
     L.cvo_tracks_point_support_device.argtypes = [vp, C.c_int, C.c_int, ip, psp, vp]
+    pmp = C.POINTER(PointMatchesDst)
+    L.cvo_point_matches.argtypes = [vp, C.c_int, fp, C.c_int, pmp, C.c_int, C.c_int]
+    L.cvo_batch_point_matches.argtypes = [vp, C.c_int, ip, pmp]
+    L.cvo_batch_point_matches_device.argtypes = [vp, C.c_int, ip, pmp, vp]
+    L.cvo_tracks_point_matches.argtypes = [vp, C.c_int, C.c_int, ip, pmp]
+    L.cvo_tracks_point_matches_device.argtypes = [vp, C.c_int, C.c_int, ip, pmp, vp]
     inp = C.POINTER(InnP)
     L.cvo_score_hypotheses.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, C.c_float, inp, ip]
     L.cvo_batch_score_hypotheses.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float, inp, ip]
@@ -752,6 +769,75 @@ def _settle_support_writer(out, out_stream):
             return
 
 
+# ---- point matches (cvo_hip.h, "point matches"): the output records of all three forms
+_MATCH_FIELDS = (("best", "<i4", 1), ("best_value", "<f4", 1), ("mean", "<f4", 3), ("sum", "<f4", 1), ("count", "<i4", 1))
+_MATCH_KEYS = tuple((f"{name}_{side}", typestr, width) for side in ("moving", "fixed") for name, typestr, width in _MATCH_FIELDS)
+_MATCH_FIT_DTYPE = np.dtype([("rows", "<i4"), ("matched", "<i4"), ("sum_w", "<f8"), ("sum_w_res2", "<f8")])     # cvo_match_fit
+
+
+def match_fit_records(raw):
+    """(fit_moving, fit_fixed) as dicts out of the 48 bytes of a point-matches `fit` array (a host copy of the device form's)"""
+    rec = np.frombuffer(np.ascontiguousarray(raw).tobytes(), _MATCH_FIT_DTYPE, count=2)
+    return tuple({k: (int(r[k]) if k in ("rows", "matched") else float(r[k])) for k in _MATCH_FIT_DTYPE.names} for r in rec)
+
+
+def _match_host_records(sizes):
+    """numpy arrays for pairs of (n_moving, n_fixed) points, their fit records, and the C records that point at them"""
+    arrays, fits = [], np.zeros((max(1, len(sizes)), 2), _MATCH_FIT_DTYPE)
+    recs = (PointMatchesDst * max(1, len(sizes)))()
+    for k, (r, (nm, nf)) in enumerate(zip(recs, sizes)):
+        a = {}
+        for key, typestr, width in _MATCH_KEYS:
+            n = nm if key.endswith("moving") else nf
+            a[key] = np.zeros(n if width == 1 else (n, width), np.dtype(typestr))
+            setattr(r, key, a[key].ctypes.data)
+        r.fit = fits[k].ctypes.data
+        arrays.append(a)
+    return arrays, fits, recs
+
+
+def _match_host_results(arrays, fits):
+    for k, a in enumerate(arrays):
+        a["fit_moving"], a["fit_fixed"] = match_fit_records(fits[k])
+    return arrays
+
+
+def _match_device_records(out, sizes):
+    """records over caller-owned device arrays: out[k] is a dict with a direction's five arrays (best_*, best_value_*, mean_* (n, 3), sum_*, count_*;
+    a direction may be left out) and optionally `fit`, 48 bytes of device memory for the two fit records (six float64 or 48 uint8; read it back
+    with match_fit_records) -- each anything with __cuda_array_interface__ (torch ROCm tensors), contiguous"""
+    if len(out) != len(sizes):
+        raise ValueError("out: one dict per pair")
+    recs = (PointMatchesDst * max(1, len(out)))()
+    known = {k for k, _, _ in _MATCH_KEYS} | {"fit"}
+    for r, o, (nm, nf) in zip(recs, out, sizes):
+        if set(o) - known:
+            raise ValueError(f"out: unknown keys {sorted(set(o) - known)}")
+        for key, typestr, width in _MATCH_KEYS + (("fit", None, 0),):
+            a = o.get(key)
+            if a is None:
+                continue
+            if not hasattr(a, "__cuda_array_interface__"):
+                raise ValueError(f"out[{key}]: device memory wanted, an object with __cuda_array_interface__ (host arrays: out=None)")
+            cai = a.__cuda_array_interface__
+            shape, item = tuple(cai["shape"]), int(cai["typestr"][2:])
+            if key == "fit":
+                if len(shape) != 1 or shape[0] * item != 48:
+                    raise ValueError(f"out[fit]: shape {shape} of {cai['typestr']}, wanted 48 bytes in one dimension")
+                want_strides = (item,)
+            else:
+                n = nm if key.endswith("moving") else nf
+                if cai["typestr"] != typestr:
+                    raise ValueError(f"out[{key}]: dtype {cai['typestr']}, wanted {typestr}")
+                if shape != ((n,) if width == 1 else (n, width)):
+                    raise ValueError(f"out[{key}]: shape {shape}, the cloud has {n} points")
+                want_strides = (4,) if width == 1 else (4 * width, 4)
+            if cai.get("strides") not in (None, want_strides):
+                raise ValueError(f"out[{key}]: not contiguous")
+            setattr(r, key, int(cai["data"][0]))
+    return recs
+
+
 class Cvo:
     """One `cvo::cvo` object (cvo.hpp:82-282) living on a gfx950 device."""
 
@@ -871,6 +957,19 @@ class Cvo:
         _check(self.L.cvo_point_support(self.h, slot_a, tp, slot_b, sa.ctypes.data_as(fp), ca.ctypes.data_as(ip), na.value,
                                         sb.ctypes.data_as(fp), cb.ctypes.data_as(ip), nb.value))
         return sa, ca, sb, cb
+
+    # -- not in the reference: what each point was matched to (cvo_hip.h, "point matches")
+    def point_matches(self, slot_a, tran_a, slot_b):
+        """A dict: per point of the cloud in slot_a (moved by tran_a when given; keys *_moving) and per point of slot_b's (*_fixed) the index of its
+        best partner in the other cloud (best, -1: none), that kernel value (best_value), the kernel-weighted mean of its partners' points in
+        slot_b's frame (mean, (n, 3)) and point_support's sum and count; fit_moving / fit_fixed: the directions' fit records as dicts
+        (cvo_slam_amd.matches: fitness, rmse, mutual, residuals)."""
+        na, nb = C.c_int(0), C.c_int(0)
+        _check(self.L.cvo_get_cloud(self.h, slot_a, None, None, 0, C.byref(na))); _check(self.L.cvo_get_cloud(self.h, slot_b, None, None, 0, C.byref(nb)))
+        arrays, fits, recs = _match_host_records([(na.value, nb.value)])
+        t, tp = _tran(tran_a)
+        _check(self.L.cvo_point_matches(self.h, slot_a, tp, slot_b, recs, na.value, nb.value))
+        return _match_host_results(arrays, fits)[0]
 
     # -- not in the reference: K start transforms scored before an alignment (cvo_hip.h, "pose hypotheses")
     def score_hypotheses(self, slot_a, slot_b, trans, ell=None):
@@ -1507,6 +1606,35 @@ class CvoBatch:
         count_fixed).  Else out is one dict per pair of device arrays under those keys (a direction may be left out) and the kernel writes them
         itself: with an out_stream (a torch.cuda.Stream or a raw hipStream_t) that stream waits for the launch and the host does not, with None
         the call waits.  Returns out."""
+        pr, sizes = self._last_pair_sizes(pairs, out)
+        ip = C.POINTER(C.c_int)
+        if out is None:
+            arrays, recs = _support_host_records(sizes)
+            _check(self.L.cvo_batch_point_support(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
+            return arrays
+        recs = _support_device_records(out, sizes)
+        _settle_support_writer(out, out_stream)
+        _check(self.L.cvo_batch_point_support_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
+        return out
+
+    # -- not in the reference: point matches of the last launch's pairs (cvo_hip.h, "point matches")
+    def point_matches(self, pairs=None, out=None, out_stream=None):
+        """For positions `pairs` of the last launch, the moving cloud under the pair's own result transform and ell against its fixed cloud: one dict
+        per pair as Cvo.point_matches returns it.  out / out_stream as point_support: out is one dict per pair of device arrays under the array keys
+        (a direction may be left out) and optionally `fit` (48 bytes; api.match_fit_records reads a host copy); the kernels write them themselves."""
+        pr, sizes = self._last_pair_sizes(pairs, out)
+        ip = C.POINTER(C.c_int)
+        if out is None:
+            arrays, fits, recs = _match_host_records(sizes)
+            _check(self.L.cvo_batch_point_matches(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
+            return _match_host_results(arrays, fits)
+        recs = _match_device_records(out, sizes)
+        _settle_support_writer(out, out_stream)
+        _check(self.L.cvo_batch_point_matches_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
+        return out
+
+    def _last_pair_sizes(self, pairs, out):
+        """(positions int32[k], [(n_moving, n_fixed)] of those positions of the last launch)"""
         last = getattr(self, "_last_slots", None)
         if pairs is None:
             if last is None and out is None:
@@ -1521,15 +1649,7 @@ class CvoBatch:
                 _check(self.L.cvo_batch_get_cloud(self.h, slot, SLOT_MOVING, None, None, 0, C.byref(nm)))
                 _check(self.L.cvo_batch_get_cloud(self.h, slot, SLOT_FIXED, None, None, 0, C.byref(nf)))
             sizes.append((nm.value, nf.value))
-        ip = C.POINTER(C.c_int)
-        if out is None:
-            arrays, recs = _support_host_records(sizes)
-            _check(self.L.cvo_batch_point_support(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
-            return arrays
-        recs = _support_device_records(out, sizes)
-        _settle_support_writer(out, out_stream)
-        _check(self.L.cvo_batch_point_support_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
-        return out
+        return pr, sizes
 
     # -- not in the reference: K start transforms per pair, scored in one launch; the next alignment can start from the best (cvo_hip.h, "pose hypotheses")
     def _hyp_args(self, trans, pairs):
@@ -1773,14 +1893,7 @@ class CvoTracks:
     def point_support(self, obj: int, streams, out=None, out_stream=None):
         """Between wait() of a step and the next commit() or step: for the listed streams of that step whose object `obj` (ODOMETRY / KEYFRAME)
         aligned, the step's frame at that object's result transform against the object's fixed cloud.  out / out_stream as CvoBatch.point_support."""
-        sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
-        sizes = []
-        for s in sl:
-            nm, nf = C.c_int(0), C.c_int(0)
-            if 0 <= s < self.max_streams and obj in (0, 1):          # (anything else is the library's to refuse)
-                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_MOVING, None, None, 0, C.byref(nm)))
-                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_FIXED, None, None, 0, C.byref(nf)))
-            sizes.append((nm.value, nf.value))
+        sl, sizes = self._stream_pair_sizes(obj, streams)
         ip = C.POINTER(C.c_int)
         if out is None:
             arrays, recs = _support_host_records(sizes)
@@ -1790,6 +1903,33 @@ class CvoTracks:
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_tracks_point_support_device(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out
+
+    # -- not in the reference: point matches of the step just waited for (cvo_hip.h, "point matches")
+    def point_matches(self, obj: int, streams, out=None, out_stream=None):
+        """Between wait() of a step and the next commit() or step, for the listed streams whose object `obj` aligned: the step's frame at that
+        object's result transform against the object's fixed cloud, one dict per stream.  out / out_stream as CvoBatch.point_matches."""
+        sl, sizes = self._stream_pair_sizes(obj, streams)
+        ip = C.POINTER(C.c_int)
+        if out is None:
+            arrays, fits, recs = _match_host_records(sizes)
+            _check(self.L.cvo_tracks_point_matches(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs))
+            return _match_host_results(arrays, fits)
+        recs = _match_device_records(out, sizes)
+        _settle_support_writer(out, out_stream)
+        _check(self.L.cvo_tracks_point_matches_device(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
+        return out
+
+    def _stream_pair_sizes(self, obj, streams):
+        """(streams int32[k], [(n_moving, n_fixed)] of their object `obj`)"""
+        sl = np.ascontiguousarray(streams, np.int32).reshape(-1)
+        sizes = []
+        for s in sl:
+            nm, nf = C.c_int(0), C.c_int(0)
+            if 0 <= s < self.max_streams and obj in (0, 1):          # (anything else is the library's to refuse)
+                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_MOVING, None, None, 0, C.byref(nm)))
+                _check(self.L.cvo_tracks_get_cloud(self.h, int(s), int(obj), SLOT_FIXED, None, None, 0, C.byref(nf)))
+            sizes.append((nm.value, nf.value))
+        return sl, sizes
 
     def get_cloud(self, s: int, obj: int, slot: int):
         """the cloud of stream s, object ODOMETRY / KEYFRAME, slot SLOT_FIXED / SLOT_MOVING / SLOT_PREVIOUS: xyz (n, 3), feat (5, n)"""

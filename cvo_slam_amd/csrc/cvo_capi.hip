@@ -112,6 +112,9 @@ hipError_t launch_score(const ScoreBatch& B, const ScoreDesc* more, int nreq, in
 int support_row_blocks(int na);
 hipError_t launch_support(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, const SupportDesc* reqs, int n_reqs, int row_blocks,
                           const DevParams& P, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
+int match_row_blocks(int na);
+hipError_t launch_match(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, const MatchDesc* reqs, int n_reqs, int row_blocks,
+                        bool with_fit, const DevParams& P, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted);
 int hyp_row_blocks(int na);
 int hyp_max();
 hipError_t launch_hypotheses(const HypDesc* descs, int n_pairs, int k, int row_blocks, const DevParams& P, double* partials, HypScore* scores, int* best,
@@ -126,6 +129,8 @@ using namespace cvohip;
 static_assert(sizeof(cvo_trace_row) == sizeof(TraceRow), "trace row layout");
 static_assert(sizeof(cvo_adaptive_row) == sizeof(AdaptiveRow), "adaptive trace row layout");
 static_assert(sizeof(cvo_inn_p) == sizeof(HypScore), "inn_p record layout");
+static_assert(sizeof(cvo_match_fit) == sizeof(MatchFit) && offsetof(cvo_match_fit, sum_w) == offsetof(MatchFit, sum_w) &&
+              offsetof(cvo_match_fit, sum_w_res2) == offsetof(MatchFit, sum_w_res2), "match fit record layout");
 static_assert(sizeof(cvo_pose_model) == sizeof(PoseModel) && offsetof(cvo_pose_model, grad) == offsetof(PoseModel, grad) &&
               offsetof(cvo_pose_model, hess) == offsetof(PoseModel, hess), "pose model record layout");
 
@@ -609,6 +614,10 @@ struct Engine {
         if (ev_support_in) { (void)hipEventDestroy(ev_support_in); ev_support_in = nullptr; }
         support_queued = false;
         d_support_tab.release(); d_support_moved.release(); d_support_out.release(); h_support_tab.release(); h_support_out.release();
+        if (ev_match) { (void)hipEventSynchronize(ev_match); (void)hipEventDestroy(ev_match); ev_match = nullptr; }
+        if (ev_match_in) { (void)hipEventDestroy(ev_match_in); ev_match_in = nullptr; }
+        match_queued = false;
+        d_match_tab.release(); d_match_moved.release(); d_match_out.release(); h_match_tab.release(); h_match_out.release();
         if (ev_hyp) { (void)hipEventSynchronize(ev_hyp); (void)hipEventDestroy(ev_hyp); ev_hyp = nullptr; }
         hyp_queued = false;
         d_hyp_tab.release(); d_hyp_partials.release(); h_hyp_tab.release(); h_hyp_out.release();
@@ -1526,6 +1535,148 @@ struct Engine {
     int support_publish(hipStream_t out_stream) {
         if (!out_stream) return support_collect();
         if (out_stream != support_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_support, 0));
+        return CVO_OK;
+    }
+
+    // Point matches (cvo_match_kernels.hip; include/cvo_hip.h: cvo_point_matches): the requests of a support call -- a, b, ell and the transform as a
+    // SupportReq names them -- with five arrays per direction (dst.*_moving: the rows of a, dst.*_fixed: the rows of b; a direction whose arrays
+    // are null is not computed) and, where dst.fit is given, a fit record per computed direction.  to_host as for support_enqueue.
+    // Buffers of its own (nothing is shared with a score block, a support, a hypothesis or a pose-model call in flight); one call at a time.
+    struct MatchReq {
+        const Cloud* a; const float* tran; const Cloud* b; float ell;
+        int from; bool tran_from_state;
+        cvo_point_matches_dst dst;
+    };
+    DevBuf d_match_tab, d_match_moved, d_match_out; PinBuf h_match_tab, h_match_out;
+    hipEvent_t ev_match = nullptr, ev_match_in = nullptr; bool match_queued = false;
+    std::vector<SupportCopy> match_copies; hipStream_t match_stream = nullptr;
+    static bool match_dir_moving(const cvo_point_matches_dst& d) { return d.best_moving != nullptr; }
+    static bool match_dir_fixed(const cvo_point_matches_dst& d) { return d.best_fixed != nullptr; }
+    int match_enqueue(const MatchReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
+        HIP_TRY(hipSetDevice(device));
+        if (n <= 0) return fail(CVO_ERR_INVALID, "bad match request count");
+        for (int r = 0; r < n; ++r) {
+            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
+            if (!match_dir_moving(rq[r].dst) && !match_dir_fixed(rq[r].dst)) return fail(CVO_ERR_INVALID, "point matches: no output array");
+            if (rq[r].tran_from_state && rq[r].from < 0) return fail(CVO_ERR_INVALID, "point matches: transform from a state that is not named");
+        }
+        if (!ev_match) HIP_TRY(hipEventCreateWithFlags(&ev_match, hipEventDisableTiming));
+        if (match_queued) { HIP_TRY(hipEventSynchronize(ev_match)); match_queued = false; }   // the last call's tables, moved planes and outputs are free
+        match_copies.clear();
+        { int rcs = flush_pending(s); if (rcs) return rcs; }
+        { int rcs = settle_uploads(s); if (rcs) return rcs; }
+        // what the call needs: a moved {x, y, z, f0} plane and its boxes per transformed cloud, the tables, and (to_host) a place per output array;
+        // a direction's arrays are 28 bytes a row, its fit record 24 bytes, placed first so that it stays 8-byte aligned
+        int n_moves = 0, n_move_max = 0, n_dirs = 0, row_blocks = 1; bool with_fit = false;
+        size_t moved_bytes = 0, out_bytes = 0;
+        for (int r = 0; r < n; ++r) {
+            const bool moved = rq[r].tran || rq[r].tran_from_state;
+            const int na = rq[r].a->n, nb = rq[r].b->n;
+            if (moved) { ++n_moves; n_move_max = std::max(n_move_max, na); moved_bytes += sizeof(float) * 4 * (size_t)na + score_box_bytes(na); }
+            if (match_dir_moving(rq[r].dst)) { ++n_dirs; out_bytes += 28 * (size_t)na; row_blocks = std::max(row_blocks, match_row_blocks(na)); }
+            if (match_dir_fixed(rq[r].dst)) { ++n_dirs; out_bytes += 28 * (size_t)nb; row_blocks = std::max(row_blocks, match_row_blocks(nb)); }
+            if (rq[r].dst.fit) with_fit = true;
+        }
+        const size_t fit_bytes = sizeof(MatchFit) * (size_t)n_dirs;
+        out_bytes += fit_bytes;
+        const size_t off_box = sizeof(SupportMoveDesc) * (size_t)n_moves, off_req = off_box + sizeof(BoxDesc) * (size_t)n_moves;
+        const size_t tab_bytes = off_req + sizeof(MatchDesc) * (size_t)n_dirs;
+        int rc;
+        if ((rc = h_match_tab.ensure(tab_bytes)) || (rc = d_match_tab.ensure(tab_bytes)) || (rc = d_match_moved.ensure(std::max(moved_bytes, (size_t)16)))) return rc;
+        if (to_host && ((rc = d_match_out.ensure(out_bytes)) || (rc = h_match_out.ensure(out_bytes)))) return rc;
+        unsigned char* const tab = static_cast<unsigned char*>(h_match_tab.p);
+        SupportMoveDesc* const mv = reinterpret_cast<SupportMoveDesc*>(tab);
+        BoxDesc* const bx = reinterpret_cast<BoxDesc*>(tab + off_box);
+        MatchDesc* const sd = reinterpret_cast<MatchDesc*>(tab + off_req);
+        std::memset(tab, 0, tab_bytes);
+        size_t moved_at = 0, out_at = fit_bytes, fit_at = 0; int im = 0, id = 0;
+        auto place_at = [&](void* host_dst, size_t& at, size_t bytes) -> void* {   // an output: the caller's device memory, or a place in d_match_out
+            if (!to_host) return host_dst;
+            match_copies.push_back(SupportCopy{host_dst, at, bytes});
+            void* p = static_cast<unsigned char*>(d_match_out.p) + at; at += bytes; return p;
+        };
+        auto place = [&](void* host_dst, size_t bytes) -> void* { return place_at(host_dst, out_at, bytes); };
+        for (int r = 0; r < n; ++r) {
+            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b; const cvo_point_matches_dst& d = rq[r].dst;
+            const PairState* from = rq[r].from >= 0 ? static_cast<const PairState*>(d_states.p) + rq[r].from : nullptr;
+            const float* a_lo = a.rec(); const float* a_box = nullptr;
+            if (rq[r].tran || rq[r].tran_from_state) {
+                float* plane = reinterpret_cast<float*>(static_cast<unsigned char*>(d_match_moved.p) + moved_at);
+                float* gbox = plane + 4 * (size_t)a.n;
+                moved_at += sizeof(float) * 4 * (size_t)a.n + score_box_bytes(a.n);
+                SupportMoveDesc& M = mv[im]; BoxDesc& B = bx[im]; ++im;
+                M.src = a.rec(); M.dst = plane; M.n = a.n; M.from = rq[r].tran_from_state ? from : nullptr;
+                for (int i = 0; i < 12; ++i) M.tran[i] = rq[r].tran_from_state ? 0.f : rq[r].tran[i];
+                B.rec = plane; B.gbox = gbox; B.self_cache = score_self_cache(gbox, a.n); B.n = a.n; B.ngroups = score_groups(a.n);
+                a_lo = plane; a_box = gbox;
+            } else if (match_dir_fixed(d)) {
+                if ((rc = ensure_boxes(a, s))) return rc;
+                a_box = static_cast<const float*>(a.boxes.p);
+            }
+            if (match_dir_moving(d)) {
+                if ((rc = ensure_boxes(b, s))) return rc;
+                MatchDesc& D = sd[id++];
+                D.a_lo = a_lo; D.a_hi = a.rec() + hi_off(a.n, 0); D.na = a.n;
+                D.b_lo = b.rec(); D.b_hi = b.rec() + hi_off(b.n, 0); D.nb = b.n;
+                D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
+                D.ell = rq[r].ell; D.from = from;
+                D.best = static_cast<int*>(place(d.best_moving, 4 * (size_t)a.n)); D.best_value = static_cast<float*>(place(d.best_value_moving, 4 * (size_t)a.n));
+                D.mean = static_cast<float*>(place(d.mean_moving, 12 * (size_t)a.n));
+                D.sum = static_cast<float*>(place(d.sum_moving, 4 * (size_t)a.n)); D.count = static_cast<int*>(place(d.count_moving, 4 * (size_t)a.n));
+                D.fit = d.fit ? static_cast<MatchFit*>(place_at(d.fit + 0, fit_at, sizeof(MatchFit))) : nullptr;
+            }
+            if (match_dir_fixed(d)) {
+                MatchDesc& D = sd[id++];
+                D.a_lo = b.rec(); D.a_hi = b.rec() + hi_off(b.n, 0); D.na = b.n;
+                D.b_lo = a_lo; D.b_hi = a.rec() + hi_off(a.n, 0); D.nb = a.n;
+                D.bbox = a_box; D.nbox = score_groups(a.n);
+                D.ell = rq[r].ell; D.from = from;
+                D.best = static_cast<int*>(place(d.best_fixed, 4 * (size_t)b.n)); D.best_value = static_cast<float*>(place(d.best_value_fixed, 4 * (size_t)b.n));
+                D.mean = static_cast<float*>(place(d.mean_fixed, 12 * (size_t)b.n));
+                D.sum = static_cast<float*>(place(d.sum_fixed, 4 * (size_t)b.n)); D.count = static_cast<int*>(place(d.count_fixed, 4 * (size_t)b.n));
+                D.fit = d.fit ? static_cast<MatchFit*>(place_at(d.fit + 1, fit_at, sizeof(MatchFit))) : nullptr;
+            }
+        }
+        if (out_stream && out_stream != s) {                         // whatever out_stream still does to the arrays comes first
+            if (!ev_match_in) HIP_TRY(hipEventCreateWithFlags(&ev_match_in, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(ev_match_in, out_stream));
+            HIP_TRY(hipStreamWaitEvent(s, ev_match_in, 0));
+        }
+        HIP_TRY(hipMemcpyAsync(d_match_tab.p, h_match_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+        const unsigned char* const dtab = static_cast<const unsigned char*>(d_match_tab.p);
+        const SupportMoveDesc* d_mv = reinterpret_cast<const SupportMoveDesc*>(dtab);
+        const BoxDesc* d_bx = reinterpret_cast<const BoxDesc*>(dtab + off_box);
+        const MatchDesc* d_sd = reinterpret_cast<const MatchDesc*>(dtab + off_req);
+        hipError_t e;
+        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the support workgroups are
+            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+            const unsigned wgs = (unsigned)row_blocks * (unsigned)n_dirs;
+            *qc->submitted_host += wgs;
+            bool sweep_submitted = false;
+            e = launch_match(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, with_fit, P, s, qc->started_dev, &sweep_submitted);
+            if (!sweep_submitted) *qc->submitted_host -= wgs;
+            else if (e != hipSuccess) resync_adopt_counters(qc);
+        } else e = launch_match(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, with_fit, P, s, nullptr, nullptr);
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("match kernel launch: ") + hipGetErrorString(e));
+        if (to_host) HIP_TRY(hipMemcpyAsync(h_match_out.p, d_match_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(ev_match, s));
+        match_queued = true; match_stream = s;
+        return CVO_OK;
+    }
+    // waits for the call queued last; its host arrays (to_host) are filled here
+    int match_collect() {
+        HIP_TRY(hipSetDevice(device));
+        if (!match_queued) return fail(CVO_ERR_INVALID, "no queued point matches");
+        HIP_TRY(hipEventSynchronize(ev_match));
+        match_queued = false;
+        for (const SupportCopy& c : match_copies) std::memcpy(c.dst, static_cast<const unsigned char*>(h_match_out.p) + c.off, c.bytes);
+        match_copies.clear();
+        return CVO_OK;
+    }
+    // the device form's ordering, as support_publish
+    int match_publish(hipStream_t out_stream) {
+        if (!out_stream) return match_collect();
+        if (out_stream != match_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_match, 0));
         return CVO_OK;
     }
 
@@ -3910,6 +4061,77 @@ int cvo_batch_point_support(cvo_batch b, int count, const int* pairs, const cvo_
 int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, void* out_stream) {
     return batch_support(b, count, pairs, dst, true, out_stream);
 }
+// ---- point matches (include/cvo_hip.h, "point matches"; cvo_match_kernels.hip)
+namespace {
+// One pair's record of a point-matches call: a direction's five arrays all given or all absent, not both absent; on_device: every array is memory the
+// device can write (the rule of cvo_device_cloud: check_device_plane), 4-byte aligned, fit two records and 8-byte aligned.  Nothing is queued here.
+int match_check_dst(int device, const cvo_point_matches_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
+    const struct { const void* p; long long bytes; const char* name; } arr[10] = {
+        {d.best_moving, 4ll * n_moving, "best_moving"}, {d.best_value_moving, 4ll * n_moving, "best_value_moving"}, {d.mean_moving, 12ll * n_moving, "mean_moving"},
+        {d.sum_moving, 4ll * n_moving, "sum_moving"}, {d.count_moving, 4ll * n_moving, "count_moving"},
+        {d.best_fixed, 4ll * n_fixed, "best_fixed"}, {d.best_value_fixed, 4ll * n_fixed, "best_value_fixed"}, {d.mean_fixed, 12ll * n_fixed, "mean_fixed"},
+        {d.sum_fixed, 4ll * n_fixed, "sum_fixed"}, {d.count_fixed, 4ll * n_fixed, "count_fixed"}};
+    for (int side = 0; side < 2; ++side) {
+        int given = 0;
+        for (int q = 0; q < 5; ++q) given += arr[5 * side + q].p ? 1 : 0;
+        if (given != 0 && given != 5) return fail(CVO_ERR_INVALID, who + "a direction needs all five of its arrays");
+    }
+    if (!d.best_moving && !d.best_fixed) return fail(CVO_ERR_INVALID, who + "no output array");
+    if (!on_device) return CVO_OK;
+    for (const auto& x : arr) {
+        if (!x.p) continue;
+        if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
+        int rc = check_device_plane(device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"); if (rc) return rc;
+    }
+    if (d.fit) {
+        if (reinterpret_cast<uintptr_t>(d.fit) & 7u) return fail(CVO_ERR_INVALID, who + "fit is not 8-byte aligned");
+        int rc = check_device_plane(device, d.fit, 2ll * sizeof(cvo_match_fit), 2ll * sizeof(cvo_match_fit), 1, who + "fit", "array"); if (rc) return rc;
+    }
+    return CVO_OK;
+}
+// The requests of the listed slots of b (their device states name transform and ell), checked; then one launch on the stream of b's last launch.
+int batch_match_run(cvo_batch b, const std::vector<int>& slots, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
+    Engine& E = b->eng;
+    if (on_device) HIP_TRY(hipSetDevice(E.device));
+    std::vector<Engine::MatchReq> rq(slots.size());
+    for (size_t k = 0; k < slots.size(); ++k) {
+        const int p = slots[k];
+        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
+        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point matches: empty cloud in the batch");
+        int rc = match_check_dst(E.device, dst[k], mv->n, fx->n, on_device, "point matches, record " + std::to_string(k) + ": "); if (rc) return rc;
+        rq[k] = Engine::MatchReq{mv, nullptr, fx, 0.f, p, true, dst[k]};
+    }
+    int rc = E.match_enqueue(rq.data(), (int)rq.size(), E.last_stream, !on_device, on_device ? static_cast<hipStream_t>(out_stream) : nullptr); if (rc) return rc;
+    return on_device ? E.match_publish(static_cast<hipStream_t>(out_stream)) : E.match_collect();
+}
+int batch_match(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
+    if (!b || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
+    int rc = check_last_clouds(b); if (rc) return rc;
+    std::vector<int> slots(count); std::vector<unsigned char> seen(b->last_n, 0);
+    for (int k = 0; k < count; ++k) {
+        const int i = pairs ? pairs[k] : k;
+        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "point matches: pair " + std::to_string(i) + " is not a position of the last launch");
+        if (seen[i]++) return fail(CVO_ERR_INVALID, "point matches: pair " + std::to_string(i) + " listed twice");
+        slots[k] = b->last_slots[i];
+    }
+    return batch_match_run(b, slots, dst, on_device, out_stream);
+}
+}  // namespace
+int cvo_point_matches(cvo_handle h, int slot_a, const float* tran_a, int slot_b, const cvo_point_matches_dst* dst, int cap_a, int cap_b) {
+    if (!h || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
+    int rc = match_check_dst(h->eng.device, *dst, a ? a->n : 0, b ? b->n : 0, false, "point matches: "); if (rc) return rc;
+    if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point matches: empty cloud slot");
+    if ((dst->best_moving && cap_a < a->n) || (dst->best_fixed && cap_b < b->n)) return fail(CVO_ERR_INVALID, "point matches: an output array is shorter than its cloud");
+    const Engine::MatchReq rq[1] = {{a, tran_a, b, h->ell, -1, false, *dst}};
+    rc = h->eng.match_enqueue(rq, 1, h->eng.stream, true); if (rc) return rc;
+    return h->eng.match_collect();
+}
+int cvo_batch_point_matches(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst) { return batch_match(b, count, pairs, dst, false, nullptr); }
+int cvo_batch_point_matches_device(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, void* out_stream) {
+    return batch_match(b, count, pairs, dst, true, out_stream);
+}
 int cvo_batch_results_to_device(cvo_batch b, void* dst_device, int n, void* stream) {
     if (!b || !dst_device || n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(b->eng.device));
@@ -4350,21 +4572,32 @@ int cvo_tracks_get_state(cvo_tracks t, int s, int object, float R[9], float T[3]
     return CVO_OK;
 }
 namespace {
-int tracks_support(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+// what the point-support and point-matches calls of a tracker check alike: the listed streams' `object` aligned in the step waited for last
+int tracks_aligned_slots(cvo_tracks_s* t, int object, int count, const int* streams, const void* dst, const std::string& who, std::vector<int>& slots) {
     int rc = tracks_check_list(t, count, streams); if (rc) return rc;
     if (!dst) return fail(CVO_ERR_INVALID, "null argument");
     if (object != 0 && object != 1) return fail(CVO_ERR_INVALID, "object must be 0 (odometry) or 1 (keyframe)");
-    if (t->in_flight || !t->support_valid) return fail(CVO_ERR_INVALID, "point support: between cvo_tracks_wait of a step and the next cvo_tracks_commit or step only");
-    std::vector<int> slots(count);
+    if (t->in_flight || !t->support_valid) return fail(CVO_ERR_INVALID, who + ": between cvo_tracks_wait of a step and the next cvo_tracks_commit or step only");
+    slots.resize(count);
     for (int k = 0; k < count; ++k) {
         const int s = streams[k];
         int at = -1;
         for (size_t q = 0; q < t->list.size(); ++q) if (t->list[q] == s) at = (int)q;
-        if (at < 0) return fail(CVO_ERR_INVALID, "point support: stream " + std::to_string(s) + " was not listed in the step");
-        if (!(object == 0 ? t->odo_ok[at] : t->key_ok[at])) return fail(CVO_ERR_INVALID, "point support: that object of stream " + std::to_string(s) + " did not align in the step");
+        if (at < 0) return fail(CVO_ERR_INVALID, who + ": stream " + std::to_string(s) + " was not listed in the step");
+        if (!(object == 0 ? t->odo_ok[at] : t->key_ok[at])) return fail(CVO_ERR_INVALID, who + ": that object of stream " + std::to_string(s) + " did not align in the step");
         slots[k] = s;                                                // (a stream's slot in both batches, and its device state's index)
     }
+    return CVO_OK;
+}
+int tracks_support(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+    std::vector<int> slots;
+    int rc = tracks_aligned_slots(t, object, count, streams, dst, "point support", slots); if (rc) return rc;
     return batch_support_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
+}
+int tracks_match(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
+    std::vector<int> slots;
+    int rc = tracks_aligned_slots(t, object, count, streams, dst, "point matches", slots); if (rc) return rc;
+    return batch_match_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
 }
 }  // namespace
 // ---- pose hypotheses (include/cvo_hip.h, "pose hypotheses"; cvo_hypothesis_kernels.hip)
@@ -4480,6 +4713,12 @@ int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* str
 }
 int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream) {
     return tracks_support(t, object, count, streams, dst, true, out_stream);
+}
+int cvo_tracks_point_matches(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst) {
+    return tracks_match(t, object, count, streams, dst, false, nullptr);
+}
+int cvo_tracks_point_matches_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst, void* out_stream) {
+    return tracks_match(t, object, count, streams, dst, true, out_stream);
 }
 
 // ---------------------------------------------------------------- multi-GPU: RCCL all-gather of the result records

@@ -277,6 +277,25 @@ struct SupportMoveDesc {
 };
 static_assert(sizeof(SupportMoveDesc) == 80, "SupportMoveDesc layout");
 
+// point matches (cvo_match_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds, rows and columns given
+// as a SupportDesc gives them -- per ROW the column of its largest a_ij, that value, the a-weighted mean of its partners' points, and the support's
+// {sum, count}; per request a fit record made from those arrays by a second kernel.  The table is copied to device memory by the call.
+struct MatchFit { int rows; int matched; double sum_w; double sum_w_res2; };    // cvo_match_fit (include/cvo_hip.h)
+static_assert(sizeof(MatchFit) == 24, "MatchFit layout");
+struct MatchDesc {
+    const float* a_lo; const float* a_hi;   // rows: na float4 {x, y, z, f0} and na float4 {f1, f2, f3, f4}
+    const float* b_lo; const float* b_hi;   // columns: nb float4 each
+    const float* bbox;                      // boxes of the columns' 32-point groups (SupportDesc::bbox)
+    int nbox, na, nb;
+    float ell;
+    const PairState* from;                  // non-null: ell comes from this device-resident state (ScoreDesc::from)
+    int* best; float* best_value;           // na each
+    float* mean;                            // na x 3
+    float* sum; int* count;                 // na each
+    MatchFit* fit;                          // null: no fit record for this request
+};
+static_assert(sizeof(MatchDesc) == 112, "MatchDesc layout");
+
 // pose hypotheses (cvo_hypothesis_kernels.hip; not in the reference): one pair of a launch -- its moving cloud under each of the launch's K transforms
 // against its fixed cloud, function_inner_product's sum per transform.  The table and the transforms are copied to device memory by the call.
 struct HypDesc {

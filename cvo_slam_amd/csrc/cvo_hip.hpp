@@ -104,6 +104,11 @@ public:
         for (int i = 0; i < k; ++i) std::memcpy(t[i], trans[i].m, sizeof(t[i]));
         if (cvo_pose_models(h_, slot_a, slot_b, k, &t[0][0], ell, out) != CVO_OK) throw std::runtime_error(std::string("pose_models: ") + cvo_last_error());
     }
+    // not in the reference: what each point of slot_a's cloud (moved by tran_a when given; dst's *_moving arrays, cap_a entries) and of slot_b's (*_fixed,
+    // cap_b) was matched to, and the directions' fit records (cvo_point_matches in include/cvo_hip.h)
+    void point_matches(int slot_a, const Affine3f* tran_a, int slot_b, const cvo_point_matches_dst& dst, int cap_a, int cap_b) {
+        if (cvo_point_matches(h_, slot_a, tran_a ? tran_a->m : nullptr, slot_b, &dst, cap_a, cap_b) != CVO_OK) throw std::runtime_error(std::string("point_matches: ") + cvo_last_error());
+    }
     void align() { if (cvo_align(h_) != CVO_OK) throw std::runtime_error(std::string("align: ") + cvo_last_error()); sync(); }
 
     void compute_innerproduct(inn_p& inn_pre, inn_p& inn_post, Matrix6d& post_hessian, Affine3f& tran, int& inliers,
@@ -157,6 +162,14 @@ inline void batch_result_models(cvo_batch b, int count, const int* pairs, cvo_po
     if (cvo_batch_result_models(b, count, pairs, out) != CVO_OK) throw std::runtime_error(std::string("batch_result_models: ") + cvo_last_error());
 }
 
+// Point matches for the pairs of a batch (include/cvo_hip.h, "point matches"): one record of host arrays per listed position of the last launch, at the
+// pair's own result transform and ell; the device form writes caller-owned device arrays and follows the out_stream ordering rule
+inline void batch_point_matches(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst) {
+    if (cvo_batch_point_matches(b, count, pairs, dst) != CVO_OK) throw std::runtime_error(std::string("batch_point_matches: ") + cvo_last_error());
+}
+inline void batch_point_matches_device(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, void* out_stream = nullptr) {
+    if (cvo_batch_point_matches_device(b, count, pairs, dst, out_stream) != CVO_OK) throw std::runtime_error(std::string("batch_point_matches_device: ") + cvo_last_error());
+}
 // K tracker streams (cvo_tracks_* in include/cvo_hip.h): each stream is the pair of objects local_tracker owns, cvo_odometry (object 0) and
 // cvo_keyframe (object 1).  Not a class of the reference: there the two objects are stepped one frame, one sequence at a time.  Member names
 // follow the C entry points; errors throw, except the statuses a step reports per stream (cvo_track_step).
@@ -215,6 +228,13 @@ public:
     }
     void get_state(int s, int object, float R[9], float T[3], float& ell, Affine3f& transform) {
         check(cvo_tracks_get_state(t_, s, object, R, T, &ell, transform.m), "get_state");
+    }
+    // point matches of the step just waited for (include/cvo_hip.h, "point matches"): host arrays, or device arrays with the out_stream ordering rule
+    void point_matches(int object, int count, const int* streams, const cvo_point_matches_dst* dst) {
+        check(cvo_tracks_point_matches(t_, object, count, streams, dst), "point_matches");
+    }
+    void point_matches_device(int object, int count, const int* streams, const cvo_point_matches_dst* dst, void* out_stream = nullptr) {
+        check(cvo_tracks_point_matches_device(t_, object, count, streams, dst, out_stream), "point_matches_device");
     }
 };
 

@@ -74,17 +74,22 @@ __global__ __launch_bounds__(SUP_BLOCK) void cvo_support_kernel(const SupportDes
 
 int support_row_blocks(int na) { return (na + SUP_BLOCK - 1) / SUP_BLOCK; }
 
-// One call's launches on `stream`, all tables in device memory: the moved planes of n_moves clouds and their group boxes, then ONE sweep over
-// the n_reqs requests (grid z), row_blocks = the blocks of the request with the most rows.
+// The pre-pass of a call on `stream`: the moved planes of n_moves clouds and their group boxes (none: nothing is launched).  The point matches
+// (cvo_match_kernels.hip) start with the same two launches.
+hipError_t launch_support_prepass(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, hipStream_t stream) {
+    if (n_moves <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cvo_support_move_kernel, dim3((n_move_max + 255) / 256, n_moves), dim3(256), 0, stream, moves);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_cloud_boxes_batch(boxes, n_moves, n_move_max, stream);
+}
+
+// One call's launches on `stream`, all tables in device memory: the pre-pass, then ONE sweep over the n_reqs requests (grid z), row_blocks = the
+// blocks of the request with the most rows.
 hipError_t launch_support(const SupportMoveDesc* moves, const BoxDesc* boxes, int n_moves, int n_move_max, const SupportDesc* reqs, int n_reqs, int row_blocks,
                           const DevParams& P, hipStream_t stream, unsigned* wgs_started, bool* sweep_submitted) {
     if (sweep_submitted) *sweep_submitted = false;
-    if (n_moves > 0) {
-        hipLaunchKernelGGL(cvo_support_move_kernel, dim3((n_move_max + 255) / 256, n_moves), dim3(256), 0, stream, moves);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if ((e = launch_cloud_boxes_batch(boxes, n_moves, n_move_max, stream)) != hipSuccess) return e;
-    }
+    { const hipError_t e = launch_support_prepass(moves, boxes, n_moves, n_move_max, stream); if (e != hipSuccess) return e; }
     hipLaunchKernelGGL(cvo_support_kernel, dim3(row_blocks, 1, n_reqs), dim3(SUP_BLOCK), 0, stream, reqs, P, wgs_started);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess && sweep_submitted) *sweep_submitted = true;   // its workgroups will count themselves as started

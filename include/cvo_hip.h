@@ -811,6 +811,48 @@ int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* str
 int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream);
 
 
+/* ======================= point matches: each point's best and mean partner under an alignment (NOT in the reference) ===========
+ * The per-point support says how much of the energy a point holds; these calls say what the point was matched to.  Rows, columns, the move of a by
+ * a transform, the two gates, a_ij = ck * k as one float and no a > sp_thres test are exactly those of "per-point support" above: the moved rows
+ * are computed once into a scratch plane both directions read, so a_ij is one float on both sides.  All coordinates below are in the FIXED frame:
+ * partners of a moving-side row are points of the fixed cloud as stored, partners of a fixed-side row are the moved moving points.  For every row
+ * i of a direction, over the inside pairs of the row:
+ *   best[i]          int32    the column j of the largest a_ij, compared as floats; the lowest j on a tie (an ascending sweep with a strict >)
+ *   best_value[i]    float    that a_ij
+ *   mean[3i..3i+2]   float    (sum_j (double)a_ij * (double)pb_j[q]) / sum_j (double)a_ij, both sums in double in ascending j, the quotient in double,
+ *                             rounded to float once: the a-weighted mean of the partners' points
+ *   sum[i], count[i]          byte for byte what cvo_*_point_support gives for the same arguments
+ * A row with no inside pair gets best = -1 and zeros in every other field.  The arrays are written by the row's own lane, no reduction, no atomics: a
+ * row's bits depend on the two clouds, the transform, ell and the parameters alone, not on what else shares the launch.
+ *
+ * Per direction there is also a fit record, made by a second small kernel (one wave per direction) from what the sweep wrote and the rows' own points:
+ *   rows = the direction's rows;  matched = rows with count > 0;  sum_w = sum_i (double)sum[i];  sum_w_res2 = sum_i (double)sum[i] * (double)res2_i,
+ *   res2_i in float: r = mean - pa per component, (r0*r0 + r1*r1) + r2*r2, pa the row's point in the fixed frame.  Lane L adds rows L, L + 64, ... in
+ *   ascending order, then the 64 lanes are added with a fixed xor-butterfly (32, 16, ..., 1): the record's bits are a function of the arrays alone.
+ * Fitness is matched / rows; the weighted RMS residual is sqrt(sum_w_res2 / sum_w) (metres; no matched row: sum_w is 0).
+ *
+ * The five entry points follow the cvo_*_point_support call of the same name in every respect: the handle form uses the handle's ell, writes host
+ * arrays (cap_a / cap_b entries each, mean three times that) and waits; the batch form reads each pair's result transform and ell from its
+ * device-resident state behind the last align launch on its stream, ONE sweep launch for all pairs and both directions; the device form checks
+ * every pointer by the rule of cvo_device_cloud (4-byte aligned; fit: device memory for two records, 8-byte aligned) and follows the out_stream
+ * ordering rule of cvo_batch_point_support_device; the tracks form is valid between cvo_tracks_wait and the next commit or step.  A direction's five
+ * arrays are all given or all NULL (not computed; its fit record stays unwritten); both directions NULL is an error.  fit may be NULL.  The errors
+ * are those of the support calls, found before anything is queued: nothing is written then.  The calls have buffers of their own: they share none
+ * with a score block, a support, seeding or pose-model call in flight, and change no state. */
+typedef struct cvo_match_fit { int rows; int matched; double sum_w; double sum_w_res2; } cvo_match_fit;
+typedef struct cvo_point_matches_dst {
+    int* best_moving; float* best_value_moving; float* mean_moving /* n x 3 */; float* sum_moving; int* count_moving;
+    int* best_fixed;  float* best_value_fixed;  float* mean_fixed  /* n x 3 */; float* sum_fixed;  int* count_fixed;
+    cvo_match_fit* fit /* [2]: moving, fixed; may be NULL */;
+} cvo_point_matches_dst;
+int cvo_point_matches(cvo_handle h, int slot_a, const float* tran_a /* 3x4 row-major or NULL */, int slot_b, const cvo_point_matches_dst* dst /* moving = a, fixed = b */,
+                      int cap_a, int cap_b);
+int cvo_batch_point_matches(cvo_batch b, int count, const int* pairs /* NULL: 0 .. count-1 */, const cvo_point_matches_dst* dst);
+int cvo_batch_point_matches_device(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, void* out_stream);
+int cvo_tracks_point_matches(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst);
+int cvo_tracks_point_matches_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst, void* out_stream);
+
+
 /* ======================= pose hypotheses: score K start transforms per pair, align from the best (NOT in the reference) ===========
  * The alignment converges from a start that is already close (the radius gate is 10 cm at ell = 0.15).  A loop-closure candidate or a re-localisation
  * has several guesses instead -- detectLoopClousure_top10 holds lc_prior and lc_prior_2 per candidate, aligns from the first and scores both afterwards
