@@ -192,6 +192,8 @@ def test_past_one_ballot_round(hiplib):
 
 @pytest.mark.parametrize("case", ["shuffled", "behind_camera"])
 def test_box_cull_edge_cases(hiplib, pairs, case):
+    """These clouds exercise ordering and padding but not skipping (in random order every group's box spans the scene);
+    tests/test_gpu_sweep_cases.py runs the clouds on which groups are skipped."""
     rng = np.random.default_rng(5)
     p = pairs[(31, 700)]
     fx, ff, mx, mf = p.fixed.xyz.copy(), p.fixed.feat.copy(), p.moving.xyz.copy(), p.moving.feat.copy()

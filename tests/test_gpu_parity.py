@@ -363,6 +363,7 @@ def test_score_block_vs_oracle(hiplib, oracle):
     rc, Ho, inl_o, Hraw = o.se3_hessian(oracle.SLOT_MOVING, tf, oracle.SLOT_FIXED)
     Hg, inl_g = g.se3_hessian(hiplib.api.SLOT_MOVING, tf, hiplib.api.SLOT_FIXED)
     assert inl_g == inl_o
+    np.testing.assert_allclose(Hg, Ho, rtol=1e-3, atol=1e-3 * np.abs(Ho).max())
     # loop-closure score block (cvo.cpp:505-561)
     t1, t2, t3 = make_tf([0, 1, 0], 0.01, [0.01, 0, 0]), make_tf([1, 0, 0], 0.02, [0, 0.01, 0]), make_tf([0, 0, 1], 0.015, [0, 0, 0.01])
     rc, lo = o.compute_innerproduct_lc(t1, t2, t3, tf); assert rc == 0
@@ -379,7 +380,8 @@ def test_score_block_vs_oracle(hiplib, oracle):
 def test_score_box_cull_edge_cases(hiplib, oracle, case):
     """The score kernels skip 32-point groups by bounding box (x, y, z, ray slope).  Point order, points at or behind the camera
     plane (no slope bound), clouds smaller than a group, a ragged last group and the widest radius (fresh object, ell = 0.15)
-    must not change a single pair: counts equal the oracle's, sums agree to f32 rounding."""
+    must not change a single pair: counts equal the oracle's, sums agree to f32 rounding.  These clouds exercise ordering and padding but
+    not skipping (in random order every group's box spans the scene); tests/test_gpu_sweep_cases.py runs the clouds on which groups are skipped."""
     from cvo_slam_amd import synth
     rng = np.random.default_rng(5)
     p = synth.make_small_pair(31, n=700)

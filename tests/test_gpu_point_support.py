@@ -97,6 +97,8 @@ def test_empty_overlap_gives_zeros(hiplib, pairs):
 # ---- 3. the cull's edge cases (tests/test_gpu_parity.py::test_score_box_cull_edge_cases)
 @pytest.mark.parametrize("case", ["shuffled", "behind_camera", "tiny", "ragged_33", "wide_ell"])
 def test_support_box_cull_edge_cases(hiplib, pairs, case):
+    """These clouds exercise ordering and padding but not skipping (in random order every group's box spans the scene);
+    tests/test_gpu_sweep_cases.py runs the clouds on which groups are skipped."""
     rng = np.random.default_rng(5)
     p = pairs[(31, 700)]
     fx, ff, mx, mf = p.fixed.xyz.copy(), p.fixed.feat.copy(), p.moving.xyz.copy(), p.moving.feat.copy()
