@@ -221,7 +221,7 @@ __device__ __forceinline__ v2u ld_ent(const gv2u* p) {
     return *p;
 }
 __device__ __forceinline__ void st_rec(gv2u* p, const v2u v) { *p = v; }
-__device__ __forceinline__ v2u ld_rec(const gv2u* p) { return *p; }
+__device__ __forceinline__ v4u ld_rec2(const gv4u* p) { return *p; }   // two records: the line search reads them in aligned pairs
 
 // ---------------------------------------------------------------- reductions
 // butterfly inside the wave (every lane ends with the wave total), one LDS slot
@@ -2177,37 +2177,48 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
             }
             __syncthreads();
         }
-        // records stream from L2 / HBM: four steps of them are in flight per lane (under load one step's arithmetic is shorter
-        // than a memory round trip)
-        constexpr int RD = 4;
+        // records stream from L2 / HBM, two per 16-byte load: a lane takes the aligned pair {2p, 2p + 1} of the stretch, and four steps of records (two loads) are in
+        // flight per lane (under load one step's arithmetic is shorter than a memory round trip).  A stretch may start at an odd record (a segment start wbase, or the
+        // start of a wave's share of a segment) and end at an even one: the pairs are aligned by ADDRESS, so the first may begin one record before the stretch and the
+        // last end one record behind it; those halves are loaded and not used (q bounds below).  They lie inside the workgroup's region of surv: the region starts at a
+        // multiple of 128 records (c.fbase; the slot's plane likewise: build_ctx) and holds an even number of them, so an aligned pair with one record inside is inside.
+        constexpr int RD = 2;
         auto walk = [&](auto ym, auto tb) {
             constexpr int YM = decltype(ym)::value;
             constexpr bool TAB = decltype(tb)::value;
             if (cnt_w <= 0) return;
-            v2u ring[RD];
+            auto term = [&](unsigned a_bits, unsigned tag) {
+                const int slot = (int)(tag >> 16), j = (int)(tag & 0xFFFFu);
+                float xi[3]; load_x(c, L, x_lds, slot, xi);
+                const float4 yj = load_y<YM>(c, L, j);
+                if (TAB) {
+                    const float4 tq = L.tab[j];
+                    float4 t0, t1, t2, t3;
+                    ls_point<false>(yj, ls, t0, t1, t2, t3);
+                    t2.w = tq.w; t3 = make_float4(tq.x, tq.y, tq.z, 0.f);
+                    const float df[3] = {xi[0] - yj.x, xi[1] - yj.y, xi[2] - yj.z};            // cvo.cpp:286
+                    ls_pair(df, __uint_as_float(a_bits), t0, t1, t2, t3, ls, acc4[0], acc4[1], acc4[2], acc4[3]);
+                } else {
+                    ls_terms(xi, yj, __uint_as_float(a_bits), ls, acc4[0], acc4[1], acc4[2], acc4[3]);
+                }
+            };
+            const int odd = (int)((reinterpret_cast<size_t>(sp) >> 3) & 1u);     // the stretch starts in the upper half of a 16-byte word
+            const gv4u* pp = reinterpret_cast<const gv4u*>(sp - odd);
+            const int np = (cnt_w + odd + 1) >> 1;                               // pairs that hold a record of the stretch: record r of it is half (r + odd) & 1 of pair (r + odd) >> 1
+            v4u ring[RD];
 #pragma unroll
-            for (int u = 0; u < RD; ++u) ring[u] = ld_rec(&sp[min(lane + 64 * u, cnt_w - 1)]);
-            for (int q0 = lane; q0 < cnt_w; q0 += 64 * RD) {
-                prio_by_remaining((cnt_w - uni(q0)) >> 11);        // units of eight trips (2048 records): the waves' shares are near equal, the one with more left goes first
+            for (int u = 0; u < RD; ++u) ring[u] = ld_rec2(&pp[min(lane + 64 * u, np - 1)]);
+            for (int q0 = lane; q0 < np; q0 += 64 * RD) {
+                prio_by_remaining((np - uni(q0)) >> 10);           // units of eight trips (2048 records): the waves' shares are near equal, the one with more left goes first
 #pragma unroll
                 for (int u = 0; u < RD; ++u) {
                     const int q = q0 + 64 * u;
-                    const v2u rec = ring[u];
-                    ring[u] = ld_rec(&sp[min(q + 64 * RD, cnt_w - 1)]);
-                    if (q < cnt_w) {
-                        const int slot = (int)(rec.y >> 16), j = (int)(rec.y & 0xFFFFu);
-                        float xi[3]; load_x(c, L, x_lds, slot, xi);
-                        const float4 yj = load_y<YM>(c, L, j);
-                        if (TAB) {
-                            const float4 tq = L.tab[j];
-                            float4 t0, t1, t2, t3;
-                            ls_point<false>(yj, ls, t0, t1, t2, t3);
-                            t2.w = tq.w; t3 = make_float4(tq.x, tq.y, tq.z, 0.f);
-                            const float df[3] = {xi[0] - yj.x, xi[1] - yj.y, xi[2] - yj.z};            // cvo.cpp:286
-                            ls_pair(df, __uint_as_float(rec.x), t0, t1, t2, t3, ls, acc4[0], acc4[1], acc4[2], acc4[3]);
-                        } else {
-                            ls_terms(xi, yj, __uint_as_float(rec.x), ls, acc4[0], acc4[1], acc4[2], acc4[3]);
-                        }
+                    const v4u r4 = ring[u];
+                    ring[u] = ld_rec2(&pp[min(q + 64 * RD, np - 1)]);
+                    const int r0 = 2 * q - odd;                    // the pair's records in the stretch: r0 (-1 for the first pair of an odd start), r0 + 1 (cnt_w behind an even end)
+                    if (q < np) {
+                        if (r0 >= 0) term(r4.x, r4.y);
+                        if (r0 + 1 < cnt_w) term(r4.z, r4.w);
                     }
                 }
             }
