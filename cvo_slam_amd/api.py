@@ -77,6 +77,15 @@ class DeviceCloud(C.Structure):         # cvo_device_cloud: a point cloud in cal
                 ("feat_channel_stride", C.c_longlong), ("n", C.c_int), ("pad_", C.c_int)]
 
 
+class ReduceParams(C.Structure):         # cvo_reduce_params: one voxel-grid filter for all clouds of a call
+    _fields_ = [("voxel", C.c_float), ("mode", C.c_int), ("min_points", C.c_int), ("pad_", C.c_int)]
+
+
+class ReducedCloud(C.Structure):         # cvo_reduced_cloud: one cloud's output arrays in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p), ("count", C.c_void_p), ("source", C.c_void_p), ("map", C.c_void_p),
+                ("cap", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -160,8 +169,13 @@ ABI_SYMBOLS = [
     "cvo_point_matches", "cvo_batch_point_matches", "cvo_batch_point_matches_device", "cvo_tracks_point_matches", "cvo_tracks_point_matches_device",
     "cvo_score_hypotheses", "cvo_batch_score_hypotheses", "cvo_batch_seed_hypotheses_async", "cvo_batch_hypothesis_results",
     "cvo_pose_models", "cvo_batch_pose_models", "cvo_batch_result_models",
+    "cvo_reducer_create", "cvo_reducer_destroy", "cvo_reducer_info", "cvo_check_reduce_clouds", "cvo_reduce_device_clouds", "cvo_count_voxels",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
+REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
+REDUCE_MODES = {"mean": REDUCE_MEAN, "central": REDUCE_CENTRAL}
+REDUCE_MAX_POINTS = 1048575              # CVO_REDUCE_MAX_POINTS
+REDUCE_MAX_VOXELS = 16                   # CVO_REDUCE_MAX_VOXELS
 
 _lib = None
 
@@ -364,6 +378,13 @@ def load_library():
     L.cvo_pose_models.argtypes = [vp, C.c_int, C.c_int, C.c_int, fp, C.c_float, pmp]
     L.cvo_batch_pose_models.argtypes = [vp, C.c_int, ip, C.c_int, fp, C.c_float, pmp]
     L.cvo_batch_result_models.argtypes = [vp, C.c_int, ip, pmp]
+    rpp = C.POINTER(ReduceParams); rcp = C.POINTER(ReducedCloud)
+    L.cvo_reducer_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.cvo_reducer_destroy.argtypes = [vp]
+    L.cvo_reducer_info.argtypes = [vp, ip, ip, C.POINTER(C.c_longlong)]
+    L.cvo_check_reduce_clouds.argtypes = [vp, C.c_int, dcp, rpp, rcp]
+    L.cvo_reduce_device_clouds.argtypes = [vp, C.c_int, dcp, rpp, rcp, ip, vp]
+    L.cvo_count_voxels.argtypes = [vp, C.c_int, dcp, C.c_int, fp, C.c_int, ip, vp]
     _lib = L
     return L
 
@@ -632,8 +653,9 @@ def selftest_ingest_images(descs, width: int, height: int, device: int = 0):
 
 
 # ---- clouds in device memory (cvo_hip.h: cvo_device_cloud): the same carriers
-def device_cloud(xyz, feat, feat_layout: str | None = None) -> DeviceCloud:
+def device_cloud(xyz, feat, feat_layout: str | None = None, max_n: int = 65535) -> DeviceCloud:
     """DeviceCloud of a cloud in device memory, from the shape and strides of its two __cuda_array_interface__ carriers.
+    max_n: the most points the receiver takes: 65535 for a hand-over, up to REDUCE_MAX_POINTS in front of a CvoReducer.
     xyz: float32 (n, 3), inner stride 4 bytes, any row stride that is a multiple of 4 and at least 12 (a slice of a wider tensor, float4 points).
     feat: float32 (5, n) (channels first) or (n, 5) (points first), told apart by the shape; a 5 x 5 tensor needs feat_layout = "channels_first"
     or "points_first".  Strides must be positive multiples of 4.  Anything else -- a host array among it -- raises ValueError."""
@@ -657,8 +679,8 @@ def device_cloud(xyz, feat, feat_layout: str | None = None) -> DeviceCloud:
     channels_first = (feat_layout == "channels_first") if feat_layout else sf[0] == 5
     if sf !=((5, n) if channels_first else (n, 5)):
         raise ValueError(f"feat: shape {(5, n) if channels_first else (n, 5)} expected for {n} points, got {sf}")
-    if n > 65535:
-        raise ValueError(f"{n} points: more than 65535 per cloud is not supported")
+    if n > max_n:
+        raise ValueError(f"{n} points: more than {max_n} per cloud is not supported")
     if n == 0:
         return DeviceCloud(None, None, 0, 0, 0, 0, 0)
     point_stride, channel_stride = (tf[1], tf[0]) if channels_first else (tf[0], tf[1])
@@ -679,9 +701,9 @@ def device_cloud(xyz, feat, feat_layout: str | None = None) -> DeviceCloud:
     return DeviceCloud(px, pf, tx[0], point_stride, channel_stride, n, 0)
 
 
-def _device_clouds(clouds):
+def _device_clouds(clouds, max_n: int = 65535):
     """(ctypes array of DeviceCloud, n) of a list whose entries are DeviceCloud, (xyz, feat) or (xyz, feat, feat_layout)"""
-    ds = [c if isinstance(c, DeviceCloud) else device_cloud(*c) for c in clouds]
+    ds = [c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=max_n) for c in clouds]
     if not ds:
         raise ValueError("no clouds")
     return (DeviceCloud * len(ds))(*ds), len(ds)
@@ -713,6 +735,98 @@ def selftest_ingest_clouds(clouds, device: int = 0):
         out.append((xyz[3 * at:3 * (at + m)].reshape(m, 3).copy(), feat[5 * at:5 * (at + m)].reshape(5, m).copy()))
         at += m
     return out, cost, bool(ok.value)
+
+
+# ---- reducing clouds (cvo_hip.h, "Reducing clouds"): a voxel-grid filter in front of the device-cloud hand-over
+class CvoReducer:
+    """cvo_reducer: reduces clouds in device memory to one row per occupied voxel, many clouds per call, the result's bits a function of the
+    input alone.  max_clouds, max_points: the most clouds per call and points per cloud (up to REDUCE_MAX_POINTS); the device scratch, 384
+    bytes per point of max_clouds x max_points, is allocated here and never grows.  Outputs are torch tensors on the reducer's device."""
+
+    def __init__(self, max_clouds: int, max_points: int, device: int = 0):
+        self.L = load_library()
+        self.max_clouds, self.max_points, self.device = int(max_clouds), int(max_points), int(device)
+        self.h = C.c_void_p()
+        _check(self.L.cvo_reducer_create(self.device, self.max_clouds, self.max_points, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.cvo_reducer_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scratch_bytes(self) -> int:
+        b = C.c_longlong(0)
+        _check(self.L.cvo_reducer_info(self.h, None, None, C.byref(b)))
+        return b.value
+
+    def _inputs(self, clouds, cloud_stream):
+        arr, n = _device_clouds(clouds, max_n=REDUCE_MAX_POINTS)
+        _settle_cloud_writer(clouds, cloud_stream)
+        return arr, n
+
+    def reduce(self, clouds, voxel: float, mode="mean", min_points: int = 1, cap: int = 65535, want=("count",), cloud_stream=None):
+        """cvo_reduce_device_clouds.  clouds: what set_pairs_clouds takes (DeviceCloud, (xyz, feat) or (xyz, feat, feat_layout)), up to
+        max_points points each.  mode: "mean" or "central".  cap: the most rows a cloud may come to (at most 65535, what a hand-over takes).
+        want: which of "count", "source", "map" to return beside xyz and feat.  cloud_stream: the stream that wrote the clouds; the outputs are
+        ordered on it (None: torch's current stream is synchronised first and everything is done on return).
+        Returns one dict per cloud: xyz (n_out, 3) and feat (n_out, 5) float32, count / source (n_out,) int32, map (n,) int32, n_out.  The
+        tensors are views of the arrays the kernel wrote and pass into device_cloud / set_pairs_clouds / advance_clouds / step_clouds as they
+        are.  Raises CvoError when a cloud has more than cap rows (then nothing is returned; count_voxels / voxel_for_budget choose a size)."""
+        import torch
+        bad = [w for w in want if w not in ("count", "source", "map")]
+        if bad:
+            raise ValueError(f"want: 'count', 'source' or 'map' expected, got {bad[0]!r}")
+        if mode not in REDUCE_MODES and mode not in REDUCE_MODES.values():
+            raise ValueError(f"mode: 'mean' or 'central' expected, got {mode!r}")
+        arr, n = self._inputs(clouds, cloud_stream)
+        ns = [int(arr[k].n) for k in range(n)]
+        caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in ns]       # (a cap out of range is the library's to refuse)
+        rows = [max(0, c) for c in caps]
+        dev = torch.device("cuda", self.device)
+        stream = None
+        if cloud_stream is not None:
+            stream = cloud_stream if isinstance(cloud_stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(cloud_stream), device=dev)
+        with torch.cuda.stream(stream):                               # (the arrays belong to the stream their readers will use)
+            xyz = torch.empty((sum(rows), 3), dtype=torch.float32, device=dev); feat = torch.empty((sum(rows), 5), dtype=torch.float32, device=dev)
+            cnt = torch.empty(sum(rows), dtype=torch.int32, device=dev) if "count" in want else None
+            src = torch.empty(sum(rows), dtype=torch.int32, device=dev) if "source" in want else None
+            mp = torch.empty(sum(ns), dtype=torch.int32, device=dev) if "map" in want else None
+        recs = (ReducedCloud * n)(); at = pt = 0; views = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = dict(xyz=xyz[at:at + rows[k]], feat=feat[at:at + rows[k]])
+            if cnt is not None: v["count"] = cnt[at:at + rows[k]]
+            if src is not None: v["source"] = src[at:at + rows[k]]
+            if mp is not None: v["map"] = mp[pt:pt + ns[k]]
+            recs[k] = ReducedCloud(ptr(v["xyz"]), ptr(v["feat"]), ptr(v.get("count")), ptr(v.get("source")), ptr(v.get("map")), caps[k], 0)
+            views.append(v); at += rows[k]; pt += ns[k]
+        prm = ReduceParams(float(voxel), int(REDUCE_MODES.get(mode, mode)), int(min_points), 0)
+        n_out = np.zeros(n, np.int32)
+        _check(self.L.cvo_reduce_device_clouds(self.h, n, arr, C.byref(prm), recs, n_out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
+        over = [k for k in range(n) if n_out[k] > caps[k]]
+        if over:
+            k = over[0]
+            raise CvoError(CVO_ERR_INVALID, f"cloud {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel (voxel_for_budget)")
+        out = []
+        for k, v in enumerate(views):
+            m = int(n_out[k])
+            out.append({key: (t if key == "map" else t[:m]) for key, t in v.items()} | dict(n_out=m))
+        return out
+
+    def count_voxels(self, clouds, voxels, min_points: int = 1, cloud_stream=None):
+        """cvo_count_voxels: the occupied-cell counts (count, k) int32 of every cloud at every one of the k <= 16 voxel sizes, by one call;
+        counts[i, j] is what reduce would return as n_out for cloud i at voxels[j]."""
+        vs = np.ascontiguousarray(voxels, np.float32).reshape(-1)
+        arr, n = self._inputs(clouds, cloud_stream)
+        out = np.zeros((n, vs.shape[0]), np.int32)
+        _check(self.L.cvo_count_voxels(self.h, n, arr, int(vs.shape[0]), vs.ctypes.data_as(C.POINTER(C.c_float)), int(min_points),
+                                       out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
+        return out
 
 
 # ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms

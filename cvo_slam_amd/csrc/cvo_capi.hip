@@ -95,6 +95,9 @@ hipError_t pcd_launch_cloud_batch(const uint8_t* map, const uint16_t* depth, con
 hipError_t pcd_launch_scatter(const PcdScatter& S, int n_max, hipStream_t s);
 hipError_t pcd_launch_ingest(const PcdIngestDesc* descs, uint8_t* bgr_stack, uint8_t* depth_stack, int w, int h, int n_img, hipStream_t s);
 hipError_t launch_ingest_clouds(const CloudIngestDesc* descs, int n_clouds, int n_max, hipStream_t s);
+hipError_t launch_reduce_clouds(const ReduceDesc* descs, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode, int min_points,
+                                hipStream_t s);
+hipError_t launch_count_voxels(const CountDesc* descs, int n_items, int n_max, int slots_max, int min_points, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -3422,13 +3425,15 @@ void cloud_strides(const cvo_device_cloud& c, long long* xs, long long* ps, long
     *ps = ref ? 4 : c.feat_point_stride; *cs = ref ? 4ll * c.n : c.feat_channel_stride;
 }
 // What every device-cloud entry point checks first, before any slot or stream changes and before anything is queued (cvo_check_device_clouds runs it alone).
-int check_device_clouds(int device, int count, const cvo_device_cloud* clouds) {
+// n_limit: 65535 for a hand-over (16-bit column indices), CVO_REDUCE_MAX_POINTS in front of a reducer.
+int check_device_clouds(int device, int count, const cvo_device_cloud* clouds, int n_limit = 65535) {
     if (count <= 0 || count > 65535) return fail(CVO_ERR_INVALID, "bad cloud count");
     if (!clouds) return fail(CVO_ERR_INVALID, "null argument: clouds");
     for (int k = 0; k < count; ++k) {
         const cvo_device_cloud& c = clouds[k];
         const std::string who = "cloud " + std::to_string(k) + ": ";
-        if (c.n < 0 || c.n > 65535) return fail(CVO_ERR_INVALID, who + "n " + std::to_string(c.n) + " is outside 0 .. 65535 (16-bit column indices)");
+        if (c.n < 0 || c.n > n_limit)
+            return fail(CVO_ERR_INVALID, who + "n " + std::to_string(c.n) + " is outside 0 .. " + std::to_string(n_limit) + (n_limit == 65535 ? " (16-bit column indices)" : ""));
         const struct { const char* name; long long v; } strides[3] = {{"xyz_stride", c.xyz_stride}, {"feat_point_stride", c.feat_point_stride}, {"feat_channel_stride", c.feat_channel_stride}};
         for (const auto& st : strides) {
             if (st.v < 0) return fail(CVO_ERR_INVALID, who + st.name + " " + std::to_string(st.v) + " is negative");
@@ -3648,6 +3653,199 @@ int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* cl
         guard(at); at += G;
     }
     *guards_intact = ok;
+    return CVO_OK;
+}
+// ---- reducing clouds (cvo_reduce_kernels.hip): a voxel-grid filter in front of the device-cloud hand-over.  The reducer holds one block of device
+// scratch, cut per call into a region per cloud (a reduction) or per (cloud, voxel size) item (a count); nothing is allocated after creation.
+struct cvo_reducer_s {
+    int device = 0, max_clouds = 0, max_points = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_out = nullptr;
+    void* scratch = nullptr; size_t scratch_bytes = 0, cloud_bytes = 0;
+    void* d_desc = nullptr; int* d_total = nullptr;                   // the launch's descriptor table and its row counts on the device
+    void* h_desc = nullptr; int* h_total = nullptr;                   // their pinned twins: written before the launches, read after the call's one wait
+};
+namespace {
+inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+// a cloud's region of a reduction, laid out for the reducer's max_points (a call's cloud uses the front of each array)
+struct ReduceLayout { size_t keys, sums, best, lowest, members, row, slot_of, block_heads, row_slot, bytes; };
+ReduceLayout reduce_layout(int max_points) {
+    const size_t P = (size_t)max_points, S = 2 * P, R = std::min<size_t>(P, 65535), B = (P + 255) / 256;
+    ReduceLayout L; size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up16(bytes); return o; };
+    L.keys = take(8 * S); L.sums = take(64 * R); L.best = take(8 * R); L.lowest = take(4 * S); L.members = take(4 * S); L.row = take(4 * S);
+    L.slot_of = take(4 * P); L.block_heads = take(4 * B); L.row_slot = take(4 * R); L.bytes = at;
+    return L;
+}
+inline size_t count_item_keys(int n) { return up16(16 * (size_t)n); }                       // 2 n slots of 8 bytes
+inline size_t count_item_bytes(int n) { return count_item_keys(n) + up16(8 * (size_t)n); }   // and their member counts
+void reducer_release(cvo_reducer r) {
+    (void)hipSetDevice(r->device);
+    if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
+    if (r->ev_in) (void)hipEventDestroy(r->ev_in);
+    if (r->ev_out) (void)hipEventDestroy(r->ev_out);
+    if (r->scratch) (void)hipFree(r->scratch);
+    if (r->d_desc) (void)hipFree(r->d_desc);
+    if (r->d_total) (void)hipFree(r->d_total);
+    if (r->h_desc) (void)hipHostFree(r->h_desc);
+    if (r->h_total) (void)hipHostFree(r->h_total);
+    delete r;
+}
+int reducer_alloc(cvo_reducer r) {
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&r->ev_in, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&r->ev_out, hipEventDisableTiming));
+    const size_t items = (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS;
+    r->cloud_bytes = reduce_layout(r->max_points).bytes;
+    r->scratch_bytes = std::max((size_t)r->max_clouds * r->cloud_bytes, items * count_item_bytes(r->max_points));
+    const size_t table = std::max((size_t)r->max_clouds * sizeof(ReduceDesc), items * sizeof(CountDesc));
+    HIP_TRY(hipMalloc(&r->scratch, r->scratch_bytes));
+    HIP_TRY(hipMalloc(&r->d_desc, table));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_total), items * sizeof(int)));
+    HIP_TRY(hipHostMalloc(&r->h_desc, table, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_total), items * sizeof(int), hipHostMallocDefault));
+    return CVO_OK;
+}
+// the input side of both entry points: cvo_check_device_clouds' rules with the reducer's limits
+int reduce_check_in(cvo_reducer r, int count, const cvo_device_cloud* in) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
+    return check_device_clouds(r->device, count, in, r->max_points);   // (n above max_points: "cloud k: n ... is outside 0 .. max_points")
+}
+int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
+    int rc = reduce_check_in(r, count, in); if (rc) return rc;
+    if (!p || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
+    if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
+    if (p->min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(p->min_points) + " is below 1");
+    for (int k = 0; k < count; ++k) {
+        const cvo_reduced_cloud& d = dst[k];
+        const std::string who = "cloud " + std::to_string(k) + ": ";
+        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+        const struct { const void* p; long long bytes; const char* name; } arr[5] = {{d.xyz, 12ll * d.cap, "dst xyz"}, {d.feat, 20ll * d.cap, "dst feat"},
+            {d.count, 4ll * d.cap, "dst count"}, {d.source, 4ll * d.cap, "dst source"}, {d.map, 4ll * in[k].n, "dst map"}};
+        for (const auto& x : arr) {
+            if (!x.p || x.bytes == 0) continue;
+            if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
+            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
+        }
+    }
+    return CVO_OK;
+}
+// The edges of a call: the reducer's stream behind the caller's, the launches (queue), their counts to pinned memory, the caller's stream behind
+// the reducer's, and the call's one host wait.
+int reducer_run(cvo_reducer r, size_t table_bytes, int n_totals, void* cloud_stream, const std::function<hipError_t()>& queue) {
+    hipStream_t cs = static_cast<hipStream_t>(cloud_stream);
+    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
+    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, table_bytes, hipMemcpyHostToDevice, r->stream));
+    const hipError_t e = queue();
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("cloud reduce kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * (size_t)n_totals, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
+    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
+    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    return CVO_OK;
+}
+}  // namespace
+int cvo_reducer_create(int device, int max_clouds, int max_points, cvo_reducer* out) {
+    if (!out) return fail(CVO_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (max_clouds < 1 || max_clouds > 4095) return fail(CVO_ERR_INVALID, "max_clouds " + std::to_string(max_clouds) + " is outside 1 .. 4095");
+    if (max_points < 1 || max_points > CVO_REDUCE_MAX_POINTS) return fail(CVO_ERR_INVALID, "max_points " + std::to_string(max_points) + " is outside 1 .. " + std::to_string(CVO_REDUCE_MAX_POINTS));
+    int rc = check_device(device, nullptr); if (rc) return rc;
+    cvo_reducer r = new cvo_reducer_s();
+    r->device = device; r->max_clouds = max_clouds; r->max_points = max_points;
+    if ((rc = reducer_alloc(r))) { reducer_release(r); return rc; }
+    *out = r;
+    return CVO_OK;
+}
+int cvo_reducer_destroy(cvo_reducer r) {
+    if (r) reducer_release(r);
+    return CVO_OK;
+}
+int cvo_reducer_info(cvo_reducer r, int* max_clouds, int* max_points, long long* scratch_bytes) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (max_clouds) *max_clouds = r->max_clouds;
+    if (max_points) *max_points = r->max_points;
+    if (scratch_bytes) *scratch_bytes = (long long)r->scratch_bytes;
+    return CVO_OK;
+}
+int cvo_check_reduce_clouds(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
+    return reduce_check(r, count, in, p, dst);
+}
+int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst, int* n_out,
+                             void* cloud_stream) {
+    int rc = reduce_check(r, count, in, p, dst); if (rc) return rc;
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    ReduceDesc* h = static_cast<ReduceDesc*>(r->h_desc);
+    std::vector<int> of; of.reserve(count);
+    int n_max = 0, rows_max = 0;
+    for (int k = 0; k < count; ++k) {
+        n_out[k] = 0;
+        const cvo_device_cloud& c = in[k];
+        if (c.n == 0) continue;
+        const int q = (int)of.size(); of.push_back(k);
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
+        ReduceDesc& D = h[q];
+        D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
+        cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
+        D.keys = reinterpret_cast<unsigned long long*>(base + L.keys); D.lowest = reinterpret_cast<unsigned*>(base + L.lowest);
+        D.members = reinterpret_cast<unsigned*>(base + L.members); D.row = reinterpret_cast<int*>(base + L.row);
+        D.slot_of = reinterpret_cast<int*>(base + L.slot_of); D.block_heads = reinterpret_cast<int*>(base + L.block_heads);
+        D.row_slot = reinterpret_cast<int*>(base + L.row_slot); D.sums = reinterpret_cast<long long*>(base + L.sums);
+        D.best = reinterpret_cast<unsigned long long*>(base + L.best);
+        D.out_xyz = static_cast<float*>(dst[k].xyz); D.out_feat = static_cast<float*>(dst[k].feat); D.out_count = static_cast<int*>(dst[k].count);
+        D.out_source = static_cast<int*>(dst[k].source); D.out_map = static_cast<int*>(dst[k].map);
+        D.total = r->d_total + q;
+        D.n = c.n; D.slots = 2 * c.n; D.cap = dst[k].cap; D.rows_cap = std::min(dst[k].cap, c.n);
+        n_max = std::max(n_max, c.n); rows_max = std::max(rows_max, D.rows_cap);
+    }
+    const int live = (int)of.size();
+    if (live == 0) return CVO_OK;
+    const cvo_reduce_params P = *p;
+    if ((rc = reducer_run(r, sizeof(ReduceDesc) * (size_t)live, live, cloud_stream, [&] {
+            return launch_reduce_clouds(static_cast<const ReduceDesc*>(r->d_desc), live, n_max, 2 * n_max, rows_max, P.voxel, P.mode, P.min_points, r->stream); })))
+        return rc;
+    for (int q = 0; q < live; ++q) n_out[of[q]] = r->h_total[q];
+    return CVO_OK;
+}
+int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k, const float* voxels, int min_points, int* counts_out, void* cloud_stream) {
+    int rc = reduce_check_in(r, count, in); if (rc) return rc;
+    if (!voxels || !counts_out) return fail(CVO_ERR_INVALID, "null argument");
+    if (k < 1 || k > CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "k " + std::to_string(k) + " is outside 1 .. " + std::to_string(CVO_REDUCE_MAX_VOXELS));
+    for (int j = 0; j < k; ++j)
+        if (!(std::isfinite(voxels[j]) && voxels[j] > 0.f)) return fail(CVO_ERR_INVALID, "voxels[" + std::to_string(j) + "] " + std::to_string(voxels[j]) + " is not a finite size above 0");
+    if (min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(min_points) + " is below 1");
+    HIP_TRY(hipSetDevice(r->device));
+    CountDesc* h = static_cast<CountDesc*>(r->h_desc);
+    std::vector<int> of; of.reserve((size_t)count * k);
+    size_t at = 0; int n_max = 0;
+    for (int i = 0; i < count; ++i) {
+        const cvo_device_cloud& c = in[i];
+        for (int j = 0; j < k; ++j) {
+            counts_out[i * k + j] = 0;
+            if (c.n == 0) continue;
+            const int q = (int)of.size(); of.push_back(i * k + j);
+            char* base = static_cast<char*>(r->scratch) + at; at += count_item_bytes(c.n);   // (at most max_clouds x 16 items of max_points: inside the scratch)
+            CountDesc& D = h[q];
+            D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
+            cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
+            D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(c.n));
+            D.total = r->d_total + q; D.n = c.n; D.slots = 2 * c.n; D.voxel = voxels[j]; D.pad_ = 0;
+        }
+        n_max = std::max(n_max, c.n);
+    }
+    const int live = (int)of.size();
+    if (live == 0) return CVO_OK;
+    if ((rc = reducer_run(r, sizeof(CountDesc) * (size_t)live, live, cloud_stream, [&] {
+            return launch_count_voxels(static_cast<const CountDesc*>(r->d_desc), live, n_max, 2 * n_max, min_points, r->stream); })))
+        return rc;
+    for (int q = 0; q < live; ++q) counts_out[of[q]] = r->h_total[q];
     return CVO_OK;
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {

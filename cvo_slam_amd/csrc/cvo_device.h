@@ -247,6 +247,34 @@ struct CloudIngestDesc {
 };
 static_assert(sizeof(CloudIngestDesc) == 64, "CloudIngestDesc layout");
 
+// one cloud of a voxel-grid reduction (cvo_reduce_kernels.hip; not in the reference), n > 0, the strides resolved as in CloudIngestDesc.  The
+// scratch arrays lie in the reducer's own memory: an open-addressing table of `slots` cells and what the rows need.
+struct ReduceDesc {
+    const float* xyz; const float* feat;
+    long long xyz_stride, feat_point_stride, feat_channel_stride;
+    unsigned long long* keys;      // slots: the cell's 63-bit key, all ones = empty
+    unsigned* lowest;              // slots: the lowest member index (atomicMin)
+    unsigned* members;             // slots: the member count
+    int* row;                      // slots: the cell's output row, -1 = dropped; written for every occupied slot by its lowest member
+    int* slot_of;                  // n: the slot of point i's cell, -1 = invalid point
+    int* block_heads;              // one per 256 points: the block's kept cells whose lowest member it holds, then their exclusive sum
+    int* row_slot;                 // rows_cap: the slot of row r
+    long long* sums;               // rows_cap x 8 (MEAN)
+    unsigned long long* best;      // rows_cap (CENTRAL): (d2 bits << 32) | index
+    float* out_xyz; float* out_feat; int* out_count; int* out_source; int* out_map;   // the caller's arrays; count, source and map may be null
+    int* total;                    // the full row count
+    int n, slots, cap, rows_cap;   // rows_cap = min(cap, n): rows at or above it are not written
+};
+static_assert(sizeof(ReduceDesc) == 176, "ReduceDesc layout");
+// one (cloud, voxel size) item of a count launch: a table of its own, no rows
+struct CountDesc {
+    const float* xyz; const float* feat;
+    long long xyz_stride, feat_point_stride, feat_channel_stride;
+    unsigned long long* keys; unsigned* members; int* total;
+    int n, slots; float voxel; int pad_;
+};
+static_assert(sizeof(CountDesc) == 80, "CountDesc layout");
+
 // the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
 struct BoxDesc {
     const float* rec;        // the cloud's two planes of n float4

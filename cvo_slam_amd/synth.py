@@ -139,6 +139,24 @@ def select_cloud(bgr8: np.ndarray, depth: np.ndarray, cam) -> Cloud:
     return Cloud(xyz=xyz, feat=feat)
 
 
+def dense_cloud(bgr8: np.ndarray, depth: np.ndarray, cam, keep_holes: bool = False) -> Cloud:
+    """Every pixel back-projected, in scan order, with select_cloud's arithmetic and features: what a dense-depth front end hands to the
+    cloud reducer.  keep_holes: pixels without depth stay in (at the origin: 640 x 480 gives 307200 points), otherwise they are left out."""
+    h, w = depth.shape
+    b = bgr8[..., 0].astype(np.float32); gch = bgr8[..., 1].astype(np.float32); r = bgr8[..., 2].astype(np.float32)
+    gray = (np.float32(0.299) * r + np.float32(0.587) * gch + np.float32(0.114) * b).astype(np.float32)
+    dx = np.zeros_like(gray); dy = np.zeros_like(gray)
+    dx[:, 1:-1] = np.float32(0.5) * (gray[:, 2:] - gray[:, :-2])
+    dy[1:-1, :] = np.float32(0.5) * (gray[2:, :] - gray[:-2, :])
+    py, px = np.nonzero(np.ones_like(depth, dtype=bool) if keep_holes else depth != 0)
+    z = (depth[py, px].astype(np.float32) / np.float32(cam["depth_factor"])).astype(np.float32)
+    x = ((px.astype(np.float32) - np.float32(cam["cx"])) * z / np.float32(cam["fx"])).astype(np.float32)
+    y = ((py.astype(np.float32) - np.float32(cam["cy"])) * z / np.float32(cam["fy"])).astype(np.float32)
+    xyz = np.ascontiguousarray(np.stack([x, y, z], axis=1), dtype=np.float32)
+    feat = np.ascontiguousarray(np.stack([b[py, px], gch[py, px], r[py, px], dx[py, px], dy[py, px]], axis=0), dtype=np.float32)
+    return Cloud(xyz=xyz, feat=feat)
+
+
 def make_pair(index: int, cam=TUM1, max_deg: float = 2.0, max_trans: float = 0.03, base_seed: int = 20240) -> Pair:
     """Pair `index` (seed = 20240 + index): fixed = frame A, moving = frame B."""
     rng = np.random.default_rng(base_seed + index)

@@ -484,6 +484,60 @@ int cvo_batch_advance_device_clouds(cvo_batch b, int count, const int* slots, co
  * cost sample's terms, samples}; *guards_intact = 1 when no guard byte changed. */
 int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* clouds, float* xyz_out, float* feat_out,
                                double* cost_out /* count x {sum, samples} */, int* guards_intact);
+/* ---- Reducing clouds (not in the reference): a voxel-grid filter in front of the device-cloud hand-over, which gives the cloud route the point
+ * budget the image route has in num_want.  Many clouds per call; the result's bits depend on the input alone (no float atomics, no table order in
+ * the output); the output is plain device memory that passes straight on as a cvo_device_cloud (xyz tight, feat "(n, 5)").
+ *
+ * The definition, for one cloud of n points (3 position and 5 feature floats), a voxel size (f32, finite, > 0), a mode and min_points >= 1:
+ *   valid point: its 8 floats are finite and below 2^15 in magnitude, and each cell coordinate c = floorf(x / voxel) has |c| < 2^20 (the correctly
+ *     rounded f32 division; floor, not truncation, for negative coordinates).  Invalid points belong to no cell.
+ *   cell: the integer triple (cx, cy, cz); its members are the valid points with that triple; cells with fewer than min_points members are dropped.
+ *   output order: ascending lowest member index of the cell; count[r] is row r's member count.
+ *   CVO_REDUCE_MEAN: each of the row's 8 values is the members' mean in a form that does not depend on the order of summation: every member
+ *     value v becomes q = llrint((double)v * 2^24), the q are added as 64-bit integers (2^20 points below 2^15: below 2^59), and the value is
+ *     (float)((double)sum / ((double)count * 16777216.0)).  source[r] is the lowest member index.
+ *   CVO_REDUCE_CENTRAL: the row is a copy of the 8 floats of the member nearest the cell's centre (c + 0.5f) * voxel (f32); d2 = dx*dx + dy*dy +
+ *     dz*dz in f32, un-fused, added in that order; a tie goes to the lowest index.  source[r] is that member's index.
+ *   map[i] (optional): the row of point i's cell, -1 for an invalid point or a dropped cell.
+ *   The occupied-cell count of a cloud and a voxel size (cvo_count_voxels) is the number of cells with at least min_points members.
+ *
+ * A reducer owns its scratch -- sized at creation for max_clouds clouds of max_points points, 384 bytes per point (what 16 voxel sizes per cloud
+ * need in cvo_count_voxels; a reduction uses under a third of it), never grown inside a call -- and its own stream.  All clouds of a call are
+ * reduced by the same launches, the cloud in the grid's second dimension.  Input descriptors are cvo_device_clouds under cvo_check_device_clouds'
+ * validation, rule for rule, except that n may go up to 1048575; further CVO_ERR_INVALID, the message naming cloud and field: n above max_points,
+ * count above max_clouds, voxel not finite or not > 0, mode not 0 or 1, min_points < 1, cap outside 0 .. 65535, k outside 1 .. 16, and, in dst, a
+ * null xyz or feat with cap > 0 or an array that is not 4-byte aligned device-writable memory of the reducer's device for its extent (xyz cap x 12,
+ * feat cap x 20, count and source cap x 4, map n x 4 bytes; pageable host memory is refused).  A refused call changes nothing.
+ * n_out[i] is always the FULL row count of cloud i; rows at or above cap are not written (no byte behind row cap - 1 is touched); map holds full
+ * row numbers.  cap == 0 with every array NULL counts only.  cloud_stream: cvo_device_cloud's rule -- with a stream one event edge in and one
+ * out, and the outputs are ordered on that stream; with NULL everything is done when the call returns.  The host waits once per call, for the
+ * counts in pinned memory. */
+#define CVO_REDUCE_MEAN 0
+#define CVO_REDUCE_CENTRAL 1
+#define CVO_REDUCE_MAX_POINTS 1048575
+#define CVO_REDUCE_MAX_VOXELS 16
+typedef struct cvo_reducer_s* cvo_reducer;
+typedef struct cvo_reduce_params { float voxel; int mode; int min_points; int pad_; } cvo_reduce_params;   /* 16 bytes */
+typedef struct cvo_reduced_cloud {      /* caller-owned DEVICE memory, one per input cloud */
+    void* xyz;      /* cap x 3 float32, rows tight (12 bytes) */
+    void* feat;     /* cap x 5 float32, rows tight (20 bytes): device_cloud's "(n, 5)" layout */
+    void* count;    /* cap int32, may be NULL */
+    void* source;   /* cap int32, may be NULL */
+    void* map;      /* n_in int32, may be NULL */
+    int cap; int pad_;
+} cvo_reduced_cloud;                    /* 48 bytes */
+int cvo_reducer_create(int device, int max_clouds /* 1 .. 4095 */, int max_points /* 1 .. 1048575 */, cvo_reducer* out);
+int cvo_reducer_destroy(cvo_reducer r);
+/* what the reducer was created with and the bytes of device scratch it holds (any pointer may be NULL) */
+int cvo_reducer_info(cvo_reducer r, int* max_clouds, int* max_points, long long* scratch_bytes);
+/* the validation of cvo_reduce_device_clouds alone: launches nothing */
+int cvo_check_reduce_clouds(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst);
+int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p /* one for all */,
+                             const cvo_reduced_cloud* dst, int* n_out /* count, host */, void* cloud_stream);
+/* the occupied-cell counts of all k voxel sizes of all clouds by one pair of launches over the count x k (cloud, size) items:
+ * counts_out[i * k + j] for cloud i and voxels[j], equal to n_out of a reduction at that size */
+int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k, const float* voxels /* k */, int min_points,
+                     int* counts_out /* count x k, host */, void* cloud_stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
