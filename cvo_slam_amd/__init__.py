@@ -5,7 +5,7 @@ include/cvo_hip.h.
 Layout
   csrc/       hand-written HIP kernels + the C-ABI implementation (libcvo_hip.so)
   api.py      ctypes mirror of the reference's `cvo::cvo` call surface (Cvo, CvoBatch, CvoTracks) and the cloud reducer (CvoReducer)
-  voxels.py   voxel size for a point budget, per-row results back to the dense cloud
+  voxels.py   voxel size for a point budget (one cloud, or a fused group), per-row results back to the dense points, a fused row's member
   synth.py    seeded synthetic RGB-D pairs (bench + tests)
   build.py    hipcc driver (gfx950 only)
 

@@ -86,6 +86,19 @@ class ReducedCloud(C.Structure):         # cvo_reduced_cloud: one cloud's output
                 ("cap", C.c_int), ("pad_", C.c_int)]
 
 
+class FuseMember(C.Structure):           # cvo_fuse_member: one posed cloud of a group (pose: row-major 3 x 4, host memory)
+    _fields_ = [("cloud", DeviceCloud), ("pose", C.c_float * 12)]
+
+
+class FuseParams(C.Structure):           # cvo_fuse_params: one filter for all groups of a call
+    _fields_ = [("voxel", C.c_float), ("mode", C.c_int), ("min_points", C.c_int), ("min_views", C.c_int)]
+
+
+class FusedCloud(C.Structure):           # cvo_fused_cloud: one group's output arrays in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p), ("count", C.c_void_p), ("source", C.c_void_p), ("map", C.c_void_p),
+                ("views", C.c_void_p), ("view_mask", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -170,12 +183,15 @@ ABI_SYMBOLS = [
     "cvo_score_hypotheses", "cvo_batch_score_hypotheses", "cvo_batch_seed_hypotheses_async", "cvo_batch_hypothesis_results",
     "cvo_pose_models", "cvo_batch_pose_models", "cvo_batch_result_models",
     "cvo_reducer_create", "cvo_reducer_destroy", "cvo_reducer_info", "cvo_check_reduce_clouds", "cvo_reduce_device_clouds", "cvo_count_voxels",
+    "cvo_check_fuse_clouds", "cvo_fuse_device_clouds",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
 REDUCE_MODES = {"mean": REDUCE_MEAN, "central": REDUCE_CENTRAL}
 REDUCE_MAX_POINTS = 1048575              # CVO_REDUCE_MAX_POINTS
 REDUCE_MAX_VOXELS = 16                   # CVO_REDUCE_MAX_VOXELS
+FUSE_MAX_MEMBERS = 64                    # members of a group: the bits of a view mask
+FUSE_WANT = ("count", "source", "map", "views", "view_mask")
 
 _lib = None
 
@@ -385,6 +401,9 @@ def load_library():
     L.cvo_check_reduce_clouds.argtypes = [vp, C.c_int, dcp, rpp, rcp]
     L.cvo_reduce_device_clouds.argtypes = [vp, C.c_int, dcp, rpp, rcp, ip, vp]
     L.cvo_count_voxels.argtypes = [vp, C.c_int, dcp, C.c_int, fp, C.c_int, ip, vp]
+    fmp = C.POINTER(FuseMember); fpp = C.POINTER(FuseParams); fcp = C.POINTER(FusedCloud)
+    L.cvo_check_fuse_clouds.argtypes = [vp, C.c_int, ip, fmp, fpp, fcp]
+    L.cvo_fuse_device_clouds.argtypes = [vp, C.c_int, ip, fmp, fpp, fcp, ip, vp]
     _lib = L
     return L
 
@@ -741,7 +760,9 @@ def selftest_ingest_clouds(clouds, device: int = 0):
 class CvoReducer:
     """cvo_reducer: reduces clouds in device memory to one row per occupied voxel, many clouds per call, the result's bits a function of the
     input alone.  max_clouds, max_points: the most clouds per call and points per cloud (up to REDUCE_MAX_POINTS); the device scratch, 384
-    bytes per point of max_clouds x max_points, is allocated here and never grows.  Outputs are torch tensors on the reducer's device."""
+    bytes per point of max_clouds x max_points, is allocated here and never grows.  Outputs are torch tensors on the reducer's device.
+    `fuse` (cvo_hip.h, "Fusing clouds") runs groups of posed clouds through the same machinery, on the same scratch: max_clouds groups per
+    call, max_points points per group."""
 
     def __init__(self, max_clouds: int, max_points: int, device: int = 0):
         self.L = load_library()
@@ -826,6 +847,85 @@ class CvoReducer:
         out = np.zeros((n, vs.shape[0]), np.int32)
         _check(self.L.cvo_count_voxels(self.h, n, arr, int(vs.shape[0]), vs.ctypes.data_as(C.POINTER(C.c_float)), int(min_points),
                                        out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
+        return out
+
+    def _fuse_inputs(self, groups, poses, min_views, mode, want):
+        """what fuse refuses before it touches the library, and its (FuseMember array, group_first, per-group member sizes)"""
+        bad = [w for w in want if w not in FUSE_WANT]
+        if bad:
+            raise ValueError(f"want: one of {FUSE_WANT} expected, got {bad[0]!r}")
+        if mode not in REDUCE_MODES and mode not in REDUCE_MODES.values():
+            raise ValueError(f"mode: 'mean' or 'central' expected, got {mode!r}")
+        if not 1 <= int(min_views) <= FUSE_MAX_MEMBERS:
+            raise ValueError(f"min_views {min_views}: 1 .. {FUSE_MAX_MEMBERS} expected")
+        groups = [list(g) for g in groups]; poses = [list(q) for q in poses]
+        if not groups:
+            raise ValueError("no groups")
+        if len(poses) != len(groups):
+            raise ValueError(f"{len(groups)} groups but {len(poses)} lists of poses")
+        members, first, sizes = [], [0], []
+        for g, (clouds, ps) in enumerate(zip(groups, poses)):
+            if not 1 <= len(clouds) <= FUSE_MAX_MEMBERS:
+                raise ValueError(f"group {g}: {len(clouds)} members, 1 .. {FUSE_MAX_MEMBERS} expected")
+            if len(ps) != len(clouds):
+                raise ValueError(f"group {g}: {len(clouds)} members but {len(ps)} poses")
+            ns = []
+            for m, (c, pose) in enumerate(zip(clouds, ps)):
+                M = np.asarray(pose, np.float32)
+                if M.shape not in ((3, 4), (4, 4)):
+                    raise ValueError(f"group {g} member {m}: a 3 x 4 or 4 x 4 pose expected, got shape {M.shape}")
+                if not np.isfinite(M[:3]).all():
+                    raise ValueError(f"group {g} member {m}: the pose is not finite")
+                d = c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS)
+                members.append(FuseMember(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist())))
+                ns.append(int(d.n))
+            first.append(len(members)); sizes.append(ns)
+        return (FuseMember * len(members))(*members), np.asarray(first, np.int32), sizes, groups
+
+    def fuse(self, groups, poses, voxel: float, mode="mean", min_points: int = 1, min_views: int = 1, cap: int = 65535, want=("count",), cloud_stream=None):
+        """cvo_fuse_device_clouds: every group of posed clouds fused into one voxel-reduced cloud -- a local map -- by one call.  groups: a list
+        of lists of what `reduce` takes for one cloud (1 .. 64 members each); poses: a matching list of lists of 3 x 4 or 4 x 4 array-likes (host;
+        the last row of a 4 x 4 is ignored).  min_views: a cell is kept when at least that many members have a point in it.  want: which of
+        "count", "source" (global index: split_source), "map" (one row number per global index: voxels.lift), "views", "view_mask" to return beside
+        xyz and feat.  cap, mode, min_points, cloud_stream: reduce's.  Returns one dict per group, as reduce does, plus `offsets`: the members'
+        base global indices (numpy int64).  Raises CvoError when a group comes to more than cap rows; cap = 0 counts only: nothing is written,
+        n_out is the full row count and the arrays are empty."""
+        arr, first, sizes, groups = self._fuse_inputs(groups, poses, min_views, mode, want)
+        import torch
+        _settle_cloud_writer([c for g in groups for c in g], cloud_stream)
+        n = len(groups)
+        ns = [sum(q) for q in sizes]
+        caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in ns]       # (a cap out of range is the library's to refuse)
+        rows = [max(0, c) for c in caps]
+        dev = torch.device("cuda", self.device)
+        stream = None
+        if cloud_stream is not None:
+            stream = cloud_stream if isinstance(cloud_stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(cloud_stream), device=dev)
+        per_row = dict(xyz=((3,), torch.float32), feat=((5,), torch.float32), count=((), torch.int32), source=((), torch.int32), views=((), torch.int32),
+                       view_mask=((), torch.int64))                   # (the mask's 64 bits in torch's signed carrier: bit 63 is the sign)
+        with torch.cuda.stream(stream):                               # (the arrays belong to the stream their readers will use)
+            whole = {k: torch.empty((sum(rows),) + sh, dtype=dt, device=dev) for k, (sh, dt) in per_row.items() if k in ("xyz", "feat") or k in want}
+            mp = torch.empty(sum(ns), dtype=torch.int32, device=dev) if "map" in want else None
+        recs = (FusedCloud * n)(); at = pt = 0; views = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = {key: t[at:at + rows[k]] for key, t in whole.items()}
+            if mp is not None: v["map"] = mp[pt:pt + ns[k]]
+            recs[k] = FusedCloud(*[ptr(v.get(key)) for key in ("xyz", "feat", "count", "source", "map", "views", "view_mask")], caps[k], 0)
+            views.append(v); at += rows[k]; pt += ns[k]
+        prm = FuseParams(float(voxel), int(REDUCE_MODES.get(mode, mode)), int(min_points), int(min_views))
+        n_out = np.zeros(n, np.int32)
+        _check(self.L.cvo_fuse_device_clouds(self.h, n, first.ctypes.data_as(C.POINTER(C.c_int)), arr, C.byref(prm), recs,
+                                             n_out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
+        over = [k for k in range(n) if n_out[k] > caps[k]] if int(cap) != 0 else []      # (cap 0 counts only: n_out is the answer)
+        if over:
+            k = over[0]
+            raise CvoError(CVO_ERR_INVALID, f"group {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel (fuse_voxel_for_budget)")
+        out = []
+        for k, v in enumerate(views):
+            m = int(n_out[k])
+            offsets = np.concatenate([[0], np.cumsum(sizes[k])[:-1]]).astype(np.int64)
+            out.append({key: (t if key == "map" else t[:m]) for key, t in v.items()} | dict(n_out=m, offsets=offsets))
         return out
 
 

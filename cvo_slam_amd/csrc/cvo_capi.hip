@@ -98,6 +98,8 @@ hipError_t launch_ingest_clouds(const CloudIngestDesc* descs, int n_clouds, int 
 hipError_t launch_reduce_clouds(const ReduceDesc* descs, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode, int min_points,
                                 hipStream_t s);
 hipError_t launch_count_voxels(const CountDesc* descs, int n_items, int n_max, int slots_max, int min_points, hipStream_t s);
+hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
+                              float voxel, int mode, int min_points, int min_views, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -3426,12 +3428,13 @@ void cloud_strides(const cvo_device_cloud& c, long long* xs, long long* ps, long
 }
 // What every device-cloud entry point checks first, before any slot or stream changes and before anything is queued (cvo_check_device_clouds runs it alone).
 // n_limit: 65535 for a hand-over (16-bit column indices), CVO_REDUCE_MAX_POINTS in front of a reducer.
-int check_device_clouds(int device, int count, const cvo_device_cloud* clouds, int n_limit = 65535) {
+// names: what to call cloud k in a message instead of "cloud k: " (a fusion's "group g member m: ").
+int check_device_clouds(int device, int count, const cvo_device_cloud* clouds, int n_limit = 65535, const std::string* names = nullptr) {
     if (count <= 0 || count > 65535) return fail(CVO_ERR_INVALID, "bad cloud count");
     if (!clouds) return fail(CVO_ERR_INVALID, "null argument: clouds");
     for (int k = 0; k < count; ++k) {
         const cvo_device_cloud& c = clouds[k];
-        const std::string who = "cloud " + std::to_string(k) + ": ";
+        const std::string who = names ? names[k] : "cloud " + std::to_string(k) + ": ";
         if (c.n < 0 || c.n > n_limit)
             return fail(CVO_ERR_INVALID, who + "n " + std::to_string(c.n) + " is outside 0 .. " + std::to_string(n_limit) + (n_limit == 65535 ? " (16-bit column indices)" : ""));
         const struct { const char* name; long long v; } strides[3] = {{"xyz_stride", c.xyz_stride}, {"feat_point_stride", c.feat_point_stride}, {"feat_channel_stride", c.feat_channel_stride}};
@@ -3452,7 +3455,7 @@ int check_device_clouds(int device, int count, const cvo_device_cloud* clouds, i
     for (int k = 0; k < count; ++k) {
         const cvo_device_cloud& c = clouds[k];
         if (c.n == 0) continue;
-        const std::string who = "cloud " + std::to_string(k) + ": ";
+        const std::string who = names ? names[k] : "cloud " + std::to_string(k) + ": ";
         long long xs, ps, cs; cloud_strides(c, &xs, &ps, &cs);
         int rc;
         if ((rc = check_device_plane(device, c.xyz, xs, 12, c.n, who + "xyz", "cloud"))) return rc;              // [xyz, xyz + (n-1)*xyz_stride + 12)
@@ -3679,6 +3682,15 @@ ReduceLayout reduce_layout(int max_points) {
 }
 inline size_t count_item_keys(int n) { return up16(16 * (size_t)n); }                       // 2 n slots of 8 bytes
 inline size_t count_item_bytes(int n) { return count_item_keys(n) + up16(8 * (size_t)n); }   // and their member counts
+// A fusion (cvo_fuse_kernels.hip): a group takes a cloud's region, and behind the max_clouds regions -- in the part of the 384 bytes per point that a
+// reduction leaves unused -- its view masks (8 bytes per slot) and the heads of its blocks (a block per 256 points of a member: up to 64 more
+// than a cloud of as many points has).  The descriptor table holds the groups' records, then the members'.
+constexpr int FUSE_MAX_MEMBERS = 64, FUSE_MAX_CALL_MEMBERS = 4096;
+inline size_t fuse_masks_bytes(int max_points) { return up16(16 * (size_t)max_points); }
+inline size_t fuse_extra_bytes(int max_points) { return fuse_masks_bytes(max_points) + up16(4 * (((size_t)max_points + 255) / 256 + FUSE_MAX_MEMBERS)); }
+inline size_t fuse_table_bytes(int max_clouds) {
+    return (size_t)max_clouds * sizeof(FuseGroupDesc) + std::min<size_t>(FUSE_MAX_CALL_MEMBERS, (size_t)max_clouds * FUSE_MAX_MEMBERS) * sizeof(FuseMemberDesc);
+}
 void reducer_release(cvo_reducer r) {
     (void)hipSetDevice(r->device);
     if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
@@ -3699,7 +3711,7 @@ int reducer_alloc(cvo_reducer r) {
     const size_t items = (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS;
     r->cloud_bytes = reduce_layout(r->max_points).bytes;
     r->scratch_bytes = std::max((size_t)r->max_clouds * r->cloud_bytes, items * count_item_bytes(r->max_points));
-    const size_t table = std::max((size_t)r->max_clouds * sizeof(ReduceDesc), items * sizeof(CountDesc));
+    const size_t table = std::max({(size_t)r->max_clouds * sizeof(ReduceDesc), items * sizeof(CountDesc), fuse_table_bytes(r->max_clouds)});
     HIP_TRY(hipMalloc(&r->scratch, r->scratch_bytes));
     HIP_TRY(hipMalloc(&r->d_desc, table));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_total), items * sizeof(int)));
@@ -3846,6 +3858,120 @@ int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k
             return launch_count_voxels(static_cast<const CountDesc*>(r->d_desc), live, n_max, 2 * n_max, min_points, r->stream); })))
         return rc;
     for (int q = 0; q < live; ++q) counts_out[of[q]] = r->h_total[q];
+    return CVO_OK;
+}
+// ---- fusing clouds (cvo_fuse_kernels.hip): groups of posed clouds through the reducer's machinery, on the reducer's scratch and stream
+namespace {
+int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (groups < 1 || groups > r->max_clouds) return fail(CVO_ERR_INVALID, "groups " + std::to_string(groups) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if (!group_first || !members || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (group_first[0] != 0) return fail(CVO_ERR_INVALID, "group_first[0] " + std::to_string(group_first[0]) + " is not 0");
+    for (int g = 0; g < groups; ++g) {
+        const long long k = (long long)group_first[g + 1] - group_first[g];
+        if (k < 0) return fail(CVO_ERR_INVALID, "group_first[" + std::to_string(g + 1) + "] " + std::to_string(group_first[g + 1]) + " is below group_first[" + std::to_string(g) + "]: not ascending");
+        if (k < 1 || k > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": " + std::to_string(k) + " members is outside 1 .. 64");
+        if (group_first[g + 1] > FUSE_MAX_CALL_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": more than 4096 members in the call");
+    }
+    const int total = group_first[groups];
+    if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
+    if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
+    if (p->min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(p->min_points) + " is below 1");
+    if (p->min_views < 1 || p->min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "min_views " + std::to_string(p->min_views) + " is outside 1 .. 64");
+    std::vector<cvo_device_cloud> clouds(total); std::vector<std::string> names(total);
+    for (int g = 0; g < groups; ++g)
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            clouds[m] = members[m].cloud;
+            names[m] = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
+            for (int k = 0; k < 12; ++k)
+                if (!std::isfinite(members[m].pose[k])) return fail(CVO_ERR_INVALID, names[m] + "pose[" + std::to_string(k) + "] is not finite");
+        }
+    int rc = check_device_clouds(r->device, total, clouds.data(), r->max_points, names.data()); if (rc) return rc;
+    for (int g = 0; g < groups; ++g) {
+        const std::string who = "group " + std::to_string(g) + ": ";
+        long long n = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += members[m].cloud.n;
+        if (n > r->max_points) return fail(CVO_ERR_INVALID, who + "its members' " + std::to_string(n) + " points are above the reducer's max_points " + std::to_string(r->max_points));
+        const cvo_fused_cloud& d = dst[g];
+        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+        const struct { const void* p; long long bytes; unsigned align; const char* name; } arr[7] = {{d.xyz, 12ll * d.cap, 4, "dst xyz"}, {d.feat, 20ll * d.cap, 4, "dst feat"},
+            {d.count, 4ll * d.cap, 4, "dst count"}, {d.source, 4ll * d.cap, 4, "dst source"}, {d.map, 4ll * n, 4, "dst map"}, {d.views, 4ll * d.cap, 4, "dst views"},
+            {d.view_mask, 8ll * d.cap, 8, "dst view_mask"}};
+        for (const auto& x : arr) {
+            if (!x.p || x.bytes == 0) continue;
+            if (reinterpret_cast<uintptr_t>(x.p) & (x.align - 1u)) return fail(CVO_ERR_INVALID, who + x.name + " is not " + std::to_string(x.align) + "-byte aligned");
+            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
+        }
+    }
+    return CVO_OK;
+}
+}  // namespace
+int cvo_check_fuse_clouds(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    return fuse_check(r, groups, group_first, members, p, dst);
+}
+int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst,
+                           int* n_out, void* cloud_stream) {
+    int rc = fuse_check(r, groups, group_first, members, p, dst); if (rc) return rc;
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    const size_t extra = fuse_extra_bytes(r->max_points), extras_at = (size_t)r->max_clouds * r->cloud_bytes;
+    if (extras_at + (size_t)r->max_clouds * extra > r->scratch_bytes) return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for the view masks");   // (never: 136 of 384 bytes per point)
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    int live_groups = 0, live_members = 0;
+    for (int g = 0; g < groups; ++g) {
+        int any = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) if (members[m].cloud.n > 0) { ++live_members; any = 1; }
+        live_groups += any;
+    }
+    for (int g = 0; g < groups; ++g) n_out[g] = 0;
+    if (live_groups == 0) return CVO_OK;
+    FuseGroupDesc* hg = static_cast<FuseGroupDesc*>(r->h_desc);
+    FuseMemberDesc* hm = reinterpret_cast<FuseMemberDesc*>(hg + live_groups);
+    const FuseGroupDesc* dg = static_cast<const FuseGroupDesc*>(r->d_desc);
+    const FuseMemberDesc* dm = reinterpret_cast<const FuseMemberDesc*>(dg + live_groups);
+    std::vector<int> of; of.reserve(groups);
+    int n_max = 0, slots_max = 0, rows_max = 0, qm = 0;
+    for (int g = 0; g < groups; ++g) {
+        int n = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += members[m].cloud.n;
+        if (n == 0) continue;
+        const int q = (int)of.size(); of.push_back(g);
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
+        char* more = static_cast<char*>(r->scratch) + extras_at + (size_t)q * extra;
+        FuseGroupDesc& G = hg[q];
+        G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(more);
+        G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
+        G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
+        G.block_heads = reinterpret_cast<int*>(more + fuse_masks_bytes(r->max_points)); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
+        G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
+        G.out_xyz = static_cast<float*>(dst[g].xyz); G.out_feat = static_cast<float*>(dst[g].feat); G.out_count = static_cast<int*>(dst[g].count);
+        G.out_source = static_cast<int*>(dst[g].source); G.out_map = static_cast<int*>(dst[g].map); G.out_views = static_cast<int*>(dst[g].views);
+        G.out_view_mask = static_cast<unsigned long long*>(dst[g].view_mask);
+        G.total = r->d_total + q;
+        G.n = n; G.slots = 2 * n; G.cap = dst[g].cap; G.rows_cap = std::min(dst[g].cap, n);
+        G.first_member = qm; G.pad_ = 0;
+        int at = 0, blocks = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            const cvo_device_cloud& c = members[m].cloud;
+            if (c.n == 0) continue;
+            FuseMemberDesc& M = hm[qm++];
+            M.xyz = static_cast<const float*>(c.xyz); M.feat = static_cast<const float*>(c.feat);
+            cloud_strides(c, &M.xyz_stride, &M.feat_point_stride, &M.feat_channel_stride);
+            std::memcpy(M.pose, members[m].pose, sizeof(M.pose));
+            M.group = q; M.base = at; M.first_block = blocks; M.n = c.n; M.bit = m - group_first[g]; M.pad_ = 0;
+            at += c.n; blocks += (c.n + 255) / 256;
+            n_max = std::max(n_max, c.n);
+        }
+        G.n_blocks = blocks; G.n_members = qm - G.first_member;
+        slots_max = std::max(slots_max, G.slots); rows_max = std::max(rows_max, G.rows_cap);
+    }
+    const cvo_fuse_params P = *p;
+    if ((rc = reducer_run(r, sizeof(FuseGroupDesc) * (size_t)live_groups + sizeof(FuseMemberDesc) * (size_t)live_members, live_groups, cloud_stream, [&] {
+            return launch_fuse_clouds(dg, live_groups, dm, live_members, n_max, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
+        return rc;
+    for (int q = 0; q < live_groups; ++q) n_out[of[q]] = r->h_total[q];
     return CVO_OK;
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {

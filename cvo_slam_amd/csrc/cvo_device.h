@@ -274,6 +274,34 @@ struct CountDesc {
     int n, slots; float voxel; int pad_;
 };
 static_assert(sizeof(CountDesc) == 80, "CountDesc layout");
+// one group of a fusion (cvo_fuse_kernels.hip; not in the reference), n > 0: ReduceDesc's scratch arrays over the group's global indices, the
+// cells' view masks beside them, and the group's blocks: its members' 256-point blocks one member after the other
+struct FuseGroupDesc {
+    unsigned long long* keys; unsigned long long* masks;   // slots: the cell's key; the OR of 1 << member number over its members
+    unsigned* lowest; unsigned* members;                   // slots: the lowest global member index, the member count
+    int* row; int* slot_of; int* block_heads; int* row_slot;   // as ReduceDesc; slot_of per global index, block_heads per block of the group
+    long long* sums; unsigned long long* best;             // rows_cap x 8 (MEAN); rows_cap (CENTRAL): (d2 bits << 32) | global index
+    float* out_xyz; float* out_feat; int* out_count; int* out_source; int* out_map; int* out_views; unsigned long long* out_view_mask;
+    int* total;                    // the full row count
+    int n, slots, cap, rows_cap;   // n: the group's points; rows_cap = min(cap, n)
+    int n_blocks;                  // the group's blocks
+    int first_member, n_members;   // its members with n > 0 in the launch's member table
+    int pad_;
+};
+static_assert(sizeof(FuseGroupDesc) == 176, "FuseGroupDesc layout");
+// one member (n > 0) of a group: the grid's second dimension in the passes over points, so no lane searches for its member
+struct FuseMemberDesc {
+    const float* xyz; const float* feat;
+    long long xyz_stride, feat_point_stride, feat_channel_stride;
+    float pose[12];                // row-major 3 x 4
+    int group;                     // its group in the launch's group table
+    int base;                      // the global index of its point 0
+    int first_block;               // the group's block number of its block 0
+    int n;
+    int bit;                       // its member number in the group (empty members counted): the bit it sets in a cell's view mask
+    int pad_;
+};
+static_assert(sizeof(FuseMemberDesc) == 112, "FuseMemberDesc layout");
 
 // the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
 struct BoxDesc {

@@ -1,5 +1,5 @@
-"""Helpers around CvoReducer (cvo_hip.h, "Reducing clouds"): choosing a voxel size for a point budget, and carrying what was computed for
-the reduced cloud's rows back to the dense cloud's points."""
+"""Helpers around CvoReducer (cvo_hip.h, "Reducing clouds" and "Fusing clouds"): choosing a voxel size for a point budget, carrying what was
+computed for the reduced cloud's rows back to the dense cloud's points, and telling which member of a fused group a row came from."""
 from __future__ import annotations
 
 import numpy as np
@@ -23,6 +23,52 @@ def voxel_for_budget(reducer, cloud, budget: int, lo: float, hi: float, steps: i
     if fits.shape[0] == 0:
         raise ValueError(f"voxel_for_budget: {int(counts[-1])} cells at the largest size {float(sizes[-1]):g} are more than the budget {budget}")
     return float(sizes[fits[0]])
+
+
+def fuse_voxel_for_budget(reducer, group, poses, budget: int, lo: float, hi: float, steps: int = 16, **filters) -> float:
+    """voxel_for_budget for a fusion: the smallest size of voxel_ladder(lo, hi, steps) at which the group (one list of clouds and one of poses, as
+    CvoReducer.fuse takes per group) comes to at most `budget` rows under `filters` (fuse's mode, min_points, min_views, cloud_stream).  Found by
+    bisection with count-only fuse calls (cap = 0), the largest size first: at most 5 calls for 16 sizes.  The bisection takes the row count as
+    falling with the size.  That holds for min_views == 1; with min_views above 1 small voxels hold one point each and keep NO row, so the
+    answer would be a uselessly small size: size the map with min_views = 1 and apply the views filter in the fusion itself (it only removes
+    rows).  Raises ValueError when even `hi` leaves more."""
+    sizes = voxel_ladder(lo, hi, steps)
+    if int(budget) < 0:
+        raise ValueError(f"fuse_voxel_for_budget: budget {budget} is negative")
+    extra = set(filters) - {"mode", "min_points", "min_views", "cloud_stream"}
+    if extra:
+        raise ValueError(f"fuse_voxel_for_budget: unknown filter {sorted(extra)[0]!r}")
+    rows = lambda k: int(reducer.fuse([group], [poses], float(sizes[k]), cap=0, want=(), **filters)[0]["n_out"])
+    top = rows(len(sizes) - 1)
+    if top > budget:
+        raise ValueError(f"fuse_voxel_for_budget: {top} rows at the largest size {float(sizes[-1]):g} are more than the budget {budget}")
+    below, fits = -1, len(sizes) - 1                                   # sizes[below] does not fit (-1: none tried), sizes[fits] does
+    while fits - below > 1:
+        mid = (below + fits) // 2
+        if rows(mid) <= budget: fits = mid
+        else: below = mid
+    return float(sizes[fits])
+
+
+def split_source(source, offsets):
+    """(member, index) of a fused group's global indices (`source` of CvoReducer.fuse, or any global index): offsets is the group's `offsets`, the
+    members' base global indices.  An empty member owns no index.  source: a numpy array or a torch tensor; the results are of its kind."""
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    if off.shape[0] == 0 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("split_source: offsets ascending from 0 expected")
+    if isinstance(source, np.ndarray) or not hasattr(source, "device"):
+        g = np.asarray(source).astype(np.int64)
+        if g.size and g.min() < 0:
+            raise ValueError("split_source: a negative global index")
+        member = np.searchsorted(off, g, side="right") - 1
+        return member.astype(np.int32), (g - off[member]).astype(np.int32)
+    import torch
+    g = source.to(torch.int64)
+    if g.numel() and int(g.min()) < 0:
+        raise ValueError("split_source: a negative global index")
+    o = torch.from_numpy(off).to(g.device)
+    member = torch.searchsorted(o, g, right=True) - 1
+    return member.to(torch.int32), (g - o[member]).to(torch.int32)
 
 
 def lift(map, per_row_values, fill):

@@ -538,6 +538,53 @@ int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* i
  * counts_out[i * k + j] for cloud i and voxels[j], equal to n_out of a reduction at that size */
 int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k, const float* voxels /* k */, int min_points,
                      int* counts_out /* count x k, host */, void* cloud_stream);
+/* ---- Fusing clouds (not in the reference): a local map -- the clouds of the last K keyframes, each under its pose, merged into one voxel-reduced
+ * cloud, with the cells that too few frames saw thrown away -- by the reducer's machinery: many groups per call, bits that depend on the input alone.
+ *
+ * The definition.  A fusion IS the reduction (above) of the concatenation of the moved members with the features unchanged, plus the views filter
+ * and the two view outputs:
+ *   group: a list of 1 .. 64 members; a member is a cvo_device_cloud (n up to 1048575, as for the reducer) and a pose: 12 f32, row-major 3 x 4 (the
+ *     layout of cvo_point_support's tran), in HOST memory.
+ *   global index: the group's points are the members' points, one member after the other: point i of member m has
+ *     g = (sum of n of the members before m) + i.
+ *   moved position: x' = (M[r,0]*x + (M[r,1]*y + M[r,2]*z)) + M[r,3] per row r, in f32 and un-fused (each product and sum rounded).  Features are
+ *     not changed.
+ *   valid point: its 8 source floats are finite and below 2^15 in magnitude, its 3 moved floats are finite and below 2^15, and each cell
+ *     coordinate floorf(x' / voxel) has magnitude below 2^20.  From here on the reducer's definition applies to the sequence (moved position,
+ *     features) in global-index order: cells, min_points, row order by ascending lowest global member index, MEAN by llrint(v * 2^24) integer
+ *     sums, CENTRAL by the least (d2 bits, global index).  In CENTRAL the row's position is the winner's MOVED position, its features the copy.
+ *   views: a cell's view mask is the 64-bit OR of 1 << m over its members' member numbers m (empty members keep their numbers); views is its
+ *     popcount.  A cell is kept when it has at least min_points members AND at least min_views views (1 .. 64).  map is -1 for dropped cells.
+ *   outputs per group, caller-owned device memory: xyz (cap x 3), feat (cap x 5); optional count, source (global index), views (int32), view_mask
+ *     (uint64), each of cap rows; optional map, one int32 per global index.  n_out[g] is the FULL row count; rows at or above cap are not written
+ *     and no byte behind row cap - 1 is touched.
+ *
+ * A fusion runs on an existing cvo_reducer and allocates nothing: a group takes the scratch region of one cloud (groups <= max_clouds, a group's
+ * points <= max_points; its table has 2 x its points slots), the view masks lie in the part of the 384 bytes per point a reduction leaves unused
+ * (cvo_reducer_info's scratch_bytes is what it was).  All groups and members of a call go through the same seven launches.  The poses travel with
+ * the descriptor table in its one host-to-device copy.
+ * Validation: CVO_ERR_INVALID, the message naming group, member and field, for everything cvo_check_reduce_clouds checks, per member cloud and per
+ * dst array (view_mask needs 8-byte alignment, extent cap x 8; views cap x 4; map (group's points) x 4); group_first not ascending from 0; a group
+ * with 0 or more than 64 members; more than 4096 members in the call; a group's points above max_points; groups outside 1 .. max_clouds; a pose
+ * float that is not finite; min_views outside 1 .. 64.  A refused call changes nothing.  cloud_stream, the one host wait for the counts, and
+ * cap == 0 with every array NULL meaning "count only" are cvo_reduce_device_clouds' rules. */
+typedef struct cvo_fuse_member { cvo_device_cloud cloud; float pose[12]; } cvo_fuse_member;                 /* 96 bytes */
+typedef struct cvo_fuse_params { float voxel; int mode; int min_points; int min_views; } cvo_fuse_params;    /* 16 bytes */
+typedef struct cvo_fused_cloud {        /* caller-owned DEVICE memory, one per group; all but xyz and feat may be NULL */
+    void* xyz;        /* cap x 3 float32 */
+    void* feat;       /* cap x 5 float32 */
+    void* count;      /* cap int32 */
+    void* source;     /* cap int32: global index */
+    void* map;        /* (group's points) int32 */
+    void* views;      /* cap int32 */
+    void* view_mask;  /* cap uint64 */
+    int cap; int pad_;
+} cvo_fused_cloud;                      /* 64 bytes */
+/* the validation of cvo_fuse_device_clouds alone: launches nothing */
+int cvo_check_fuse_clouds(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_member* members,
+                          const cvo_fuse_params* p, const cvo_fused_cloud* dst);
+int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_member* members,
+                           const cvo_fuse_params* p /* one for all */, const cvo_fused_cloud* dst, int* n_out /* groups, host */, void* cloud_stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
