@@ -2128,8 +2128,22 @@ CVO_ITERATION_PHASE void phase_candidates(const PairDesc* Dp_in, int g_in, int G
     __syncthreads();
 }
 
+// every wave an equal share of the workgroup's nonzero records instead of the segment it compacted itself?  Where the deal could not balance the segments (fewer than
+// two blocks per wave: a member of a pair on many workgroups) and there is enough to share; the resident float4 layout only.
+__device__ __forceinline__ bool ls_even_shares(int y_lds) {
+    const Shared* sh = reinterpret_cast<const Shared*>(cvo_smem);
+    const int nwaves = (int)blockDim.x >> 6;
+    if (y_lds != 1 || sh->dense_mode || ((sh->ctx_nrows + 63) >> 6) >= 2 * nwaves) return false;
+    int cnt_wg = 0;
+    for (int w = 0; w < nwaves; ++w) cnt_wg += sh->wcnt[w];
+    return cnt_wg >= LS_EVEN_MIN * nwaves;
+}
+
 // ---- L: compute_step_size sums (cvo.cpp:239-315); f64 terms, one lane per nonzero
-template <bool EVEN>
+// XG: the instance for a workgroup whose padded rows exceed the tile (finish_slots: Shared::x_lds == 0), which gathers x_i from the cloud in memory.  Every other
+// instance reads x_i from LDS, and knows it when it is compiled: in the resident layouts the record ring's loads are then the only vector-memory instructions of
+// the walk's loop, the compiler can count them, and the wait before a ring element is used leaves the newer ones in flight.
+template <bool EVEN, bool XG = false>
 __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) {
     const PairDesc* Dp = uni_ptr(Dp_in); const int g = uni(g_in), G = uni(G_in), tgeo = uni(tile_in), y_lds = uni(y_lds_in), k = uni(k_in);
     const Lds L = lds_layout(tgeo, y_lds); Shared* sh = L.sh;
@@ -2151,7 +2165,6 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
     if (!sh->dense_mode) {
         // every wave walks the nonzeros it compacted itself: the candidate phase deals the rows so that the waves' shares are
         // near equal, and a wave's segment is one contiguous run
-        const bool x_lds = sh->x_lds != 0;
         const int wave = tid >> 6;
         int cnt_wg = 0;
         for (int w = 0; w < nwaves; ++w) cnt_wg += sh->wcnt[w];
@@ -2160,14 +2173,15 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
         // (cvo.cpp:309-314): every wave takes an EQUAL share of the records, wherever they lie -- a stretch of one segment, or the end of one and the start of the next.
         // (Only where the deal could not balance -- fewer than two blocks per wave -- and there is enough to share: with the waves' segments near equal, or a few
         // hundred records in all, a second stretch per wave costs more than it evens out: -1.5 % under load, +5 % on a tracker's frame, measured.)
-        constexpr bool even = EVEN;                                   // (decided by the caller: ls_even_shares)
+        const bool even = XG ? ls_even_shares(y_lds) : EVEN;          // (decided by the caller: phase_linesearch_any; the x-from-memory instance serves both)
         const int share_lo = (int)(((long long)cnt_wg * wave) / nwaves), share_hi = (int)(((long long)cnt_wg * (wave + 1)) / nwaves);
         int cnt_w = 0; const gv2u* sp = c.surv + c.fbase;             // the stretch being walked (set per segment below)
         // With several nonzeros per column the last quarter of the point part ({2*z4, |z2|^2 + 2 z1.z3}: 33 of a nonzero's ~120
         // instructions) is tabulated once per iteration, 16 bytes per column in LDS over the rebuild scratch.  (Tabulating all of
         // the point part was measured: its four 16-byte gathers per nonzero make the LDS the bottleneck -- 88 against 118 cycles
         // per 64 nonzeros -- and two table passes need the records binned by column in the candidate phase; one gather does not.)
-        const bool use_table = sh->tab_cols >= c.nm && cnt_wg > LS_TAB_FACTOR * c.nm && y_lds != 0;
+        // (Not in the x-from-memory instance: tabled and untabled terms are the same float sequence.)
+        const bool use_table = !XG && sh->tab_cols >= c.nm && cnt_wg > LS_TAB_FACTOR * c.nm && y_lds != 0;
         if (use_table) {
             for (int j = tid; j < c.nm; j += nthreads) {
                 const float4 yj = y_lds == 1 ? load_y<1>(c, L, j) : load_y<2>(c, L, j);
@@ -2177,20 +2191,21 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
             }
             __syncthreads();
         }
-        // records stream from L2 / HBM, two per 16-byte load: a lane takes the aligned pair {2p, 2p + 1} of the stretch, and four steps of records (two loads) are in
-        // flight per lane (under load one step's arithmetic is shorter than a memory round trip).  A stretch may start at an odd record (a segment start wbase, or the
+        // records stream from L2 / HBM, two per 16-byte load: a lane takes the aligned pair {2p, 2p + 1} of the stretch, from a ring of two loads: while a lane works on
+        // the two records of one, the other is in flight (a ring of three, two in flight, measured no better: profiles/linesearch_counted_loads.txt).  A stretch may start at an odd record (a segment start wbase, or the
         // start of a wave's share of a segment) and end at an even one: the pairs are aligned by ADDRESS, so the first may begin one record before the stretch and the
         // last end one record behind it; those halves are loaded and not used (q bounds below).  They lie inside the workgroup's region of surv: the region starts at a
         // multiple of 128 records (c.fbase; the slot's plane likewise: build_ctx) and holds an even number of them, so an aligned pair with one record inside is inside.
         constexpr int RD = 2;
         auto walk = [&](auto ym, auto tb) {
-            constexpr int YM = decltype(ym)::value;
+            constexpr int YM = decltype(ym)::value;                              // (-1: the layout is read at run time)
             constexpr bool TAB = decltype(tb)::value;
             if (cnt_w <= 0) return;
             auto term = [&](unsigned a_bits, unsigned tag) {
                 const int slot = (int)(tag >> 16), j = (int)(tag & 0xFFFFu);
-                float xi[3]; load_x(c, L, x_lds, slot, xi);
-                const float4 yj = load_y<YM>(c, L, j);
+                float xi[3];
+                if (XG) load_x(c, L, false, slot, xi); else { xi[0] = L.lx[slot]; xi[1] = L.ly[slot]; xi[2] = L.lz[slot]; }
+                const float4 yj = YM < 0 ? load_y_rt(c, L, y_lds, j) : load_y<(YM < 0 ? 0 : YM)>(c, L, j);
                 if (TAB) {
                     const float4 tq = L.tab[j];
                     float4 t0, t1, t2, t3;
@@ -2202,30 +2217,33 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
                     ls_terms(xi, yj, __uint_as_float(a_bits), ls, acc4[0], acc4[1], acc4[2], acc4[3]);
                 }
             };
-            const int odd = (int)((reinterpret_cast<size_t>(sp) >> 3) & 1u);     // the stretch starts in the upper half of a 16-byte word
+            const int odd = uni((int)((reinterpret_cast<size_t>(sp) >> 3) & 1u));     // the stretch starts in the upper half of a 16-byte word
             const gv4u* pp = reinterpret_cast<const gv4u*>(sp - odd);
-            const int np = (cnt_w + odd + 1) >> 1;                               // pairs that hold a record of the stretch: record r of it is half (r + odd) & 1 of pair (r + odd) >> 1
+            const int np = uni((cnt_w + odd + 1) >> 1);                              // pairs that hold a record of the stretch: record r of it is half (r + odd) & 1 of pair (r + odd) >> 1
             v4u ring[RD];
 #pragma unroll
-            for (int u = 0; u < RD; ++u) ring[u] = ld_rec2(&pp[min(lane + 64 * u, np - 1)]);
-            for (int q0 = lane; q0 < np; q0 += 64 * RD) {
-                prio_by_remaining((np - uni(q0)) >> 10);           // units of eight trips (2048 records): the waves' shares are near equal, the one with more left goes first
+            for (int u = 0; u < RD; ++u) { ring[u] = ld_rec2(&pp[min(lane + 64 * u, np - 1)]); __builtin_amdgcn_sched_barrier(0); }   // (in the order of their use, as the loop refills them: one count for both ways into it)
+            for (int b0 = 0; b0 < np; b0 += 64 * RD) {              // (np is the same in every lane: the trip count is the wave's)
+                prio_by_remaining((np - b0) >> 10);                // units of eight trips (2048 records): the waves' shares are near equal, the one with more left goes first
 #pragma unroll
                 for (int u = 0; u < RD; ++u) {
-                    const int q = q0 + 64 * u;
+                    const int q = b0 + 64 * u + lane;
                     const v4u r4 = ring[u];
-                    ring[u] = ld_rec2(&pp[min(q + 64 * RD, np - 1)]);
                     const int r0 = 2 * q - odd;                    // the pair's records in the stretch: r0 (-1 for the first pair of an odd start), r0 + 1 (cnt_w behind an even end)
                     if (q < np) {
                         if (r0 >= 0) term(r4.x, r4.y);
                         if (r0 + 1 < cnt_w) term(r4.z, r4.w);
                     }
+                    // refilled BEHIND its use, into the registers just read: the element loaded ahead of its use needs registers of its own and a copy at the end of
+                    // the trip, and a copy of a load in flight is a wait for all of them.  RD - 1 elements stay in flight while one is used.
+                    ring[u] = ld_rec2(&pp[min(q + 64 * RD, np - 1)]);
                 }
             }
         };
         using T1 = std::true_type; using T0 = std::false_type;
         auto dispatch = [&]() {
-            if (use_table) { if (y_lds == 1) walk(std::integral_constant<int, 1>{}, T1{}); else walk(std::integral_constant<int, 2>{}, T1{}); }
+            if (XG) walk(std::integral_constant<int, -1>{}, T0{});
+            else if (use_table) { if (y_lds == 1) walk(std::integral_constant<int, 1>{}, T1{}); else walk(std::integral_constant<int, 2>{}, T1{}); }
             else if (y_lds == 1) walk(std::integral_constant<int, 1>{}, T0{}); else if (y_lds == 2) walk(std::integral_constant<int, 2>{}, T0{}); else walk(std::integral_constant<int, 0>{}, T0{});
         };
         if (!even) {                                                   // the wave's own segment (the common path: as it always was)
@@ -2239,7 +2257,8 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
                 seg_first += seg_n;
                 if (lo >= hi) continue;
                 cnt_w = hi - lo; sp = c.surv + c.fbase + (size_t)sh->wbase[s] + lo;
-                if (use_table) walk(std::integral_constant<int, 1>{}, T1{}); else walk(std::integral_constant<int, 1>{}, T0{});   // (the resident float4 layout only: two instances more, not five)
+                if (XG) walk(std::integral_constant<int, -1>{}, T0{});
+                else if (use_table) walk(std::integral_constant<int, 1>{}, T1{}); else walk(std::integral_constant<int, 1>{}, T0{});   // (the resident float4 layout only: two instances more, not five)
             }
         }
     } else {
@@ -2275,19 +2294,17 @@ __device__ __forceinline__ void linesearch_body(const PairDesc* Dp_in, int g_in,
     }
 }
 
-// every wave an equal share of the workgroup's nonzero records instead of the segment it compacted itself?  Where the deal could not balance the segments (fewer than
-// two blocks per wave: a member of a pair on many workgroups) and there is enough to share; the resident float4 layout only.
-__device__ __forceinline__ bool ls_even_shares(int y_lds) {
-    const Shared* sh = reinterpret_cast<const Shared*>(cvo_smem);
-    const int nwaves = (int)blockDim.x >> 6;
-    if (y_lds != 1 || sh->dense_mode || ((sh->ctx_nrows + 63) >> 6) >= 2 * nwaves) return false;
-    int cnt_wg = 0;
-    for (int w = 0; w < nwaves; ++w) cnt_wg += sh->wcnt[w];
-    return cnt_wg >= LS_EVEN_MIN * nwaves;
-}
 CVO_ITERATION_PHASE void phase_linesearch(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<false>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
 // (a function of its own whatever the build: the common path's function does not carry its code)
 static __device__ __noinline__ void phase_linesearch_even(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<true>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
+// x_i from the cloud in memory (more padded rows than the tile holds): correct, not fast -- one walk for every layout and for both ways of sharing the records, no column table
+static __device__ __noinline__ void phase_linesearch_xmem(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) { linesearch_body<false, true>(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); }
+// phase L: the instance for where x_i lies and how the waves share the records
+__device__ __forceinline__ void phase_linesearch_any(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in) {
+    if (uni(reinterpret_cast<const Shared*>(cvo_smem)->x_lds) == 0) phase_linesearch_xmem(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in);
+    else if (ls_even_shares(uni(y_lds_in))) phase_linesearch_even(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in);
+    else phase_linesearch(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in);
+}
 
 // ---- E: one lane finishes the iteration (every workgroup of the pair computes the same bits)
 CVO_ITERATION_PHASE void phase_epilogue(const PairDesc* Dp_in, int g_in, int G_in, int tile_in, int y_lds_in, int k_in, int max_iter_in) {
@@ -2420,7 +2437,7 @@ static __device__ __noinline__ void phase_iteration(const PairDesc* Dp_in, int g
     if (tid == 0) { atomicAdd(&sh->cand_total, (unsigned long long)sh->cand); atomicAdd(&sh->nnz_total, (unsigned long long)sh->nnz); }
     { const unsigned long long t_now = CVO_NOW(); if (tid == 0) atomicAdd(&sh->ticks[1], t_now - t_prev); t_prev = t_now; }
     if (sh->status != 0) return;
-    if (ls_even_shares(uni(y_lds_in))) phase_linesearch_even(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in); else phase_linesearch(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in);
+    phase_linesearch_any(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in);
     { const unsigned long long t_now = CVO_NOW(); if (tid == 0) atomicAdd(&sh->ticks[3], t_now - t_prev); t_prev = t_now; }
     if (sh->status != 0) return;
     phase_epilogue(Dp_in, g_in, G_in, tile_in, y_lds_in, k_in, max_iter_in);
@@ -2768,7 +2785,7 @@ static __device__ __noinline__ void run_pair(const PairDesc* descs_in, int ps_in
         if (tid == 0) { atomicAdd(&sh->cand_total, (unsigned long long)sh->cand); atomicAdd(&sh->nnz_total, (unsigned long long)sh->nnz); }
         CVO_PHASE(1);
         if (sh->status != 0) break;
-        if (ls_even_shares(y_lds)) phase_linesearch_even(Dp, ge, Ge, tgeo, y_lds, k); else phase_linesearch(Dp, ge, Ge, tgeo, y_lds, k);
+        phase_linesearch_any(Dp, ge, Ge, tgeo, y_lds, k);
         CVO_PHASE(3);
         if (sh->status != 0) break;
         phase_epilogue(Dp, ge, Ge, tgeo, y_lds, k, max_iter);
