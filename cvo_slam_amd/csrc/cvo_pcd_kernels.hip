@@ -32,11 +32,14 @@ __global__ void pcd_gray_kernel(const uint8_t* __restrict__ bgr, float* __restri
 
 // ---- make_pyramid: 2x2 box down-sampling (pcd_generator.cpp:103-118)
 // (pn: elements of the parent level's plane, the stride of its images)
-__global__ void pcd_down_kernel(const float* __restrict__ P, int pw, int pn, float* __restrict__ I, int wl, int hl) {
+// The parent's rows are stepped by the reference's prev_wl = wl*2 (:103), not by the parent's width: the same for an even parent width; for
+// an odd one the parent is read sheared, a pixel further per row pair -- what the reference computes.  The last element read is
+// 2wl * 2hl - 1, inside the parent plane (2wl <= its width, 2hl <= its height).
+__global__ void pcd_down_kernel(const float* __restrict__ P, int pn, float* __restrict__ I, int wl, int hl) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= wl * hl) return;
     P += (size_t)pn * blockIdx.y; I += (size_t)wl * hl * blockIdx.y;
-    const int x = i % wl, y = i / wl;
+    const int x = i % wl, y = i / wl, pw = 2 * wl;
     const float* p = P + (size_t)2 * x + (size_t)2 * y * pw;
     I[i] = 0.25f * (p[0] + p[1] + p[pw] + p[pw + 1]);
 }
@@ -539,9 +542,9 @@ hipError_t pcd_launch_pyramid(const uint8_t* bgr, int w, int h, float* I0, float
     const int w1 = w / 2, h1 = h / 2, w2 = w1 / 2, h2 = h1 / 2;
     PCD_LAUNCH_2D(pcd_gray_kernel, w * h, n_img, s, bgr, I0, w * h);
     PCD_LAUNCH_2D(pcd_grad_kernel, w * h, n_img, s, I0, w, h, dx0, dy0, abs0);
-    PCD_LAUNCH_2D(pcd_down_kernel, w1 * h1, n_img, s, I0, w, w * h, I1, w1, h1);
+    PCD_LAUNCH_2D(pcd_down_kernel, w1 * h1, n_img, s, I0, w * h, I1, w1, h1);
     PCD_LAUNCH_2D(pcd_grad_kernel, w1 * h1, n_img, s, I1, w1, h1, (float*)nullptr, (float*)nullptr, abs1);
-    PCD_LAUNCH_2D(pcd_down_kernel, w2 * h2, n_img, s, I1, w1, w1 * h1, I2, w2, h2);
+    PCD_LAUNCH_2D(pcd_down_kernel, w2 * h2, n_img, s, I1, w1 * h1, I2, w2, h2);
     PCD_LAUNCH_2D(pcd_grad_kernel, w2 * h2, n_img, s, I2, w2, h2, (float*)nullptr, (float*)nullptr, abs2);
     return hipGetLastError();
 }

@@ -61,18 +61,21 @@ struct Frame {                     // cvo::frame, data_type.h:44-69 (what the se
     std::vector<float> I[3], dx0, dy0, abs2[3];
 };
 
-// make_pyramid, pcd_generator.cpp:50-143
-void make_pyramid(const unsigned char* gray, int w, int h, Frame& f) {
+// make_pyramid, pcd_generator.cpp:50-143.  true_parent_width: the mutant of orc_pcd_generate_variant (variant 1), never the reference
+void make_pyramid(const unsigned char* gray, int w, int h, Frame& f, bool true_parent_width = false) {
     f.w = w; f.h = h;
     int wl = w, hl = h;
     for (int l = 0; l < 3; ++l) { f.I[l].assign((size_t)wl * hl, 0.f); f.abs2[l].assign((size_t)wl * hl, 0.f); wl /= 2; hl /= 2; }
     f.dx0.assign((size_t)w * h, 0.f); f.dy0.assign((size_t)w * h, 0.f);
     for (long i = 0; i < (long)w * h; ++i) f.I[0][i] = gray[i];                      // :83-87
     wl = w; hl = h;
+    int parent_w = w;
     for (int lvl = 0; lvl < 3; ++lvl) {
         std::vector<float>& I = f.I[lvl];
         if (lvl > 0) {                                                               // :103-118
-            const int pw = wl * 2;
+            // prev_wl = wl*2 (:103): for an odd parent width the rows of the parent are read sheared, one pixel more per row pair;
+            // the last index read is 2wl*2hl - 1, inside the parent plane
+            const int pw = true_parent_width ? parent_w : wl * 2;
             const std::vector<float>& P = f.I[lvl - 1];
             for (int y = 0; y < hl; ++y)
                 for (int x = 0; x < wl; ++x)
@@ -86,6 +89,7 @@ void make_pyramid(const unsigned char* gray, int w, int h, Frame& f) {
             if (lvl == 0) { f.dx0[idx] = dx; f.dy0[idx] = dy; }
             f.abs2[lvl][idx] = dx * dx + dy * dy;
         }
+        parent_w = wl;
         wl /= 2; hl /= 2;
     }
 }
@@ -183,7 +187,7 @@ struct Selector {                  // dso::PixelSelector, PixelSelector2.cpp:34-
         n[0] = n2; n[1] = n3; n[2] = n4;
     }
     // makeMaps, PixelSelector2.cpp:136-282 (the FAST branch is commented out in the reference)
-    int make_maps(const Frame& f, float* map, float density, int recursions_left, int* pot_used) {
+    int make_maps(const Frame& f, float* map, float density, int recursions_left, int* pot_used, int* subsampled = nullptr) {
         float num_have = 0, num_want = density, quotia;
         int ideal = current_potential;
         int n[3];
@@ -197,12 +201,13 @@ struct Selector {                  // dso::PixelSelector, PixelSelector2.cpp:34-
         if (recursions_left > 0 && quotia > 1.25 && current_potential > 1) {
             if (ideal >= current_potential) ideal = current_potential - 1;
             current_potential = ideal;
-            return make_maps(f, map, density, recursions_left - 1, pot_used);
+            return make_maps(f, map, density, recursions_left - 1, pot_used, subsampled);
         } else if (recursions_left > 0 && quotia < 0.25) {
             if (ideal <= current_potential) ideal = current_potential + 1;
             current_potential = ideal;
-            return make_maps(f, map, density, recursions_left - 1, pot_used);
+            return make_maps(f, map, density, recursions_left - 1, pot_used, subsampled);
         }
+        if (subsampled) *subsampled = quotia < 0.95 ? 1 : 0;
         int num_have_sub = num_have;
         if (quotia < 0.95) {
             const int wh = w * h;
@@ -225,19 +230,23 @@ struct Selector {                  // dso::PixelSelector, PixelSelector2.cpp:34-
  * xyz: n x 3 (AoS, data_type.h:30), feat: 5 channel-major arrays of `cap` floats (channel c of point i at feat[c*cap + i]),
  * px: n x 2 selected pixel (x, y) (frame::selected_points, pcd_generator.cpp:488-489).  Returns the number of points, or
  * -(needed) if cap is too small.  Optional debug outputs may be NULL: gray (w*h), map (w*h, after sub-sampling),
- * ths_smoothed ((w/32)*(h/32)), info[4] = {potential used by the last select, pixels marked in the final map, makeMaps' return value, 0}. */
-int orc_pcd_generate(const unsigned char* bgr, const unsigned short* depth, int w, int h, const orc_camera* cam, int num_want,
-                     float* xyz, float* feat, unsigned short* px, int cap,
-                     unsigned char* gray_out, float* map_out, float* ths_out, int* info) {
+ * ths_smoothed ((w/32)*(h/32)), info[4] = {potential used by the last select, pixels marked in the final map, makeMaps' return value,
+ * 1 if the random sub-sampling ran (quotia < 0.95, PixelSelector2.cpp:252) else 0}.
+ * variant: 0 = the reference.  1 = a MUTANT for tests/test_pcd_cases.py: the pyramid is down-sampled with the parent level's true width
+ * instead of the reference's 2*wl -- the same thing for even parent widths, another image for odd ones.  It shows that a case list can tell
+ * the two apart; nothing is ever checked against it. */
+int orc_pcd_generate_variant(const unsigned char* bgr, const unsigned short* depth, int w, int h, const orc_camera* cam, int num_want,
+                             float* xyz, float* feat, unsigned short* px, int cap,
+                             unsigned char* gray_out, float* map_out, float* ths_out, int* info, int variant) {
     std::vector<unsigned char> gray((size_t)w * h);
     orc_gray(bgr, w, h, gray.data());                                                // load_image, pcd_generator.cpp:618-630
     Frame f;
-    make_pyramid(gray.data(), w, h, f);                                              // select_point, :150
+    make_pyramid(gray.data(), w, h, f, variant == 1);                                // select_point, :150
     std::vector<float> map((size_t)w * h);
     Selector sel(w, h);                                                              // :154 (a new selector per frame: potential 3, same pattern)
     sel.make_hists(f);                                                               // makeMaps :185 (gradHistFrame != frame)
-    int pot_used = 0;
-    const int after = sel.make_maps(f, map.data(), (float)num_want, 1, &pot_used);   // :155
+    int pot_used = 0, subsampled = 0;
+    const int after = sel.make_maps(f, map.data(), (float)num_want, 1, &pot_used, &subsampled);   // :155
     int marked = 0;
     if (gray_out) std::memcpy(gray_out, gray.data(), gray.size());
     if (map_out) std::memcpy(map_out, map.data(), sizeof(float) * map.size());
@@ -265,8 +274,14 @@ int orc_pcd_generate(const unsigned char* bgr, const unsigned short* depth, int 
                 ++idx;
             }
         }
-    if (info) { info[0] = pot_used; info[1] = marked; info[2] = after; info[3] = 0; }
+    if (info) { info[0] = pot_used; info[1] = marked; info[2] = after; info[3] = subsampled; }
     return idx <= cap ? idx : -idx;
+}
+
+int orc_pcd_generate(const unsigned char* bgr, const unsigned short* depth, int w, int h, const orc_camera* cam, int num_want,
+                     float* xyz, float* feat, unsigned short* px, int cap,
+                     unsigned char* gray_out, float* map_out, float* ths_out, int* info) {
+    return orc_pcd_generate_variant(bgr, depth, w, h, cam, num_want, xyz, feat, px, cap, gray_out, map_out, ths_out, info, 0);
 }
 
 }  // extern "C"

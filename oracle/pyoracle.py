@@ -379,9 +379,11 @@ def glibc_rand_bytes(seed: int, n: int) -> np.ndarray:
     return out
 
 
-def pcd_generate(bgr8, depth16, camera, num_want: int = 3000, cap: int = 20000, debug: bool = False):
+def pcd_generate(bgr8, depth16, camera, num_want: int = 3000, cap: int = 20000, debug: bool = False, variant: int = 0):
     """pcd_generator::create_pointcloud(1, ...) of the reference on one frame (cvo.cpp:355-366).
-    camera = (scaling_factor, fx, fy, cx, cy).  Returns dict(xyz (n,3), feat (5,n), px (n,2)[, gray, map, ths, info])."""
+    camera = (scaling_factor, fx, fy, cx, cy).  Returns dict(xyz (n,3), feat (5,n), px (n,2)[, gray, map, ths, info]).
+    info = (potential of the last selection, pixels marked, makeMaps' return value, 1 if the sub-sampling ran).
+    variant 1: the mutant of orc_pcd_generate_variant (pyramid down-sampled with the true parent width), for tests/test_pcd_cases.py only."""
     bgr = np.ascontiguousarray(bgr8, np.uint8); dep = np.ascontiguousarray(depth16, np.uint16)
     h, w = dep.shape
     assert bgr.shape == (h, w, 3)
@@ -389,10 +391,11 @@ def pcd_generate(bgr8, depth16, camera, num_want: int = 3000, cap: int = 20000, 
     xyz = np.zeros((cap, 3), np.float32); feat = np.zeros((5, cap), np.float32); px = np.zeros((cap, 2), np.uint16)
     gray = np.zeros((h, w), np.uint8); mp = np.zeros((h, w), np.float32); ths = np.zeros((h // 32, w // 32), np.float32); info = np.zeros(4, np.int32)
     L = lib()
-    L.orc_pcd_generate.restype = C.c_int
-    n = L.orc_pcd_generate(bgr.ctypes.data_as(C.c_void_p), dep.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h), C.byref(cam), C.c_int(num_want),
-                           xyz.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p), px.ctypes.data_as(C.c_void_p), C.c_int(cap),
-                           gray.ctypes.data_as(C.c_void_p), mp.ctypes.data_as(C.c_void_p), ths.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p))
+    L.orc_pcd_generate_variant.restype = C.c_int
+    n = L.orc_pcd_generate_variant(bgr.ctypes.data_as(C.c_void_p), dep.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h), C.byref(cam), C.c_int(num_want),
+                                   xyz.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p), px.ctypes.data_as(C.c_void_p), C.c_int(cap),
+                                   gray.ctypes.data_as(C.c_void_p), mp.ctypes.data_as(C.c_void_p), ths.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p),
+                                   C.c_int(int(variant)))
     if n < 0:
         raise ValueError(f"cap {cap} too small: {-n} points")
     out = dict(xyz=xyz[:n].copy(), feat=feat[:, :n].copy(), px=px[:n].copy(), n=n)
