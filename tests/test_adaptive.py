@@ -42,16 +42,8 @@ def test_oracle_adaptive_reproduces_the_unfilled_ayy_rows(oracle):
     assert a["trace"][0]["dl"] != b["trace"][0]["dl"]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("seed,n,drop", [(11, 600, 0), (12, 450, 70), (13, 300, 0)])
-def test_hip_adaptive_align_matches_the_oracle(hiplib, oracle, seed, n, drop):
-    from cvo_slam_amd import synth, api
-    p = synth.make_small_pair(seed, n=n)
-    fx, ff, mx, mf = _normalised(p)
-    if drop:                                                           # num_moving > num_fixed: the rows of Ayy that do count (adaptive_cvo.cpp:243-266)
-        fx, ff = fx[:-drop], np.ascontiguousarray(ff[:, :-drop])
-    rc, want = oracle.adaptive_align(fx, ff, mx, mf, trace_cap=400)
-    got = api.adaptive_align(fx, ff, mx, mf, trace_cap=400)
+def assert_matches_the_oracle(rc, got, want):
+    """the HIP path's adaptive alignment against the oracle's: one set of assertions for every shape"""
     assert rc == 0 and got["iter"] == want["iter"] and len(got["trace"]) == len(want["trace"])
     for k, (g, w) in enumerate(zip(got["trace"], want["trace"])):
         assert (g["nnz_xy"], g["nnz_xx"], g["nnz_yy"]) == (w["nnz_xy"], w["nnz_xx"], w["nnz_yy"]), k
@@ -64,6 +56,34 @@ def test_hip_adaptive_align_matches_the_oracle(hiplib, oracle, seed, n, drop):
     rot, tr = rot_trans_err(got["transform"], want["transform"])
     assert rot <= 1e-4 and tr <= 1e-4
     assert got["ell"] == pytest.approx(want["ell"], rel=1e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n,drop", [(11, 600, 0), (12, 450, 70), (13, 300, 0)])
+def test_hip_adaptive_align_matches_the_oracle(hiplib, oracle, seed, n, drop):
+    from cvo_slam_amd import synth, api
+    p = synth.make_small_pair(seed, n=n)
+    fx, ff, mx, mf = _normalised(p)
+    if drop:                                                           # num_moving > num_fixed: the rows of Ayy that do count (adaptive_cvo.cpp:243-266)
+        fx, ff = fx[:-drop], np.ascontiguousarray(ff[:, :-drop])
+    rc, want = oracle.adaptive_align(fx, ff, mx, mf, trace_cap=400)
+    got = api.adaptive_align(fx, ff, mx, mf, trace_cap=400)
+    assert_matches_the_oracle(rc, got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["1x700", "7x700", "700x7", "64x600", "600x65", "129x1500"])
+def test_hip_adaptive_align_matches_the_oracle_on_lopsided_pairs(hiplib, oracle, name):
+    """Clouds of very different sizes (tests/lopsided_cases.py; ADP_ROWS = 64 rows per workgroup: one row, seven rows, one block, one block and one row,
+    two blocks and one row; with num_moving far above num_fixed nearly every row of Ayy counts, adaptive_cvo.cpp:243-266), with the assertions of test_hip_adaptive_align_matches_the_oracle.  Only shapes whose
+    dl is finite in every iteration of the oracle's trace are here (tests/test_lopsided_cases.py asserts it): on equal-sized tiny clouds dl is 0 / 0."""
+    from cvo_slam_amd import api
+    import lopsided_cases as lc
+    assert name in lc.ADAPTIVE_NAMES
+    fx, ff, mx, mf = lc.adaptive_case(name)
+    rc, want = lc.adaptive_run(oracle, name)
+    got = api.adaptive_align(fx, ff, mx, mf, trace_cap=400)
+    assert_matches_the_oracle(rc, got, want)
 
 
 @pytest.mark.gpu
