@@ -4,8 +4,8 @@ include/cvo_hip.h.
 
 Layout
   csrc/       hand-written HIP kernels + the C-ABI implementation (libcvo_hip.so)
-  api.py      ctypes mirror of the reference's `cvo::cvo` call surface (Cvo, CvoBatch, CvoTracks) and the cloud reducer (CvoReducer)
-  voxels.py   voxel size for a point budget (one cloud, or a fused group), per-row results back to the dense points, a fused row's member
+  api.py      ctypes mirror of the reference's `cvo::cvo` call surface (Cvo, CvoBatch, CvoTracks) and the cloud and frame reducer (CvoReducer)
+  voxels.py   voxel size for a point budget (one cloud, one frame, or a fused group), per-row results back to the dense points, a fused row's member
   synth.py    seeded synthetic RGB-D pairs (bench + tests)
   build.py    hipcc driver (gfx950 only)
 

@@ -99,6 +99,14 @@ class FusedCloud(C.Structure):           # cvo_fused_cloud: one group's output a
                 ("views", C.c_void_p), ("view_mask", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
 
 
+class FrameCloud(C.Structure):           # cvo_frame_cloud: one frame's dense cloud in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p)]
+
+
+class FuseFrame(C.Structure):            # cvo_fuse_frame: one posed frame of a group (pose: row-major 3 x 4, host memory; cam: index into the call's cameras)
+    _fields_ = [("image", DeviceImage), ("pose", C.c_float * 12), ("cam", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -184,6 +192,8 @@ ABI_SYMBOLS = [
     "cvo_pose_models", "cvo_batch_pose_models", "cvo_batch_result_models",
     "cvo_reducer_create", "cvo_reducer_destroy", "cvo_reducer_info", "cvo_check_reduce_clouds", "cvo_reduce_device_clouds", "cvo_count_voxels",
     "cvo_check_fuse_clouds", "cvo_fuse_device_clouds",
+    "cvo_check_device_frames", "cvo_frames_to_device_clouds", "cvo_reduce_device_frames", "cvo_count_frame_voxels", "cvo_check_fuse_frames",
+    "cvo_fuse_device_frames",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
@@ -192,6 +202,7 @@ REDUCE_MAX_POINTS = 1048575              # CVO_REDUCE_MAX_POINTS
 REDUCE_MAX_VOXELS = 16                   # CVO_REDUCE_MAX_VOXELS
 FUSE_MAX_MEMBERS = 64                    # members of a group: the bits of a view mask
 FUSE_WANT = ("count", "source", "map", "views", "view_mask")
+FRAME_MAX_STEP = 16                      # a frame's sub-grid step: 1 .. 16
 
 _lib = None
 
@@ -404,6 +415,14 @@ def load_library():
     fmp = C.POINTER(FuseMember); fpp = C.POINTER(FuseParams); fcp = C.POINTER(FusedCloud)
     L.cvo_check_fuse_clouds.argtypes = [vp, C.c_int, ip, fmp, fpp, fcp]
     L.cvo_fuse_device_clouds.argtypes = [vp, C.c_int, ip, fmp, fpp, fcp, ip, vp]
+    cap_ = C.POINTER(Camera); frame = [vp, C.c_int, dip, C.c_int, C.c_int, C.c_int, cap_, ip]   # r, count, images, width, height, step, cams, cam_index
+    L.cvo_check_device_frames.argtypes = frame
+    L.cvo_frames_to_device_clouds.argtypes = frame + [C.POINTER(FrameCloud), vp]
+    L.cvo_reduce_device_frames.argtypes = frame + [rpp, rcp, ip, vp]
+    L.cvo_count_frame_voxels.argtypes = frame + [C.c_int, fp, C.c_int, ip, vp]
+    ffp = C.POINTER(FuseFrame)
+    L.cvo_check_fuse_frames.argtypes = [vp, C.c_int, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, fpp, fcp]
+    L.cvo_fuse_device_frames.argtypes = [vp, C.c_int, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, fpp, fcp, ip, vp]
     _lib = L
     return L
 
@@ -798,14 +817,24 @@ class CvoReducer:
         Returns one dict per cloud: xyz (n_out, 3) and feat (n_out, 5) float32, count / source (n_out,) int32, map (n,) int32, n_out.  The
         tensors are views of the arrays the kernel wrote and pass into device_cloud / set_pairs_clouds / advance_clouds / step_clouds as they
         are.  Raises CvoError when a cloud has more than cap rows (then nothing is returned; count_voxels / voxel_for_budget choose a size)."""
-        import torch
+        self._reduce_args(mode, want)
+        arr, n = self._inputs(clouds, cloud_stream)
+        ns = [int(arr[k].n) for k in range(n)]
+        call = lambda prm, recs, n_out: self.L.cvo_reduce_device_clouds(self.h, n, arr, C.byref(prm), recs, n_out, _stream_arg(cloud_stream))
+        return self._run_reduce(call, ns, voxel, mode, min_points, cap, want, cloud_stream, "cloud", "voxel_for_budget", False)
+
+    @staticmethod
+    def _reduce_args(mode, want):
         bad = [w for w in want if w not in ("count", "source", "map")]
         if bad:
             raise ValueError(f"want: 'count', 'source' or 'map' expected, got {bad[0]!r}")
         if mode not in REDUCE_MODES and mode not in REDUCE_MODES.values():
             raise ValueError(f"mode: 'mean' or 'central' expected, got {mode!r}")
-        arr, n = self._inputs(clouds, cloud_stream)
-        ns = [int(arr[k].n) for k in range(n)]
+
+    def _run_reduce(self, call, ns, voxel, mode, min_points, cap, want, cloud_stream, what, helper, count_only):
+        """the output arrays of a reduction of len(ns) clouds of ns points, the call, and the per-cloud dicts.  count_only: cap == 0 counts"""
+        import torch
+        n = len(ns)
         caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in ns]       # (a cap out of range is the library's to refuse)
         rows = [max(0, c) for c in caps]
         dev = torch.device("cuda", self.device)
@@ -828,11 +857,11 @@ class CvoReducer:
             views.append(v); at += rows[k]; pt += ns[k]
         prm = ReduceParams(float(voxel), int(REDUCE_MODES.get(mode, mode)), int(min_points), 0)
         n_out = np.zeros(n, np.int32)
-        _check(self.L.cvo_reduce_device_clouds(self.h, n, arr, C.byref(prm), recs, n_out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
-        over = [k for k in range(n) if n_out[k] > caps[k]]
+        _check(call(prm, recs, n_out.ctypes.data_as(C.POINTER(C.c_int))))
+        over = [k for k in range(n) if n_out[k] > caps[k]] if not (count_only and int(cap) == 0) else []
         if over:
             k = over[0]
-            raise CvoError(CVO_ERR_INVALID, f"cloud {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel (voxel_for_budget)")
+            raise CvoError(CVO_ERR_INVALID, f"{what} {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel ({helper})")
         out = []
         for k, v in enumerate(views):
             m = int(n_out[k])
@@ -851,6 +880,20 @@ class CvoReducer:
 
     def _fuse_inputs(self, groups, poses, min_views, mode, want):
         """what fuse refuses before it touches the library, and its (FuseMember array, group_first, per-group member sizes)"""
+        groups, poses = self._fuse_args(groups, poses, min_views, mode, want)
+        members, first, sizes = [], [0], []
+        for g, (clouds, ps) in enumerate(zip(groups, poses)):
+            ns = []
+            for c, M in zip(clouds, ps):
+                d = c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS)
+                members.append(FuseMember(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist())))
+                ns.append(int(d.n))
+            first.append(len(members)); sizes.append(ns)
+        return (FuseMember * len(members))(*members), np.asarray(first, np.int32), sizes, groups
+
+    @staticmethod
+    def _fuse_args(groups, poses, min_views, mode, want):
+        """the argument checks of a fusion: (groups as lists, poses as float32 arrays)"""
         bad = [w for w in want if w not in FUSE_WANT]
         if bad:
             raise ValueError(f"want: one of {FUSE_WANT} expected, got {bad[0]!r}")
@@ -863,24 +906,22 @@ class CvoReducer:
             raise ValueError("no groups")
         if len(poses) != len(groups):
             raise ValueError(f"{len(groups)} groups but {len(poses)} lists of poses")
-        members, first, sizes = [], [0], []
+        out = []
         for g, (clouds, ps) in enumerate(zip(groups, poses)):
             if not 1 <= len(clouds) <= FUSE_MAX_MEMBERS:
                 raise ValueError(f"group {g}: {len(clouds)} members, 1 .. {FUSE_MAX_MEMBERS} expected")
             if len(ps) != len(clouds):
                 raise ValueError(f"group {g}: {len(clouds)} members but {len(ps)} poses")
-            ns = []
-            for m, (c, pose) in enumerate(zip(clouds, ps)):
+            Ms = []
+            for m, pose in enumerate(ps):
                 M = np.asarray(pose, np.float32)
                 if M.shape not in ((3, 4), (4, 4)):
                     raise ValueError(f"group {g} member {m}: a 3 x 4 or 4 x 4 pose expected, got shape {M.shape}")
                 if not np.isfinite(M[:3]).all():
                     raise ValueError(f"group {g} member {m}: the pose is not finite")
-                d = c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS)
-                members.append(FuseMember(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist())))
-                ns.append(int(d.n))
-            first.append(len(members)); sizes.append(ns)
-        return (FuseMember * len(members))(*members), np.asarray(first, np.int32), sizes, groups
+                Ms.append(M)
+            out.append(Ms)
+        return groups, out
 
     def fuse(self, groups, poses, voxel: float, mode="mean", min_points: int = 1, min_views: int = 1, cap: int = 65535, want=("count",), cloud_stream=None):
         """cvo_fuse_device_clouds: every group of posed clouds fused into one voxel-reduced cloud -- a local map -- by one call.  groups: a list
@@ -891,9 +932,15 @@ class CvoReducer:
         base global indices (numpy int64).  Raises CvoError when a group comes to more than cap rows; cap = 0 counts only: nothing is written,
         n_out is the full row count and the arrays are empty."""
         arr, first, sizes, groups = self._fuse_inputs(groups, poses, min_views, mode, want)
-        import torch
         _settle_cloud_writer([c for g in groups for c in g], cloud_stream)
-        n = len(groups)
+        call = lambda prm, recs, n_out: self.L.cvo_fuse_device_clouds(self.h, len(groups), first.ctypes.data_as(C.POINTER(C.c_int)), arr, C.byref(prm), recs,
+                                                                      n_out, _stream_arg(cloud_stream))
+        return self._run_fuse(call, sizes, voxel, mode, min_points, min_views, cap, want, cloud_stream, "fuse_voxel_for_budget")
+
+    def _run_fuse(self, call, sizes, voxel, mode, min_points, min_views, cap, want, cloud_stream, helper):
+        """the output arrays of a fusion of len(sizes) groups whose members have sizes[g] points, the call, and the per-group dicts"""
+        import torch
+        n = len(sizes)
         ns = [sum(q) for q in sizes]
         caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in ns]       # (a cap out of range is the library's to refuse)
         rows = [max(0, c) for c in caps]
@@ -915,18 +962,110 @@ class CvoReducer:
             views.append(v); at += rows[k]; pt += ns[k]
         prm = FuseParams(float(voxel), int(REDUCE_MODES.get(mode, mode)), int(min_points), int(min_views))
         n_out = np.zeros(n, np.int32)
-        _check(self.L.cvo_fuse_device_clouds(self.h, n, first.ctypes.data_as(C.POINTER(C.c_int)), arr, C.byref(prm), recs,
-                                             n_out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(cloud_stream)))
+        _check(call(prm, recs, n_out.ctypes.data_as(C.POINTER(C.c_int))))
         over = [k for k in range(n) if n_out[k] > caps[k]] if int(cap) != 0 else []      # (cap 0 counts only: n_out is the answer)
         if over:
             k = over[0]
-            raise CvoError(CVO_ERR_INVALID, f"group {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel (fuse_voxel_for_budget)")
+            raise CvoError(CVO_ERR_INVALID, f"group {k}: {int(n_out[k])} rows at voxel {float(voxel):g} are more than cap {int(cap)}: choose a larger voxel ({helper})")
         out = []
         for k, v in enumerate(views):
             m = int(n_out[k])
             offsets = np.concatenate([[0], np.cumsum(sizes[k])[:-1]]).astype(np.int64)
             out.append({key: (t if key == "map" else t[:m]) for key, t in v.items()} | dict(n_out=m, offsets=offsets))
         return out
+
+    # ---- frames read in place (cvo_hip.h, "Reducing frames"): the same calls with RGB-D frames where the clouds were
+    @staticmethod
+    def _frame_list(frames, cameras, cam_index, step, swap_rb):
+        """what the frame calls refuse before they touch the library, and (descriptors [DeviceImage], w, h, step, Camera array, cam index per frame)"""
+        frames = list(frames)
+        if not frames:
+            raise ValueError("no frames")
+        if int(step) != step or not 1 <= int(step) <= FRAME_MAX_STEP:
+            raise ValueError(f"step {step}: an integer in 1 .. {FRAME_MAX_STEP} expected")
+        ims = _device_images(frames, swap_rb)
+        w, h = ims[0][1], ims[0][2]
+        if any((q[1], q[2]) != (w, h) for q in ims):
+            raise ValueError("all frames of one call must have the same size")
+        if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+            cameras = [cameras]
+        cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+        ci = np.zeros(len(ims), np.int32) if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+        if ci.shape[0] != len(ims) or ci.min() < 0 or ci.max() >= len(cameras):
+            raise ValueError("cam_index: one index into cameras per frame")
+        return [q[0] for q in ims], w, h, int(step), cams, ci
+
+    def _frame_inputs(self, frames, cameras, cam_index, step, swap_rb, image_stream):
+        """the leading arguments of a frame call (r, count, images, width, height, step, cams, cam_index), the points per frame, what must stay alive"""
+        descs, w, h, step, cams, ci = self._frame_list(frames, cameras, cam_index, step, swap_rb)
+        _settle_writer(list(frames), image_stream)
+        arr = (DeviceImage * len(descs))(*descs)
+        n = -(-w // step) * -(-h // step)
+        return (self.h, len(descs), arr, w, h, step, cams, ci.ctypes.data_as(C.POINTER(C.c_int))), n, (arr, cams, ci, frames)
+
+    def check_frames(self, frames, cameras, cam_index=None, step: int = 1, swap_rb=False):
+        """cvo_check_device_frames: the validation every frame call runs first, alone (nothing is launched)"""
+        descs, w, h, step, cams, ci = self._frame_list(frames, cameras, cam_index, step, swap_rb)
+        arr = (DeviceImage * len(descs))(*descs)
+        _check(self.L.cvo_check_device_frames(self.h, len(descs), arr, w, h, step, cams, ci.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def dense_frames(self, frames, cameras, cam_index=None, step: int = 1, swap_rb=False, image_stream=None):
+        """cvo_frames_to_device_clouds: the dense cloud of every frame -- one point per pixel of the sub-grid of `step`, n = ceil(w / step) *
+        ceil(h / step), row-major; a pixel without depth is a row of NaN positions.  frames: a list of (bgr, depth) device images of one size,
+        what device_image takes (torch tensors, crops, BGRA); cameras: one (scaling_factor, fx, fy, cx, cy) or a list, with cam_index one index
+        per frame; swap_rb: one flag or one per frame.  Returns one (xyz (n, 3), feat (n, 5)) pair of float32 tensors per frame, which pass
+        into reduce / fuse as they are.  The reduce, count and fuse calls below compute exactly what those do on these clouds, without them."""
+        import torch
+        args, n, keep = self._frame_inputs(frames, cameras, cam_index, step, swap_rb, image_stream)
+        count = args[1]
+        dev = torch.device("cuda", self.device)
+        stream = None
+        if image_stream is not None:
+            stream = image_stream if isinstance(image_stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(image_stream), device=dev)
+        with torch.cuda.stream(stream):
+            xyz = torch.empty((count, n, 3), dtype=torch.float32, device=dev); feat = torch.empty((count, n, 5), dtype=torch.float32, device=dev)
+        dst = (FrameCloud * count)(*[FrameCloud(xyz[k].data_ptr(), feat[k].data_ptr()) for k in range(count)])
+        _check(self.L.cvo_frames_to_device_clouds(*args, dst, _stream_arg(image_stream)))
+        return [(xyz[k], feat[k]) for k in range(count)]
+
+    def reduce_frames(self, frames, cameras, voxel: float, cam_index=None, step: int = 1, mode="mean", min_points: int = 1, cap: int = 65535,
+                      want=("count",), swap_rb=False, image_stream=None):
+        """cvo_reduce_device_frames: `reduce` of the frames' dense clouds (dense_frames), which never exist in memory: each pixel's point is
+        computed where it is needed.  frames, cameras, cam_index, step, swap_rb: dense_frames'; the rest and the result: reduce's, with map one
+        row number per sub-grid pixel and source a sub-grid pixel's index i (pixel ((i % ws) * step, (i // ws) * step)).  cap = 0 counts
+        only."""
+        self._reduce_args(mode, want)
+        args, n, keep = self._frame_inputs(frames, cameras, cam_index, step, swap_rb, image_stream)
+        call = lambda prm, recs, n_out: self.L.cvo_reduce_device_frames(*args, C.byref(prm), recs, n_out, _stream_arg(image_stream))
+        return self._run_reduce(call, [n] * args[1], voxel, mode, min_points, cap, want, image_stream, "frame", "frame_voxel_for_budget", True)
+
+    def count_frame_voxels(self, frames, cameras, voxels, cam_index=None, step: int = 1, min_points: int = 1, swap_rb=False, image_stream=None):
+        """cvo_count_frame_voxels: count_voxels of the frames' dense clouds: (count, k) int32, counts[i, j] what reduce_frames would return as
+        n_out for frame i at voxels[j].  Reads 2 bytes per pixel and size."""
+        vs = np.ascontiguousarray(voxels, np.float32).reshape(-1)
+        args, n, keep = self._frame_inputs(frames, cameras, cam_index, step, swap_rb, image_stream)
+        out = np.zeros((args[1], vs.shape[0]), np.int32)
+        _check(self.L.cvo_count_frame_voxels(*args, int(vs.shape[0]), vs.ctypes.data_as(C.POINTER(C.c_float)), int(min_points),
+                                             out.ctypes.data_as(C.POINTER(C.c_int)), _stream_arg(image_stream)))
+        return out
+
+    def fuse_frames(self, groups, poses, cameras, voxel: float, cam_index=None, step: int = 1, mode="mean", min_points: int = 1, min_views: int = 1,
+                    cap: int = 65535, want=("count",), swap_rb: bool = False, image_stream=None):
+        """cvo_fuse_device_frames: `fuse` of the frames' dense clouds, which never exist in memory.  groups: a list of lists of (bgr, depth)
+        device images, all of one size (a keyframe window per group); poses: fuse's; cameras: one camera or a list, with cam_index a list of
+        lists of indices shaped like groups.  The rest and the result: fuse's (every member has ceil(w / step) * ceil(h / step) points)."""
+        groups, Ms = self._fuse_args(groups, poses, min_views, mode, want)
+        flat = [f for g in groups for f in g]
+        ci = None if cam_index is None else [int(c) for q in cam_index for c in q]
+        descs, w, h, step, cams, ci = self._frame_list(flat, cameras, ci, step, swap_rb)
+        _settle_writer(flat, image_stream)
+        flat_M = [M for q in Ms for M in q]
+        arr = (FuseFrame * len(descs))(*[FuseFrame(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist()), int(c), 0) for d, M, c in zip(descs, flat_M, ci)])
+        first = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+        n = -(-w // step) * -(-h // step)
+        call = lambda prm, recs, n_out: self.L.cvo_fuse_device_frames(self.h, len(groups), first.ctypes.data_as(C.POINTER(C.c_int)), arr, w, h, step, cams,
+                                                                      C.byref(prm), recs, n_out, _stream_arg(image_stream))
+        return self._run_fuse(call, [[n] * len(g) for g in groups], voxel, mode, min_points, min_views, cap, want, image_stream, "a count-only fuse_frames call, cap = 0")
 
 
 # ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms

@@ -98,6 +98,12 @@ hipError_t launch_ingest_clouds(const CloudIngestDesc* descs, int n_clouds, int 
 hipError_t launch_reduce_clouds(const ReduceDesc* descs, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode, int min_points,
                                 hipStream_t s);
 hipError_t launch_count_voxels(const CountDesc* descs, int n_items, int n_max, int slots_max, int min_points, hipStream_t s);
+hipError_t launch_reduce_frames(const ReduceDesc* descs, const FrameDesc* frames, int n_frames, int n, int rows_max, float voxel, int mode, int min_points,
+                                hipStream_t s);
+hipError_t launch_count_frame_voxels(const CountDesc* descs, const FrameDesc* frames, int n_items, int n, int min_points, hipStream_t s);
+hipError_t launch_frames_to_clouds(const FrameDesc* frames, const FrameCloudDst* dst, int n_frames, int n, hipStream_t s);
+hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n, int slots_max,
+                              int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s);
 hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
                               float voxel, int mode, int min_points, int min_views, hipStream_t s);
 int score_nout();
@@ -3688,9 +3694,8 @@ inline size_t count_item_bytes(int n) { return count_item_keys(n) + up16(8 * (si
 constexpr int FUSE_MAX_MEMBERS = 64, FUSE_MAX_CALL_MEMBERS = 4096;
 inline size_t fuse_masks_bytes(int max_points) { return up16(16 * (size_t)max_points); }
 inline size_t fuse_extra_bytes(int max_points) { return fuse_masks_bytes(max_points) + up16(4 * (((size_t)max_points + 255) / 256 + FUSE_MAX_MEMBERS)); }
-inline size_t fuse_table_bytes(int max_clouds) {
-    return (size_t)max_clouds * sizeof(FuseGroupDesc) + std::min<size_t>(FUSE_MAX_CALL_MEMBERS, (size_t)max_clouds * FUSE_MAX_MEMBERS) * sizeof(FuseMemberDesc);
-}
+inline size_t fuse_max_call_members(int max_clouds) { return std::min<size_t>(FUSE_MAX_CALL_MEMBERS, (size_t)max_clouds * FUSE_MAX_MEMBERS); }
+inline size_t fuse_table_bytes(int max_clouds) { return (size_t)max_clouds * sizeof(FuseGroupDesc) + fuse_max_call_members(max_clouds) * sizeof(FuseMemberDesc); }
 void reducer_release(cvo_reducer r) {
     (void)hipSetDevice(r->device);
     if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
@@ -3711,7 +3716,11 @@ int reducer_alloc(cvo_reducer r) {
     const size_t items = (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS;
     r->cloud_bytes = reduce_layout(r->max_points).bytes;
     r->scratch_bytes = std::max((size_t)r->max_clouds * r->cloud_bytes, items * count_item_bytes(r->max_points));
-    const size_t table = std::max({(size_t)r->max_clouds * sizeof(ReduceDesc), items * sizeof(CountDesc), fuse_table_bytes(r->max_clouds)});
+    // the descriptor table of a call: its records, and for frames read in place (FrameDesc) one more record per frame behind them
+    const size_t frames = (size_t)r->max_clouds * sizeof(FrameDesc);
+    const size_t table = std::max({(size_t)r->max_clouds * sizeof(ReduceDesc) + frames, items * sizeof(CountDesc) + frames,
+                                   fuse_table_bytes(r->max_clouds) + fuse_max_call_members(r->max_clouds) * sizeof(FrameDesc),
+                                   frames + (size_t)r->max_clouds * sizeof(FrameCloudDst)});
     HIP_TRY(hipMalloc(&r->scratch, r->scratch_bytes));
     HIP_TRY(hipMalloc(&r->d_desc, table));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_total), items * sizeof(int)));
@@ -3725,8 +3734,9 @@ int reduce_check_in(cvo_reducer r, int count, const cvo_device_cloud* in) {
     if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
     return check_device_clouds(r->device, count, in, r->max_points);   // (n above max_points: "cloud k: n ... is outside 0 .. max_points")
 }
-int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
-    int rc = reduce_check_in(r, count, in); if (rc) return rc;
+// the parameters and the output side of a reduction of `count` clouds; n_of(k): cloud k's points (its map's entries)
+int reduce_check_out(cvo_reducer r, int count, const std::function<int(int)>& n_of, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
+    int rc;
     if (!p || !dst) return fail(CVO_ERR_INVALID, "null argument");
     if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
     if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
@@ -3738,7 +3748,7 @@ int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo
         if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
         if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
         const struct { const void* p; long long bytes; const char* name; } arr[5] = {{d.xyz, 12ll * d.cap, "dst xyz"}, {d.feat, 20ll * d.cap, "dst feat"},
-            {d.count, 4ll * d.cap, "dst count"}, {d.source, 4ll * d.cap, "dst source"}, {d.map, 4ll * in[k].n, "dst map"}};
+            {d.count, 4ll * d.cap, "dst count"}, {d.source, 4ll * d.cap, "dst source"}, {d.map, 4ll * n_of(k), "dst map"}};
         for (const auto& x : arr) {
             if (!x.p || x.bytes == 0) continue;
             if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
@@ -3746,6 +3756,33 @@ int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo
         }
     }
     return CVO_OK;
+}
+int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
+    int rc = reduce_check_in(r, count, in); if (rc) return rc;
+    return reduce_check_out(r, count, [&](int k) { return in[k].n; }, p, dst);
+}
+int count_check_sizes(int k, const float* voxels, int min_points, const int* counts_out) {
+    if (!voxels || !counts_out) return fail(CVO_ERR_INVALID, "null argument");
+    if (k < 1 || k > CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "k " + std::to_string(k) + " is outside 1 .. " + std::to_string(CVO_REDUCE_MAX_VOXELS));
+    for (int j = 0; j < k; ++j)
+        if (!(std::isfinite(voxels[j]) && voxels[j] > 0.f)) return fail(CVO_ERR_INVALID, "voxels[" + std::to_string(j) + "] " + std::to_string(voxels[j]) + " is not a finite size above 0");
+    if (min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(min_points) + " is below 1");
+    return CVO_OK;
+}
+// cloud q's region of the scratch in its record
+void reduce_desc_scratch(cvo_reducer r, const ReduceLayout& L, int q, ReduceDesc& D) {
+    char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
+    D.keys = reinterpret_cast<unsigned long long*>(base + L.keys); D.lowest = reinterpret_cast<unsigned*>(base + L.lowest);
+    D.members = reinterpret_cast<unsigned*>(base + L.members); D.row = reinterpret_cast<int*>(base + L.row);
+    D.slot_of = reinterpret_cast<int*>(base + L.slot_of); D.block_heads = reinterpret_cast<int*>(base + L.block_heads);
+    D.row_slot = reinterpret_cast<int*>(base + L.row_slot); D.sums = reinterpret_cast<long long*>(base + L.sums);
+    D.best = reinterpret_cast<unsigned long long*>(base + L.best);
+    D.total = r->d_total + q;
+}
+void reduce_desc_out(const cvo_reduced_cloud& d, int n, ReduceDesc& D) {
+    D.out_xyz = static_cast<float*>(d.xyz); D.out_feat = static_cast<float*>(d.feat); D.out_count = static_cast<int*>(d.count);
+    D.out_source = static_cast<int*>(d.source); D.out_map = static_cast<int*>(d.map);
+    D.n = n; D.slots = 2 * n; D.cap = d.cap; D.rows_cap = std::min(d.cap, n);
 }
 // The edges of a call: the reducer's stream behind the caller's, the launches (queue), their counts to pinned memory, the caller's stream behind
 // the reducer's, and the call's one host wait.
@@ -3755,7 +3792,7 @@ int reducer_run(cvo_reducer r, size_t table_bytes, int n_totals, void* cloud_str
     HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, table_bytes, hipMemcpyHostToDevice, r->stream));
     const hipError_t e = queue();
     if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("cloud reduce kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * (size_t)n_totals, hipMemcpyDeviceToHost, r->stream));
+    if (n_totals > 0) HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * (size_t)n_totals, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipEventRecord(r->ev_out, r->stream));
     if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
     HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
@@ -3802,19 +3839,11 @@ int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* i
         const cvo_device_cloud& c = in[k];
         if (c.n == 0) continue;
         const int q = (int)of.size(); of.push_back(k);
-        char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
         ReduceDesc& D = h[q];
         D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
         cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
-        D.keys = reinterpret_cast<unsigned long long*>(base + L.keys); D.lowest = reinterpret_cast<unsigned*>(base + L.lowest);
-        D.members = reinterpret_cast<unsigned*>(base + L.members); D.row = reinterpret_cast<int*>(base + L.row);
-        D.slot_of = reinterpret_cast<int*>(base + L.slot_of); D.block_heads = reinterpret_cast<int*>(base + L.block_heads);
-        D.row_slot = reinterpret_cast<int*>(base + L.row_slot); D.sums = reinterpret_cast<long long*>(base + L.sums);
-        D.best = reinterpret_cast<unsigned long long*>(base + L.best);
-        D.out_xyz = static_cast<float*>(dst[k].xyz); D.out_feat = static_cast<float*>(dst[k].feat); D.out_count = static_cast<int*>(dst[k].count);
-        D.out_source = static_cast<int*>(dst[k].source); D.out_map = static_cast<int*>(dst[k].map);
-        D.total = r->d_total + q;
-        D.n = c.n; D.slots = 2 * c.n; D.cap = dst[k].cap; D.rows_cap = std::min(dst[k].cap, c.n);
+        reduce_desc_scratch(r, L, q, D);
+        reduce_desc_out(dst[k], c.n, D);
         n_max = std::max(n_max, c.n); rows_max = std::max(rows_max, D.rows_cap);
     }
     const int live = (int)of.size();
@@ -3828,11 +3857,7 @@ int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* i
 }
 int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k, const float* voxels, int min_points, int* counts_out, void* cloud_stream) {
     int rc = reduce_check_in(r, count, in); if (rc) return rc;
-    if (!voxels || !counts_out) return fail(CVO_ERR_INVALID, "null argument");
-    if (k < 1 || k > CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "k " + std::to_string(k) + " is outside 1 .. " + std::to_string(CVO_REDUCE_MAX_VOXELS));
-    for (int j = 0; j < k; ++j)
-        if (!(std::isfinite(voxels[j]) && voxels[j] > 0.f)) return fail(CVO_ERR_INVALID, "voxels[" + std::to_string(j) + "] " + std::to_string(voxels[j]) + " is not a finite size above 0");
-    if (min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(min_points) + " is below 1");
+    if ((rc = count_check_sizes(k, voxels, min_points, counts_out))) return rc;
     HIP_TRY(hipSetDevice(r->device));
     CountDesc* h = static_cast<CountDesc*>(r->h_desc);
     std::vector<int> of; of.reserve((size_t)count * k);
@@ -3848,7 +3873,7 @@ int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k
             D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
             cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
             D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(c.n));
-            D.total = r->d_total + q; D.n = c.n; D.slots = 2 * c.n; D.voxel = voxels[j]; D.pad_ = 0;
+            D.total = r->d_total + q; D.n = c.n; D.slots = 2 * c.n; D.voxel = voxels[j]; D.src = 0;
         }
         n_max = std::max(n_max, c.n);
     }
@@ -3862,7 +3887,8 @@ int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k
 }
 // ---- fusing clouds (cvo_fuse_kernels.hip): groups of posed clouds through the reducer's machinery, on the reducer's scratch and stream
 namespace {
-int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+// the groups' shape and the filter of a fusion (members: the call's member array, looked at for null only)
+int fuse_check_shape(cvo_reducer r, int groups, const int* group_first, const void* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
     if (!r) return fail(CVO_ERR_INVALID, "null reducer");
     if (groups < 1 || groups > r->max_clouds) return fail(CVO_ERR_INVALID, "groups " + std::to_string(groups) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
     if (!group_first || !members || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
@@ -3873,24 +3899,24 @@ int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse
         if (k < 1 || k > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": " + std::to_string(k) + " members is outside 1 .. 64");
         if (group_first[g + 1] > FUSE_MAX_CALL_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": more than 4096 members in the call");
     }
-    const int total = group_first[groups];
     if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
     if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
     if (p->min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(p->min_points) + " is below 1");
     if (p->min_views < 1 || p->min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "min_views " + std::to_string(p->min_views) + " is outside 1 .. 64");
-    std::vector<cvo_device_cloud> clouds(total); std::vector<std::string> names(total);
-    for (int g = 0; g < groups; ++g)
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
-            clouds[m] = members[m].cloud;
-            names[m] = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
-            for (int k = 0; k < 12; ++k)
-                if (!std::isfinite(members[m].pose[k])) return fail(CVO_ERR_INVALID, names[m] + "pose[" + std::to_string(k) + "] is not finite");
-        }
-    int rc = check_device_clouds(r->device, total, clouds.data(), r->max_points, names.data()); if (rc) return rc;
+    return CVO_OK;
+}
+int fuse_check_pose(const float* pose, const std::string& who) {
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(CVO_ERR_INVALID, who + "pose[" + std::to_string(k) + "] is not finite");
+    return CVO_OK;
+}
+// the groups' sizes and the output side of a fusion; n_of(m): the points of member m of the call
+int fuse_check_out(cvo_reducer r, int groups, const int* group_first, const std::function<long long(int)>& n_of, const cvo_fused_cloud* dst) {
+    int rc;
     for (int g = 0; g < groups; ++g) {
         const std::string who = "group " + std::to_string(g) + ": ";
         long long n = 0;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += members[m].cloud.n;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += n_of(m);
         if (n > r->max_points) return fail(CVO_ERR_INVALID, who + "its members' " + std::to_string(n) + " points are above the reducer's max_points " + std::to_string(r->max_points));
         const cvo_fused_cloud& d = dst[g];
         if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
@@ -3907,6 +3933,41 @@ int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse
     }
     return CVO_OK;
 }
+int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
+    const int total = group_first[groups];
+    std::vector<cvo_device_cloud> clouds(total); std::vector<std::string> names(total);
+    for (int g = 0; g < groups; ++g)
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            clouds[m] = members[m].cloud;
+            names[m] = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
+            if ((rc = fuse_check_pose(members[m].pose, names[m]))) return rc;
+        }
+    if ((rc = check_device_clouds(r->device, total, clouds.data(), r->max_points, names.data()))) return rc;
+    return fuse_check_out(r, groups, group_first, [&](int m) { return (long long)members[m].cloud.n; }, dst);
+}
+// live group q's regions of the scratch and group g's output arrays in its record
+void fuse_group_desc(cvo_reducer r, const ReduceLayout& L, int q, const cvo_fused_cloud& d, int n, FuseGroupDesc& G) {
+    const size_t extra = fuse_extra_bytes(r->max_points), extras_at = (size_t)r->max_clouds * r->cloud_bytes;
+    char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
+    char* more = static_cast<char*>(r->scratch) + extras_at + (size_t)q * extra;
+    G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(more);
+    G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
+    G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
+    G.block_heads = reinterpret_cast<int*>(more + fuse_masks_bytes(r->max_points)); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
+    G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
+    G.out_xyz = static_cast<float*>(d.xyz); G.out_feat = static_cast<float*>(d.feat); G.out_count = static_cast<int*>(d.count);
+    G.out_source = static_cast<int*>(d.source); G.out_map = static_cast<int*>(d.map); G.out_views = static_cast<int*>(d.views);
+    G.out_view_mask = static_cast<unsigned long long*>(d.view_mask);
+    G.total = r->d_total + q;
+    G.n = n; G.slots = 2 * n; G.cap = d.cap; G.rows_cap = std::min(d.cap, n);
+    G.pad_ = 0;
+}
+int fuse_scratch_fits(cvo_reducer r) {
+    if ((size_t)r->max_clouds * (r->cloud_bytes + fuse_extra_bytes(r->max_points)) > r->scratch_bytes)
+        return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for the view masks");   // (never: 136 of 384 bytes per point)
+    return CVO_OK;
+}
 }  // namespace
 int cvo_check_fuse_clouds(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
     return fuse_check(r, groups, group_first, members, p, dst);
@@ -3915,8 +3976,7 @@ int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first, co
                            int* n_out, void* cloud_stream) {
     int rc = fuse_check(r, groups, group_first, members, p, dst); if (rc) return rc;
     if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
-    const size_t extra = fuse_extra_bytes(r->max_points), extras_at = (size_t)r->max_clouds * r->cloud_bytes;
-    if (extras_at + (size_t)r->max_clouds * extra > r->scratch_bytes) return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for the view masks");   // (never: 136 of 384 bytes per point)
+    if ((rc = fuse_scratch_fits(r))) return rc;
     HIP_TRY(hipSetDevice(r->device));
     const ReduceLayout L = reduce_layout(r->max_points);
     int live_groups = 0, live_members = 0;
@@ -3938,20 +3998,9 @@ int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first, co
         for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += members[m].cloud.n;
         if (n == 0) continue;
         const int q = (int)of.size(); of.push_back(g);
-        char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
-        char* more = static_cast<char*>(r->scratch) + extras_at + (size_t)q * extra;
         FuseGroupDesc& G = hg[q];
-        G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(more);
-        G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
-        G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
-        G.block_heads = reinterpret_cast<int*>(more + fuse_masks_bytes(r->max_points)); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
-        G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
-        G.out_xyz = static_cast<float*>(dst[g].xyz); G.out_feat = static_cast<float*>(dst[g].feat); G.out_count = static_cast<int*>(dst[g].count);
-        G.out_source = static_cast<int*>(dst[g].source); G.out_map = static_cast<int*>(dst[g].map); G.out_views = static_cast<int*>(dst[g].views);
-        G.out_view_mask = static_cast<unsigned long long*>(dst[g].view_mask);
-        G.total = r->d_total + q;
-        G.n = n; G.slots = 2 * n; G.cap = dst[g].cap; G.rows_cap = std::min(dst[g].cap, n);
-        G.first_member = qm; G.pad_ = 0;
+        fuse_group_desc(r, L, q, dst[g], n, G);
+        G.first_member = qm;
         int at = 0, blocks = 0;
         for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
             const cvo_device_cloud& c = members[m].cloud;
@@ -3972,6 +4021,186 @@ int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first, co
             return launch_fuse_clouds(dg, live_groups, dm, live_members, n_max, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
         return rc;
     for (int q = 0; q < live_groups; ++q) n_out[of[q]] = r->h_total[q];
+    return CVO_OK;
+}
+// ---- reducing frames (cvo_hip.h, "Reducing frames"): the same launches with the frame as the point source -- a FrameDesc per frame behind the
+// call's records in the descriptor table, the records' cloud fields 0
+namespace {
+inline int frame_sub(int v, int step) { return (v + step - 1) / step; }
+int frames_check_grid(cvo_reducer r, int width, int height, int step) {
+    if (step < 1 || step > 16) return fail(CVO_ERR_INVALID, "step " + std::to_string(step) + " is outside 1 .. 16");
+    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
+    if (n > r->max_points) return fail(CVO_ERR_INVALID, "a frame's " + std::to_string(n) + " points at step " + std::to_string(step) + " are above the reducer's max_points " + std::to_string(r->max_points));
+    return CVO_OK;
+}
+int frames_check_camera(const cvo_camera* cams, int ci, const std::string& who) {
+    if (ci < 0) return fail(CVO_ERR_INVALID, who + "camera index " + std::to_string(ci) + " is out of range");
+    const cvo_camera& c = cams[ci];
+    const struct { float v; const char* name; bool nonzero; } f[5] = {{c.scaling_factor, "scaling_factor", true}, {c.fx, "fx", true}, {c.fy, "fy", true}, {c.cx, "cx", false}, {c.cy, "cy", false}};
+    for (const auto& x : f) {
+        if (!std::isfinite(x.v)) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is not finite");
+        if (x.nonzero && x.v == 0.f) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is 0");
+    }
+    return CVO_OK;
+}
+int frames_check(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    int rc = check_device_images(r->device, count, images, width, height); if (rc) return rc;
+    if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if ((rc = frames_check_grid(r, width, height, step))) return rc;
+    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
+    for (int k = 0; k < count; ++k)
+        if ((rc = frames_check_camera(cams, cam_index ? cam_index[k] : 0, "frame " + std::to_string(k) + ": "))) return rc;
+    return CVO_OK;
+}
+void frame_desc(const cvo_device_image& im, int w, int h, int step, const cvo_camera& c, FrameDesc& F) {
+    F.bgr = static_cast<const uint8_t*>(im.bgr8); F.depth = static_cast<const uint8_t*>(im.depth16);
+    F.bgr_pitch = im.bgr_pitch ? im.bgr_pitch : (long long)w * im.pixel_bytes;
+    F.depth_pitch = im.depth_pitch ? im.depth_pitch : 2ll * w;
+    F.pixel_bytes = im.pixel_bytes; F.swap_rb = im.swap_rb;
+    F.w = w; F.h = h; F.step = step; F.ws = frame_sub(w, step);
+    F.scaling_factor = c.scaling_factor; F.fx = c.fx; F.fy = c.fy; F.cx = c.cx; F.cy = c.cy; F.pad_ = 0;
+}
+int fuse_frames_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                      const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
+    const int total = group_first[groups];
+    std::vector<cvo_device_image> images(total);
+    for (int m = 0; m < total; ++m) images[m] = members[m].image;
+    if ((rc = check_device_images(r->device, total, images.data(), width, height))) return rc;   // ("image m": the member's place in the call)
+    if ((rc = frames_check_grid(r, width, height, step))) return rc;
+    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
+    for (int g = 0; g < groups; ++g)
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            const std::string who = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
+            if ((rc = fuse_check_pose(members[m].pose, who)) || (rc = frames_check_camera(cams, members[m].cam, who))) return rc;
+        }
+    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
+    return fuse_check_out(r, groups, group_first, [&](int) { return n; }, dst);
+}
+}  // namespace
+int cvo_check_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
+    return frames_check(r, count, images, width, height, step, cams, cam_index);
+}
+int cvo_frames_to_device_clouds(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                                const int* cam_index, const cvo_frame_cloud* dst, void* image_stream) {
+    int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
+    if (!dst) return fail(CVO_ERR_INVALID, "null argument: dst");
+    const int n = frame_sub(width, step) * frame_sub(height, step);
+    for (int k = 0; k < count; ++k) {
+        const std::string who = "frame " + std::to_string(k) + ": ";
+        const struct { const void* p; long long bytes; const char* name; } arr[2] = {{dst[k].xyz, 12ll * n, "dst xyz"}, {dst[k].feat, 20ll * n, "dst feat"}};
+        for (const auto& x : arr) {
+            if (!x.p) return fail(CVO_ERR_INVALID, who + x.name + " is null");
+            if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
+            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
+        }
+    }
+    HIP_TRY(hipSetDevice(r->device));
+    FrameDesc* hf = static_cast<FrameDesc*>(r->h_desc);
+    FrameCloudDst* hd = reinterpret_cast<FrameCloudDst*>(hf + count);
+    const FrameDesc* df = static_cast<const FrameDesc*>(r->d_desc);
+    const FrameCloudDst* dd = reinterpret_cast<const FrameCloudDst*>(df + count);
+    for (int k = 0; k < count; ++k) {
+        frame_desc(images[k], width, height, step, cams[cam_index ? cam_index[k] : 0], hf[k]);
+        hd[k].xyz = static_cast<float*>(dst[k].xyz); hd[k].feat = static_cast<float*>(dst[k].feat);
+    }
+    return reducer_run(r, (sizeof(FrameDesc) + sizeof(FrameCloudDst)) * (size_t)count, 0, image_stream, [&] { return launch_frames_to_clouds(df, dd, count, n, r->stream); });
+}
+int cvo_reduce_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                             const int* cam_index, const cvo_reduce_params* p, const cvo_reduced_cloud* dst, int* n_out, void* image_stream) {
+    int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
+    const int n = frame_sub(width, step) * frame_sub(height, step);
+    if ((rc = reduce_check_out(r, count, [&](int) { return n; }, p, dst))) return rc;
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    ReduceDesc* h = static_cast<ReduceDesc*>(r->h_desc);
+    FrameDesc* hf = reinterpret_cast<FrameDesc*>(h + count);
+    const ReduceDesc* d = static_cast<const ReduceDesc*>(r->d_desc);
+    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(d + count);
+    int rows_max = 0;
+    for (int k = 0; k < count; ++k) {
+        ReduceDesc& D = h[k];
+        D.xyz = nullptr; D.feat = nullptr; D.xyz_stride = D.feat_point_stride = D.feat_channel_stride = 0;
+        reduce_desc_scratch(r, L, k, D);
+        reduce_desc_out(dst[k], n, D);
+        frame_desc(images[k], width, height, step, cams[cam_index ? cam_index[k] : 0], hf[k]);
+        rows_max = std::max(rows_max, D.rows_cap);
+    }
+    const cvo_reduce_params P = *p;
+    if ((rc = reducer_run(r, (sizeof(ReduceDesc) + sizeof(FrameDesc)) * (size_t)count, count, image_stream, [&] {
+            return launch_reduce_frames(d, df, count, n, rows_max, P.voxel, P.mode, P.min_points, r->stream); })))
+        return rc;
+    for (int k = 0; k < count; ++k) n_out[k] = r->h_total[k];
+    return CVO_OK;
+}
+int cvo_count_frame_voxels(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                           const int* cam_index, int k, const float* voxels, int min_points, int* counts_out, void* image_stream) {
+    int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
+    if ((rc = count_check_sizes(k, voxels, min_points, counts_out))) return rc;
+    HIP_TRY(hipSetDevice(r->device));
+    const int n = frame_sub(width, step) * frame_sub(height, step), items = count * k;
+    CountDesc* h = static_cast<CountDesc*>(r->h_desc);
+    FrameDesc* hf = reinterpret_cast<FrameDesc*>(h + items);
+    const CountDesc* d = static_cast<const CountDesc*>(r->d_desc);
+    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(d + items);
+    for (int i = 0; i < count; ++i) {
+        frame_desc(images[i], width, height, step, cams[cam_index ? cam_index[i] : 0], hf[i]);
+        for (int j = 0; j < k; ++j) {
+            const int q = i * k + j;
+            char* base = static_cast<char*>(r->scratch) + (size_t)q * count_item_bytes(n);   // (at most max_clouds x 16 items of max_points: inside the scratch)
+            CountDesc& D = h[q];
+            D.xyz = nullptr; D.feat = nullptr; D.xyz_stride = D.feat_point_stride = D.feat_channel_stride = 0;
+            D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(n));
+            D.total = r->d_total + q; D.n = n; D.slots = 2 * n; D.voxel = voxels[j]; D.src = i;
+        }
+    }
+    if ((rc = reducer_run(r, sizeof(CountDesc) * (size_t)items + sizeof(FrameDesc) * (size_t)count, items, image_stream, [&] {
+            return launch_count_frame_voxels(d, df, items, n, min_points, r->stream); })))
+        return rc;
+    for (int q = 0; q < items; ++q) counts_out[q] = r->h_total[q];
+    return CVO_OK;
+}
+int cvo_check_fuse_frames(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                          const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    return fuse_frames_check(r, groups, group_first, members, width, height, step, cams, p, dst);
+}
+int cvo_fuse_device_frames(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                           const cvo_fuse_params* p, const cvo_fused_cloud* dst, int* n_out, void* image_stream) {
+    int rc = fuse_frames_check(r, groups, group_first, members, width, height, step, cams, p, dst); if (rc) return rc;
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    if ((rc = fuse_scratch_fits(r))) return rc;
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    const int n = frame_sub(width, step) * frame_sub(height, step), total = group_first[groups], blocks = (n + 255) / 256;
+    FuseGroupDesc* hg = static_cast<FuseGroupDesc*>(r->h_desc);                // every group and every member is live: a frame has n > 0 points
+    FuseMemberDesc* hm = reinterpret_cast<FuseMemberDesc*>(hg + groups);
+    FrameDesc* hf = reinterpret_cast<FrameDesc*>(hm + total);
+    const FuseGroupDesc* dg = static_cast<const FuseGroupDesc*>(r->d_desc);
+    const FuseMemberDesc* dm = reinterpret_cast<const FuseMemberDesc*>(dg + groups);
+    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(dm + total);
+    int slots_max = 0, rows_max = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int k = group_first[g + 1] - group_first[g];
+        FuseGroupDesc& G = hg[g];
+        fuse_group_desc(r, L, g, dst[g], k * n, G);
+        G.first_member = group_first[g]; G.n_members = k; G.n_blocks = k * blocks;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            const int j = m - group_first[g];
+            FuseMemberDesc& M = hm[m];
+            M.xyz = nullptr; M.feat = nullptr; M.xyz_stride = M.feat_point_stride = M.feat_channel_stride = 0;
+            std::memcpy(M.pose, members[m].pose, sizeof(M.pose));
+            M.group = g; M.base = j * n; M.first_block = j * blocks; M.n = n; M.bit = j; M.pad_ = 0;
+            frame_desc(members[m].image, width, height, step, cams[members[m].cam], hf[m]);
+        }
+        slots_max = std::max(slots_max, G.slots); rows_max = std::max(rows_max, G.rows_cap);
+    }
+    const cvo_fuse_params P = *p;
+    if ((rc = reducer_run(r, sizeof(FuseGroupDesc) * (size_t)groups + (sizeof(FuseMemberDesc) + sizeof(FrameDesc)) * (size_t)total, groups, image_stream, [&] {
+            return launch_fuse_frames(dg, groups, dm, df, total, n, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
+        return rc;
+    for (int g = 0; g < groups; ++g) n_out[g] = r->h_total[g];
     return CVO_OK;
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {

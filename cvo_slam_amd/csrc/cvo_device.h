@@ -271,9 +271,27 @@ struct CountDesc {
     const float* xyz; const float* feat;
     long long xyz_stride, feat_point_stride, feat_channel_stride;
     unsigned long long* keys; unsigned* members; int* total;
-    int n, slots; float voxel; int pad_;
+    int n, slots; float voxel;
+    int src;                       // the item's frame in the launch's frame table (FrameDesc; 0 for a cloud)
 };
 static_assert(sizeof(CountDesc) == 80, "CountDesc layout");
+// one RGB-D frame read in place as a dense cloud (cvo_hip.h, "Reducing frames"; not in the reference): the descriptor of a cvo_device_image with
+// the pitches resolved (never 0), the sub-grid and the camera.  A reduction, a count or a fusion of frames has one per frame in a table beside
+// its ReduceDesc / CountDesc / FuseMemberDesc records, whose xyz, feat and strides stay 0: point i of the frame is pixel
+// ((i % ws) * step, (i / ws) * step), i < ws * ceil(h / step).
+struct FrameDesc {
+    const uint8_t* bgr;      // pixel (x, y) at bgr + y * bgr_pitch + x * pixel_bytes
+    const uint8_t* depth;    // uint16 (x, y) at depth + y * depth_pitch + 2 * x
+    long long bgr_pitch, depth_pitch;
+    int pixel_bytes, swap_rb;
+    int w, h, step, ws;
+    float scaling_factor, fx, fy, cx, cy;
+    int pad_;
+};
+static_assert(sizeof(FrameDesc) == 80, "FrameDesc layout");
+// one frame of cvo_frames_to_device_clouds: where its dense cloud goes (xyz n x 3, feat n x 5, tight rows)
+struct FrameCloudDst { float* xyz; float* feat; };
+static_assert(sizeof(FrameCloudDst) == 16, "FrameCloudDst layout");
 // one group of a fusion (cvo_fuse_kernels.hip; not in the reference), n > 0: ReduceDesc's scratch arrays over the group's global indices, the
 // cells' view masks beside them, and the group's blocks: its members' 256-point blocks one member after the other
 struct FuseGroupDesc {

@@ -22,6 +22,8 @@
 //   gather   map[g]; MEAN adds q = llrint((double)v * 2^24) of the moved position and the features, CENTRAL takes the least (d2 bits, g)
 //   write    a lane per (row, value); views and view_mask beside count and source
 // Integer atomics only (add, min, or, compare-and-swap of a key).
+// insert, gather and write take the point source as a template parameter, as the reducer's passes do (cvo_voxel_table.hpp): a member is a
+// cvo_device_cloud (CloudSource) or an RGB-D frame read in place (FrameSource, member q's frame at frames[q]; cvo_fuse_device_frames).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cvo_device.h"
@@ -33,9 +35,10 @@ namespace {
 __device__ __forceinline__ float move_row(const float* M, int r, float x, float y, float z) {
     return __fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], x), __fadd_rn(__fmul_rn(M[4 * r + 1], y), __fmul_rn(M[4 * r + 2], z))), M[4 * r + 3]);
 }
-// member point i (i < n): its source floats v, and w = (moved position, features)
-__device__ __forceinline__ void load_moved(const FuseMemberDesc& M, int i, float v[8], float w[8]) {
-    load_point(M.xyz, M.feat, M.xyz_stride, M.feat_point_stride, M.feat_channel_stride, i, v);
+// member point i (i < n): its source floats v, and w = (moved position, features); for_cell: what validity and cell need (point_for_cell)
+template <class Src>
+__device__ __forceinline__ void load_moved(const FuseMemberDesc& M, typename Src::Table T, int which, int i, bool for_cell, float v[8], float w[8]) {
+    if (for_cell) point_for_cell<Src>(M, T, which, i, v); else Src::point(M, T, which, i, v);
 #pragma unroll
     for (int r = 0; r < 3; ++r) w[r] = move_row(M.pose, r, v[0], v[1], v[2]);
 #pragma unroll
@@ -55,7 +58,9 @@ __global__ __launch_bounds__(RB) void cvo_fuse_clear_kernel(const FuseGroupDesc*
     if (g < 8ll * G.rows_cap) G.sums[g] = 0;
     if (g < G.rows_cap) G.best[g] = KEY_EMPTY;
 }
-__global__ __launch_bounds__(RB) void cvo_fuse_insert_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, float voxel) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_fuse_insert_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, typename Src::Table T,
+                                                             float voxel) {
     const FuseMemberDesc& M = mem[blockIdx.y];
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63;
     if ((int)blockIdx.x * RB >= M.n) return;                          // (uniform over the block; past that every lane stays for the shuffles)
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(RB) void cvo_fuse_insert_kernel(const FuseGroupDesc
     u64 key = KEY_EMPTY;                                              // (an invalid point, or none: no cell)
     if (i < M.n) {
         float v[8], w[8], c[3];
-        load_moved(M, i, v, w);
+        load_moved<Src>(M, T, blockIdx.y, i, true, v, w);
         const bool src_ok = fabsf(v[0]) < 32768.f && fabsf(v[1]) < 32768.f && fabsf(v[2]) < 32768.f;   // (the features are w's)
         if (!cell_of(w, voxel, c, &key) || !src_ok) key = KEY_EMPTY;
     }
@@ -131,7 +136,9 @@ __global__ __launch_bounds__(RB) void cvo_fuse_rows_kernel(const FuseGroupDesc* 
         if (r < G.rows_cap) G.row_slot[r] = s;
     }
 }
-__global__ __launch_bounds__(RB) void cvo_fuse_gather_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, float voxel, int mode) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_fuse_gather_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, typename Src::Table T,
+                                                             float voxel, int mode) {
     const FuseMemberDesc& M = mem[blockIdx.y];
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63;
     if ((int)blockIdx.x * RB >= M.n) return;                          // (uniform over the block; past that every lane stays for the shuffles)
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(RB) void cvo_fuse_gather_kernel(const FuseGroupDesc
         if (r >= G.rows_cap) r = -1;
     }
     float v[8], w[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (r >= 0) load_moved(M, i, v, w);
+    if (r >= 0) load_moved<Src>(M, T, blockIdx.y, i, false, v, w);
     if (mode == 0) {                                                  // CVO_REDUCE_MEAN: a run of lanes with one row adds its q on chip (integers: any order gives the same sum)
         u64 q[8];
 #pragma unroll
@@ -183,7 +190,9 @@ __global__ __launch_bounds__(RB) void cvo_fuse_gather_kernel(const FuseGroupDesc
         if (r >= 0 && tail) atomicMin(&G.best[r], best);
     }
 }
-__global__ __launch_bounds__(RB) void cvo_fuse_write_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, int mode) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_fuse_write_kernel(const FuseGroupDesc* __restrict__ groups, const FuseMemberDesc* __restrict__ mem, typename Src::Table T,
+                                                            int mode) {
     const FuseGroupDesc& G = groups[blockIdx.y];
     const int g = blockIdx.x * RB + threadIdx.x, r = g >> 3, k = g & 7;
     if (r >= min(*G.total, G.rows_cap)) return;
@@ -200,10 +209,11 @@ __global__ __launch_bounds__(RB) void cvo_fuse_write_kernel(const FuseGroupDesc*
         const FuseMemberDesc& M = mem[m];
         const long long i = (long long)src - M.base;                  // (0 <= i < M.n: a member of the row's cell)
         if (k < 3) {
-            const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(M.xyz) + i * M.xyz_stride);
+            float p[3];
+            Src::position(M, T, m, (int)i, p);
             val = move_row(M.pose, k, p[0], p[1], p[2]);              // the winner's MOVED position: the bits insert and gather saw
         } else {
-            val = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(M.feat) + i * M.feat_point_stride + (k - 3) * M.feat_channel_stride);
+            val = Src::feature(M, T, m, i, k - 3);
         }
     }
     if (k < 3) G.out_xyz[3 * (size_t)r + k] = val; else G.out_feat[5 * (size_t)r + (k - 3)] = val;
@@ -216,20 +226,33 @@ __global__ __launch_bounds__(RB) void cvo_fuse_write_kernel(const FuseGroupDesc*
     }
 }
 
+namespace {
 // groups, mem: the device's copies of the two tables: every group with points, every member with n > 0 (members of a group consecutive, in order).
 // n_max: the largest member n; slots_max, rows_max: the largest slots and rows_cap among the groups.
-hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
-                              float voxel, int mode, int min_points, int min_views, hipStream_t s) {
+template <class Src>
+hipError_t launch_fuse(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, typename Src::Table T, int n_members, int n_max, int slots_max,
+                       int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s) {
     if (n_groups <= 0 || n_members <= 0 || n_max <= 0) return hipSuccess;
     const dim3 blk(RB), pts((n_max + RB - 1) / RB, n_members);
     const long long clear = slots_max > 8ll * rows_max ? slots_max : 8ll * rows_max;
     hipLaunchKernelGGL(cvo_fuse_clear_kernel, dim3((unsigned)((clear + RB - 1) / RB), n_groups), blk, 0, s, groups);
-    hipLaunchKernelGGL(cvo_fuse_insert_kernel, pts, blk, 0, s, groups, mem, voxel);
+    hipLaunchKernelGGL(cvo_fuse_insert_kernel<Src>, pts, blk, 0, s, groups, mem, T, voxel);
     hipLaunchKernelGGL(cvo_fuse_heads_kernel, pts, blk, 0, s, groups, mem, min_points, min_views);
     hipLaunchKernelGGL(cvo_fuse_offsets_kernel, dim3(1, n_groups), blk, 0, s, groups);
     hipLaunchKernelGGL(cvo_fuse_rows_kernel, pts, blk, 0, s, groups, mem, min_points, min_views);
-    hipLaunchKernelGGL(cvo_fuse_gather_kernel, pts, blk, 0, s, groups, mem, voxel, mode);
-    if (rows_max > 0) hipLaunchKernelGGL(cvo_fuse_write_kernel, dim3((8 * rows_max + RB - 1) / RB, n_groups), blk, 0, s, groups, mem, mode);
+    hipLaunchKernelGGL(cvo_fuse_gather_kernel<Src>, pts, blk, 0, s, groups, mem, T, voxel, mode);
+    if (rows_max > 0) hipLaunchKernelGGL(cvo_fuse_write_kernel<Src>, dim3((8 * rows_max + RB - 1) / RB, n_groups), blk, 0, s, groups, mem, T, mode);
     return hipGetLastError();
+}
+}  // namespace
+hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
+                              float voxel, int mode, int min_points, int min_views, hipStream_t s) {
+    return launch_fuse<CloudSource>(groups, n_groups, mem, CloudSource::Table(), n_members, n_max, slots_max, rows_max, voxel, mode, min_points, min_views, s);
+}
+// the same over frames read in place: frames[q] is the frame of mem[q]
+hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n, int slots_max,
+                              int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s) {
+    const FrameSource::Table T = {frames};
+    return launch_fuse<FrameSource>(groups, n_groups, mem, T, n_members, n, slots_max, rows_max, voxel, mode, min_points, min_views, s);
 }
 }  // namespace cvohip

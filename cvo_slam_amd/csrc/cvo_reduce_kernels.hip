@@ -26,6 +26,13 @@
 // cvo_count_voxels runs clear + insert alone over (cloud, voxel size) items, each with a table of its own: with min_points == 1 a cell is
 // counted by the lane whose compare-and-swap claimed its slot, otherwise by the lane whose atomicAdd brought `members` to min_points -- one
 // lane per counted cell either way; a block adds its lanes with __syncthreads_count and does one atomicAdd into the item's total.
+//
+// Point sources.  The passes that read points -- insert, gather, CENTRAL's write, count-insert -- take the source as a template parameter
+// (cvo_voxel_table.hpp): CloudSource reads a cvo_device_cloud's arrays as before; FrameSource computes the point of a sub-grid pixel of an RGB-D
+// frame where it is needed (cvo_hip.h, "Reducing frames"), so a frame is reduced without a dense cloud in memory: insert and count-insert read
+// the pixel's depth alone (2 bytes; a frame's features cannot be invalid), gather recomputes position and features from the pixel and its four
+// flat neighbours (bytes another lane of the block has just read), the write recomputes the winner.  clear, heads, offsets and rows read no
+// point and have one form.  cvo_frames_to_clouds_kernel writes the dense clouds themselves for callers that want them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cvo_device.h"
@@ -49,14 +56,15 @@ __global__ __launch_bounds__(RB) void cvo_reduce_clear_kernel(const ReduceDesc* 
     if (g < 8ll * D.rows_cap) D.sums[g] = 0;
     if (g < D.rows_cap) D.best[g] = KEY_EMPTY;
 }
-__global__ __launch_bounds__(RB) void cvo_reduce_insert_kernel(const ReduceDesc* __restrict__ descs, float voxel) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_reduce_insert_kernel(const ReduceDesc* __restrict__ descs, typename Src::Table T, float voxel) {
     const ReduceDesc& D = descs[blockIdx.y];
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63;
     if ((int)blockIdx.x * RB >= D.n) return;                          // (uniform over the block; past that every lane stays for the shuffles)
     u64 key = KEY_EMPTY;                                              // (an invalid point, or none: no cell)
     if (i < D.n) {
         float v[8], c[3];
-        load_point(D.xyz, D.feat, D.xyz_stride, D.feat_point_stride, D.feat_channel_stride, i, v);
+        point_for_cell<Src>(D, T, blockIdx.y, i, v);
         if (!cell_of(v, voxel, c, &key)) key = KEY_EMPTY;
     }
     int start; bool tail, fresh;
@@ -118,7 +126,8 @@ __global__ __launch_bounds__(RB) void cvo_reduce_rows_kernel(const ReduceDesc* _
         if (r < D.rows_cap) D.row_slot[r] = s;
     }
 }
-__global__ __launch_bounds__(RB) void cvo_reduce_gather_kernel(const ReduceDesc* __restrict__ descs, float voxel, int mode) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_reduce_gather_kernel(const ReduceDesc* __restrict__ descs, typename Src::Table T, float voxel, int mode) {
     const ReduceDesc& D = descs[blockIdx.y];
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63;
     if ((int)blockIdx.x * RB >= D.n) return;                          // (uniform over the block; past that every lane stays for the shuffles)
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(RB) void cvo_reduce_gather_kernel(const ReduceDesc*
         if (r >= D.rows_cap) r = -1;
     }
     float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (r >= 0) load_point(D.xyz, D.feat, D.xyz_stride, D.feat_point_stride, D.feat_channel_stride, i, v);
+    if (r >= 0) Src::point(D, T, blockIdx.y, i, v);
     if (mode == 0) {                                                  // CVO_REDUCE_MEAN: a run of lanes with one row adds its q on chip (integers: any order gives the same sum)
         u64 q[8];
 #pragma unroll
@@ -168,7 +177,8 @@ __global__ __launch_bounds__(RB) void cvo_reduce_gather_kernel(const ReduceDesc*
         if (r >= 0 && tail) atomicMin(&D.best[r], best);
     }
 }
-__global__ __launch_bounds__(RB) void cvo_reduce_write_kernel(const ReduceDesc* __restrict__ descs, int mode) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_reduce_write_kernel(const ReduceDesc* __restrict__ descs, typename Src::Table T, int mode) {
     const ReduceDesc& D = descs[blockIdx.y];
     const int g = blockIdx.x * RB + threadIdx.x, r = g >> 3, k = g & 7;
     if (r >= min(*D.total, D.rows_cap)) return;
@@ -180,8 +190,13 @@ __global__ __launch_bounds__(RB) void cvo_reduce_write_kernel(const ReduceDesc* 
         val = (float)((double)D.sums[g] / ((double)cnt * 16777216.0));
     } else {
         src = (unsigned)(D.best[r] & 0xFFFFFFFFull);
-        val = k < 3 ? *reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.xyz) + (long long)src * D.xyz_stride + 4 * k)
-                    : *reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.feat) + (long long)src * D.feat_point_stride + (k - 3) * D.feat_channel_stride);
+        if (k < 3) {
+            float p[3];
+            Src::position(D, T, blockIdx.y, (int)src, p);
+            val = k == 0 ? p[0] : k == 1 ? p[1] : p[2];
+        } else {
+            val = Src::feature(D, T, blockIdx.y, (long long)src, k - 3);
+        }
     }
     if (k < 3) D.out_xyz[3 * (size_t)r + k] = val; else D.out_feat[5 * (size_t)r + (k - 3)] = val;
     if (k == 0) {
@@ -196,14 +211,15 @@ __global__ __launch_bounds__(RB) void cvo_count_clear_kernel(const CountDesc* __
     if (g < D.slots) { D.keys[g] = KEY_EMPTY; D.members[g] = 0u; }
     if (g == 0) *D.total = 0;
 }
-__global__ __launch_bounds__(RB) void cvo_count_insert_kernel(const CountDesc* __restrict__ descs, int min_points) {
+template <class Src>
+__global__ __launch_bounds__(RB) void cvo_count_insert_kernel(const CountDesc* __restrict__ descs, typename Src::Table T, int min_points) {
     const CountDesc& D = descs[blockIdx.y];
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63;
     if ((int)blockIdx.x * RB >= D.n) return;                          // (uniform over the block)
     u64 key = KEY_EMPTY;
     if (i < D.n) {
         float v[8], c[3];
-        load_point(D.xyz, D.feat, D.xyz_stride, D.feat_point_stride, D.feat_channel_stride, i, v);
+        point_for_cell<Src>(D, T, D.src, i, v);
         if (!cell_of(v, D.voxel, c, &key)) key = KEY_EMPTY;
     }
     int start; bool tail, counted = false;
@@ -221,25 +237,65 @@ __global__ __launch_bounds__(RB) void cvo_count_insert_kernel(const CountDesc* _
     if (threadIdx.x == 0 && k) atomicAdd(D.total, k);
 }
 
+// the dense clouds of frames themselves (cvo_frames_to_device_clouds): a lane per sub-grid pixel writes its point's 8 floats
+__global__ __launch_bounds__(RB) void cvo_frames_to_clouds_kernel(const FrameDesc* __restrict__ frames, const FrameCloudDst* __restrict__ dst, int n) {
+    const int i = blockIdx.x * RB + threadIdx.x;
+    if (i >= n) return;
+    const FrameSource::Table T = {frames};
+    const FrameCloudDst O = dst[blockIdx.y];
+    float v[8];
+    FrameSource::point(O, T, blockIdx.y, i, v);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) O.xyz[3 * (size_t)i + k] = v[k];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) O.feat[5 * (size_t)i + k] = v[3 + k];
+}
+
+namespace {
 // descs: the device's copy of the table, every cloud with n > 0.  n_max, slots_max, rows_max: the largest n, slots and rows_cap among them.
-hipError_t launch_reduce_clouds(const ReduceDesc* descs, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode, int min_points,
-                                hipStream_t s) {
+template <class Src>
+hipError_t launch_reduce(const ReduceDesc* descs, typename Src::Table T, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode,
+                         int min_points, hipStream_t s) {
     if (n_clouds <= 0 || n_max <= 0) return hipSuccess;
     const dim3 blk(RB), pts((n_max + RB - 1) / RB, n_clouds);
     const long long clear = slots_max > 8ll * rows_max ? slots_max : 8ll * rows_max;
     hipLaunchKernelGGL(cvo_reduce_clear_kernel, dim3((unsigned)((clear + RB - 1) / RB), n_clouds), blk, 0, s, descs);
-    hipLaunchKernelGGL(cvo_reduce_insert_kernel, pts, blk, 0, s, descs, voxel);
+    hipLaunchKernelGGL(cvo_reduce_insert_kernel<Src>, pts, blk, 0, s, descs, T, voxel);
     hipLaunchKernelGGL(cvo_reduce_heads_kernel, pts, blk, 0, s, descs, min_points);
     hipLaunchKernelGGL(cvo_reduce_offsets_kernel, dim3(1, n_clouds), blk, 0, s, descs);
     hipLaunchKernelGGL(cvo_reduce_rows_kernel, pts, blk, 0, s, descs, min_points);
-    hipLaunchKernelGGL(cvo_reduce_gather_kernel, pts, blk, 0, s, descs, voxel, mode);
-    if (rows_max > 0) hipLaunchKernelGGL(cvo_reduce_write_kernel, dim3((8 * rows_max + RB - 1) / RB, n_clouds), blk, 0, s, descs, mode);
+    hipLaunchKernelGGL(cvo_reduce_gather_kernel<Src>, pts, blk, 0, s, descs, T, voxel, mode);
+    if (rows_max > 0) hipLaunchKernelGGL(cvo_reduce_write_kernel<Src>, dim3((8 * rows_max + RB - 1) / RB, n_clouds), blk, 0, s, descs, T, mode);
     return hipGetLastError();
 }
-hipError_t launch_count_voxels(const CountDesc* descs, int n_items, int n_max, int slots_max, int min_points, hipStream_t s) {
+template <class Src>
+hipError_t launch_count(const CountDesc* descs, typename Src::Table T, int n_items, int n_max, int slots_max, int min_points, hipStream_t s) {
     if (n_items <= 0 || n_max <= 0) return hipSuccess;
     hipLaunchKernelGGL(cvo_count_clear_kernel, dim3((slots_max + RB - 1) / RB, n_items), dim3(RB), 0, s, descs);
-    hipLaunchKernelGGL(cvo_count_insert_kernel, dim3((n_max + RB - 1) / RB, n_items), dim3(RB), 0, s, descs, min_points);
+    hipLaunchKernelGGL(cvo_count_insert_kernel<Src>, dim3((n_max + RB - 1) / RB, n_items), dim3(RB), 0, s, descs, T, min_points);
+    return hipGetLastError();
+}
+}  // namespace
+hipError_t launch_reduce_clouds(const ReduceDesc* descs, int n_clouds, int n_max, int slots_max, int rows_max, float voxel, int mode, int min_points,
+                                hipStream_t s) {
+    return launch_reduce<CloudSource>(descs, CloudSource::Table(), n_clouds, n_max, slots_max, rows_max, voxel, mode, min_points, s);
+}
+hipError_t launch_count_voxels(const CountDesc* descs, int n_items, int n_max, int slots_max, int min_points, hipStream_t s) {
+    return launch_count<CloudSource>(descs, CloudSource::Table(), n_items, n_max, slots_max, min_points, s);
+}
+// the same over frames read in place: frames[q] is the frame of descs[q] (a reduction) or of descs[q].src (a count)
+hipError_t launch_reduce_frames(const ReduceDesc* descs, const FrameDesc* frames, int n_frames, int n, int rows_max, float voxel, int mode, int min_points,
+                                hipStream_t s) {
+    const FrameSource::Table T = {frames};
+    return launch_reduce<FrameSource>(descs, T, n_frames, n, 2 * n, rows_max, voxel, mode, min_points, s);
+}
+hipError_t launch_count_frame_voxels(const CountDesc* descs, const FrameDesc* frames, int n_items, int n, int min_points, hipStream_t s) {
+    const FrameSource::Table T = {frames};
+    return launch_count<FrameSource>(descs, T, n_items, n, 2 * n, min_points, s);
+}
+hipError_t launch_frames_to_clouds(const FrameDesc* frames, const FrameCloudDst* dst, int n_frames, int n, hipStream_t s) {
+    if (n_frames <= 0 || n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cvo_frames_to_clouds_kernel, dim3((n + RB - 1) / RB, n_frames), dim3(RB), 0, s, frames, dst, n);
     return hipGetLastError();
 }
 }  // namespace cvohip

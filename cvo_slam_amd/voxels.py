@@ -25,6 +25,18 @@ def voxel_for_budget(reducer, cloud, budget: int, lo: float, hi: float, steps: i
     return float(sizes[fits[0]])
 
 
+def frame_voxel_for_budget(reducer, frame, camera, budget: int, lo: float, hi: float, steps: int = 16, step: int = 1, **kw) -> float:
+    """voxel_for_budget for a frame read in place: the smallest size of voxel_ladder(lo, hi, steps) at which the dense cloud of `frame` (one
+    (bgr, depth) device image, under `camera`, on the sub-grid of `step`) has at most `budget` occupied cells, by ONE count_frame_voxels call,
+    which reads the frame's depth alone.  kw: count_frame_voxels' min_points, swap_rb, image_stream.  Raises ValueError when even `hi` leaves more."""
+    sizes = voxel_ladder(lo, hi, steps)
+    counts = np.asarray(reducer.count_frame_voxels([frame], camera, sizes, step=step, **kw)).reshape(-1)
+    fits = np.flatnonzero(counts <= budget)
+    if fits.shape[0] == 0:
+        raise ValueError(f"frame_voxel_for_budget: {int(counts[-1])} cells at the largest size {float(sizes[-1]):g} are more than the budget {budget}")
+    return float(sizes[fits[0]])
+
+
 def fuse_voxel_for_budget(reducer, group, poses, budget: int, lo: float, hi: float, steps: int = 16, **filters) -> float:
     """voxel_for_budget for a fusion: the smallest size of voxel_ladder(lo, hi, steps) at which the group (one list of clouds and one of poses, as
     CvoReducer.fuse takes per group) comes to at most `budget` rows under `filters` (fuse's mode, min_points, min_views, cloud_stream).  Found by

@@ -585,6 +585,64 @@ int cvo_check_fuse_clouds(cvo_reducer r, int groups, const int* group_first /* g
                           const cvo_fuse_params* p, const cvo_fused_cloud* dst);
 int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_member* members,
                            const cvo_fuse_params* p /* one for all */, const cvo_fused_cloud* dst, int* n_out /* groups, host */, void* cloud_stream);
+/* ---- Reducing frames (not in the reference): the reducer and the fuser reading RGB-D frames in place.  A lane takes a pixel and computes that
+ * pixel's point on the fly, by the generator's own float sequence, so no dense cloud exists in memory and a reduced frame carries the numbers a
+ * selected frame carries.  Everything behind the point -- table, rows, means, views -- is the machinery above.
+ *
+ * The dense cloud of a frame.  A frame is a cvo_device_image of width x height (w x h), a cvo_camera and a step in 1 .. 16.  With
+ * ws = ceil(w / step) and hs = ceil(h / step) the cloud has n = ws * hs points; point i is pixel (x, y) = ((i % ws) * step, (i / ws) * step),
+ * row-major over the sub-grid, and p = y * w + x is the pixel's flat index.
+ *   position, all in f32, un-fused, in this order: z = (float)d / scaling_factor with d the uint16 depth; X = ((float)x - cx) * z / fx;
+ *     Y = ((float)y - cy) * z / fy (pcd_generator.cpp:456-499).  d == 0 gives X = Y = Z = quiet NaN (0x7FC00000): the reducer's validity rule
+ *     drops the point, no mask is needed.
+ *   features 0 .. 2: the pixel's B, G, R bytes as floats; swap_rb is resolved as the ingest resolves it, so feature 0 is always B.
+ *   features 3, 4: the generator's level-0 gradients on the FLAT index (pcd_generator.cpp:122-136): with
+ *     I[q] = (float)((B*4899 + G*9617 + R*1868 + 8192) >> 14), for w <= p < w*(h-1): dx = 0.5f*(I[p+1] - I[p-1]), dy = 0.5f*(I[p+w] - I[p-w]);
+ *     elsewhere both are 0.  Rows are not special: at x = 0 the left neighbour is the previous row's last pixel.  For a crop descriptor w, h and
+ *     the neighbours are the crop's.  A step > 1 cloud is a row subset of the step-1 cloud: gradients always come from full-resolution neighbours.
+ *   The kernels read no byte outside the image's rows.
+ * The cloud that cvo_set_pcd_images generates from a frame is a row subset of the frame's step-1 dense cloud (the rows of its selected pixels
+ * with d != 0), bit for bit.
+ *
+ * Reduction, counting and fusion of frames are exactly cvo_reduce_device_clouds, cvo_count_voxels and cvo_fuse_device_clouds applied to the
+ * dense clouds: validity, cells, min_points, row order, MEAN and CENTRAL, cap, n_out, map, views, view_mask, global indices and "count only" are
+ * those calls' rules, word for word.  map has n = ws * hs entries, one per sub-grid pixel.  In a fusion a member is {cvo_device_image, pose[12],
+ * camera index}; all members of a call share width, height and step, their points are moved by the fuser's rule, and a group's points are
+ * members * n <= max_points.  A frame's features are bounded by construction (bytes, and half differences of bytes), so a pixel's validity and
+ * cell depend on its depth alone: the insert and count passes read 2 bytes per pixel; the gather recomputes position and features from the
+ * pixel and its four flat neighbours; CENTRAL's write recomputes the winner.
+ *
+ * All calls work on an existing cvo_reducer and allocate nothing.  image_stream follows cvo_device_image's ordering rule with the reducer's
+ * stream as the library's own: with a stream one event edge in and one out (the outputs are ordered on that stream), with NULL everything is
+ * done when the call returns; the counts cost one host wait.
+ * Validation (cvo_check_device_frames): cvo_check_device_images' rules on the reducer's device, and CVO_ERR_INVALID for step outside 1 .. 16,
+ * count above max_clouds, ws * hs above max_points, a null cams, a cam_index entry that is negative (cam_index NULL: cams[0] for every frame;
+ * cams holds max(cam_index) + 1 cameras), a camera float that is not finite, and scaling_factor, fx or fy equal to 0.  The reduce, count and fuse
+ * calls add the checks of their cloud twins on params and dst (for a fusion: group_first, 1 .. 64 members per group, at most 4096 per call,
+ * members * n <= max_points, finite poses, min_views).  A refused call changes nothing and launches nothing. */
+typedef struct cvo_frame_cloud {        /* caller-owned DEVICE memory: one frame's dense cloud, n = ws * hs rows */
+    void* xyz;      /* n x 3 float32, rows tight */
+    void* feat;     /* n x 5 float32, rows tight: device_cloud's "(n, 5)" layout */
+} cvo_frame_cloud;                      /* 16 bytes */
+typedef struct cvo_fuse_frame { cvo_device_image image; float pose[12]; int cam; int pad_; } cvo_fuse_frame;   /* 96 bytes */
+int cvo_check_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                            const int* cam_index /* NULL: cams[0] for every frame */);
+/* the dense clouds themselves, one launch for all frames: the definition made visible (dst arrays: 4-byte aligned device memory of n x 12 and
+ * n x 20 bytes) */
+int cvo_frames_to_device_clouds(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                                const int* cam_index, const cvo_frame_cloud* dst, void* image_stream);
+int cvo_reduce_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                             const int* cam_index, const cvo_reduce_params* p /* one for all */, const cvo_reduced_cloud* dst /* map: n entries */,
+                             int* n_out /* count, host */, void* image_stream);
+int cvo_count_frame_voxels(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
+                           const int* cam_index, int k, const float* voxels /* k */, int min_points, int* counts_out /* count x k, host */,
+                           void* image_stream);
+/* the validation of cvo_fuse_device_frames alone: launches nothing.  cams holds max(members[].cam) + 1 cameras */
+int cvo_check_fuse_frames(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_frame* members, int width, int height,
+                          int step, const cvo_camera* cams, const cvo_fuse_params* p, const cvo_fused_cloud* dst);
+int cvo_fuse_device_frames(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_frame* members, int width, int height,
+                           int step, const cvo_camera* cams, const cvo_fuse_params* p /* one for all */, const cvo_fused_cloud* dst,
+                           int* n_out /* groups, host */, void* image_stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
