@@ -3666,6 +3666,9 @@ int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* cl
 }
 // ---- reducing clouds (cvo_reduce_kernels.hip): a voxel-grid filter in front of the device-cloud hand-over.  The reducer holds one block of device
 // scratch, cut per call into a region per cloud (a reduction) or per (cloud, voxel size) item (a count); nothing is allocated after creation.
+// Fusing clouds (cvo_fuse_kernels.hip) runs groups of posed clouds through the same machinery, on the reducer's scratch and stream.  Reducing frames
+// (cvo_hip.h, "Reducing frames") is the same launches with the frame as the point source: a FrameDesc per frame behind the call's records in the
+// descriptor table, the records' cloud fields 0.
 struct cvo_reducer_s {
     int device = 0, max_clouds = 0, max_points = 0;
     hipStream_t stream = nullptr;
@@ -3673,7 +3676,9 @@ struct cvo_reducer_s {
     void* scratch = nullptr; size_t scratch_bytes = 0, cloud_bytes = 0;
     void* d_desc = nullptr; int* d_total = nullptr;                   // the launch's descriptor table and its row counts on the device
     void* h_desc = nullptr; int* h_total = nullptr;                   // their pinned twins: written before the launches, read after the call's one wait
+    size_t table_bytes = 0;                                           // the size of d_desc and of h_desc
 };
+extern "C++" {                                                        // (the helpers below have templates among them)
 namespace {
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 // a cloud's region of a reduction, laid out for the reducer's max_points (a call's cloud uses the front of each array)
@@ -3688,9 +3693,9 @@ ReduceLayout reduce_layout(int max_points) {
 }
 inline size_t count_item_keys(int n) { return up16(16 * (size_t)n); }                       // 2 n slots of 8 bytes
 inline size_t count_item_bytes(int n) { return count_item_keys(n) + up16(8 * (size_t)n); }   // and their member counts
-// A fusion (cvo_fuse_kernels.hip): a group takes a cloud's region, and behind the max_clouds regions -- in the part of the 384 bytes per point that a
-// reduction leaves unused -- its view masks (8 bytes per slot) and the heads of its blocks (a block per 256 points of a member: up to 64 more
-// than a cloud of as many points has).  The descriptor table holds the groups' records, then the members'.
+// A fusion: a group takes a cloud's region, and behind the max_clouds regions -- in the part of the 384 bytes per point that a reduction leaves
+// unused -- its view masks (8 bytes per slot) and the heads of its blocks (a block per 256 points of a member: up to 64 more than a cloud of as
+// many points has).  The descriptor table holds the groups' records, then the members'.
 constexpr int FUSE_MAX_MEMBERS = 64, FUSE_MAX_CALL_MEMBERS = 4096;
 inline size_t fuse_masks_bytes(int max_points) { return up16(16 * (size_t)max_points); }
 inline size_t fuse_extra_bytes(int max_points) { return fuse_masks_bytes(max_points) + up16(4 * (((size_t)max_points + 255) / 256 + FUSE_MAX_MEMBERS)); }
@@ -3718,43 +3723,73 @@ int reducer_alloc(cvo_reducer r) {
     r->scratch_bytes = std::max((size_t)r->max_clouds * r->cloud_bytes, items * count_item_bytes(r->max_points));
     // the descriptor table of a call: its records, and for frames read in place (FrameDesc) one more record per frame behind them
     const size_t frames = (size_t)r->max_clouds * sizeof(FrameDesc);
-    const size_t table = std::max({(size_t)r->max_clouds * sizeof(ReduceDesc) + frames, items * sizeof(CountDesc) + frames,
-                                   fuse_table_bytes(r->max_clouds) + fuse_max_call_members(r->max_clouds) * sizeof(FrameDesc),
-                                   frames + (size_t)r->max_clouds * sizeof(FrameCloudDst)});
+    r->table_bytes = std::max({(size_t)r->max_clouds * sizeof(ReduceDesc) + frames, items * sizeof(CountDesc) + frames,
+                               fuse_table_bytes(r->max_clouds) + fuse_max_call_members(r->max_clouds) * sizeof(FrameDesc),
+                               frames + (size_t)r->max_clouds * sizeof(FrameCloudDst)});
     HIP_TRY(hipMalloc(&r->scratch, r->scratch_bytes));
-    HIP_TRY(hipMalloc(&r->d_desc, table));
+    HIP_TRY(hipMalloc(&r->d_desc, r->table_bytes));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_total), items * sizeof(int)));
-    HIP_TRY(hipHostMalloc(&r->h_desc, table, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(&r->h_desc, r->table_bytes, hipHostMallocDefault));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_total), items * sizeof(int), hipHostMallocDefault));
     return CVO_OK;
 }
-// the input side of both entry points: cvo_check_device_clouds' rules with the reducer's limits
+// A call's descriptor table, carved record array by record array: the pinned array to fill and the device's copy of it at the same offset.
+struct DescTable {
+    cvo_reducer r; size_t used = 0;                                   // used: what the call copies to the device (reducer_run)
+    template <class T> int take(size_t count, T** host, const T** dev) {
+        *host = reinterpret_cast<T*>(static_cast<char*>(r->h_desc) + used);
+        *dev = reinterpret_cast<const T*>(static_cast<const char*>(r->d_desc) + used);
+        used += sizeof(T) * count;
+        if (used > r->table_bytes)                                    // (never: reducer_alloc sizes the table for the checked limits of every entry point)
+            return fail(CVO_ERR_INVALID, "the reducer's descriptor table has no room for the call's " + std::to_string(used) + " bytes of records");
+        return CVO_OK;
+    }
+};
+
+// -- what the entry points check
+// the input side of a reduction or a count of clouds: cvo_check_device_clouds' rules with the reducer's limits
 int reduce_check_in(cvo_reducer r, int count, const cvo_device_cloud* in) {
     if (!r) return fail(CVO_ERR_INVALID, "null reducer");
     if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
     return check_device_clouds(r->device, count, in, r->max_points);   // (n above max_points: "cloud k: n ... is outside 0 .. max_points")
 }
+// the filter of a reduction or a fusion
+int check_filter(float voxel, int mode, int min_points) {
+    if (!(std::isfinite(voxel) && voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(voxel) + " is not a finite size above 0");
+    if (mode != CVO_REDUCE_MEAN && mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
+    if (min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(min_points) + " is below 1");
+    return CVO_OK;
+}
+// the caller's arrays of one output (`who`: "cloud 3: "): aligned, and device memory to their last byte.  An array that is not required may be
+// null, and one of no bytes (cap 0) is not looked at.
+struct OutArray { const void* p; long long bytes; unsigned align; const char* name; bool required; };
+int check_out_arrays(int device, const std::string& who, std::initializer_list<OutArray> arrays) {
+    int rc;
+    for (const OutArray& x : arrays) {
+        if (!x.p && x.required) return fail(CVO_ERR_INVALID, who + x.name + " is null");
+        if (!x.p || x.bytes == 0) continue;
+        if (reinterpret_cast<uintptr_t>(x.p) & (x.align - 1u)) return fail(CVO_ERR_INVALID, who + x.name + " is not " + std::to_string(x.align) + "-byte aligned");
+        if ((rc = check_device_plane(device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
+    }
+    return CVO_OK;
+}
+// the output side of a reduction (Dst: cvo_reduced_cloud) or a fusion (cvo_fused_cloud) of n points: the cap and the five arrays both have
+template <class Dst>
+int check_out_rows(int device, const std::string& who, const Dst& d, long long n, std::initializer_list<OutArray> more) {
+    if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+    if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+    if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+    int rc = check_out_arrays(device, who, {{d.xyz, 12ll * d.cap, 4, "dst xyz", false}, {d.feat, 20ll * d.cap, 4, "dst feat", false}, {d.count, 4ll * d.cap, 4, "dst count", false},
+                                            {d.source, 4ll * d.cap, 4, "dst source", false}, {d.map, 4ll * n, 4, "dst map", false}});
+    return rc ? rc : check_out_arrays(device, who, more);
+}
 // the parameters and the output side of a reduction of `count` clouds; n_of(k): cloud k's points (its map's entries)
 int reduce_check_out(cvo_reducer r, int count, const std::function<int(int)>& n_of, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
     int rc;
     if (!p || !dst) return fail(CVO_ERR_INVALID, "null argument");
-    if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
-    if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
-    if (p->min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(p->min_points) + " is below 1");
-    for (int k = 0; k < count; ++k) {
-        const cvo_reduced_cloud& d = dst[k];
-        const std::string who = "cloud " + std::to_string(k) + ": ";
-        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
-        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
-        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
-        const struct { const void* p; long long bytes; const char* name; } arr[5] = {{d.xyz, 12ll * d.cap, "dst xyz"}, {d.feat, 20ll * d.cap, "dst feat"},
-            {d.count, 4ll * d.cap, "dst count"}, {d.source, 4ll * d.cap, "dst source"}, {d.map, 4ll * n_of(k), "dst map"}};
-        for (const auto& x : arr) {
-            if (!x.p || x.bytes == 0) continue;
-            if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
-            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
-        }
-    }
+    if ((rc = check_filter(p->voxel, p->mode, p->min_points))) return rc;
+    for (int k = 0; k < count; ++k)
+        if ((rc = check_out_rows(r->device, "cloud " + std::to_string(k) + ": ", dst[k], n_of(k), {}))) return rc;
     return CVO_OK;
 }
 int reduce_check(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst) {
@@ -3769,19 +3804,150 @@ int count_check_sizes(int k, const float* voxels, int min_points, const int* cou
     if (min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(min_points) + " is below 1");
     return CVO_OK;
 }
-// cloud q's region of the scratch in its record
-void reduce_desc_scratch(cvo_reducer r, const ReduceLayout& L, int q, ReduceDesc& D) {
+// the groups' shape and the filter of a fusion (members: the call's member array, looked at for null only)
+int fuse_check_shape(cvo_reducer r, int groups, const int* group_first, const void* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (groups < 1 || groups > r->max_clouds) return fail(CVO_ERR_INVALID, "groups " + std::to_string(groups) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if (!group_first || !members || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    if (group_first[0] != 0) return fail(CVO_ERR_INVALID, "group_first[0] " + std::to_string(group_first[0]) + " is not 0");
+    for (int g = 0; g < groups; ++g) {
+        const long long k = (long long)group_first[g + 1] - group_first[g];
+        if (k < 0) return fail(CVO_ERR_INVALID, "group_first[" + std::to_string(g + 1) + "] " + std::to_string(group_first[g + 1]) + " is below group_first[" + std::to_string(g) + "]: not ascending");
+        if (k < 1 || k > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": " + std::to_string(k) + " members is outside 1 .. 64");
+        if (group_first[g + 1] > FUSE_MAX_CALL_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": more than 4096 members in the call");
+    }
+    if (int rc = check_filter(p->voxel, p->mode, p->min_points)) return rc;
+    if (p->min_views < 1 || p->min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "min_views " + std::to_string(p->min_views) + " is outside 1 .. 64");
+    return CVO_OK;
+}
+int fuse_check_pose(const float* pose, const std::string& who) {
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(CVO_ERR_INVALID, who + "pose[" + std::to_string(k) + "] is not finite");
+    return CVO_OK;
+}
+// the groups' sizes and the output side of a fusion; n_of(m): the points of member m of the call
+int fuse_check_out(cvo_reducer r, int groups, const int* group_first, const std::function<long long(int)>& n_of, const cvo_fused_cloud* dst) {
+    int rc;
+    for (int g = 0; g < groups; ++g) {
+        const std::string who = "group " + std::to_string(g) + ": ";
+        long long n = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += n_of(m);
+        if (n > r->max_points) return fail(CVO_ERR_INVALID, who + "its members' " + std::to_string(n) + " points are above the reducer's max_points " + std::to_string(r->max_points));
+        const cvo_fused_cloud& d = dst[g];
+        if ((rc = check_out_rows(r->device, who, d, n, {{d.views, 4ll * d.cap, 4, "dst views", false}, {d.view_mask, 8ll * d.cap, 8, "dst view_mask", false}}))) return rc;
+    }
+    return CVO_OK;
+}
+int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
+    const int total = group_first[groups];
+    std::vector<cvo_device_cloud> clouds(total); std::vector<std::string> names(total);
+    for (int g = 0; g < groups; ++g)
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            clouds[m] = members[m].cloud;
+            names[m] = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
+            if ((rc = fuse_check_pose(members[m].pose, names[m]))) return rc;
+        }
+    if ((rc = check_device_clouds(r->device, total, clouds.data(), r->max_points, names.data()))) return rc;
+    return fuse_check_out(r, groups, group_first, [&](int m) { return (long long)members[m].cloud.n; }, dst);
+}
+int fuse_scratch_fits(cvo_reducer r) {
+    if ((size_t)r->max_clouds * (r->cloud_bytes + fuse_extra_bytes(r->max_points)) > r->scratch_bytes)
+        return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for the view masks");   // (never: 136 of 384 bytes per point)
+    return CVO_OK;
+}
+inline int frame_sub(int v, int step) { return (v + step - 1) / step; }
+int frames_check_grid(cvo_reducer r, int width, int height, int step) {
+    if (step < 1 || step > 16) return fail(CVO_ERR_INVALID, "step " + std::to_string(step) + " is outside 1 .. 16");
+    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
+    if (n > r->max_points) return fail(CVO_ERR_INVALID, "a frame's " + std::to_string(n) + " points at step " + std::to_string(step) + " are above the reducer's max_points " + std::to_string(r->max_points));
+    return CVO_OK;
+}
+int frames_check_camera(const cvo_camera* cams, int ci, const std::string& who) {
+    if (ci < 0) return fail(CVO_ERR_INVALID, who + "camera index " + std::to_string(ci) + " is out of range");
+    const cvo_camera& c = cams[ci];
+    const struct { float v; const char* name; bool nonzero; } f[5] = {{c.scaling_factor, "scaling_factor", true}, {c.fx, "fx", true}, {c.fy, "fy", true}, {c.cx, "cx", false}, {c.cy, "cy", false}};
+    for (const auto& x : f) {
+        if (!std::isfinite(x.v)) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is not finite");
+        if (x.nonzero && x.v == 0.f) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is 0");
+    }
+    return CVO_OK;
+}
+int frames_check(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    int rc = check_device_images(r->device, count, images, width, height); if (rc) return rc;
+    if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if ((rc = frames_check_grid(r, width, height, step))) return rc;
+    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
+    for (int k = 0; k < count; ++k)
+        if ((rc = frames_check_camera(cams, cam_index ? cam_index[k] : 0, "frame " + std::to_string(k) + ": "))) return rc;
+    return CVO_OK;
+}
+int fuse_frames_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                      const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
+    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
+    const int total = group_first[groups];
+    std::vector<cvo_device_image> images(total);
+    for (int m = 0; m < total; ++m) images[m] = members[m].image;
+    if ((rc = check_device_images(r->device, total, images.data(), width, height))) return rc;   // ("image m": the member's place in the call)
+    if ((rc = frames_check_grid(r, width, height, step))) return rc;
+    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
+    for (int g = 0; g < groups; ++g)
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            const std::string who = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
+            if ((rc = fuse_check_pose(members[m].pose, who)) || (rc = frames_check_camera(cams, members[m].cam, who))) return rc;
+        }
+    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
+    return fuse_check_out(r, groups, group_first, [&](int) { return n; }, dst);
+}
+
+// -- what the entry points write into their records
+// a record's point source: a cloud's arrays with the strides resolved, or 0 in all five fields -- a frame read in place (its FrameDesc says where)
+template <class Rec>
+void set_cloud_source(Rec& D, const cvo_device_cloud* c) {
+    D.xyz = c ? static_cast<const float*>(c->xyz) : nullptr; D.feat = c ? static_cast<const float*>(c->feat) : nullptr;
+    D.xyz_stride = D.feat_point_stride = D.feat_channel_stride = 0;
+    if (c) cloud_strides(*c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
+}
+void frame_desc(const cvo_device_image& im, int w, int h, int step, const cvo_camera& c, FrameDesc& F) {
+    F.bgr = static_cast<const uint8_t*>(im.bgr8); F.depth = static_cast<const uint8_t*>(im.depth16);
+    F.bgr_pitch = im.bgr_pitch ? im.bgr_pitch : (long long)w * im.pixel_bytes;
+    F.depth_pitch = im.depth_pitch ? im.depth_pitch : 2ll * w;
+    F.pixel_bytes = im.pixel_bytes; F.swap_rb = im.swap_rb;
+    F.w = w; F.h = h; F.step = step; F.ws = frame_sub(w, step);
+    F.scaling_factor = c.scaling_factor; F.fx = c.fx; F.fy = c.fy; F.cx = c.cx; F.cy = c.cy; F.pad_ = 0;
+}
+// Where the points of a call's items come from (a reduction's or a count's clouds, a fusion's members): device clouds, or frames read in place,
+// all of frame_n > 0 points and each with a FrameDesc row behind the records
+struct PointSource {
+    std::function<const cvo_device_cloud*(int)> cloud;                // item k's cloud; unset: the items are frames
+    std::function<void(int, FrameDesc&)> frame;                       // item k's frame row
+    int frame_n = 0;
+    bool frames() const { return !cloud; }
+    int n(int k) const { return cloud ? cloud(k)->n : frame_n; }
+    template <class Rec> void fill(int k, Rec& D, FrameDesc* rows, int at) const {   // rows[at]: the row of D's frame (not looked at with clouds)
+        set_cloud_source(D, cloud ? cloud(k) : nullptr);
+        if (!cloud) frame(k, rows[at]);
+    }
+};
+PointSource frames_source(const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
+    PointSource src;
+    src.frame = [=](int k, FrameDesc& F) { frame_desc(images[k], width, height, step, cams[cam_index ? cam_index[k] : 0], F); };
+    src.frame_n = frame_sub(width, step) * frame_sub(height, step);
+    return src;
+}
+// region q of the scratch and the output arrays of d (a cvo_reduced_cloud or a cvo_fused_cloud, of n points) in record D
+template <class Rec, class Dst>
+void desc_scratch_out(cvo_reducer r, const ReduceLayout& L, int q, const Dst& d, int n, Rec& D) {
     char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
     D.keys = reinterpret_cast<unsigned long long*>(base + L.keys); D.lowest = reinterpret_cast<unsigned*>(base + L.lowest);
     D.members = reinterpret_cast<unsigned*>(base + L.members); D.row = reinterpret_cast<int*>(base + L.row);
     D.slot_of = reinterpret_cast<int*>(base + L.slot_of); D.block_heads = reinterpret_cast<int*>(base + L.block_heads);
     D.row_slot = reinterpret_cast<int*>(base + L.row_slot); D.sums = reinterpret_cast<long long*>(base + L.sums);
     D.best = reinterpret_cast<unsigned long long*>(base + L.best);
-    D.total = r->d_total + q;
-}
-void reduce_desc_out(const cvo_reduced_cloud& d, int n, ReduceDesc& D) {
     D.out_xyz = static_cast<float*>(d.xyz); D.out_feat = static_cast<float*>(d.feat); D.out_count = static_cast<int*>(d.count);
     D.out_source = static_cast<int*>(d.source); D.out_map = static_cast<int*>(d.map);
+    D.total = r->d_total + q;
     D.n = n; D.slots = 2 * n; D.cap = d.cap; D.rows_cap = std::min(d.cap, n);
 }
 // The edges of a call: the reducer's stream behind the caller's, the launches (queue), their counts to pinned memory, the caller's stream behind
@@ -3798,7 +3964,125 @@ int reducer_run(cvo_reducer r, size_t table_bytes, int n_totals, void* cloud_str
     HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
     return CVO_OK;
 }
+
+// -- reduce, count and fuse, each once over a point source: the checked call's items with points (a frame always has some) get records, in order
+int reduce_points(cvo_reducer r, int count, const PointSource& src, const cvo_reduce_params* p, const cvo_reduced_cloud* dst, int* n_out, void* stream) {
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    std::vector<int> of; of.reserve(count);
+    for (int k = 0; k < count; ++k) { n_out[k] = 0; if (src.n(k) > 0) of.push_back(k); }
+    const int live = (int)of.size();
+    if (live == 0) return CVO_OK;
+    DescTable tab{r};
+    ReduceDesc* h; const ReduceDesc* d; FrameDesc* hf = nullptr; const FrameDesc* df = nullptr;
+    int rc = tab.take(live, &h, &d); if (rc) return rc;
+    if (src.frames() && (rc = tab.take(live, &hf, &df))) return rc;
+    int n_max = 0, rows_max = 0;
+    for (int q = 0; q < live; ++q) {
+        const int k = of[q], n = src.n(k);
+        src.fill(k, h[q], hf, q);
+        desc_scratch_out(r, L, q, dst[k], n, h[q]);
+        n_max = std::max(n_max, n); rows_max = std::max(rows_max, h[q].rows_cap);
+    }
+    const cvo_reduce_params P = *p;
+    if ((rc = reducer_run(r, tab.used, live, stream, [&] {
+            return src.frames() ? launch_reduce_frames(d, df, live, n_max, rows_max, P.voxel, P.mode, P.min_points, r->stream)
+                                : launch_reduce_clouds(d, live, n_max, 2 * n_max, rows_max, P.voxel, P.mode, P.min_points, r->stream); })))
+        return rc;
+    for (int q = 0; q < live; ++q) n_out[of[q]] = r->h_total[q];
+    return CVO_OK;
+}
+// item (i, j) is source i at voxels[j]: a table of its own, one after the other in the scratch
+int count_points(cvo_reducer r, int count, const PointSource& src, int k, const float* voxels, int min_points, int* counts_out, void* stream) {
+    HIP_TRY(hipSetDevice(r->device));
+    std::vector<int> of; of.reserve(count);
+    for (int i = 0; i < count; ++i) {
+        for (int j = 0; j < k; ++j) counts_out[i * k + j] = 0;
+        if (src.n(i) > 0) of.push_back(i);
+    }
+    const int sources = (int)of.size(), live = sources * k;
+    if (live == 0) return CVO_OK;
+    DescTable tab{r};
+    CountDesc* h; const CountDesc* d; FrameDesc* hf = nullptr; const FrameDesc* df = nullptr;
+    int rc = tab.take(live, &h, &d); if (rc) return rc;
+    if (src.frames() && (rc = tab.take(sources, &hf, &df))) return rc;
+    size_t at = 0; int n_max = 0;
+    for (int f = 0; f < sources; ++f) {
+        const int i = of[f], n = src.n(i);
+        for (int j = 0; j < k; ++j) {
+            const int q = f * k + j;
+            char* base = static_cast<char*>(r->scratch) + at; at += count_item_bytes(n);   // (at most max_clouds x 16 items of max_points: inside the scratch)
+            CountDesc& D = h[q];
+            src.fill(i, D, hf, f);
+            D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(n));
+            D.total = r->d_total + q; D.n = n; D.slots = 2 * n; D.voxel = voxels[j]; D.src = src.frames() ? f : 0;
+        }
+        n_max = std::max(n_max, n);
+    }
+    if ((rc = reducer_run(r, tab.used, live, stream, [&] {
+            return src.frames() ? launch_count_frame_voxels(d, df, live, n_max, min_points, r->stream)
+                                : launch_count_voxels(d, live, n_max, 2 * n_max, min_points, r->stream); })))
+        return rc;
+    for (int q = 0; q < live; ++q) counts_out[of[q / k] * k + q % k] = r->h_total[q];
+    return CVO_OK;
+}
+// src's item m is member m of the call, pose(m) its 12 floats; a group with points gets a record, and behind the groups' records its members with points
+int fuse_points(cvo_reducer r, int groups, const int* group_first, const PointSource& src, const std::function<const float*(int)>& pose, const cvo_fuse_params* p,
+                const cvo_fused_cloud* dst, int* n_out, void* stream) {
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    int rc = fuse_scratch_fits(r); if (rc) return rc;
+    HIP_TRY(hipSetDevice(r->device));
+    const ReduceLayout L = reduce_layout(r->max_points);
+    std::vector<int> of; of.reserve(groups);
+    int live_members = 0;
+    for (int g = 0; g < groups; ++g) {
+        n_out[g] = 0;
+        const int before = live_members;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) live_members += src.n(m) > 0;
+        if (live_members > before) of.push_back(g);
+    }
+    const int live_groups = (int)of.size();
+    if (live_groups == 0) return CVO_OK;
+    DescTable tab{r};
+    FuseGroupDesc* hg; const FuseGroupDesc* dg; FuseMemberDesc* hm; const FuseMemberDesc* dm; FrameDesc* hf = nullptr; const FrameDesc* df = nullptr;
+    if ((rc = tab.take(live_groups, &hg, &dg)) || (rc = tab.take(live_members, &hm, &dm))) return rc;
+    if (src.frames() && (rc = tab.take(live_members, &hf, &df))) return rc;
+    const size_t extra = fuse_extra_bytes(r->max_points), extras_at = (size_t)r->max_clouds * r->cloud_bytes;
+    int n_max = 0, slots_max = 0, rows_max = 0, qm = 0;
+    for (int q = 0; q < live_groups; ++q) {
+        const int g = of[q];
+        FuseGroupDesc& G = hg[q];
+        G.first_member = qm;
+        int at = 0, blocks = 0;
+        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
+            const int n = src.n(m);
+            if (n == 0) continue;
+            FuseMemberDesc& M = hm[qm];
+            src.fill(m, M, hf, qm);
+            ++qm;
+            std::memcpy(M.pose, pose(m), sizeof(M.pose));
+            M.group = q; M.base = at; M.first_block = blocks; M.n = n; M.bit = m - group_first[g]; M.pad_ = 0;
+            at += n; blocks += (n + 255) / 256;
+            n_max = std::max(n_max, n);
+        }
+        desc_scratch_out(r, L, q, dst[g], at, G);
+        char* more = static_cast<char*>(r->scratch) + extras_at + (size_t)q * extra;   // the group's masks and block heads: behind the regions
+        G.masks = reinterpret_cast<unsigned long long*>(more); G.block_heads = reinterpret_cast<int*>(more + fuse_masks_bytes(r->max_points));
+        G.out_views = static_cast<int*>(dst[g].views); G.out_view_mask = static_cast<unsigned long long*>(dst[g].view_mask);
+        G.n_blocks = blocks; G.n_members = qm - G.first_member; G.pad_ = 0;
+        slots_max = std::max(slots_max, G.slots); rows_max = std::max(rows_max, G.rows_cap);
+    }
+    const cvo_fuse_params P = *p;
+    if ((rc = reducer_run(r, tab.used, live_groups, stream, [&] {
+            return src.frames() ? launch_fuse_frames(dg, live_groups, dm, df, live_members, n_max, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream)
+                                : launch_fuse_clouds(dg, live_groups, dm, live_members, n_max, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
+        return rc;
+    for (int q = 0; q < live_groups; ++q) n_out[of[q]] = r->h_total[q];
+    return CVO_OK;
+}
 }  // namespace
+}  // extern "C++"
 int cvo_reducer_create(int device, int max_clouds, int max_points, cvo_reducer* out) {
     if (!out) return fail(CVO_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -3828,257 +4112,24 @@ int cvo_check_reduce_clouds(cvo_reducer r, int count, const cvo_device_cloud* in
 int cvo_reduce_device_clouds(cvo_reducer r, int count, const cvo_device_cloud* in, const cvo_reduce_params* p, const cvo_reduced_cloud* dst, int* n_out,
                              void* cloud_stream) {
     int rc = reduce_check(r, count, in, p, dst); if (rc) return rc;
-    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
-    HIP_TRY(hipSetDevice(r->device));
-    const ReduceLayout L = reduce_layout(r->max_points);
-    ReduceDesc* h = static_cast<ReduceDesc*>(r->h_desc);
-    std::vector<int> of; of.reserve(count);
-    int n_max = 0, rows_max = 0;
-    for (int k = 0; k < count; ++k) {
-        n_out[k] = 0;
-        const cvo_device_cloud& c = in[k];
-        if (c.n == 0) continue;
-        const int q = (int)of.size(); of.push_back(k);
-        ReduceDesc& D = h[q];
-        D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
-        cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
-        reduce_desc_scratch(r, L, q, D);
-        reduce_desc_out(dst[k], c.n, D);
-        n_max = std::max(n_max, c.n); rows_max = std::max(rows_max, D.rows_cap);
-    }
-    const int live = (int)of.size();
-    if (live == 0) return CVO_OK;
-    const cvo_reduce_params P = *p;
-    if ((rc = reducer_run(r, sizeof(ReduceDesc) * (size_t)live, live, cloud_stream, [&] {
-            return launch_reduce_clouds(static_cast<const ReduceDesc*>(r->d_desc), live, n_max, 2 * n_max, rows_max, P.voxel, P.mode, P.min_points, r->stream); })))
-        return rc;
-    for (int q = 0; q < live; ++q) n_out[of[q]] = r->h_total[q];
-    return CVO_OK;
+    PointSource src; src.cloud = [&](int k) { return &in[k]; };
+    return reduce_points(r, count, src, p, dst, n_out, cloud_stream);
 }
 int cvo_count_voxels(cvo_reducer r, int count, const cvo_device_cloud* in, int k, const float* voxels, int min_points, int* counts_out, void* cloud_stream) {
     int rc = reduce_check_in(r, count, in); if (rc) return rc;
     if ((rc = count_check_sizes(k, voxels, min_points, counts_out))) return rc;
-    HIP_TRY(hipSetDevice(r->device));
-    CountDesc* h = static_cast<CountDesc*>(r->h_desc);
-    std::vector<int> of; of.reserve((size_t)count * k);
-    size_t at = 0; int n_max = 0;
-    for (int i = 0; i < count; ++i) {
-        const cvo_device_cloud& c = in[i];
-        for (int j = 0; j < k; ++j) {
-            counts_out[i * k + j] = 0;
-            if (c.n == 0) continue;
-            const int q = (int)of.size(); of.push_back(i * k + j);
-            char* base = static_cast<char*>(r->scratch) + at; at += count_item_bytes(c.n);   // (at most max_clouds x 16 items of max_points: inside the scratch)
-            CountDesc& D = h[q];
-            D.xyz = static_cast<const float*>(c.xyz); D.feat = static_cast<const float*>(c.feat);
-            cloud_strides(c, &D.xyz_stride, &D.feat_point_stride, &D.feat_channel_stride);
-            D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(c.n));
-            D.total = r->d_total + q; D.n = c.n; D.slots = 2 * c.n; D.voxel = voxels[j]; D.src = 0;
-        }
-        n_max = std::max(n_max, c.n);
-    }
-    const int live = (int)of.size();
-    if (live == 0) return CVO_OK;
-    if ((rc = reducer_run(r, sizeof(CountDesc) * (size_t)live, live, cloud_stream, [&] {
-            return launch_count_voxels(static_cast<const CountDesc*>(r->d_desc), live, n_max, 2 * n_max, min_points, r->stream); })))
-        return rc;
-    for (int q = 0; q < live; ++q) counts_out[of[q]] = r->h_total[q];
-    return CVO_OK;
+    PointSource src; src.cloud = [&](int i) { return &in[i]; };
+    return count_points(r, count, src, k, voxels, min_points, counts_out, cloud_stream);
 }
-// ---- fusing clouds (cvo_fuse_kernels.hip): groups of posed clouds through the reducer's machinery, on the reducer's scratch and stream
-namespace {
-// the groups' shape and the filter of a fusion (members: the call's member array, looked at for null only)
-int fuse_check_shape(cvo_reducer r, int groups, const int* group_first, const void* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
-    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
-    if (groups < 1 || groups > r->max_clouds) return fail(CVO_ERR_INVALID, "groups " + std::to_string(groups) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
-    if (!group_first || !members || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
-    if (group_first[0] != 0) return fail(CVO_ERR_INVALID, "group_first[0] " + std::to_string(group_first[0]) + " is not 0");
-    for (int g = 0; g < groups; ++g) {
-        const long long k = (long long)group_first[g + 1] - group_first[g];
-        if (k < 0) return fail(CVO_ERR_INVALID, "group_first[" + std::to_string(g + 1) + "] " + std::to_string(group_first[g + 1]) + " is below group_first[" + std::to_string(g) + "]: not ascending");
-        if (k < 1 || k > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": " + std::to_string(k) + " members is outside 1 .. 64");
-        if (group_first[g + 1] > FUSE_MAX_CALL_MEMBERS) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + ": more than 4096 members in the call");
-    }
-    if (!(std::isfinite(p->voxel) && p->voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(p->voxel) + " is not a finite size above 0");
-    if (p->mode != CVO_REDUCE_MEAN && p->mode != CVO_REDUCE_CENTRAL) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p->mode) + " is neither CVO_REDUCE_MEAN nor CVO_REDUCE_CENTRAL");
-    if (p->min_points < 1) return fail(CVO_ERR_INVALID, "min_points " + std::to_string(p->min_points) + " is below 1");
-    if (p->min_views < 1 || p->min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, "min_views " + std::to_string(p->min_views) + " is outside 1 .. 64");
-    return CVO_OK;
-}
-int fuse_check_pose(const float* pose, const std::string& who) {
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(pose[k])) return fail(CVO_ERR_INVALID, who + "pose[" + std::to_string(k) + "] is not finite");
-    return CVO_OK;
-}
-// the groups' sizes and the output side of a fusion; n_of(m): the points of member m of the call
-int fuse_check_out(cvo_reducer r, int groups, const int* group_first, const std::function<long long(int)>& n_of, const cvo_fused_cloud* dst) {
-    int rc;
-    for (int g = 0; g < groups; ++g) {
-        const std::string who = "group " + std::to_string(g) + ": ";
-        long long n = 0;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += n_of(m);
-        if (n > r->max_points) return fail(CVO_ERR_INVALID, who + "its members' " + std::to_string(n) + " points are above the reducer's max_points " + std::to_string(r->max_points));
-        const cvo_fused_cloud& d = dst[g];
-        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
-        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
-        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
-        const struct { const void* p; long long bytes; unsigned align; const char* name; } arr[7] = {{d.xyz, 12ll * d.cap, 4, "dst xyz"}, {d.feat, 20ll * d.cap, 4, "dst feat"},
-            {d.count, 4ll * d.cap, 4, "dst count"}, {d.source, 4ll * d.cap, 4, "dst source"}, {d.map, 4ll * n, 4, "dst map"}, {d.views, 4ll * d.cap, 4, "dst views"},
-            {d.view_mask, 8ll * d.cap, 8, "dst view_mask"}};
-        for (const auto& x : arr) {
-            if (!x.p || x.bytes == 0) continue;
-            if (reinterpret_cast<uintptr_t>(x.p) & (x.align - 1u)) return fail(CVO_ERR_INVALID, who + x.name + " is not " + std::to_string(x.align) + "-byte aligned");
-            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
-        }
-    }
-    return CVO_OK;
-}
-int fuse_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
-    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
-    const int total = group_first[groups];
-    std::vector<cvo_device_cloud> clouds(total); std::vector<std::string> names(total);
-    for (int g = 0; g < groups; ++g)
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
-            clouds[m] = members[m].cloud;
-            names[m] = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
-            if ((rc = fuse_check_pose(members[m].pose, names[m]))) return rc;
-        }
-    if ((rc = check_device_clouds(r->device, total, clouds.data(), r->max_points, names.data()))) return rc;
-    return fuse_check_out(r, groups, group_first, [&](int m) { return (long long)members[m].cloud.n; }, dst);
-}
-// live group q's regions of the scratch and group g's output arrays in its record
-void fuse_group_desc(cvo_reducer r, const ReduceLayout& L, int q, const cvo_fused_cloud& d, int n, FuseGroupDesc& G) {
-    const size_t extra = fuse_extra_bytes(r->max_points), extras_at = (size_t)r->max_clouds * r->cloud_bytes;
-    char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
-    char* more = static_cast<char*>(r->scratch) + extras_at + (size_t)q * extra;
-    G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(more);
-    G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
-    G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
-    G.block_heads = reinterpret_cast<int*>(more + fuse_masks_bytes(r->max_points)); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
-    G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
-    G.out_xyz = static_cast<float*>(d.xyz); G.out_feat = static_cast<float*>(d.feat); G.out_count = static_cast<int*>(d.count);
-    G.out_source = static_cast<int*>(d.source); G.out_map = static_cast<int*>(d.map); G.out_views = static_cast<int*>(d.views);
-    G.out_view_mask = static_cast<unsigned long long*>(d.view_mask);
-    G.total = r->d_total + q;
-    G.n = n; G.slots = 2 * n; G.cap = d.cap; G.rows_cap = std::min(d.cap, n);
-    G.pad_ = 0;
-}
-int fuse_scratch_fits(cvo_reducer r) {
-    if ((size_t)r->max_clouds * (r->cloud_bytes + fuse_extra_bytes(r->max_points)) > r->scratch_bytes)
-        return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for the view masks");   // (never: 136 of 384 bytes per point)
-    return CVO_OK;
-}
-}  // namespace
 int cvo_check_fuse_clouds(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
     return fuse_check(r, groups, group_first, members, p, dst);
 }
 int cvo_fuse_device_clouds(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_member* members, const cvo_fuse_params* p, const cvo_fused_cloud* dst,
                            int* n_out, void* cloud_stream) {
     int rc = fuse_check(r, groups, group_first, members, p, dst); if (rc) return rc;
-    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
-    if ((rc = fuse_scratch_fits(r))) return rc;
-    HIP_TRY(hipSetDevice(r->device));
-    const ReduceLayout L = reduce_layout(r->max_points);
-    int live_groups = 0, live_members = 0;
-    for (int g = 0; g < groups; ++g) {
-        int any = 0;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) if (members[m].cloud.n > 0) { ++live_members; any = 1; }
-        live_groups += any;
-    }
-    for (int g = 0; g < groups; ++g) n_out[g] = 0;
-    if (live_groups == 0) return CVO_OK;
-    FuseGroupDesc* hg = static_cast<FuseGroupDesc*>(r->h_desc);
-    FuseMemberDesc* hm = reinterpret_cast<FuseMemberDesc*>(hg + live_groups);
-    const FuseGroupDesc* dg = static_cast<const FuseGroupDesc*>(r->d_desc);
-    const FuseMemberDesc* dm = reinterpret_cast<const FuseMemberDesc*>(dg + live_groups);
-    std::vector<int> of; of.reserve(groups);
-    int n_max = 0, slots_max = 0, rows_max = 0, qm = 0;
-    for (int g = 0; g < groups; ++g) {
-        int n = 0;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) n += members[m].cloud.n;
-        if (n == 0) continue;
-        const int q = (int)of.size(); of.push_back(g);
-        FuseGroupDesc& G = hg[q];
-        fuse_group_desc(r, L, q, dst[g], n, G);
-        G.first_member = qm;
-        int at = 0, blocks = 0;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
-            const cvo_device_cloud& c = members[m].cloud;
-            if (c.n == 0) continue;
-            FuseMemberDesc& M = hm[qm++];
-            M.xyz = static_cast<const float*>(c.xyz); M.feat = static_cast<const float*>(c.feat);
-            cloud_strides(c, &M.xyz_stride, &M.feat_point_stride, &M.feat_channel_stride);
-            std::memcpy(M.pose, members[m].pose, sizeof(M.pose));
-            M.group = q; M.base = at; M.first_block = blocks; M.n = c.n; M.bit = m - group_first[g]; M.pad_ = 0;
-            at += c.n; blocks += (c.n + 255) / 256;
-            n_max = std::max(n_max, c.n);
-        }
-        G.n_blocks = blocks; G.n_members = qm - G.first_member;
-        slots_max = std::max(slots_max, G.slots); rows_max = std::max(rows_max, G.rows_cap);
-    }
-    const cvo_fuse_params P = *p;
-    if ((rc = reducer_run(r, sizeof(FuseGroupDesc) * (size_t)live_groups + sizeof(FuseMemberDesc) * (size_t)live_members, live_groups, cloud_stream, [&] {
-            return launch_fuse_clouds(dg, live_groups, dm, live_members, n_max, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
-        return rc;
-    for (int q = 0; q < live_groups; ++q) n_out[of[q]] = r->h_total[q];
-    return CVO_OK;
+    PointSource src; src.cloud = [&](int m) { return &members[m].cloud; };
+    return fuse_points(r, groups, group_first, src, [&](int m) { return members[m].pose; }, p, dst, n_out, cloud_stream);
 }
-// ---- reducing frames (cvo_hip.h, "Reducing frames"): the same launches with the frame as the point source -- a FrameDesc per frame behind the
-// call's records in the descriptor table, the records' cloud fields 0
-namespace {
-inline int frame_sub(int v, int step) { return (v + step - 1) / step; }
-int frames_check_grid(cvo_reducer r, int width, int height, int step) {
-    if (step < 1 || step > 16) return fail(CVO_ERR_INVALID, "step " + std::to_string(step) + " is outside 1 .. 16");
-    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
-    if (n > r->max_points) return fail(CVO_ERR_INVALID, "a frame's " + std::to_string(n) + " points at step " + std::to_string(step) + " are above the reducer's max_points " + std::to_string(r->max_points));
-    return CVO_OK;
-}
-int frames_check_camera(const cvo_camera* cams, int ci, const std::string& who) {
-    if (ci < 0) return fail(CVO_ERR_INVALID, who + "camera index " + std::to_string(ci) + " is out of range");
-    const cvo_camera& c = cams[ci];
-    const struct { float v; const char* name; bool nonzero; } f[5] = {{c.scaling_factor, "scaling_factor", true}, {c.fx, "fx", true}, {c.fy, "fy", true}, {c.cx, "cx", false}, {c.cy, "cy", false}};
-    for (const auto& x : f) {
-        if (!std::isfinite(x.v)) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is not finite");
-        if (x.nonzero && x.v == 0.f) return fail(CVO_ERR_INVALID, who + "camera " + std::to_string(ci) + ": " + x.name + " is 0");
-    }
-    return CVO_OK;
-}
-int frames_check(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
-    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
-    int rc = check_device_images(r->device, count, images, width, height); if (rc) return rc;
-    if (count > r->max_clouds) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is above the reducer's max_clouds " + std::to_string(r->max_clouds));
-    if ((rc = frames_check_grid(r, width, height, step))) return rc;
-    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
-    for (int k = 0; k < count; ++k)
-        if ((rc = frames_check_camera(cams, cam_index ? cam_index[k] : 0, "frame " + std::to_string(k) + ": "))) return rc;
-    return CVO_OK;
-}
-void frame_desc(const cvo_device_image& im, int w, int h, int step, const cvo_camera& c, FrameDesc& F) {
-    F.bgr = static_cast<const uint8_t*>(im.bgr8); F.depth = static_cast<const uint8_t*>(im.depth16);
-    F.bgr_pitch = im.bgr_pitch ? im.bgr_pitch : (long long)w * im.pixel_bytes;
-    F.depth_pitch = im.depth_pitch ? im.depth_pitch : 2ll * w;
-    F.pixel_bytes = im.pixel_bytes; F.swap_rb = im.swap_rb;
-    F.w = w; F.h = h; F.step = step; F.ws = frame_sub(w, step);
-    F.scaling_factor = c.scaling_factor; F.fx = c.fx; F.fy = c.fy; F.cx = c.cx; F.cy = c.cy; F.pad_ = 0;
-}
-int fuse_frames_check(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
-                      const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
-    int rc = fuse_check_shape(r, groups, group_first, members, p, dst); if (rc) return rc;
-    const int total = group_first[groups];
-    std::vector<cvo_device_image> images(total);
-    for (int m = 0; m < total; ++m) images[m] = members[m].image;
-    if ((rc = check_device_images(r->device, total, images.data(), width, height))) return rc;   // ("image m": the member's place in the call)
-    if ((rc = frames_check_grid(r, width, height, step))) return rc;
-    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
-    for (int g = 0; g < groups; ++g)
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
-            const std::string who = "group " + std::to_string(g) + " member " + std::to_string(m - group_first[g]) + ": ";
-            if ((rc = fuse_check_pose(members[m].pose, who)) || (rc = frames_check_camera(cams, members[m].cam, who))) return rc;
-        }
-    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
-    return fuse_check_out(r, groups, group_first, [&](int) { return n; }, dst);
-}
-}  // namespace
 int cvo_check_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams, const int* cam_index) {
     return frames_check(r, count, images, width, height, step, cams, cam_index);
 }
@@ -4086,81 +4137,32 @@ int cvo_frames_to_device_clouds(cvo_reducer r, int count, const cvo_device_image
                                 const int* cam_index, const cvo_frame_cloud* dst, void* image_stream) {
     int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
     if (!dst) return fail(CVO_ERR_INVALID, "null argument: dst");
-    const int n = frame_sub(width, step) * frame_sub(height, step);
-    for (int k = 0; k < count; ++k) {
-        const std::string who = "frame " + std::to_string(k) + ": ";
-        const struct { const void* p; long long bytes; const char* name; } arr[2] = {{dst[k].xyz, 12ll * n, "dst xyz"}, {dst[k].feat, 20ll * n, "dst feat"}};
-        for (const auto& x : arr) {
-            if (!x.p) return fail(CVO_ERR_INVALID, who + x.name + " is null");
-            if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
-            if ((rc = check_device_plane(r->device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"))) return rc;
-        }
-    }
+    const PointSource src = frames_source(images, width, height, step, cams, cam_index);
+    const int n = src.frame_n;
+    for (int k = 0; k < count; ++k)
+        if ((rc = check_out_arrays(r->device, "frame " + std::to_string(k) + ": ", {{dst[k].xyz, 12ll * n, 4, "dst xyz", true}, {dst[k].feat, 20ll * n, 4, "dst feat", true}}))) return rc;
     HIP_TRY(hipSetDevice(r->device));
-    FrameDesc* hf = static_cast<FrameDesc*>(r->h_desc);
-    FrameCloudDst* hd = reinterpret_cast<FrameCloudDst*>(hf + count);
-    const FrameDesc* df = static_cast<const FrameDesc*>(r->d_desc);
-    const FrameCloudDst* dd = reinterpret_cast<const FrameCloudDst*>(df + count);
+    DescTable tab{r};
+    FrameDesc* hf; const FrameDesc* df; FrameCloudDst* hd; const FrameCloudDst* dd;
+    if ((rc = tab.take(count, &hf, &df)) || (rc = tab.take(count, &hd, &dd))) return rc;
     for (int k = 0; k < count; ++k) {
-        frame_desc(images[k], width, height, step, cams[cam_index ? cam_index[k] : 0], hf[k]);
+        src.frame(k, hf[k]);
         hd[k].xyz = static_cast<float*>(dst[k].xyz); hd[k].feat = static_cast<float*>(dst[k].feat);
     }
-    return reducer_run(r, (sizeof(FrameDesc) + sizeof(FrameCloudDst)) * (size_t)count, 0, image_stream, [&] { return launch_frames_to_clouds(df, dd, count, n, r->stream); });
+    return reducer_run(r, tab.used, 0, image_stream, [&] { return launch_frames_to_clouds(df, dd, count, n, r->stream); });
 }
 int cvo_reduce_device_frames(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
                              const int* cam_index, const cvo_reduce_params* p, const cvo_reduced_cloud* dst, int* n_out, void* image_stream) {
     int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
-    const int n = frame_sub(width, step) * frame_sub(height, step);
-    if ((rc = reduce_check_out(r, count, [&](int) { return n; }, p, dst))) return rc;
-    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
-    HIP_TRY(hipSetDevice(r->device));
-    const ReduceLayout L = reduce_layout(r->max_points);
-    ReduceDesc* h = static_cast<ReduceDesc*>(r->h_desc);
-    FrameDesc* hf = reinterpret_cast<FrameDesc*>(h + count);
-    const ReduceDesc* d = static_cast<const ReduceDesc*>(r->d_desc);
-    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(d + count);
-    int rows_max = 0;
-    for (int k = 0; k < count; ++k) {
-        ReduceDesc& D = h[k];
-        D.xyz = nullptr; D.feat = nullptr; D.xyz_stride = D.feat_point_stride = D.feat_channel_stride = 0;
-        reduce_desc_scratch(r, L, k, D);
-        reduce_desc_out(dst[k], n, D);
-        frame_desc(images[k], width, height, step, cams[cam_index ? cam_index[k] : 0], hf[k]);
-        rows_max = std::max(rows_max, D.rows_cap);
-    }
-    const cvo_reduce_params P = *p;
-    if ((rc = reducer_run(r, (sizeof(ReduceDesc) + sizeof(FrameDesc)) * (size_t)count, count, image_stream, [&] {
-            return launch_reduce_frames(d, df, count, n, rows_max, P.voxel, P.mode, P.min_points, r->stream); })))
-        return rc;
-    for (int k = 0; k < count; ++k) n_out[k] = r->h_total[k];
-    return CVO_OK;
+    const PointSource src = frames_source(images, width, height, step, cams, cam_index);
+    if ((rc = reduce_check_out(r, count, [&](int) { return src.frame_n; }, p, dst))) return rc;
+    return reduce_points(r, count, src, p, dst, n_out, image_stream);
 }
 int cvo_count_frame_voxels(cvo_reducer r, int count, const cvo_device_image* images, int width, int height, int step, const cvo_camera* cams,
                            const int* cam_index, int k, const float* voxels, int min_points, int* counts_out, void* image_stream) {
     int rc = frames_check(r, count, images, width, height, step, cams, cam_index); if (rc) return rc;
     if ((rc = count_check_sizes(k, voxels, min_points, counts_out))) return rc;
-    HIP_TRY(hipSetDevice(r->device));
-    const int n = frame_sub(width, step) * frame_sub(height, step), items = count * k;
-    CountDesc* h = static_cast<CountDesc*>(r->h_desc);
-    FrameDesc* hf = reinterpret_cast<FrameDesc*>(h + items);
-    const CountDesc* d = static_cast<const CountDesc*>(r->d_desc);
-    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(d + items);
-    for (int i = 0; i < count; ++i) {
-        frame_desc(images[i], width, height, step, cams[cam_index ? cam_index[i] : 0], hf[i]);
-        for (int j = 0; j < k; ++j) {
-            const int q = i * k + j;
-            char* base = static_cast<char*>(r->scratch) + (size_t)q * count_item_bytes(n);   // (at most max_clouds x 16 items of max_points: inside the scratch)
-            CountDesc& D = h[q];
-            D.xyz = nullptr; D.feat = nullptr; D.xyz_stride = D.feat_point_stride = D.feat_channel_stride = 0;
-            D.keys = reinterpret_cast<unsigned long long*>(base); D.members = reinterpret_cast<unsigned*>(base + count_item_keys(n));
-            D.total = r->d_total + q; D.n = n; D.slots = 2 * n; D.voxel = voxels[j]; D.src = i;
-        }
-    }
-    if ((rc = reducer_run(r, sizeof(CountDesc) * (size_t)items + sizeof(FrameDesc) * (size_t)count, items, image_stream, [&] {
-            return launch_count_frame_voxels(d, df, items, n, min_points, r->stream); })))
-        return rc;
-    for (int q = 0; q < items; ++q) counts_out[q] = r->h_total[q];
-    return CVO_OK;
+    return count_points(r, count, frames_source(images, width, height, step, cams, cam_index), k, voxels, min_points, counts_out, image_stream);
 }
 int cvo_check_fuse_frames(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
                           const cvo_fuse_params* p, const cvo_fused_cloud* dst) {
@@ -4169,39 +4171,10 @@ int cvo_check_fuse_frames(cvo_reducer r, int groups, const int* group_first, con
 int cvo_fuse_device_frames(cvo_reducer r, int groups, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
                            const cvo_fuse_params* p, const cvo_fused_cloud* dst, int* n_out, void* image_stream) {
     int rc = fuse_frames_check(r, groups, group_first, members, width, height, step, cams, p, dst); if (rc) return rc;
-    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
-    if ((rc = fuse_scratch_fits(r))) return rc;
-    HIP_TRY(hipSetDevice(r->device));
-    const ReduceLayout L = reduce_layout(r->max_points);
-    const int n = frame_sub(width, step) * frame_sub(height, step), total = group_first[groups], blocks = (n + 255) / 256;
-    FuseGroupDesc* hg = static_cast<FuseGroupDesc*>(r->h_desc);                // every group and every member is live: a frame has n > 0 points
-    FuseMemberDesc* hm = reinterpret_cast<FuseMemberDesc*>(hg + groups);
-    FrameDesc* hf = reinterpret_cast<FrameDesc*>(hm + total);
-    const FuseGroupDesc* dg = static_cast<const FuseGroupDesc*>(r->d_desc);
-    const FuseMemberDesc* dm = reinterpret_cast<const FuseMemberDesc*>(dg + groups);
-    const FrameDesc* df = reinterpret_cast<const FrameDesc*>(dm + total);
-    int slots_max = 0, rows_max = 0;
-    for (int g = 0; g < groups; ++g) {
-        const int k = group_first[g + 1] - group_first[g];
-        FuseGroupDesc& G = hg[g];
-        fuse_group_desc(r, L, g, dst[g], k * n, G);
-        G.first_member = group_first[g]; G.n_members = k; G.n_blocks = k * blocks;
-        for (int m = group_first[g]; m < group_first[g + 1]; ++m) {
-            const int j = m - group_first[g];
-            FuseMemberDesc& M = hm[m];
-            M.xyz = nullptr; M.feat = nullptr; M.xyz_stride = M.feat_point_stride = M.feat_channel_stride = 0;
-            std::memcpy(M.pose, members[m].pose, sizeof(M.pose));
-            M.group = g; M.base = j * n; M.first_block = j * blocks; M.n = n; M.bit = j; M.pad_ = 0;
-            frame_desc(members[m].image, width, height, step, cams[members[m].cam], hf[m]);
-        }
-        slots_max = std::max(slots_max, G.slots); rows_max = std::max(rows_max, G.rows_cap);
-    }
-    const cvo_fuse_params P = *p;
-    if ((rc = reducer_run(r, sizeof(FuseGroupDesc) * (size_t)groups + (sizeof(FuseMemberDesc) + sizeof(FrameDesc)) * (size_t)total, groups, image_stream, [&] {
-            return launch_fuse_frames(dg, groups, dm, df, total, n, slots_max, rows_max, P.voxel, P.mode, P.min_points, P.min_views, r->stream); })))
-        return rc;
-    for (int g = 0; g < groups; ++g) n_out[g] = r->h_total[g];
-    return CVO_OK;
+    PointSource src;
+    src.frame = [&](int m, FrameDesc& F) { frame_desc(members[m].image, width, height, step, cams[members[m].cam], F); };
+    src.frame_n = frame_sub(width, step) * frame_sub(height, step);
+    return fuse_points(r, groups, group_first, src, [&](int m) { return members[m].pose; }, p, dst, n_out, image_stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

@@ -1,6 +1,7 @@
 // cvo_voxel_table.hpp -- the device helpers the voxel-grid kernels share (cvo_reduce_kernels.hip, cvo_fuse_kernels.hip): reading a point of a
-// cvo_device_cloud or of a frame read in place (the two point sources), its validity and cell key, the open-addressing table's insert, and the
-// runs of lanes with one cell.  Every one is inlined into its kernel; nothing here has a symbol.
+// cvo_device_cloud or of a frame read in place (the two point sources), its validity and cell key, the open-addressing table's insert, the
+// runs of lanes with one cell, and -- each written once, over the record type -- the seven passes of a reduction and of a fusion.  Every one is
+// inlined into its kernel; nothing here has a symbol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -142,6 +143,169 @@ __device__ __forceinline__ void lane_runs(Id id, int lane, int* start, bool* tai
     const u64 heads = __ballot(lane == 0 || prev != id);
     *start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
     *tail = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0ull;
+}
+
+// ---- The passes of a reduction (cvo_reduce_kernels.hip: a record per cloud) and of a fusion (cvo_fuse_kernels.hip: a record per group of posed
+// members), each written once over the record type Rec -- ReduceDesc or FuseGroupDesc, which name their table, rows and outputs alike.  A kernel
+// finds its record, its point's index g in the record's numbering (a cloud's index; a group's global index, member after member) and its block's
+// number among the record's 256-point blocks, loads the (moved) point, and calls its pass.  In stream order, seven launches:
+//   clear    the table's keys to empty, lowest to all ones, members to 0; the rows' sums to 0 and bests to all ones
+//   insert   a lane per point: validity, key, CAS-insert; atomicMin of g into the slot's `lowest`, atomicAdd into its `members`; the point's slot
+//            (-1: invalid) is kept in slot_of for the later passes
+//   heads    a block counts its heads: points that are their cell's lowest member in a cell that is kept (at least min_points members)
+//   offsets  a block per record turns the blocks' counts into their exclusive sums and writes the record's row count
+//   rows     a head's row is its block's offset + the heads before it in the block: rows ascend with the lowest member's g.  The head writes
+//            the row into its slot (-1 for the lowest member of a dropped cell), and the slot into row_slot[row] for rows below rows_cap
+//   gather   a lane per point again: map[g] = its cell's row; for rows below rows_cap, MEAN adds q = llrint((double)v * 2^24) of its 8 values
+//            into the row's 64-bit sums (|v| < 2^15 and n < 2^20: below 2^59), CENTRAL does a 64-bit atomicMin of (d2 bits << 32) | g
+//   write    a lane per (row, value): MEAN (float)((double)sum / ((double)count * 16777216.0)), CENTRAL the value of the winning member
+// Every value that reaches an output is independent of the order in which points arrive: integer atomicAdd / atomicMin / compare-and-swap of a
+// key only, no float atomics, and the place of a cell in the table never shows.
+// Runs: neighbouring points of a dense cloud mostly share a cell, so in insert and gather a run of consecutive lanes of a wave with one cell acts
+// once -- its first lane inserts and gives its g to `lowest`, its last lane adds the run's length to `members`, the run's q (or its least
+// (d2, g)) are combined with a segmented scan over __shfl_up and its last lane does the atomics.  Integer sums and minima: the same bits as a
+// lane-by-lane form.
+// `slot_too(g)` (clear), `kept_too(s)` (head test) and `row_too(r, s)` (write) are where a caller adds what its record has beside these names.
+
+// clear, lane g of the record's grid
+template <class Rec, class SlotToo>
+__device__ __forceinline__ void clear_pass(const Rec& D, long long g, SlotToo slot_too) {
+    if (g < D.slots) { D.keys[g] = KEY_EMPTY; slot_too(g); D.lowest[g] = 0xFFFFFFFFu; D.members[g] = 0u; }
+    if (g < 8ll * D.rows_cap) D.sums[g] = 0;
+    if (g < D.rows_cap) D.best[g] = KEY_EMPTY;
+}
+// insert: the slot of point g's cell `key` (KEY_EMPTY: an invalid point, or a lane past the points: no cell, -1).  All 64 lanes of the wave take
+// part.  *run_tail: this lane ends a run with a cell -- where a caller does its own once-per-run atomics on the slot.
+template <class Rec>
+__device__ __forceinline__ int insert_pass(const Rec& D, u64 key, unsigned g, int lane, bool* run_tail) {
+    int start; bool tail, fresh;
+    lane_runs(key, lane, &start, &tail);
+    int s = -1;
+    if (key != KEY_EMPTY && lane == start) {                          // a run's first lane holds its lowest index
+        s = (int)table_insert(D.keys, (unsigned)D.slots, key, &fresh);
+        atomicMin(&D.lowest[s], g);
+    }
+    s = __shfl(s, start);
+    *run_tail = key != KEY_EMPTY && tail;
+    if (*run_tail) atomicAdd(&D.members[s], (unsigned)(lane - start + 1));
+    return s;
+}
+// head test: is point g, in slot s (-1: an invalid point, or a lane past the points), the lowest member of a kept cell (1) / of a dropped one
+// (2); 0: neither
+template <class Rec, class KeptToo>
+__device__ __forceinline__ int head_of(const Rec& D, int g, int s, int min_points, KeptToo kept_too) {
+    if (s < 0 || D.lowest[s] != (unsigned)g) return 0;
+    return D.members[s] >= (unsigned)min_points && kept_too(s) ? 1 : 2;
+}
+// offsets, one block per record with nb blocks of points: thread t owns `per` consecutive blocks' counts; their sums are scanned through LDS
+template <class Rec>
+__device__ __forceinline__ void offsets_pass(const Rec& D, int nb) {
+    __shared__ int part[RB];
+    const int per = (nb + RB - 1) / RB, t = threadIdx.x;
+    const int from = min(nb, t * per), to = min(nb, from + per);
+    int sum = 0;
+    for (int j = from; j < to; ++j) sum += D.block_heads[j];
+    part[t] = sum;
+    __syncthreads();
+    for (int d = 1; d < RB; d <<= 1) {
+        const int add = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    int at = part[t] - sum;
+    for (int j = from; j < to; ++j) { const int k = D.block_heads[j]; D.block_heads[j] = at; at += k; }
+    if (t == RB - 1) *D.total = part[t];
+}
+// rows, every lane of the record's block number `block`: `what` and s are the lane's head_of
+template <class Rec>
+__device__ __forceinline__ void rows_pass(const Rec& D, int block, int what, int s) {
+    __shared__ int wave_heads[RB / 64];
+    const bool head = what == 1, dropped = what == 2;
+    const u64 b = __ballot(head);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) wave_heads[w] = __popcll(b);
+    __syncthreads();
+    if (dropped) D.row[s] = -1;
+    if (head) {
+        int r = D.block_heads[block] + __popcll(b & ((1ull << lane) - 1ull));
+        for (int q = 0; q < w; ++q) r += wave_heads[q];
+        D.row[s] = r;
+        if (r < D.rows_cap) D.row_slot[r] = s;
+    }
+}
+// row-of-point: map[g], and the point's row if it is one that is written (-1: none)
+template <class Rec>
+__device__ __forceinline__ int row_of_point(const Rec& D, bool in, int g) {
+    int r = -1;
+    if (in) {
+        const int s = D.slot_of[g];
+        r = s >= 0 ? D.row[s] : -1;
+        if (D.out_map) D.out_map[g] = r;
+        if (r >= D.rows_cap) r = -1;
+    }
+    return r;
+}
+// gather: point g with row r (row_of_point) and the 8 values v that count for it (zeros with r < 0).  All 64 lanes of the wave take part.
+template <class Rec>
+__device__ __forceinline__ void gather_pass(const Rec& D, int r, const float v[8], unsigned g, int lane, float voxel, int mode) {
+    int start; bool tail;
+    lane_runs(r, lane, &start, &tail);
+    if (mode == 0) {                                                  // CVO_REDUCE_MEAN: a run of lanes with one row adds its q on chip (integers: any order gives the same sum)
+        u64 q[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) q[k] = (u64)__double2ll_rn((double)v[k] * 16777216.0);   // (two's complement: the signed sum)
+        for (int d = 1; d < 64; d <<= 1) {                            // segmented inclusive scan: a run's last lane ends with the run's sums
+            const bool take = lane - d >= start;
+            if (__ballot(take) == 0ull) break;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const u64 up = __shfl_up(q[k], d); if (take) q[k] += up; }
+        }
+        if (r >= 0 && tail) {
+            u64* sums = reinterpret_cast<u64*>(D.sums) + 8 * (size_t)r;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) atomicAdd(&sums[k], q[k]);
+        }
+    } else {                                                          // CVO_REDUCE_CENTRAL: a run's least (d2 bits, g) the same way
+        float d2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float c = floorf(__fdiv_rn(v[k], voxel));
+            const float d = __fsub_rn(v[k], __fmul_rn(__fadd_rn(c, 0.5f), voxel));
+            d2 = k == 0 ? __fmul_rn(d, d) : __fadd_rn(d2, __fmul_rn(d, d));
+        }
+        u64 best = r >= 0 ? ((u64)__float_as_uint(d2) << 32) | (u64)g : KEY_EMPTY;
+        for (int d = 1; d < 64; d <<= 1) {
+            const bool take = lane - d >= start;
+            if (__ballot(take) == 0ull) break;
+            const u64 up = __shfl_up(best, d);
+            if (take && up < best) best = up;
+        }
+        if (r >= 0 && tail) atomicMin(&D.best[r], best);
+    }
+}
+// write, lane g of the record's grid: value k = g & 7 of row g >> 3.  winner(src, k): value k of member src, CENTRAL's winner -- the caller's,
+// which knows where its points are and whether they move
+template <class Rec, class Winner, class RowToo>
+__device__ __forceinline__ void write_pass(const Rec& D, int g, int mode, Winner winner, RowToo row_too) {
+    const int r = g >> 3, k = g & 7;
+    if (r >= min(*D.total, D.rows_cap)) return;
+    const int s = D.row_slot[r];
+    const unsigned cnt = D.members[s];
+    unsigned src; float val;
+    if (mode == 0) {
+        src = D.lowest[s];
+        val = (float)((double)D.sums[g] / ((double)cnt * 16777216.0));
+    } else {
+        src = (unsigned)(D.best[r] & 0xFFFFFFFFull);
+        val = winner(src, k);
+    }
+    if (k < 3) D.out_xyz[3 * (size_t)r + k] = val; else D.out_feat[5 * (size_t)r + (k - 3)] = val;
+    if (k == 0) {
+        if (D.out_count) D.out_count[r] = (int)cnt;
+        if (D.out_source) D.out_source[r] = (int)src;
+        row_too(r, s);
+    }
 }
 }  // namespace
 }  // namespace cvohip

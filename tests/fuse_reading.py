@@ -85,6 +85,19 @@ def surface(rng, n, noise=0.0):
     return np.ascontiguousarray(x, np.float32), rng.uniform(0, 255, (n, 5)).astype(np.float32)
 
 
+LONE_SIZES = (1, 63, 64, 65, 255, 256, 257, 3000)
+
+
+def lone_clouds():
+    """a cloud of each of LONE_SIZES points -- one point, wave edges, block edges, many blocks -- on the noisy sheet: each fused alone under the
+    identity pose is its own reduction.  No coordinate is -0.0, which 1 * x + (0 * y + 0 * z) + 0 would turn into +0.0"""
+    rng = np.random.default_rng(21)
+    clouds = [surface(rng, n, 0.01) for n in LONE_SIZES]
+    for x, f in clouds:
+        assert not (np.signbit(x) & (x == 0)).any()
+    return clouds
+
+
 def windows(rng, members=4, n=4000, noise=0.004):
     """the same sheet seen `members` times: an overlapping window of it each, with noise, given in a camera frame of its own -- so that under the
     poses cells with one view and cells with several both exist.  ([(xyz, feat)], [4 x 4 pose])"""

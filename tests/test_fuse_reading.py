@@ -28,6 +28,21 @@ def test_one_member_under_the_identity_is_the_reduction(mode):
 
 
 @pytest.mark.parametrize("mode", ["mean", "central"])
+def test_lone_clouds_under_the_identity_are_their_reductions(mode):
+    """what tests/test_gpu_fuse_clouds.py asks of the two kernel families -- a group of one member under the identity gives the reduction's
+    bytes -- holds between the two readings, on the same clouds"""
+    for x, f in fr.lone_clouds():
+        assert not (np.signbit(x) & (x == 0)).any()
+        got = fr.fuse_reading([(x, f)], [np.eye(4, dtype=np.float32)], 0.05, mode)
+        want = vr.reduce_reading(x, f, 0.05, mode, 1)
+        assert got["n_out"] == want["n_out"] >= 1
+        for key in KEYS:
+            assert got[key].dtype == want[key].dtype and got[key].tobytes() == want[key].tobytes(), (x.shape[0], key)
+        assert (got["views"] == 1).all() and (got["view_mask"] == 1).all()
+    assert want["n_out"] > 100 and (want["count"] > 1).any()          # (the 3000-point cloud: many rows, and cells with several members)
+
+
+@pytest.mark.parametrize("mode", ["mean", "central"])
 def test_fusing_is_reducing_the_concatenation_of_the_moved_members(mode):
     rng = np.random.default_rng(2)
     members = [surface(rng, n, 0.01) for n in (700, 0, 1300, 257, 900)]

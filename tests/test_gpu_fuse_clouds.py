@@ -401,7 +401,31 @@ def test_reduce_fuse_reduce_on_one_reducer(hiplib, torch, reducer, seen_four_tim
     assert reducer.scratch_bytes() == before
 
 
-# ---- 10. end to end
+# ---- 10. the two kernel families share their passes
+@pytest.mark.parametrize("mode", ["mean", "central"])
+def test_one_member_under_the_identity_is_the_reduction(hiplib, torch, reducer, mode):
+    """groups of one member under the identity pose, one fusion for all of them, against one reduction of the same clouds: the same bytes
+    (tests/test_fuse_reading.py holds the two readings to the same on these clouds)"""
+    clouds = fr.lone_clouds()
+    assert tuple(x.shape[0] for x, f in clouds) == (1, 63, 64, 65, 255, 256, 257, 3000)
+    for x, f in clouds:
+        assert not (np.signbit(x) & (x == 0)).any()                    # an identity move would make a -0.0 a +0.0
+    tens = dev(torch, clouds)
+    fused = [{k: (host(v).copy() if hasattr(v, "cpu") else v) for k, v in g.items()}
+             for g in reducer.fuse([[t] for t in tens], [[EYE]] * len(tens), 0.05, mode, want=WANT)]
+    reduced = reducer.reduce(tens, 0.05, mode, 1, want=("count", "source", "map"))
+    assert len(fused) == len(reduced) == len(clouds)
+    for (x, f), a, b in zip(clouds, fused, reduced):
+        n = x.shape[0]
+        assert a["n_out"] == b["n_out"] >= 1, n
+        for key in ("xyz", "feat", "count", "source", "map"):
+            want = host(b[key])
+            assert a[key].dtype == want.dtype and a[key].shape == want.shape and a[key].tobytes() == want.tobytes(), (n, key)
+        assert a["map"].shape == (n,) and (a["views"] == 1).all() and (a["view_mask"] == 1).all(), n
+    assert fused[-1]["n_out"] > 100
+
+
+# ---- 11. end to end
 def test_a_fused_map_aligns_like_the_reading_s_rows(hiplib, torch):
     from cvo_slam_amd import synth
     from cvo_slam_amd.voxels import fuse_voxel_for_budget, split_source, lift
