@@ -107,6 +107,20 @@ class FuseFrame(C.Structure):            # cvo_fuse_frame: one posed frame of a 
     _fields_ = [("image", DeviceImage), ("pose", C.c_float * 12), ("cam", C.c_int), ("pad_", C.c_int)]
 
 
+class View(C.Structure):                 # cvo_view: one posed cloud seen by one camera (pose: row-major 3 x 4, host memory; cam: index into the call's cameras)
+    _fields_ = [("cloud", DeviceCloud), ("pose", C.c_float * 12), ("cam", C.c_int), ("pad_", C.c_int)]
+
+
+class ViewParams(C.Structure):           # cvo_view_params: one image grid, mode and depth range for all views of a call
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("cell", C.c_int), ("mode", C.c_int),
+                ("z_near", C.c_float), ("z_far", C.c_float), ("slack", C.c_float), ("depth_tol", C.c_float)]
+
+
+class ViewedCloud(C.Structure):          # cvo_viewed_cloud: one view's output arrays in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p), ("source", C.c_void_p), ("pixel", C.c_void_p), ("relation", C.c_void_p),
+                ("map", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -194,6 +208,7 @@ ABI_SYMBOLS = [
     "cvo_check_fuse_clouds", "cvo_fuse_device_clouds",
     "cvo_check_device_frames", "cvo_frames_to_device_clouds", "cvo_reduce_device_frames", "cvo_count_frame_voxels", "cvo_check_fuse_frames",
     "cvo_fuse_device_frames",
+    "cvo_check_view_clouds", "cvo_view_device_clouds",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
@@ -203,6 +218,11 @@ REDUCE_MAX_VOXELS = 16                   # CVO_REDUCE_MAX_VOXELS
 FUSE_MAX_MEMBERS = 64                    # members of a group: the bits of a view mask
 FUSE_WANT = ("count", "source", "map", "views", "view_mask")
 FRAME_MAX_STEP = 16                      # a frame's sub-grid step: 1 .. 16
+VIEW_FRONT, VIEW_SURFACE = 0, 1          # CVO_VIEW_FRONT, CVO_VIEW_SURFACE
+VIEW_MODES = {"front": VIEW_FRONT, "surface": VIEW_SURFACE}
+VIEW_WANT = ("source", "pixel", "relation", "map", "depth", "index")
+VIEW_MAX_CELL = 16                       # a z-cell's side in pixels: 1 .. 16
+VIEW_MAX_SIZE = 8192                     # the most pixels along either side of a view's image
 
 _lib = None
 
@@ -423,6 +443,9 @@ def load_library():
     ffp = C.POINTER(FuseFrame)
     L.cvo_check_fuse_frames.argtypes = [vp, C.c_int, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, fpp, fcp]
     L.cvo_fuse_device_frames.argtypes = [vp, C.c_int, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, fpp, fcp, ip, vp]
+    vwp = C.POINTER(View); vpp = C.POINTER(ViewParams); vcp = C.POINTER(ViewedCloud)
+    L.cvo_check_view_clouds.argtypes = [vp, C.c_int, vwp, cap_, vpp, dip, vcp]
+    L.cvo_view_device_clouds.argtypes = [vp, C.c_int, vwp, cap_, vpp, dip, vcp, ip, ip, vp]
     _lib = L
     return L
 
@@ -781,7 +804,8 @@ class CvoReducer:
     input alone.  max_clouds, max_points: the most clouds per call and points per cloud (up to REDUCE_MAX_POINTS); the device scratch, 384
     bytes per point of max_clouds x max_points, is allocated here and never grows.  Outputs are torch tensors on the reducer's device.
     `fuse` (cvo_hip.h, "Fusing clouds") runs groups of posed clouds through the same machinery, on the same scratch: max_clouds groups per
-    call, max_points points per group."""
+    call, max_points points per group.  `view` (cvo_hip.h, "Viewing clouds") renders posed clouds at a camera on the same scratch: max_clouds
+    views per call, max_points points per cloud and z-cells per image."""
 
     def __init__(self, max_clouds: int, max_points: int, device: int = 0):
         self.L = load_library()
@@ -1066,6 +1090,150 @@ class CvoReducer:
         call = lambda prm, recs, n_out: self.L.cvo_fuse_device_frames(self.h, len(groups), first.ctypes.data_as(C.POINTER(C.c_int)), arr, w, h, step, cams,
                                                                       C.byref(prm), recs, n_out, _stream_arg(image_stream))
         return self._run_fuse(call, [[n] * len(g) for g in groups], voxel, mode, min_points, min_views, cap, want, image_stream, "a count-only fuse_frames call, cap = 0")
+
+    # ---- viewing clouds (cvo_hip.h, "Viewing clouds"): posed clouds seen from a camera
+    @staticmethod
+    def _observed_depth(o, w, h, k):
+        """the DeviceImage of view k's observed depth: a uint16 / int16 (h, w) device array, or a (bgr, depth) pair whose depth is taken"""
+        d = o[1] if isinstance(o, (tuple, list)) else o
+        if not hasattr(d, "__cuda_array_interface__"):
+            raise ValueError(f"observed {k}: a depth image is an object with __cuda_array_interface__")
+        cd = d.__cuda_array_interface__
+        if cd["typestr"] not in ("<u2", "<i2"):
+            raise ValueError(f"observed {k}: little-endian uint16 or int16 expected, got typestr {cd['typestr']!r}")
+        sd, td = _strides_of(cd, 2)
+        if sd != (h, w):
+            raise ValueError(f"observed {k}: shape {(h, w)} expected, got {sd}")
+        if td[1] != 2 or td[0] < 2 * w:
+            raise ValueError(f"observed {k}: element stride 2 and a row stride of at least {2 * w} bytes expected, got {td}")
+        if not cd["data"][0]:
+            raise ValueError(f"observed {k}: null device pointer")
+        return DeviceImage(None, cd["data"][0], 0, td[0], 3, 0)
+
+    @staticmethod
+    def _view_args(clouds, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index):
+        """what view refuses before it touches the library, and (View array, Camera array, ViewParams, DeviceImage array or None, points per view)"""
+        bad = [w for w in want if w not in VIEW_WANT]
+        if bad:
+            raise ValueError(f"want: one of {VIEW_WANT} expected, got {bad[0]!r}")
+        if "relation" in want and observed is None:
+            raise ValueError("want: 'relation' needs observed")
+        if mode not in VIEW_MODES and mode not in VIEW_MODES.values():
+            raise ValueError(f"mode: 'front' or 'surface' expected, got {mode!r}")
+        if int(cell) != cell or not 1 <= int(cell) <= VIEW_MAX_CELL:
+            raise ValueError(f"cell {cell}: an integer in 1 .. {VIEW_MAX_CELL} expected")
+        w, h = (int(v) for v in size)
+        if not (1 <= w <= VIEW_MAX_SIZE and 1 <= h <= VIEW_MAX_SIZE):
+            raise ValueError(f"size {(w, h)}: (width, height), each in 1 .. {VIEW_MAX_SIZE}, expected")
+        near, far = (float(np.float32(v)) for v in z_range)
+        if not (np.isfinite(near) and near > 0.0):
+            raise ValueError(f"z_range: near {near} is not a finite depth above 0")
+        if not (np.isfinite(far) and far > near and far <= 32768.0):
+            raise ValueError(f"z_range: far {far} is not a finite depth above near {near} and at most 32768")
+        if not (np.isfinite(slack) and slack >= 0.0):
+            raise ValueError(f"slack {slack}: a finite number, at least 0, expected")
+        if not (np.isfinite(depth_tol) and depth_tol >= 0.0):
+            raise ValueError(f"depth_tol {depth_tol}: a finite number, at least 0, expected")
+        clouds = list(clouds); poses = list(poses)
+        if not clouds:
+            raise ValueError("no clouds")
+        if len(poses) != len(clouds):
+            raise ValueError(f"{len(clouds)} clouds but {len(poses)} poses")
+        if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
+            cameras = [cameras]
+        cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
+        ci = np.zeros(len(clouds), np.int32) if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+        if ci.shape[0] != len(clouds) or ci.min() < 0 or ci.max() >= len(cameras):
+            raise ValueError("cam_index: one index into cameras per view")
+        views = []
+        for k, (c, pose) in enumerate(zip(clouds, poses)):
+            M = np.asarray(pose, np.float32)
+            if M.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"view {k}: a 3 x 4 or 4 x 4 pose expected, got shape {M.shape}")
+            if not np.isfinite(M[:3]).all():
+                raise ValueError(f"view {k}: the pose is not finite")
+            d = c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS)
+            views.append(View(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist()), int(ci[k]), 0))
+        obs = None
+        if observed is not None:
+            observed = list(observed)
+            if len(observed) != len(clouds):
+                raise ValueError(f"{len(clouds)} clouds but {len(observed)} observed depth images")
+            obs = (DeviceImage * len(observed))(*[CvoReducer._observed_depth(o, w, h, k) for k, o in enumerate(observed)])
+        prm = ViewParams(w, h, int(cell), int(VIEW_MODES.get(mode, mode)), near, far, float(slack), float(depth_tol))
+        return (View * len(views))(*views), cams, prm, obs, [int(v.cloud.n) for v in views]
+
+    def check_view(self, clouds, poses, cameras, size, cell=1, mode="front", slack=0.0, z_range=(0.05, 30.0), observed=None, depth_tol=0.02,
+                   cam_index=None):
+        """cvo_check_view_clouds on the inputs of `view` with no output arrays (cap 0): the validation alone, nothing is launched"""
+        arr, cams, prm, obs, ns = self._view_args(clouds, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, (), cam_index)
+        recs = (ViewedCloud * len(ns))()
+        _check(self.L.cvo_check_view_clouds(self.h, len(ns), arr, cams, C.byref(prm), obs, recs))
+
+    def view(self, clouds, poses, cameras, size, cell=1, mode="front", slack=0.0, z_range=(0.05, 30.0), observed=None, depth_tol=0.02, cap=65535,
+             want=("source",), cam_index=None, stream=None):
+        """cvo_view_device_clouds: every posed cloud -- a fused local map -- seen from a camera: the z-buffered subset of its points that the
+        camera can see, in input order, by one call.  clouds: a list of what `reduce` takes for one cloud (the same cloud may be listed for
+        several views); poses: one 3 x 4 or 4 x 4 array-like per view (host; the cloud's frame to the camera's; the last row of a 4 x 4 is
+        ignored); cameras: one (scaling_factor, fx, fy, cx, cy) or a list, with cam_index one index per view; size: (width, height) of the image.
+        cell: the side of a z-cell in pixels, 1 .. 16 (voxels.view_cell_for_budget chooses it for a point budget).  mode "front": the nearest
+        point of every z-cell alone, at most ceil(w / cell) * ceil(h / cell) rows; "surface": every point within slack (relative) of its
+        z-cell's front depth.  z_range: (near, far), points outside are out of view.  observed: one uint16 (h, w) device depth image per view
+        (or a (bgr, depth) pair); with it `relation` says per row how the point stands to the measured depth within depth_tol (relative):
+        0 unknown, 1 in front (the camera saw through it), 2 agrees, 3 behind, and relation_counts counts the four.  want: which of "source"
+        (the input index), "pixel" (py * width + px), "relation", "map" (per input point: its row, -1 hidden, -2 out of view, -3 invalid),
+        "depth" and "index" (the z-buffer, (gh, gw): the front's depth and input index, 0 and -1 where empty) to return beside xyz and feat.
+        cap, stream: reduce's cap and cloud_stream; the observed images fall under the stream's rule with the clouds: with a stream both must
+        have been written on it (or be ordered before it by the caller), with None torch's current stream is synchronised for both and
+        anything written on another stream is the caller's to synchronise.  Returns one dict per view; xyz (n_out, 3) is the MOVED position and feat (n_out, 5), and
+        they pass into set_pairs_clouds as they are.  Raises CvoError when a view comes to more than cap rows; cap = 0 counts only."""
+        import torch
+        clouds = list(clouds); observed = None if observed is None else list(observed)
+        arr, cams, prm, obs, ns = self._view_args(clouds, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index)
+        _settle_cloud_writer(clouds, stream)
+        if observed:                                                  # (the depth images' writer too: they may be tensors where the clouds are descriptors)
+            _settle_writer([(observed[0][1] if isinstance(observed[0], (tuple, list)) else observed[0], None)], stream)
+        n = len(ns)
+        gw, gh = -(-prm.width // prm.cell), -(-prm.height // prm.cell)
+        most = [min(m, gw * gh) if prm.mode == VIEW_FRONT else m for m in ns]              # (the fronts alone: a row per z-cell at the most)
+        caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in most]   # (a cap out of range is the library's to refuse)
+        rows = [max(0, c) for c in caps]
+        dev = torch.device("cuda", self.device)
+        ts = None
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        per_row = dict(xyz=((3,), torch.float32), feat=((5,), torch.float32), source=((), torch.int32), pixel=((), torch.int32), relation=((), torch.int32))
+        with torch.cuda.stream(ts):                                   # (the arrays belong to the stream their readers will use)
+            whole = {k: torch.empty((sum(rows),) + sh, dtype=dt, device=dev) for k, (sh, dt) in per_row.items() if k in ("xyz", "feat") or k in want}
+            mp = torch.empty(sum(ns), dtype=torch.int32, device=dev) if "map" in want else None
+            depth = torch.empty((n, gh, gw), dtype=torch.float32, device=dev) if "depth" in want else None
+            index = torch.empty((n, gh, gw), dtype=torch.int32, device=dev) if "index" in want else None
+        recs = (ViewedCloud * n)(); at = pt = 0; outs = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = {key: t[at:at + rows[k]] for key, t in whole.items()}
+            if mp is not None: v["map"] = mp[pt:pt + ns[k]]
+            if depth is not None: v["depth"] = depth[k]
+            if index is not None: v["index"] = index[k]
+            recs[k] = ViewedCloud(*[ptr(v.get(key)) for key in ("xyz", "feat", "source", "pixel", "relation", "map", "depth", "index")], caps[k], 0)
+            outs.append(v); at += rows[k]; pt += ns[k]
+        n_out = np.zeros(n, np.int32); counts = np.zeros((n, 4), np.int32)
+        ip = C.POINTER(C.c_int)
+        _check(self.L.cvo_view_device_clouds(self.h, n, arr, cams, C.byref(prm), obs, recs, n_out.ctypes.data_as(ip),
+                                             counts.ctypes.data_as(ip) if obs is not None else None, _stream_arg(stream)))
+        over = [k for k in range(n) if n_out[k] > caps[k]] if int(cap) != 0 else []      # (cap 0 counts only: n_out is the answer)
+        if over:
+            k = over[0]
+            raise CvoError(CVO_ERR_INVALID, f"view {k}: {int(n_out[k])} rows at cell {prm.cell} are more than cap {int(cap)}: choose a larger cell (view_cell_for_budget)")
+        out = []
+        whole_cloud = ("map", "depth", "index")
+        for k, v in enumerate(outs):
+            m = int(n_out[k])
+            res = {key: (t if key in whole_cloud else t[:m]) for key, t in v.items()} | dict(n_out=m)
+            if obs is not None:
+                res["relation_counts"] = counts[k].copy()
+            out.append(res)
+        return out
 
 
 # ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms

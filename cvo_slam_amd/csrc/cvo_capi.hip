@@ -106,6 +106,7 @@ hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const F
                               int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s);
 hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
                               float voxel, int mode, int min_points, int min_views, hipStream_t s);
+hipError_t launch_view_clouds(const ViewDesc* views, int n_views, int n_max, const ViewParams& P, bool observed, bool images, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -3668,7 +3669,7 @@ int cvo_selftest_ingest_clouds(int device, int count, const cvo_device_cloud* cl
 // scratch, cut per call into a region per cloud (a reduction) or per (cloud, voxel size) item (a count); nothing is allocated after creation.
 // Fusing clouds (cvo_fuse_kernels.hip) runs groups of posed clouds through the same machinery, on the reducer's scratch and stream.  Reducing frames
 // (cvo_hip.h, "Reducing frames") is the same launches with the frame as the point source: a FrameDesc per frame behind the call's records in the
-// descriptor table, the records' cloud fields 0.
+// descriptor table, the records' cloud fields 0.  Viewing clouds (cvo_view_kernels.hip) uses the reducer's scratch, stream and counts for z-buffers.
 struct cvo_reducer_s {
     int device = 0, max_clouds = 0, max_points = 0;
     hipStream_t stream = nullptr;
@@ -4081,6 +4082,113 @@ int fuse_points(cvo_reducer r, int groups, const int* group_first, const PointSo
     for (int q = 0; q < live_groups; ++q) n_out[of[q]] = r->h_total[q];
     return CVO_OK;
 }
+
+// -- viewing clouds (cvo_view_kernels.hip; cvo_hip.h, "Viewing clouds").  View q takes region q of the scratch -- its z-buffer, its points' code
+// words, its blocks' counts and their relation counts, laid out for max_points -- and five of the reducer's counts: its rows, then its four
+// relation counts.
+struct ViewLayout { size_t code, block_heads, block_relations, bytes; };   // (the z-buffer is at 0)
+ViewLayout view_layout(int max_points) {
+    const size_t P = (size_t)max_points;
+    ViewLayout L;
+    const size_t B = (P + 255) / 256;
+    L.code = up16(8 * P); L.block_heads = L.code + up16(4 * P); L.block_relations = L.block_heads + up16(4 * B); L.bytes = L.block_relations + up16(16 * B);
+    return L;
+}
+constexpr int VIEW_COUNTS = 5;
+int view_check_params(cvo_reducer r, const cvo_view_params& p) {
+    const struct { int v; const char* name; } sizes[2] = {{p.width, "width"}, {p.height, "height"}};
+    for (const auto& s : sizes)
+        if (s.v < 1 || s.v > 8192) return fail(CVO_ERR_INVALID, std::string(s.name) + " " + std::to_string(s.v) + " is outside 1 .. 8192");
+    if (p.cell < 1 || p.cell > 16) return fail(CVO_ERR_INVALID, "cell " + std::to_string(p.cell) + " is outside 1 .. 16");
+    if (p.mode != CVO_VIEW_FRONT && p.mode != CVO_VIEW_SURFACE) return fail(CVO_ERR_INVALID, "mode " + std::to_string(p.mode) + " is neither CVO_VIEW_FRONT nor CVO_VIEW_SURFACE");
+    if (!(std::isfinite(p.z_near) && p.z_near > 0.f)) return fail(CVO_ERR_INVALID, "z_near " + std::to_string(p.z_near) + " is not a finite depth above 0");
+    if (!(std::isfinite(p.z_far) && p.z_far > p.z_near && p.z_far <= 32768.f))
+        return fail(CVO_ERR_INVALID, "z_far " + std::to_string(p.z_far) + " is not a finite depth above z_near " + std::to_string(p.z_near) + " and at most 32768");
+    if (!(std::isfinite(p.slack) && p.slack >= 0.f)) return fail(CVO_ERR_INVALID, "slack " + std::to_string(p.slack) + " is not finite and at least 0");
+    if (!(std::isfinite(p.depth_tol) && p.depth_tol >= 0.f)) return fail(CVO_ERR_INVALID, "depth_tol " + std::to_string(p.depth_tol) + " is not finite and at least 0");
+    const long long cells = (long long)frame_sub(p.width, p.cell) * frame_sub(p.height, p.cell);
+    if (cells > r->max_points) return fail(CVO_ERR_INVALID, "the " + std::to_string(cells) + " z-cells of " + std::to_string(p.width) + " x " + std::to_string(p.height) + " at cell " +
+                                           std::to_string(p.cell) + " are above the reducer's max_points " + std::to_string(r->max_points));
+    return CVO_OK;
+}
+// the depth plane of a view's observed image: cvo_check_device_images' rules for that plane alone (the colour fields are not looked at)
+int view_check_observed(int device, const cvo_device_image& im, int width, int height, const std::string& who) {
+    const long long drow = 2ll * width;
+    if (!im.depth16) return fail(CVO_ERR_INVALID, who + "observed depth16 is null");
+    if (im.depth_pitch < 0 || (im.depth_pitch != 0 && im.depth_pitch < drow)) return fail(CVO_ERR_INVALID, who + "observed depth_pitch " + std::to_string(im.depth_pitch) + " is below the row's " + std::to_string(drow) + " bytes");
+    if (reinterpret_cast<uintptr_t>(im.depth16) & 1u) return fail(CVO_ERR_INVALID, who + "observed depth16 is not 2-byte aligned");
+    if (im.depth_pitch & 1) return fail(CVO_ERR_INVALID, who + "observed depth_pitch is not a multiple of 2");
+    return check_device_plane(device, im.depth16, im.depth_pitch ? im.depth_pitch : drow, drow, height, who + "observed depth16");
+}
+int view_check(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+               const cvo_viewed_cloud* dst) {
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (views < 1 || views > r->max_clouds) return fail(CVO_ERR_INVALID, "views " + std::to_string(views) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if (!v || !cams || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = view_check_params(r, *p); if (rc) return rc;
+    if (view_layout(r->max_points).bytes > r->cloud_bytes) return fail(CVO_ERR_INVALID, "the reducer's scratch has no room for a view");   // (never: under 13 of 384 bytes per point)
+    std::vector<cvo_device_cloud> clouds(views); std::vector<std::string> names(views);
+    for (int k = 0; k < views; ++k) {
+        clouds[k] = v[k].cloud; names[k] = "view " + std::to_string(k) + ": ";
+        if ((rc = fuse_check_pose(v[k].pose, names[k])) || (rc = frames_check_camera(cams, v[k].cam, names[k]))) return rc;
+    }
+    if ((rc = check_device_clouds(r->device, views, clouds.data(), r->max_points, names.data()))) return rc;
+    const long long cells = (long long)frame_sub(p->width, p->cell) * frame_sub(p->height, p->cell);
+    for (int k = 0; k < views; ++k) {
+        const cvo_viewed_cloud& d = dst[k];
+        const std::string& who = names[k];
+        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+        if (d.relation && !observed) return fail(CVO_ERR_INVALID, who + "dst relation is set but observed is null");
+        if (observed && (rc = view_check_observed(r->device, observed[k], p->width, p->height, who))) return rc;
+        if ((rc = check_out_arrays(r->device, who, {{d.xyz, 12ll * d.cap, 4, "dst xyz", false}, {d.feat, 20ll * d.cap, 4, "dst feat", false},
+                                                    {d.source, 4ll * d.cap, 4, "dst source", false}, {d.pixel, 4ll * d.cap, 4, "dst pixel", false},
+                                                    {d.relation, 4ll * d.cap, 4, "dst relation", false}, {d.map, 4ll * v[k].cloud.n, 4, "dst map", false},
+                                                    {d.depth, 4 * cells, 4, "dst depth", false}, {d.index, 4 * cells, 4, "dst index", false}}))) return rc;
+    }
+    return CVO_OK;
+}
+// every view gets a record, an empty cloud too: its depth and index images are written all the same
+int view_points(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                const cvo_viewed_cloud* dst, int* n_out, int* relation_counts, void* stream) {
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    HIP_TRY(hipSetDevice(r->device));
+    const ViewLayout L = view_layout(r->max_points);
+    DescTable tab{r};
+    ViewDesc* h; const ViewDesc* d;
+    int rc = tab.take(views, &h, &d); if (rc) return rc;
+    ViewParams P;
+    P.width = p->width; P.height = p->height; P.cell = p->cell; P.mode = p->mode; P.gw = frame_sub(p->width, p->cell); P.gh = frame_sub(p->height, p->cell);
+    P.z_near = p->z_near; P.z_far = p->z_far; P.slack = p->slack; P.depth_tol = p->depth_tol;
+    int n_max = 0; bool images = false;
+    for (int q = 0; q < views; ++q) {
+        ViewDesc& V = h[q];
+        const cvo_camera& c = cams[v[q].cam];
+        set_cloud_source(V, &v[q].cloud);
+        std::memcpy(V.pose, v[q].pose, sizeof(V.pose));
+        V.fx = c.fx; V.fy = c.fy; V.cx = c.cx; V.cy = c.cy; V.scaling_factor = c.scaling_factor; V.n = v[q].cloud.n;
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * r->cloud_bytes;
+        V.zbuf = reinterpret_cast<unsigned long long*>(base); V.code = reinterpret_cast<int*>(base + L.code); V.block_heads = reinterpret_cast<int*>(base + L.block_heads);
+        V.block_relations = reinterpret_cast<int*>(base + L.block_relations);
+        V.total = r->d_total + VIEW_COUNTS * q; V.relation_counts = V.total + 1;
+        V.observed = observed ? static_cast<const uint8_t*>(observed[q].depth16) : nullptr;
+        V.observed_pitch = observed && observed[q].depth_pitch ? observed[q].depth_pitch : 2ll * p->width;
+        const cvo_viewed_cloud& o = dst[q];
+        V.out_xyz = static_cast<float*>(o.xyz); V.out_feat = static_cast<float*>(o.feat); V.out_source = static_cast<int*>(o.source);
+        V.out_pixel = static_cast<int*>(o.pixel); V.out_relation = static_cast<int*>(o.relation); V.out_map = static_cast<int*>(o.map);
+        V.out_depth = static_cast<float*>(o.depth); V.out_index = static_cast<int*>(o.index);
+        V.cap = o.cap; V.pad_ = 0;
+        n_max = std::max(n_max, V.n); images = images || o.depth || o.index;
+    }
+    if ((rc = reducer_run(r, tab.used, VIEW_COUNTS * views, stream, [&] { return launch_view_clouds(d, views, n_max, P, observed != nullptr, images, r->stream); }))) return rc;
+    for (int q = 0; q < views; ++q) {
+        n_out[q] = r->h_total[VIEW_COUNTS * q];
+        if (relation_counts)
+            for (int k = 0; k < 4; ++k) relation_counts[4 * q + k] = observed ? r->h_total[VIEW_COUNTS * q + 1 + k] : 0;
+    }
+    return CVO_OK;
+}
 }  // namespace
 }  // extern "C++"
 int cvo_reducer_create(int device, int max_clouds, int max_points, cvo_reducer* out) {
@@ -4175,6 +4283,15 @@ int cvo_fuse_device_frames(cvo_reducer r, int groups, const int* group_first, co
     src.frame = [&](int m, FrameDesc& F) { frame_desc(members[m].image, width, height, step, cams[members[m].cam], F); };
     src.frame_n = frame_sub(width, step) * frame_sub(height, step);
     return fuse_points(r, groups, group_first, src, [&](int m) { return members[m].pose; }, p, dst, n_out, image_stream);
+}
+int cvo_check_view_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                          const cvo_viewed_cloud* dst) {
+    return view_check(r, views, v, cams, p, observed, dst);
+}
+int cvo_view_device_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                           const cvo_viewed_cloud* dst, int* n_out, int* relation_counts, void* cloud_stream) {
+    int rc = view_check(r, views, v, cams, p, observed, dst); if (rc) return rc;
+    return view_points(r, views, v, cams, p, observed, dst, n_out, relation_counts, cloud_stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

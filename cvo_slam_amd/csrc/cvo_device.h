@@ -320,6 +320,32 @@ struct FuseMemberDesc {
     int pad_;
 };
 static_assert(sizeof(FuseMemberDesc) == 112, "FuseMemberDesc layout");
+// one view of a viewing call (cvo_view_kernels.hip; not in the reference; cvo_hip.h, "Viewing clouds"): a cloud (n may be 0: its images are
+// still written), its pose and camera, its part of the reducer's scratch and the caller's arrays.  The grid's second dimension in every pass.
+struct ViewDesc {
+    const float* xyz; const float* feat;
+    long long xyz_stride, feat_point_stride, feat_channel_stride;
+    float pose[12];                // row-major 3 x 4: the cloud's frame to the camera's
+    float fx, fy, cx, cy, scaling_factor;
+    int n;
+    unsigned long long* zbuf;      // gw * gh: the z-cell's least (z' bits << 32) | index, all ones = empty
+    int* code;                     // n: the point's z-cell number; -2 valid but not in view; -3 invalid
+    int* block_heads;              // one per 256 points: the block's visible points, then their exclusive sum
+    int* block_relations;          // four per 256 points: the block's rows of each relation value (with observed)
+    int* total;                    // the full row count, and behind it ...
+    int* relation_counts;          // ... the four relation counts over all rows
+    const uint8_t* observed;       // uint16 (x, y) at observed + y * observed_pitch + 2 * x; null: no relation
+    long long observed_pitch;
+    float* out_xyz; float* out_feat; int* out_source; int* out_pixel; int* out_relation; int* out_map; float* out_depth; int* out_index;
+    int cap;                       // rows at or above it are not written
+    int pad_;
+};
+static_assert(sizeof(ViewDesc) == 248, "ViewDesc layout");
+// what all views of a call share
+struct ViewParams {
+    int width, height, cell, mode, gw, gh;
+    float z_near, z_far, slack, depth_tol;
+};
 
 // the group boxes of many clouds in one launch (cvo_cloud_boxes_batch_kernel): one descriptor per cloud, n > 0
 struct BoxDesc {

@@ -1,5 +1,6 @@
-"""Helpers around CvoReducer (cvo_hip.h, "Reducing clouds" and "Fusing clouds"): choosing a voxel size for a point budget, carrying what was
-computed for the reduced cloud's rows back to the dense cloud's points, and telling which member of a fused group a row came from."""
+"""Helpers around CvoReducer (cvo_hip.h, "Reducing clouds", "Fusing clouds" and "Viewing clouds"): choosing a voxel size or a z-cell side for a
+point budget, carrying what was computed for the reduced cloud's rows back to the dense cloud's points, and telling which member of a fused
+group a row came from."""
 from __future__ import annotations
 
 import numpy as np
@@ -60,6 +61,18 @@ def fuse_voxel_for_budget(reducer, group, poses, budget: int, lo: float, hi: flo
         if rows(mid) <= budget: fits = mid
         else: below = mid
     return float(sizes[fits])
+
+
+def view_cell_for_budget(width: int, height: int, budget: int) -> int:
+    """The smallest z-cell side `cell` in 1 .. 16 at which a view of width x height in mode "front" (CvoReducer.view) has at most `budget`
+    rows: ceil(width / cell) * ceil(height / cell) <= budget.  Arithmetic: no call is made.  Raises ValueError when none fits."""
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise ValueError(f"view_cell_for_budget: a width and a height of at least 1 expected, got {(width, height)}")
+    for cell in range(1, 17):
+        if -(-w // cell) * -(-h // cell) <= budget:
+            return cell
+    raise ValueError(f"view_cell_for_budget: {-(-w // 16) * -(-h // 16)} z-cells at cell 16 are more than the budget {budget}")
 
 
 def split_source(source, offsets):

@@ -643,6 +643,62 @@ int cvo_check_fuse_frames(cvo_reducer r, int groups, const int* group_first /* g
 int cvo_fuse_device_frames(cvo_reducer r, int groups, const int* group_first /* groups + 1 */, const cvo_fuse_frame* members, int width, int height,
                            int step, const cvo_camera* cams, const cvo_fuse_params* p /* one for all */, const cvo_fused_cloud* dst,
                            int* n_out /* groups, host */, void* image_stream);
+/* ---- Viewing clouds (not in the reference): a posed device cloud -- a fused local map -- seen from a camera: the z-buffered subset of its points
+ * that the camera can see, which is what a frame-to-model tracker aligns against, and the z-buffer itself.  Many views per call; as in the
+ * reducer the result's bits depend on the input alone (integer atomics only, no float atomics, no table or arrival order in any output).
+ *
+ * The definition.  A view is a cvo_device_cloud under the reducer's validation (n up to 1048575), a pose (12 f32, row-major 3 x 4, HOST memory)
+ * taking the cloud's frame to the camera's frame, and a camera index into cams.  One cvo_view_params holds for all views of a call: width,
+ * height, cell (1 .. 16), mode, z_near, z_far, slack, depth_tol; gw = ceil(width / cell), gh = ceil(height / cell).
+ *   moved position: the fuser's rule, bit for bit: x' = (M[r,0]*x + (M[r,1]*y + M[r,2]*z)) + M[r,3] per row r, f32, un-fused.  Features pass
+ *     through.
+ *   valid point: the fuser's rule: its 8 source floats and its 3 moved floats are finite and below 2^15 in magnitude.
+ *   in view: a valid point is in range when z_near <= z' && z' <= z_far.  Its image coordinates are u = (x' * fx) / z' + cx and
+ *     v = (y' * fy) / z' + cy, in f32 with every product, quotient and sum rounded, in that order (the inverse of the generator's
+ *     X = ((float)x - cx) * z / fx: every pixel of a frame with depth reprojects onto itself).  Both must be finite and below 2^20 in magnitude;
+ *     px = (int)floorf(u + 0.5f), py = (int)floorf(v + 0.5f), and 0 <= px < width, 0 <= py < height.
+ *   z-cell: (px / cell, py / cell); z-cell number (py / cell) * gw + px / cell.
+ *   front: a z-cell's front is the in-view point with the least 64-bit key (bits of z' << 32) | index: z' > 0, so the bits order as the floats
+ *     do; a tie in z' goes to the lowest index.
+ *   visible: CVO_VIEW_FRONT: the fronts alone (at most gw * gh rows: cell is the point budget).  CVO_VIEW_SURFACE: every in-view point with
+ *     z' <= zf + slack * zf, zf its z-cell's front depth, in f32 with product and sum rounded; slack = 0 keeps exactly the points whose z' equals
+ *     the front's.
+ *   rows: the visible points in ascending input index: a viewed cloud is a row subset of the moved cloud, in order.
+ *   outputs per view, caller-owned device memory, all optional but xyz and feat: xyz (cap x 3, the moved position), feat (cap x 5, the "(n, 5)"
+ *     layout: the result passes on as a cvo_device_cloud), source (cap int32, the input index), pixel (cap int32, py * width + px), relation
+ *     (cap int32, below), map (n int32: the full row number if visible, -1 in view but hidden, -2 valid but out of range or outside the image,
+ *     -3 invalid), depth (gw * gh f32: the front's z', 0 for an empty z-cell), index (gw * gh int32: the front's input index, -1 for an empty
+ *     z-cell).  n_out[i] is always the FULL row count; cap is 0 .. 65535; rows at or above cap are not written and no byte behind row cap - 1
+ *     is touched.  cap == 0 with the row arrays NULL counts only; depth, index and map may still be asked for.
+ *   relation needs `observed`: one cvo_device_image per view, of width x height, of which only depth16 and depth_pitch are read and validated
+ *     (NULL for the call: no relation is computed; a relation array without observed is refused).  For a row at (px, py) with observed d:
+ *     d == 0 gives 0, unknown.  Otherwise zo = (float)d / scaling_factor and t = depth_tol * zo, in f32; z' < zo - t gives 1 (in front: the
+ *     camera saw through the point), z' > zo + t gives 3 (behind), anything else 2 (agrees).  relation_counts (views x 4 ints, host, may be
+ *     NULL) holds the four counts over ALL rows, those at or above cap included.
+ *
+ * A call runs on an existing cvo_reducer and allocates nothing.  A view takes one cloud's scratch region: its z-buffer (8 bytes x gw * gh), a
+ * per-point z-cell or code word (4 bytes x n) and its per-block counts -- hence gw * gh <= max_points; cvo_reducer_info's scratch_bytes is what
+ * it was.  The same cloud may appear in several views of one call (one map seen from K streams' predicted poses, or from K hypotheses).  All
+ * views of a call go through the same launches, the view in the grid's second dimension; poses and cameras travel with the descriptor table.
+ * Validation: CVO_ERR_INVALID, the message naming view and field, for everything cvo_check_reduce_clouds checks per cloud and per output array
+ * (extents: pixel and relation cap x 4 bytes, depth and index gw * gh x 4, map n x 4); views outside 1 .. max_clouds; n > max_points;
+ * gw * gh > max_points; width or height outside 1 .. 8192; cell outside 1 .. 16; mode not 0 or 1; z_near not finite or not > 0; z_far not
+ * finite, not > z_near, or above 32768; slack or depth_tol not finite or negative; a pose float that is not finite; a negative camera index; a
+ * camera float that is not finite, or fx, fy or scaling_factor equal to 0; observed with a null or misaligned depth16, a bad depth_pitch, or rows
+ * outside a device-readable allocation (cvo_device_image's rule, for the depth plane only).  A refused call changes nothing and launches nothing.
+ * cloud_stream: the reducer's rule -- with a stream one event edge in and one out, with NULL everything is done on return; one host wait, for
+ * the counts. */
+#define CVO_VIEW_FRONT 0
+#define CVO_VIEW_SURFACE 1
+typedef struct cvo_view { cvo_device_cloud cloud; float pose[12]; int cam; int pad_; } cvo_view;               /* 104 bytes */
+typedef struct cvo_view_params { int width, height, cell, mode; float z_near, z_far, slack, depth_tol; } cvo_view_params;   /* 32 bytes */
+typedef struct cvo_viewed_cloud { void *xyz, *feat, *source, *pixel, *relation, *map, *depth, *index; int cap; int pad_; } cvo_viewed_cloud;   /* 72 bytes */
+/* the validation of cvo_view_device_clouds alone: launches nothing.  cams holds max(v[].cam) + 1 cameras */
+int cvo_check_view_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p,
+                          const cvo_device_image* observed /* NULL or views */, const cvo_viewed_cloud* dst);
+int cvo_view_device_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p /* one for all */,
+                           const cvo_device_image* observed /* NULL or views */, const cvo_viewed_cloud* dst, int* n_out /* views, host */,
+                           int* relation_counts /* views x 4, host, may be NULL */, void* cloud_stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
