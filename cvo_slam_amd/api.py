@@ -121,6 +121,19 @@ class ViewedCloud(C.Structure):          # cvo_viewed_cloud: one view's output a
                 ("map", C.c_void_p), ("depth", C.c_void_p), ("index", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
 
 
+class MapFilter(C.Structure):            # cvo_map_filter: which rows of one resident map an extract keeps
+    _fields_ = [("min_points", C.c_int), ("min_views", C.c_int), ("min_last_stamp", C.c_int), ("pad_", C.c_int)]
+
+
+class MapKeep(C.Structure):              # cvo_map_keep: which rows of one resident map survive a compaction
+    _fields_ = [("min_last_stamp", C.c_int), ("min_views", C.c_int), ("probation_from", C.c_int), ("pad_", C.c_int)]
+
+
+class MapCloud(C.Structure):             # cvo_map_cloud: one map's extracted arrays in caller-owned device memory
+    _fields_ = [("xyz", C.c_void_p), ("feat", C.c_void_p), ("count", C.c_void_p), ("views", C.c_void_p), ("view_mask", C.c_void_p),
+                ("last_stamp", C.c_void_p), ("born", C.c_void_p), ("row", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -209,6 +222,9 @@ ABI_SYMBOLS = [
     "cvo_check_device_frames", "cvo_frames_to_device_clouds", "cvo_reduce_device_frames", "cvo_count_frame_voxels", "cvo_check_fuse_frames",
     "cvo_fuse_device_frames",
     "cvo_check_view_clouds", "cvo_view_device_clouds",
+    "cvo_maps_create", "cvo_maps_destroy", "cvo_maps_info", "cvo_maps_clear", "cvo_maps_rows", "cvo_check_maps_integrate_clouds",
+    "cvo_check_maps_integrate_frames", "cvo_maps_integrate_clouds", "cvo_maps_integrate_frames", "cvo_check_maps_extract", "cvo_maps_extract",
+    "cvo_check_maps_compact", "cvo_maps_compact",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
@@ -223,6 +239,10 @@ VIEW_MODES = {"front": VIEW_FRONT, "surface": VIEW_SURFACE}
 VIEW_WANT = ("source", "pixel", "relation", "map", "depth", "index")
 VIEW_MAX_CELL = 16                       # a z-cell's side in pixels: 1 .. 16
 VIEW_MAX_SIZE = 8192                     # the most pixels along either side of a view's image
+MAP_MAX_ROWS = 1048575                   # CVO_MAP_MAX_ROWS
+MAP_MAX_COUNT = 16777215                 # CVO_MAP_MAX_COUNT
+MAP_INTEGRATE, MAP_REMOVE, MAP_REMOVE_PRESENT = 1, -1, -2      # CVO_MAP_*: the sign of an update
+MAP_WANT = ("count", "views", "view_mask", "last_stamp", "born", "row")
 
 _lib = None
 
@@ -446,6 +466,20 @@ def load_library():
     vwp = C.POINTER(View); vpp = C.POINTER(ViewParams); vcp = C.POINTER(ViewedCloud)
     L.cvo_check_view_clouds.argtypes = [vp, C.c_int, vwp, cap_, vpp, dip, vcp]
     L.cvo_view_device_clouds.argtypes = [vp, C.c_int, vwp, cap_, vpp, dip, vcp, ip, ip, vp]
+    mfp = C.POINTER(MapFilter); mkp = C.POINTER(MapKeep); mcp = C.POINTER(MapCloud); vpp_ = C.POINTER(vp)
+    L.cvo_maps_create.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.POINTER(vp)]
+    L.cvo_maps_destroy.argtypes = [vp]
+    L.cvo_maps_info.argtypes = [vp, ip, ip, fp, C.POINTER(C.c_longlong)]
+    L.cvo_maps_clear.argtypes = [vp, C.c_int, ip, vp]
+    L.cvo_maps_rows.argtypes = [vp, C.c_int, ip, ip, ip]
+    L.cvo_check_maps_integrate_clouds.argtypes = [vp, C.c_int, ip, ip, fmp, ip, C.c_int]
+    L.cvo_maps_integrate_clouds.argtypes = [vp, C.c_int, ip, ip, fmp, ip, C.c_int, vp]
+    L.cvo_check_maps_integrate_frames.argtypes = [vp, C.c_int, ip, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, ip, C.c_int]
+    L.cvo_maps_integrate_frames.argtypes = [vp, C.c_int, ip, ip, ffp, C.c_int, C.c_int, C.c_int, cap_, ip, C.c_int, vp]
+    L.cvo_check_maps_extract.argtypes = [vp, C.c_int, ip, mfp, mcp]
+    L.cvo_maps_extract.argtypes = [vp, C.c_int, ip, mfp, mcp, ip, vp]
+    L.cvo_check_maps_compact.argtypes = [vp, C.c_int, ip, mkp, vpp_, vpp_]
+    L.cvo_maps_compact.argtypes = [vp, C.c_int, ip, mkp, vpp_, vpp_, ip, vp]
     _lib = L
     return L
 
@@ -814,8 +848,9 @@ class CvoReducer:
         _check(self.L.cvo_reducer_create(self.device, self.max_clouds, self.max_points, C.byref(self.h)))
 
     def close(self):
+        """cvo_reducer_destroy.  Raises CvoError, and keeps the reducer, while CvoMaps objects created on it are open: close those first."""
         if getattr(self, "h", None) and self.h.value:
-            self.L.cvo_reducer_destroy(self.h); self.h = C.c_void_p()
+            _check(self.L.cvo_reducer_destroy(self.h)); self.h = C.c_void_p()
 
     def __del__(self):
         try:
@@ -1234,6 +1269,267 @@ class CvoReducer:
                 res["relation_counts"] = counts[k].copy()
             out.append(res)
         return out
+
+
+# ---- resident maps (cvo_hip.h, "Resident maps"): voxel maps that stay on the device between calls
+class CvoMaps:
+    """cvo_maps: max_maps independent voxel maps of at most max_rows rows at one voxel size, resident in device memory -- one per tracker
+    stream -- to which posed clouds or frames are added (`integrate`) and from which they are taken away again (`remove`), exactly: the sums
+    are integers.  Created on a CvoReducer, whose scratch and stream every call uses; close the maps before the reducer.  Every call takes a
+    list of map numbers (each at most once) and handles all of them in the same launches.  Outputs are torch tensors on the reducer's device."""
+
+    def __init__(self, reducer: "CvoReducer", max_maps: int, max_rows: int, voxel: float):
+        self.L = reducer.L
+        self.reducer, self.device = reducer, reducer.device
+        self.max_maps, self.max_rows, self.voxel = int(max_maps), int(max_rows), float(voxel)
+        self.h = C.c_void_p()
+        _check(self.L.cvo_maps_create(reducer.h, self.max_maps, self.max_rows, self.voxel, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.cvo_maps_destroy(self.h); self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """cvo_maps_info: dict(max_maps, max_rows, voxel, device_bytes)"""
+        a, b, v, n = C.c_int(0), C.c_int(0), C.c_float(0), C.c_longlong(0)
+        _check(self.L.cvo_maps_info(self.h, C.byref(a), C.byref(b), C.byref(v), C.byref(n)))
+        return dict(max_maps=a.value, max_rows=b.value, voxel=v.value, device_bytes=n.value)
+
+    def _maps(self, maps):
+        """the call's map numbers as an int32 array: all maps for None; refuses an empty list, a number out of range or given twice"""
+        ms = list(range(self.max_maps)) if maps is None else [maps] if isinstance(maps, (int, np.integer)) else list(maps)
+        if not ms:
+            raise ValueError("no maps")
+        if any(int(k) != k for k in ms):
+            raise ValueError("maps: integers expected")
+        ms = [int(k) for k in ms]
+        bad = [k for k in ms if not 0 <= k < self.max_maps]
+        if bad:
+            raise ValueError(f"map {bad[0]}: 0 .. {self.max_maps - 1} expected")
+        if len(set(ms)) != len(ms):
+            raise ValueError(f"map {[k for k in ms if ms.count(k) > 1][0]} appears twice in the call")
+        return np.asarray(ms, np.int32)
+
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.POINTER(C.c_int))
+
+    def rows(self, maps=None, live: bool = True):
+        """cvo_maps_rows: (rows, live_rows) int32 arrays, one entry per listed map: its rows, dead ones included, and those with count >= 1
+        (live = False: rows alone, which the host knows: no wait, live_rows is None)"""
+        ms = self._maps(maps)
+        rows = np.zeros(len(ms), np.int32); alive = np.zeros(len(ms), np.int32) if live else None
+        _check(self.L.cvo_maps_rows(self.h, len(ms), self._ip(ms), self._ip(rows), self._ip(alive) if live else None))
+        return rows, alive
+
+    def clear(self, maps=None, stream=None):
+        """cvo_maps_clear: the listed maps (None: all) become empty"""
+        ms = self._maps(maps)
+        _check(self.L.cvo_maps_clear(self.h, len(ms), self._ip(ms), _stream_arg(stream)))
+
+    def _stamps(self, ms, groups, stamps):
+        """the flat int32 stamps of an update's members: one list of integers >= 0 per group, shaped like groups"""
+        if len(groups) != len(ms):
+            raise ValueError(f"{len(ms)} maps but {len(groups)} groups")
+        stamps = [[q] if isinstance(q, (int, np.integer)) else list(q) for q in stamps]
+        if len(stamps) != len(groups):
+            raise ValueError(f"{len(groups)} groups but {len(stamps)} lists of stamps")
+        flat = []
+        for g, (members, st) in enumerate(zip(groups, stamps)):
+            if len(st) != len(members):
+                raise ValueError(f"group {g}: {len(members)} members but {len(st)} stamps")
+            for m, v in enumerate(st):
+                if int(v) != v or not 0 <= int(v) < 2 ** 31:
+                    raise ValueError(f"group {g} member {m}: stamp {v!r}: an integer in 0 .. 2^31 - 1 expected")
+                flat.append(int(v))
+        return np.asarray(flat, np.int32)
+
+    def _cloud_update(self, maps, groups, poses, stamps):
+        ms = self._maps(maps)
+        groups, Ms = CvoReducer._fuse_args(groups, poses, 1, "mean", ())
+        st = self._stamps(ms, groups, stamps)
+        arr, first, sizes, groups = self.reducer._fuse_inputs(groups, Ms, 1, "mean", ())
+        return ms, groups, arr, first, st
+
+    def check_integrate(self, maps, groups, poses, stamps, sign: int = 1):
+        """cvo_check_maps_integrate_clouds: the validation of integrate (sign 1) or remove (sign -1) alone, nothing is launched"""
+        ms, groups, arr, first, st = self._cloud_update(maps, groups, poses, stamps)
+        _check(self.L.cvo_check_maps_integrate_clouds(self.h, len(ms), self._ip(ms), self._ip(first), arr, self._ip(st), int(sign)))
+
+    def _update(self, maps, groups, poses, stamps, sign, cloud_stream):
+        ms, groups, arr, first, st = self._cloud_update(maps, groups, poses, stamps)
+        _settle_cloud_writer([c for g in groups for c in g], cloud_stream)
+        _check(self.L.cvo_maps_integrate_clouds(self.h, len(ms), self._ip(ms), self._ip(first), arr, self._ip(st), sign, _stream_arg(cloud_stream)))
+
+    def integrate(self, maps, groups, poses, stamps, cloud_stream=None):
+        """cvo_maps_integrate_clouds, sign +1: group g -- a list of 1 .. 64 posed clouds, what CvoReducer.fuse takes -- is added to map maps[g].
+        stamps: a list of lists of integers >= 0 shaped like groups, one per member: the member's bit in view_mask is stamp & 63, and
+        last_stamp / born are kept per row.  Raises CvoError, with every map unchanged, when a map would outgrow max_rows or a cell's count
+        16777215.  The clouds are read before the call returns."""
+        self._update(maps, groups, poses, stamps, 1, cloud_stream)
+
+    def remove(self, maps, groups, poses, stamps, cloud_stream=None, present: bool = False):
+        """cvo_maps_integrate_clouds, sign -1: the members go out of their maps again -- the same clouds, poses and stamps that were
+        integrated.  Rows whose count reaches 0 are dead until a `compact`.  Raises CvoError, with every map unchanged, when a cell is absent
+        or holds fewer members than are taken out.  present = True (sign -2, "remove what is still there"): for maps whose compactions drop
+        live rows (drop masks, probation): a cell that is absent, or whose row has none of the members' stamp bits (it was dropped and made
+        again by others), is skipped; a row that has some of the bits and not others refuses the call.  After such a compaction plain
+        removal is unsupported."""
+        self._update(maps, groups, poses, stamps, MAP_REMOVE_PRESENT if present else MAP_REMOVE, cloud_stream)
+
+    def _frame_update(self, maps, groups, poses, stamps, cameras, cam_index, step, swap_rb):
+        ms = self._maps(maps)
+        groups, Ms = CvoReducer._fuse_args(groups, poses, 1, "mean", ())
+        st = self._stamps(ms, groups, stamps)
+        flat = [f for g in groups for f in g]
+        ci = None if cam_index is None else [int(c) for q in cam_index for c in q]
+        descs, w, h, step, cams, ci = CvoReducer._frame_list(flat, cameras, ci, step, swap_rb)
+        arr = (FuseFrame * len(descs))(*[FuseFrame(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist()), int(c), 0) for d, M, c in zip(descs, [M for q in Ms for M in q], ci)])
+        first = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+        return (self.h, len(ms), self._ip(ms), self._ip(first), arr, w, h, step, cams, self._ip(st)), flat, (ms, first, st, arr, cams)
+
+    def check_integrate_frames(self, maps, groups, poses, stamps, cameras, cam_index=None, step: int = 1, swap_rb=False, sign: int = 1):
+        """cvo_check_maps_integrate_frames: the validation of integrate_frames / remove_frames alone"""
+        args, flat, keep = self._frame_update(maps, groups, poses, stamps, cameras, cam_index, step, swap_rb)
+        _check(self.L.cvo_check_maps_integrate_frames(*args, int(sign)))
+
+    def _update_frames(self, maps, groups, poses, stamps, cameras, cam_index, step, swap_rb, sign, image_stream):
+        args, flat, keep = self._frame_update(maps, groups, poses, stamps, cameras, cam_index, step, swap_rb)
+        _settle_writer(flat, image_stream)
+        _check(self.L.cvo_maps_integrate_frames(*args, sign, _stream_arg(image_stream)))
+
+    def integrate_frames(self, maps, groups, poses, stamps, cameras, cam_index=None, step: int = 1, swap_rb=False, image_stream=None):
+        """cvo_maps_integrate_frames, sign +1: `integrate` of the frames' dense clouds (CvoReducer.fuse_frames' members), read in place"""
+        self._update_frames(maps, groups, poses, stamps, cameras, cam_index, step, swap_rb, 1, image_stream)
+
+    def remove_frames(self, maps, groups, poses, stamps, cameras, cam_index=None, step: int = 1, swap_rb=False, image_stream=None, present: bool = False):
+        """cvo_maps_integrate_frames, sign -1: `remove` of the frames that were integrated (present = True: sign -2, as in `remove`)"""
+        self._update_frames(maps, groups, poses, stamps, cameras, cam_index, step, swap_rb, MAP_REMOVE_PRESENT if present else MAP_REMOVE, image_stream)
+
+    @staticmethod
+    def _per_map(v, n, name, lo, hi):
+        vs = list(v) if hasattr(v, "__len__") else [v] * n
+        if len(vs) != n:
+            raise ValueError(f"{name}: one value or one per map expected")
+        for x in vs:
+            if int(x) != x or not lo <= int(x) <= hi:
+                raise ValueError(f"{name} {x!r}: an integer in {lo} .. {hi} expected")
+        return [int(x) for x in vs]
+
+    def _filters(self, ms, min_points, min_views, min_last_stamp, want):
+        bad = [w for w in want if w not in MAP_WANT]
+        if bad:
+            raise ValueError(f"want: one of {MAP_WANT} expected, got {bad[0]!r}")
+        n = len(ms)
+        cols = (self._per_map(min_points, n, "min_points", 0, 2 ** 31 - 1), self._per_map(min_views, n, "min_views", 0, FUSE_MAX_MEMBERS),
+                self._per_map(min_last_stamp, n, "min_last_stamp", -2 ** 31, 2 ** 31 - 1))
+        return (MapFilter * n)(*[MapFilter(a, b, c, 0) for a, b, c in zip(*cols)])
+
+    def check_extract(self, maps=None, min_points=1, min_views=1, min_last_stamp=0):
+        """cvo_check_maps_extract with no output arrays (cap 0): the validation alone"""
+        ms = self._maps(maps)
+        flt = self._filters(ms, min_points, min_views, min_last_stamp, ())
+        _check(self.L.cvo_check_maps_extract(self.h, len(ms), self._ip(ms), flt, (MapCloud * len(ms))()))
+
+    def extract(self, maps=None, min_points=1, min_views=1, min_last_stamp=0, cap: int = 65535, want=("count",), stream=None):
+        """cvo_maps_extract: the rows of every listed map with count >= max(1, min_points), at least min_views bits in view_mask and
+        last_stamp >= min_last_stamp (each one value, or one per map), in ascending row number.  want: which of "count", "views", "view_mask",
+        "last_stamp", "born", "row" (the map's row number) to return beside xyz and feat.  Returns one dict per map, as CvoReducer.fuse does:
+        xyz (n_out, 3), feat (n_out, 5), the wanted arrays, n_out; the tensors pass into device_cloud / set_pairs_clouds / view as they are.
+        Raises CvoError when a map comes to more than cap rows; cap = 0 counts only.  cap is at most 65535 and there is no paging: a
+        map may hold up to max_rows rows, but an extract returns its kept rows only when the filter keeps at most 65535 of them."""
+        import torch
+        ms = self._maps(maps)
+        flt = self._filters(ms, min_points, min_views, min_last_stamp, want)
+        n = len(ms)
+        have, _ = self.rows(ms, live=False)
+        caps = [min(int(cap), int(m)) if 0 <= int(cap) <= 65535 else int(cap) for m in have]   # (a cap out of range is the library's to refuse)
+        rows = [max(0, c) for c in caps]
+        dev = torch.device("cuda", self.device)
+        ts = None
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        per_row = dict(xyz=((3,), torch.float32), feat=((5,), torch.float32), count=((), torch.int32), views=((), torch.int32), view_mask=((), torch.int64),
+                       last_stamp=((), torch.int32), born=((), torch.int32), row=((), torch.int32))   # (view_mask: 64 bits in torch's signed carrier)
+        with torch.cuda.stream(ts):
+            whole = {k: torch.empty((sum(rows),) + sh, dtype=dt, device=dev) for k, (sh, dt) in per_row.items() if k in ("xyz", "feat") or k in want}
+        recs = (MapCloud * n)(); at = 0; outs = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = {key: t[at:at + rows[k]] for key, t in whole.items()}
+            recs[k] = MapCloud(*[ptr(v.get(key)) for key in per_row], caps[k], 0)
+            outs.append(v); at += rows[k]
+        n_out = np.zeros(n, np.int32)
+        _check(self.L.cvo_maps_extract(self.h, n, self._ip(ms), flt, recs, self._ip(n_out), _stream_arg(stream)))
+        over = [k for k in range(n) if n_out[k] > caps[k]] if int(cap) != 0 else []
+        if over:
+            k = over[0]
+            raise CvoError(CVO_ERR_INVALID, f"map {int(ms[k])}: {int(n_out[k])} rows are more than cap {int(cap)}: filter harder, compact, or use a larger voxel")
+        return [{key: t[:int(n_out[k])] for key, t in v.items()} | dict(n_out=int(n_out[k])) for k, v in enumerate(outs)]
+
+    def _compact_args(self, maps, min_last_stamp, min_views, probation_from, drop):
+        ms = self._maps(maps)
+        n = len(ms)
+        cols = (self._per_map(min_last_stamp, n, "min_last_stamp", -2 ** 31, 2 ** 31 - 1), self._per_map(min_views, n, "min_views", 0, FUSE_MAX_MEMBERS),
+                self._per_map(probation_from, n, "probation_from", -2 ** 31, 2 ** 31 - 1))
+        keep = (MapKeep * n)(*[MapKeep(a, b, c, 0) for a, b, c in zip(*cols)])
+        drops = None
+        if drop is not None:
+            drop = list(drop)
+            if len(drop) != n:
+                raise ValueError(f"{n} maps but {len(drop)} drop masks")
+            ptrs = []
+            for k, d in enumerate(drop):
+                if d is None:
+                    ptrs.append(None); continue
+                cai = getattr(d, "__cuda_array_interface__", None)
+                if cai is None:
+                    raise ValueError(f"drop {k}: a device array (__cuda_array_interface__) expected")
+                if cai["typestr"] not in ("|u1", "|b1", "|i1") or len(cai["shape"]) != 1 or cai.get("strides") not in (None, (1,)):
+                    raise ValueError(f"drop {k}: a contiguous 1-D array of bytes (uint8 or bool) expected")
+                ptrs.append(cai["data"][0] if cai["shape"][0] else None)
+            drops = (C.c_void_p * n)(*ptrs)
+        return ms, keep, drop, drops
+
+    def check_compact(self, maps=None, min_last_stamp=0, min_views=0, probation_from=0, drop=None):
+        """cvo_check_maps_compact: the validation alone"""
+        ms, keep, drop, drops = self._compact_args(maps, min_last_stamp, min_views, probation_from, drop)
+        _check(self.L.cvo_check_maps_compact(self.h, len(ms), self._ip(ms), keep, drops, None))
+
+    def compact(self, maps=None, min_last_stamp=0, min_views=0, probation_from=0, drop=None, new_row: bool = False, stream=None):
+        """cvo_maps_compact: in every listed map a row stays when count >= 1, last_stamp >= min_last_stamp, (its views >= min_views or
+        born >= probation_from), and its byte in drop[k] is 0 (drop: None, or one 1-D uint8 / bool device array of the map's rows, or None,
+        per map; voxels.carve_mask makes one from a view).  The survivors keep their order and are renumbered from 0.  The defaults drop the
+        dead rows alone.  Returns the new row counts (int32 array), and with new_row also a list of int32 tensors: each old row's new number
+        or -1."""
+        import torch
+        ms, keep, drop, drops = self._compact_args(maps, min_last_stamp, min_views, probation_from, drop)
+        n = len(ms)
+        have, _ = self.rows(ms, live=False)
+        if drop is not None:
+            for k, d in enumerate(drop):
+                if d is not None and int(d.__cuda_array_interface__["shape"][0]) != int(have[k]):
+                    raise ValueError(f"drop {k}: {int(d.__cuda_array_interface__['shape'][0])} bytes for map {int(ms[k])}'s {int(have[k])} rows")
+        news = ptrs = None
+        if new_row:
+            dev = torch.device("cuda", self.device)
+            ts = None
+            if stream is not None:
+                ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+            with torch.cuda.stream(ts):
+                news = [torch.empty(int(m), dtype=torch.int32, device=dev) for m in have]
+            ptrs = (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in news])
+        out = np.zeros(n, np.int32)
+        if stream is None and drop is not None and "torch" in sys.modules:
+            sys.modules["torch"].cuda.current_stream(self.device).synchronize()          # (the masks' writer: torch's current stream)
+        _check(self.L.cvo_maps_compact(self.h, n, self._ip(ms), keep, drops, ptrs, self._ip(out), _stream_arg(stream)))
+        return (out, news) if new_row else out
 
 
 # ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms

@@ -107,6 +107,13 @@ hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const F
 hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
                               float voxel, int mode, int min_points, int min_views, hipStream_t s);
 hipError_t launch_view_clouds(const ViewDesc* views, int n_views, int n_max, const ViewParams& P, bool observed, bool images, hipStream_t s);
+hipError_t launch_fuse_cells(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n_max, int slots_max,
+                             int rows_max, float voxel, hipStream_t s);
+hipError_t launch_map_lookup(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int n_max, hipStream_t s);
+hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, hipStream_t s);
+hipError_t launch_map_extract(const MapDesc* maps, int n_maps, int rows_max, bool write, hipStream_t s);
+hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hipStream_t s);
+hipError_t launch_map_clear(const MapDesc* maps, int n_maps, int slots, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -3678,6 +3685,7 @@ struct cvo_reducer_s {
     void* d_desc = nullptr; int* d_total = nullptr;                   // the launch's descriptor table and its row counts on the device
     void* h_desc = nullptr; int* h_total = nullptr;                   // their pinned twins: written before the launches, read after the call's one wait
     size_t table_bytes = 0;                                           // the size of d_desc and of h_desc
+    int live_maps = 0;                                                // cvo_maps objects created on this reducer and not yet destroyed
 };
 extern "C++" {                                                        // (the helpers below have templates among them)
 namespace {
@@ -4204,6 +4212,8 @@ int cvo_reducer_create(int device, int max_clouds, int max_points, cvo_reducer* 
     return CVO_OK;
 }
 int cvo_reducer_destroy(cvo_reducer r) {
+    if (r && r->live_maps > 0)
+        return fail(CVO_ERR_INVALID, std::to_string(r->live_maps) + " cvo_maps object(s) still live on this reducer: destroy the maps first");
     if (r) reducer_release(r);
     return CVO_OK;
 }
@@ -4292,6 +4302,377 @@ int cvo_view_device_clouds(cvo_reducer r, int views, const cvo_view* v, const cv
                            const cvo_viewed_cloud* dst, int* n_out, int* relation_counts, void* cloud_stream) {
     int rc = view_check(r, views, v, cams, p, observed, dst); if (rc) return rc;
     return view_points(r, views, v, cams, p, observed, dst, n_out, relation_counts, cloud_stream);
+}
+// ---- resident maps (cvo_map_kernels.hip; cvo_hip.h, "Resident maps"): voxel maps that stay on the device between calls.  The object owns the
+// maps' rows (twice: a compaction moves them to the other side), their tables and block counts, and a descriptor table of its own (a MapDesc per
+// map of a call); an update's fusion passes run in the reducer's scratch, a group per region of map_layout, with the reducer's descriptor table,
+// counts and stream.  A call's figures are four ints per map of the call in the reducer's counts.
+struct cvo_maps_s {
+    cvo_reducer r = nullptr;
+    int max_maps = 0, max_rows = 0; float voxel = 0.f;
+    char* mem = nullptr; size_t bytes = 0, map_bytes = 0;             // all maps' device memory, a map's share
+    int* d_live = nullptr;                                            // max_maps ints at the front of mem
+    MapDesc* d_desc = nullptr; MapDesc* h_desc = nullptr;             // max_maps records: the device's and the pinned twin
+    std::vector<int> rows; std::vector<char> side;                    // per map: its rows (dead ones included), which side holds them
+};
+extern "C++" {
+namespace {
+constexpr int MAP_FIGURES = 4;                                        // per map of a call: cells or rows out, births, refusal bits, unused
+// a group's region of the scratch in an update: a fusion's arrays with one row per point (the cap is the group's points), and cell_row
+struct MapLayout { size_t keys, masks, sums, best, lowest, members, row, slot_of, row_slot, cell_row, block_heads, bytes; };
+MapLayout map_layout(int max_points) {
+    const size_t P = (size_t)max_points, S = 2 * P, B = (P + 255) / 256 + FUSE_MAX_MEMBERS;
+    MapLayout L; size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += up16(bytes); return o; };
+    L.keys = take(8 * S); L.masks = take(8 * S); L.sums = take(64 * P); L.best = take(8 * P); L.lowest = take(4 * S); L.members = take(4 * S);
+    L.row = take(4 * S); L.slot_of = take(4 * P); L.row_slot = take(4 * P); L.cell_row = take(4 * P); L.block_heads = take(4 * B); L.bytes = at;
+    return L;
+}
+// a map's share of the object's memory: two sides of rows, the table, the block counts
+struct MapRowsLayout { size_t keys, sums, count, mask, last_stamp, born, bytes; };
+MapRowsLayout map_rows_layout(int max_rows) {
+    const size_t R = (size_t)max_rows;
+    MapRowsLayout L; size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 127) & ~(size_t)127; return o; };   // (arrays start on cache lines)
+    L.sums = take(64 * R); L.keys = take(8 * R); L.mask = take(8 * R); L.count = take(4 * R); L.last_stamp = take(4 * R); L.born = take(4 * R); L.bytes = at;
+    return L;
+}
+inline size_t map_table_keys(int max_rows) { return (16 * (size_t)max_rows + 127) & ~(size_t)127; }
+inline size_t map_table_rows(int max_rows) { return (8 * (size_t)max_rows + 127) & ~(size_t)127; }
+inline size_t map_blocks(cvo_maps m) { return (size_t)std::max(m->max_rows, m->r->max_points) / 256 + 1; }
+void maps_release(cvo_maps m) {
+    (void)hipSetDevice(m->r->device);
+    (void)hipStreamSynchronize(m->r->stream);
+    if (m->mem) (void)hipFree(m->mem);
+    if (m->d_desc) (void)hipFree(m->d_desc);
+    if (m->h_desc) (void)hipHostFree(m->h_desc);
+    --m->r->live_maps;
+    delete m;
+}
+MapRows map_rows_at(char* base, const MapRowsLayout& L) {
+    MapRows R;
+    R.keys = reinterpret_cast<unsigned long long*>(base + L.keys); R.sums = reinterpret_cast<long long*>(base + L.sums);
+    R.count = reinterpret_cast<unsigned*>(base + L.count); R.mask = reinterpret_cast<unsigned long long*>(base + L.mask);
+    R.last_stamp = reinterpret_cast<int*>(base + L.last_stamp); R.born = reinterpret_cast<int*>(base + L.born);
+    return R;
+}
+// record q of a call: map `k` as it stands, its figures at the reducer's counts 4 q ..; everything a single kind of call sets stays 0
+MapDesc& maps_desc(cvo_maps m, int q, int k) {
+    MapDesc& D = m->h_desc[q];
+    std::memset(&D, 0, sizeof(D));
+    const MapRowsLayout L = map_rows_layout(m->max_rows);
+    char* base = m->mem + up16(4 * (size_t)m->max_maps) + (size_t)k * m->map_bytes;
+    base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 127) & ~(uintptr_t)127);
+    D.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); D.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
+    char* table = base + 2 * L.bytes;
+    D.tkeys = reinterpret_cast<unsigned long long*>(table); D.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
+    D.block_heads = reinterpret_cast<int*>(table + map_table_keys(m->max_rows) + map_table_rows(m->max_rows));
+    D.live = m->d_live + k;
+    D.total = m->r->d_total + MAP_FIGURES * q;
+    D.rows = m->rows[k]; D.slots = 2 * m->max_rows;
+    return D;
+}
+int maps_check_list(cvo_maps m, int count, const int* maps, const char* what) {
+    if (!m) return fail(CVO_ERR_INVALID, "null maps object");
+    if (count < 1 || count > m->max_maps) return fail(CVO_ERR_INVALID, std::string(what) + " " + std::to_string(count) + " is outside 1 .. max_maps " + std::to_string(m->max_maps));
+    if (!maps) return fail(CVO_ERR_INVALID, "null argument: maps");
+    std::vector<char> seen(m->max_maps, 0);
+    for (int q = 0; q < count; ++q) {
+        if (maps[q] < 0 || maps[q] >= m->max_maps) return fail(CVO_ERR_INVALID, "maps[" + std::to_string(q) + "] " + std::to_string(maps[q]) + " is outside 0 .. " + std::to_string(m->max_maps - 1));
+        if (seen[maps[q]]) return fail(CVO_ERR_INVALID, "map " + std::to_string(maps[q]) + " appears twice in the call");
+        seen[maps[q]] = 1;
+    }
+    return CVO_OK;
+}
+int maps_check_update(cvo_maps m, int groups, const int* maps, const int* group_first, const int* stamps, int sign) {
+    int rc = maps_check_list(m, groups, maps, "groups"); if (rc) return rc;
+    if (sign != CVO_MAP_INTEGRATE && sign != CVO_MAP_REMOVE && sign != CVO_MAP_REMOVE_PRESENT)
+        return fail(CVO_ERR_INVALID, "sign " + std::to_string(sign) + " is neither +1 (integrate), -1 (remove) nor -2 (remove what is still there)");
+    if (!group_first || !stamps) return fail(CVO_ERR_INVALID, "null argument");
+    return CVO_OK;
+}
+int maps_check_stamps(int groups, const int* group_first, const int* stamps) {
+    for (int g = 0; g < groups; ++g)
+        for (int k = group_first[g]; k < group_first[g + 1]; ++k)
+            if (stamps[k] < 0) return fail(CVO_ERR_INVALID, "group " + std::to_string(g) + " member " + std::to_string(k - group_first[g]) + ": stamp " + std::to_string(stamps[k]) + " is negative");
+    return CVO_OK;
+}
+// the fuser's own validation of an update's members: a MEAN fusion at the maps' voxel that keeps every cell and writes nothing
+int maps_check_clouds(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_member* members, const int* stamps, int sign) {
+    int rc = maps_check_update(m, groups, maps, group_first, stamps, sign); if (rc) return rc;
+    const cvo_fuse_params P = {m->voxel, CVO_REDUCE_MEAN, 1, 1};
+    std::vector<cvo_fused_cloud> none(groups); std::memset(none.data(), 0, sizeof(cvo_fused_cloud) * groups);
+    if ((rc = fuse_check(m->r, groups, group_first, members, &P, none.data()))) return rc;
+    return maps_check_stamps(groups, group_first, stamps);
+}
+int maps_check_frames(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step,
+                      const cvo_camera* cams, const int* stamps, int sign) {
+    int rc = maps_check_update(m, groups, maps, group_first, stamps, sign); if (rc) return rc;
+    const cvo_fuse_params P = {m->voxel, CVO_REDUCE_MEAN, 1, 1};
+    std::vector<cvo_fused_cloud> none(groups); std::memset(none.data(), 0, sizeof(cvo_fused_cloud) * groups);
+    if ((rc = fuse_frames_check(m->r, groups, group_first, members, width, height, step, cams, &P, none.data()))) return rc;
+    return maps_check_stamps(groups, group_first, stamps);
+}
+// the edges of a maps call: reducer_run's, with the call's MapDesc records copied beside the reducer's table (fuse_bytes of it; 0: none)
+int maps_run(cvo_maps m, int n_maps, size_t fuse_bytes, void* stream, const std::function<hipError_t()>& queue) {
+    cvo_reducer r = m->r;
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
+    if (fuse_bytes) HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, fuse_bytes, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemcpyAsync(m->d_desc, m->h_desc, sizeof(MapDesc) * (size_t)n_maps, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_total, 0, sizeof(int) * MAP_FIGURES * (size_t)n_maps, r->stream));
+    const hipError_t e = queue();
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("resident maps kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * MAP_FIGURES * (size_t)n_maps, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
+    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
+    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    return CVO_OK;
+}
+// src's item k is member k of the call, pose(k) its 12 floats.  A group with points gets a FuseGroupDesc, its members with points FuseMemberDescs
+// behind them (fuse_points' tables), and its map a MapDesc; a group without points changes nothing.
+int maps_update(cvo_maps m, int groups, const int* maps, const int* group_first, const PointSource& src, const std::function<const float*(int)>& pose,
+                const int* stamps, int sign, void* stream) {
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    const MapLayout L = map_layout(r->max_points);
+    std::vector<int> of; of.reserve(groups);
+    int live_members = 0;
+    for (int g = 0; g < groups; ++g) {
+        const int before = live_members;
+        for (int k = group_first[g]; k < group_first[g + 1]; ++k) live_members += src.n(k) > 0;
+        if (live_members > before) of.push_back(g);
+    }
+    const int live = (int)of.size();
+    if (live == 0) return CVO_OK;
+    DescTable tab{r};
+    FuseGroupDesc* hg; const FuseGroupDesc* dg; FuseMemberDesc* hm; const FuseMemberDesc* dm; FrameDesc* hf = nullptr; const FrameDesc* df = nullptr;
+    int rc;
+    if ((rc = tab.take(live, &hg, &dg)) || (rc = tab.take(live_members, &hm, &dm))) return rc;
+    if (src.frames() && (rc = tab.take(live_members, &hf, &df))) return rc;
+    int n_max = 0, group_max = 0, qm = 0;
+    for (int q = 0; q < live; ++q) {
+        const int g = of[q];
+        FuseGroupDesc& G = hg[q];
+        std::memset(&G, 0, sizeof(G));                                // (no output arrays: the cells stay in the scratch)
+        MapDesc& D = maps_desc(m, q, maps[g]);
+        G.first_member = qm;
+        int at = 0, blocks = 0;
+        for (int k = group_first[g]; k < group_first[g + 1]; ++k) {
+            D.stamps[k - group_first[g]] = stamps[k];
+            const int n = src.n(k);
+            if (n == 0) continue;
+            FuseMemberDesc& M = hm[qm];
+            src.fill(k, M, hf, qm);
+            ++qm;
+            std::memcpy(M.pose, pose(k), sizeof(M.pose));
+            M.group = q; M.base = at; M.first_block = blocks; M.n = n; M.bit = k - group_first[g]; M.pad_ = 0;
+            at += n; blocks += (n + 255) / 256;
+            n_max = std::max(n_max, n);
+        }
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * L.bytes;
+        G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(base + L.masks);
+        G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
+        G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
+        G.block_heads = reinterpret_cast<int*>(base + L.block_heads); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
+        G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
+        G.total = D.total;
+        G.n = at; G.slots = 2 * at; G.cap = at; G.rows_cap = at;
+        G.n_blocks = blocks; G.n_members = qm - G.first_member;
+        D.cell_row = reinterpret_cast<int*>(base + L.cell_row);
+        D.group = q; D.sign = sign;
+        group_max = std::max(group_max, at);
+    }
+    const float voxel = m->voxel;
+    if ((rc = maps_run(m, live, tab.used, stream, [&] {
+            const hipError_t e = launch_fuse_cells(dg, live, dm, df, live_members, n_max, 2 * group_max, group_max, voxel, r->stream);
+            return e != hipSuccess ? e : launch_map_lookup(m->d_desc, live, dg, group_max, r->stream); })))
+        return rc;
+    // the figures: refuse with every map as it was, or go on
+    int cells_max = 0;
+    for (int q = 0; q < live; ++q) {
+        const int* fig = r->h_total + MAP_FIGURES * q;
+        const int k = maps[of[q]];
+        const std::string who = "map " + std::to_string(k) + " (group " + std::to_string(of[q]) + "): ";
+        if (fig[2] & 1) return fail(CVO_ERR_INVALID, who + "the integration would take a cell's count above " + std::to_string(CVO_MAP_MAX_COUNT));
+        if (fig[2] & 2) return fail(CVO_ERR_INVALID, who + "the removal names a cell that is absent from the map");
+        if (fig[2] & 4) return fail(CVO_ERR_INVALID, who + "the removal takes more members out of a cell than its count");
+        if (fig[2] & 8) return fail(CVO_ERR_INVALID, who + "the removal's group is partly present in a row: some of the stamps of the members that touch a cell are in its view_mask, some are not");
+        if ((long long)m->rows[k] + fig[1] > m->max_rows)
+            return fail(CVO_ERR_INVALID, who + "its " + std::to_string(m->rows[k]) + " rows and the integration's " + std::to_string(fig[1]) + " new cells are above max_rows " + std::to_string(m->max_rows));
+        cells_max = std::max(cells_max, fig[0]);
+    }
+    const hipError_t e = launch_map_merge(m->d_desc, live, dg, cells_max, r->stream);   // behind it runs every later call on the reducer
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("resident maps kernel launch: ") + hipGetErrorString(e));
+    for (int q = 0; q < live; ++q) m->rows[maps[of[q]]] += r->h_total[MAP_FIGURES * q + 1];
+    return CVO_OK;
+}
+int maps_check_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter, const cvo_map_cloud* dst) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    if (!filter || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    for (int q = 0; q < count; ++q) {
+        const std::string who = "map " + std::to_string(maps[q]) + ": ";
+        const cvo_map_cloud& d = dst[q];
+        if (filter[q].min_views < 0 || filter[q].min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(filter[q].min_views) + " is outside 0 .. 64");
+        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+        if ((rc = check_out_arrays(m->r->device, who, {{d.xyz, 12ll * d.cap, 4, "dst xyz", false}, {d.feat, 20ll * d.cap, 4, "dst feat", false},
+                {d.count, 4ll * d.cap, 4, "dst count", false}, {d.views, 4ll * d.cap, 4, "dst views", false}, {d.view_mask, 8ll * d.cap, 8, "dst view_mask", false},
+                {d.last_stamp, 4ll * d.cap, 4, "dst last_stamp", false}, {d.born, 4ll * d.cap, 4, "dst born", false}, {d.row, 4ll * d.cap, 4, "dst row", false}})))
+            return rc;
+    }
+    return CVO_OK;
+}
+int maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter, const cvo_map_cloud* dst, int* n_out, void* stream) {
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    HIP_TRY(hipSetDevice(m->r->device));
+    int rows_max = 0, cap_max = 0;
+    for (int q = 0; q < count; ++q) {
+        n_out[q] = 0;
+        MapDesc& D = maps_desc(m, q, maps[q]);
+        const cvo_map_cloud& d = dst[q];
+        D.out_xyz = static_cast<float*>(d.xyz); D.out_feat = static_cast<float*>(d.feat); D.out_count = static_cast<int*>(d.count);
+        D.out_views = static_cast<int*>(d.views); D.out_view_mask = static_cast<unsigned long long*>(d.view_mask);
+        D.out_last_stamp = static_cast<int*>(d.last_stamp); D.out_born = static_cast<int*>(d.born); D.out_row = static_cast<int*>(d.row);
+        D.cap = d.cap; D.min_points = filter[q].min_points; D.min_views = filter[q].min_views; D.min_last_stamp = filter[q].min_last_stamp;
+        rows_max = std::max(rows_max, D.rows); cap_max = std::max(cap_max, d.cap);
+    }
+    if (rows_max == 0) return CVO_OK;
+    int rc = maps_run(m, count, 0, stream, [&] { return launch_map_extract(m->d_desc, count, rows_max, cap_max > 0, m->r->stream); });
+    if (rc) return rc;
+    for (int q = 0; q < count; ++q) n_out[q] = m->r->h_total[MAP_FIGURES * q];
+    return CVO_OK;
+}
+int maps_check_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    if (!keep) return fail(CVO_ERR_INVALID, "null argument: keep");
+    for (int q = 0; q < count; ++q) {
+        const std::string who = "map " + std::to_string(maps[q]) + ": ";
+        if (keep[q].min_views < 0 || keep[q].min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(keep[q].min_views) + " is outside 0 .. 64");
+        const long long rows = m->rows[maps[q]];
+        if ((rc = check_out_arrays(m->r->device, who, {{drop ? drop[q] : nullptr, rows, 1, "drop", false}, {new_row ? new_row[q] : nullptr, 4 * rows, 4, "new_row", false}}))) return rc;
+    }
+    return CVO_OK;
+}
+int maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row, int* rows_out, void* stream) {
+    HIP_TRY(hipSetDevice(m->r->device));
+    int rows_max = 0;
+    for (int q = 0; q < count; ++q) {
+        if (rows_out) rows_out[q] = 0;
+        MapDesc& D = maps_desc(m, q, maps[q]);
+        D.drop = drop ? static_cast<const uint8_t*>(drop[q]) : nullptr; D.new_row = new_row ? static_cast<int*>(new_row[q]) : nullptr;
+        D.min_last_stamp = keep[q].min_last_stamp; D.min_views = keep[q].min_views; D.probation_from = keep[q].probation_from;
+        rows_max = std::max(rows_max, D.rows);
+    }
+    if (rows_max == 0) return CVO_OK;
+    int rc = maps_run(m, count, 0, stream, [&] { return launch_map_compact(m->d_desc, count, rows_max, m->r->stream); });
+    if (rc) return rc;
+    for (int q = 0; q < count; ++q) {
+        const int k = maps[q];
+        if (m->rows[k] > 0) { m->rows[k] = m->r->h_total[MAP_FIGURES * q]; m->side[k] ^= 1; }   // (a map without rows was not touched)
+        if (rows_out) rows_out[q] = m->rows[k];
+    }
+    return CVO_OK;
+}
+}  // namespace
+}  // extern "C++"
+int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out) {
+    if (!out) return fail(CVO_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (!r) return fail(CVO_ERR_INVALID, "null reducer");
+    if (max_maps < 1 || max_maps > r->max_clouds) return fail(CVO_ERR_INVALID, "max_maps " + std::to_string(max_maps) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if (max_rows < 1 || max_rows > CVO_MAP_MAX_ROWS) return fail(CVO_ERR_INVALID, "max_rows " + std::to_string(max_rows) + " is outside 1 .. " + std::to_string(CVO_MAP_MAX_ROWS));
+    if (!(std::isfinite(voxel) && voxel > 0.f)) return fail(CVO_ERR_INVALID, "voxel " + std::to_string(voxel) + " is not a finite size above 0");
+    if ((size_t)max_maps * map_layout(r->max_points).bytes > r->scratch_bytes)
+        return fail(CVO_ERR_INVALID, "the reducer's scratch (" + std::to_string(r->scratch_bytes) + " bytes) has no room for " + std::to_string(max_maps) + " groups of max_points " +
+                                     std::to_string(r->max_points) + " (" + std::to_string(map_layout(r->max_points).bytes) + " bytes each): create the reducer with a larger max_points or more max_clouds");
+    if ((size_t)max_maps * MAP_FIGURES > (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "the reducer's counts have no room");   // (never: 4 of 16 per cloud)
+    HIP_TRY(hipSetDevice(r->device));
+    cvo_maps m = new cvo_maps_s();
+    m->r = r; m->max_maps = max_maps; m->max_rows = max_rows; m->voxel = voxel;
+    m->rows.assign(max_maps, 0); m->side.assign(max_maps, 0);
+    ++r->live_maps;
+    m->map_bytes = 2 * map_rows_layout(max_rows).bytes + map_table_keys(max_rows) + map_table_rows(max_rows) + ((4 * map_blocks(m) + 127) & ~(size_t)127);
+    m->bytes = up16(4 * (size_t)max_maps) + 128 + (size_t)max_maps * m->map_bytes;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->mem), m->bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->d_desc), sizeof(MapDesc) * (size_t)max_maps);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&m->h_desc), sizeof(MapDesc) * (size_t)max_maps, hipHostMallocDefault);
+    if (e == hipSuccess) {                                            // every table empty (all ones), every live count 0
+        m->d_live = reinterpret_cast<int*>(m->mem);
+        e = hipMemsetAsync(m->mem, 0, up16(4 * (size_t)max_maps), r->stream);
+        for (int k = 0; k < max_maps && e == hipSuccess; ++k) e = hipMemsetAsync(maps_desc(m, 0, k).tkeys, 0xFF, 16 * (size_t)max_rows, r->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    }
+    if (e != hipSuccess) { maps_release(m); return fail(CVO_ERR_HIP, std::string("cvo_maps_create: ") + hipGetErrorString(e)); }
+    *out = m;
+    return CVO_OK;
+}
+int cvo_maps_destroy(cvo_maps m) {
+    if (m) maps_release(m);
+    return CVO_OK;
+}
+int cvo_maps_info(cvo_maps m, int* max_maps, int* max_rows, float* voxel, long long* device_bytes) {
+    if (!m) return fail(CVO_ERR_INVALID, "null maps object");
+    if (max_maps) *max_maps = m->max_maps;
+    if (max_rows) *max_rows = m->max_rows;
+    if (voxel) *voxel = m->voxel;
+    if (device_bytes) *device_bytes = (long long)(m->bytes + sizeof(MapDesc) * (size_t)m->max_maps);
+    return CVO_OK;
+}
+int cvo_maps_clear(cvo_maps m, int count, const int* maps, void* stream) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    HIP_TRY(hipSetDevice(m->r->device));
+    for (int q = 0; q < count; ++q) maps_desc(m, q, maps[q]);
+    if ((rc = maps_run(m, count, 0, stream, [&] { return launch_map_clear(m->d_desc, count, 2 * m->max_rows, m->r->stream); }))) return rc;
+    for (int q = 0; q < count; ++q) m->rows[maps[q]] = 0;
+    return CVO_OK;
+}
+int cvo_maps_rows(cvo_maps m, int count, const int* maps, int* rows, int* live_rows) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    for (int q = 0; q < count && rows; ++q) rows[q] = m->rows[maps[q]];
+    if (!live_rows) return CVO_OK;
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipMemcpyAsync(r->h_total, m->d_live, sizeof(int) * (size_t)m->max_maps, hipMemcpyDeviceToHost, r->stream));   // (max_maps <= max_clouds ints)
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    for (int q = 0; q < count; ++q) live_rows[q] = r->h_total[maps[q]];
+    return CVO_OK;
+}
+int cvo_check_maps_integrate_clouds(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_member* members, const int* stamps, int sign) {
+    return maps_check_clouds(m, groups, maps, group_first, members, stamps, sign);
+}
+int cvo_check_maps_integrate_frames(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step,
+                                    const cvo_camera* cams, const int* stamps, int sign) {
+    return maps_check_frames(m, groups, maps, group_first, members, width, height, step, cams, stamps, sign);
+}
+int cvo_maps_integrate_clouds(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_member* members, const int* stamps, int sign,
+                              void* cloud_stream) {
+    int rc = maps_check_clouds(m, groups, maps, group_first, members, stamps, sign); if (rc) return rc;
+    PointSource src; src.cloud = [&](int k) { return &members[k].cloud; };
+    return maps_update(m, groups, maps, group_first, src, [&](int k) { return members[k].pose; }, stamps, sign, cloud_stream);
+}
+int cvo_maps_integrate_frames(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step,
+                              const cvo_camera* cams, const int* stamps, int sign, void* image_stream) {
+    int rc = maps_check_frames(m, groups, maps, group_first, members, width, height, step, cams, stamps, sign); if (rc) return rc;
+    PointSource src;
+    src.frame = [&](int k, FrameDesc& F) { frame_desc(members[k].image, width, height, step, cams[members[k].cam], F); };
+    src.frame_n = frame_sub(width, step) * frame_sub(height, step);
+    return maps_update(m, groups, maps, group_first, src, [&](int k) { return members[k].pose; }, stamps, sign, image_stream);
+}
+int cvo_check_maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter, const cvo_map_cloud* dst) {
+    return maps_check_extract(m, count, maps, filter, dst);
+}
+int cvo_maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter, const cvo_map_cloud* dst, int* n_out, void* stream) {
+    int rc = maps_check_extract(m, count, maps, filter, dst); if (rc) return rc;
+    return maps_extract(m, count, maps, filter, dst, n_out, stream);
+}
+int cvo_check_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row) {
+    return maps_check_compact(m, count, maps, keep, drop, new_row);
+}
+int cvo_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row, int* rows_out, void* stream) {
+    int rc = maps_check_compact(m, count, maps, keep, drop, new_row); if (rc) return rc;
+    return maps_compact(m, count, maps, keep, drop, new_row, rows_out, stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

@@ -320,6 +320,35 @@ struct FuseMemberDesc {
     int pad_;
 };
 static_assert(sizeof(FuseMemberDesc) == 112, "FuseMemberDesc layout");
+// one map of a resident-maps call (cvo_map_kernels.hip; not in the reference; cvo_hip.h, "Resident maps"): the grid's second dimension in every
+// pass.  A map's rows are a structure of arrays, one array per field, except the 8 sums of a row, which lie together (64 bytes: a wave's rows
+// are whole cache lines in the merge's scattered reads and in the extract's dense ones).  The rows exist twice: `to` is where a compaction
+// moves them (the call's host side then swaps the two).  The table maps a cell key to its row: 2 x max_rows slots, open addressing.
+struct MapRows {
+    unsigned long long* keys;      // the row's cell key
+    long long* sums;               // 8 per row
+    unsigned* count;
+    unsigned long long* mask;      // view_mask
+    int* last_stamp; int* born;
+};
+struct MapDesc {
+    MapRows at, to;
+    unsigned long long* tkeys; int* trow;   // slots: key (all ones = empty) and row
+    int* live;                     // the map's rows with count >= 1
+    int* block_heads;              // one per 256 rows (extract, compact) or per 256 call-cells (an update's births), then their exclusive sum
+    int* cell_row;                 // an update: the map row of the call-cell of rank r; -1: absent; after the merge -(row) - 1 for a cell born there
+    int* total;                    // the call's figures: [0] rows out (extract, compact) / call-cells, [1] an update's births, [2] its refusal bits
+    float* out_xyz; float* out_feat; int* out_count; int* out_views; unsigned long long* out_view_mask;   // extract's arrays, all but xyz, feat may be null
+    int* out_last_stamp; int* out_born; int* out_row;
+    const uint8_t* drop; int* new_row;   // compact's, either may be null
+    int rows, slots, cap;
+    int group;                     // an update: its group in the launch's FuseGroupDesc table
+    int sign;                      // +1 integrate, -1 remove, -2 remove what is still there (CVO_MAP_*)
+    int min_points, min_views, min_last_stamp, probation_from;   // extract's filter / compact's keep rule
+    int pad_;
+    int stamps[64];                // an update: the stamp of member number m of the group
+};
+static_assert(sizeof(MapRows) == 48 && sizeof(MapDesc) == 520, "MapDesc layout");
 // one view of a viewing call (cvo_view_kernels.hip; not in the reference; cvo_hip.h, "Viewing clouds"): a cloud (n may be 0: its images are
 // still written), its pose and camera, its part of the reducer's scratch and the caller's arrays.  The grid's second dimension in every pass.
 struct ViewDesc {

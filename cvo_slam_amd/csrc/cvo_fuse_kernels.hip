@@ -123,10 +123,11 @@ __global__ __launch_bounds__(RB) void cvo_fuse_write_kernel(const FuseGroupDesc*
 
 namespace {
 // groups, mem: the device's copies of the two tables: every group with points, every member with n > 0 (members of a group consecutive, in order).
-// n_max: the largest member n; slots_max, rows_max: the largest slots and rows_cap among the groups.
+// n_max: the largest member n; slots_max, rows_max: the largest slots and rows_cap among the groups.  write == false: the passes clear .. gather
+// alone -- the groups' cells with their undivided sums stay in the scratch for the caller's own passes (cvo_map_kernels.hip).
 template <class Src>
 hipError_t launch_fuse(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, typename Src::Table T, int n_members, int n_max, int slots_max,
-                       int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s) {
+                       int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s, bool write = true) {
     if (n_groups <= 0 || n_members <= 0 || n_max <= 0) return hipSuccess;
     const dim3 blk(RB), pts((n_max + RB - 1) / RB, n_members);
     const long long clear = slots_max > 8ll * rows_max ? slots_max : 8ll * rows_max;
@@ -136,7 +137,7 @@ hipError_t launch_fuse(const FuseGroupDesc* groups, int n_groups, const FuseMemb
     hipLaunchKernelGGL(cvo_fuse_offsets_kernel, dim3(1, n_groups), blk, 0, s, groups);
     hipLaunchKernelGGL(cvo_fuse_rows_kernel, pts, blk, 0, s, groups, mem, min_points, min_views);
     hipLaunchKernelGGL(cvo_fuse_gather_kernel<Src>, pts, blk, 0, s, groups, mem, T, voxel, mode);
-    if (rows_max > 0) hipLaunchKernelGGL(cvo_fuse_write_kernel<Src>, dim3((8 * rows_max + RB - 1) / RB, n_groups), blk, 0, s, groups, mem, T, mode);
+    if (rows_max > 0 && write) hipLaunchKernelGGL(cvo_fuse_write_kernel<Src>, dim3((8 * rows_max + RB - 1) / RB, n_groups), blk, 0, s, groups, mem, T, mode);
     return hipGetLastError();
 }
 }  // namespace
@@ -149,5 +150,12 @@ hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const F
                               int rows_max, float voxel, int mode, int min_points, int min_views, hipStream_t s) {
     const FrameSource::Table T = {frames};
     return launch_fuse<FrameSource>(groups, n_groups, mem, T, n_members, n, slots_max, rows_max, voxel, mode, min_points, min_views, s);
+}
+// a fusion's cells without its write: MEAN, every cell kept (min_points = min_views = 1); frames == nullptr: the members are clouds
+hipError_t launch_fuse_cells(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n_max, int slots_max,
+                             int rows_max, float voxel, hipStream_t s) {
+    const FrameSource::Table T = {frames};
+    return frames ? launch_fuse<FrameSource>(groups, n_groups, mem, T, n_members, n_max, slots_max, rows_max, voxel, 0, 1, 1, s, false)
+                  : launch_fuse<CloudSource>(groups, n_groups, mem, CloudSource::Table(), n_members, n_max, slots_max, rows_max, voxel, 0, 1, 1, s, false);
 }
 }  // namespace cvohip

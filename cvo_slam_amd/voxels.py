@@ -96,6 +96,35 @@ def split_source(source, offsets):
     return member.to(torch.int32), (g - o[member]).to(torch.int32)
 
 
+def carve_mask(rows: int, row, source, relation, relations=(1,)):
+    """The `drop` mask of CvoMaps.compact for one map of `rows` rows (free-space carving): byte r is 1 when a viewed row of the map's extract
+    has a relation in `relations` (1: the camera saw through the point).  row: the extract's "row" output (the map's row number per extracted
+    row); source, relation: the "source" and "relation" outputs of CvoReducer.view of that extract.  All three are numpy arrays or torch
+    tensors of one device; the mask is a uint8 array of their kind."""
+    if int(rows) < 0:
+        raise ValueError(f"carve_mask: rows {rows} is negative")
+    if len(source) != len(relation):
+        raise ValueError(f"carve_mask: {len(source)} sources but {len(relation)} relations")
+    if isinstance(row, np.ndarray) or not hasattr(row, "device"):
+        row = np.asarray(row).astype(np.int64); src = np.asarray(source).astype(np.int64)
+        if src.size and (src.min() < 0 or src.max() >= row.shape[0]):
+            raise ValueError("carve_mask: a source outside the extract's rows")
+        hit = np.isin(np.asarray(relation), list(relations))
+        out = np.zeros(int(rows), np.uint8)
+        if row.size and (row.min() < 0 or row.max() >= int(rows)):
+            raise ValueError("carve_mask: a row number outside the map's rows")
+        out[row[src[hit]]] = 1
+        return out
+    import torch
+    src = source.to(torch.int64)
+    hit = torch.zeros_like(src, dtype=torch.bool)
+    for v in relations:
+        hit |= relation == int(v)
+    out = torch.zeros(int(rows), dtype=torch.uint8, device=row.device)
+    out[row.to(torch.int64)[src[hit]]] = 1
+    return out
+
+
 def lift(map, per_row_values, fill):
     """per_row_values[map[i]] for every point i of the dense cloud, `fill` where map[i] == -1 (an invalid point or a dropped cell).  map and
     per_row_values are both numpy arrays or both torch tensors (of one device); values may have trailing dimensions."""

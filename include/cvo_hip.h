@@ -699,6 +699,108 @@ int cvo_check_view_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo
 int cvo_view_device_clouds(cvo_reducer r, int views, const cvo_view* v, const cvo_camera* cams, const cvo_view_params* p /* one for all */,
                            const cvo_device_image* observed /* NULL or views */, const cvo_viewed_cloud* dst, int* n_out /* views, host */,
                            int* relation_counts /* views x 4, host, may be NULL */, void* cloud_stream);
+/* ---- Resident maps (not in the reference): voxel maps that stay in device memory between calls, one per tracker stream, to which posed clouds or
+ * frames are added and from which they are taken away again.  A cvo_maps object holds max_maps independent maps of at most max_rows rows at one
+ * voxel size.  It is created on an existing cvo_reducer: every call uses the reducer's scratch and stream, and nothing is allocated after
+ * creation.  Every call takes a list of maps (each map at most once) and handles all of them in the same launches, the map in the grid's second
+ * dimension.  As everywhere in the reducer, every output's bits depend on the calls alone: integer atomics only, and the table's layout never
+ * shows.
+ *
+ * The definition, per map.
+ *   row: a map is an ordered list of rows, one per cell that was ever occupied since the last compaction.  A row holds the cell key (the
+ *     reducer's 63-bit key of the moved position at `voxel`), eight signed 64-bit sums of llrint((double)v * 2^24), count (unsigned), view_mask
+ *     (64 bits), last_stamp and born (int32).  A table from key to row exists (2 x max_rows slots); nothing about it reaches an output.
+ *   member: the fuser's member (cvo_fuse_member, or cvo_fuse_frame with width, height, step and cameras) plus an int32 stamp >= 0, one per member
+ *     of the call, in HOST memory.  Moved position, validity and cell are the fuser's rules, bit for bit.
+ *   the update's own cells: an update of one map with a group of 1 .. 64 members first forms the group's cells exactly as cvo_fuse_device_clouds /
+ *     cvo_fuse_device_frames does in CVO_REDUCE_MEAN with min_points = min_views = 1 and the cap at the group's points: every cell with its
+ *     undivided sums, its member count, its mask of member numbers and its rank in the fusion's row order (ascending lowest global index).
+ *   integrate (sign = +1): every call-cell in rank order.  Key in the map: the sums are added, count += members, view_mask |= the OR of
+ *     1 << (stamp & 63) over the members that touched the cell, last_stamp = max(last_stamp, those stamps), and if count was 0 (a dead row is
+ *     revived) born = the least of those stamps.  Key absent: the cell is born; its row number is rows + (its rank among this call's born
+ *     cells), sums, count and mask are the call's, born the least and last_stamp the largest of its stamps.
+ *   remove (sign = -1), with the members, poses and stamps that were integrated: the sums and the count are subtracted, the stamps' bits are
+ *     cleared, last_stamp and born stay.  A row whose count reaches 0 is dead: it keeps its place and its key until a compaction.
+ *   remove what is still there (sign = -2, CVO_MAP_REMOVE_PRESENT): the removal for maps whose compactions drop LIVE rows (carving, probation;
+ *     below).  Per call-cell, with B the OR of 1 << (stamp & 63) over the members that touched it: key absent -- the cell is skipped; the row's
+ *     view_mask has none of B -- skipped (the row was dropped with these members in it and made again by others); it has all of B -- removed as
+ *     by sign -1 (more members than the count: refused); it has some of B -- the call is refused.  This is exact as long as the stamps of the
+ *     members a map holds are distinct modulo 64, and a group's members went in together or one per group (a group of one member can never
+ *     be partly present).
+ *   refusals after the count: an integration that would take rows above max_rows or a cell's count above 16777215 (under which the sums stay
+ *     below 2^63), a removal of a cell that is absent or of more members than a cell's count: CVO_ERR_INVALID naming the first offending map
+ *     of the call, with EVERY map unchanged.  For this an update runs in three steps: the fusion passes and a lookup-and-count pass; the call's
+ *     one host wait, for the per-map figures; then the launches that write the maps, queued on the reducer's stream, behind which every later
+ *     call on the reducer runs.  The members are read in the first step only.
+ *   extract: map k is filtered by filter[k]: a row is kept when count >= max(1, min_points), popcount(view_mask) >= min_views and
+ *     last_stamp >= min_last_stamp.  Kept rows go out in ascending row number.  xyz and feat are (float)((double)sum / ((double)count *
+ *     16777216.0)), the reducer's MEAN expression: the result passes on as a cvo_device_cloud.  Optional outputs: count, views (int32),
+ *     view_mask (uint64), last_stamp, born, row (int32: the map's row number).  cap (0 .. 65535), n_out (always the FULL count), "no byte behind
+ *     row cap - 1" and "cap == 0 with every array NULL counts only" are cvo_reduce_device_clouds' rules.
+ *   compact: map k takes keep[k] and optionally a device byte per row, drop[k].  A row stays when count >= 1, last_stamp >= min_last_stamp,
+ *     (popcount(view_mask) >= min_views or born >= probation_from), and drop[k] is NULL or drop[k][row] == 0.  Surviving rows keep their order and
+ *     are renumbered from 0; the table is rebuilt from them; new_row[k] (optional, device, one int32 per old row) gets each old row's new number
+ *     or -1.  One call serves ageing, throwing out unconfirmed one-view cells after their probation, and free-space carving (drop from a view's
+ *     relation == 1 through its source and extract's row).
+ *   compaction and removal.  A compaction that drops only dead rows (min_last_stamp <= 0, min_views = 0, drop NULL) changes
+ *     no later call.  One that drops LIVE rows -- drop, min_views with probation_from, min_last_stamp -- takes members' points out of the map for
+ *     good: a later sign -1 removal of such a member is refused (its cell is absent), and if another member has made the cell again in between
+ *     it is NOT refused and subtracts what the row never received: sign -1 after such a compaction is unsupported.  Remove those members with
+ *     sign -2, which skips what is gone.  Then a map is no longer the fusion of its window: it is that fusion minus the dropped rows' members.
+ *   extract's ceiling: cap is at most 65535 (what a hand-over takes) and there is no paging: a map may hold up to max_rows rows, but one
+ *     extract call returns a map's kept rows whole only when the filter keeps at most 65535 (n_out still says how many there are).
+ *
+ * Consequences (tests/map_reading.py restates the definition; the tests hold the kernels to it byte for byte).  Integrating one group in one
+ * call with stamps 0 .. k-1 and extracting with (min_points, min_views) gives cvo_fuse_device_clouds' MEAN result for that group byte for byte
+ * and in row order: xyz, feat, count, views, view_mask.  Integrating the same members in any split into consecutive calls gives the same bytes:
+ * a cell is born in the earliest member that holds it and is ranked inside that call by lowest index -- ascending lowest global index -- and
+ * integer sums do not care about grouping.  Removing a member gives, as a SET of rows, the fusion of the remaining members (sums, count and mean
+ * bytes equal, mask bits at the stamps' positions) in the map's own order, birth order over its history: a sliding window costs two members a
+ * step.  Extract, compact with a rule that drops nothing live, extract: the same bytes.
+ *
+ * Memory: per map and row 2 x 92 bytes (the rows exist twice: a compaction moves them from one side to the other, no lane waits for another)
+ * and 24 for the table; cvo_maps_info gives the total.  In the reducer's scratch a group takes about 140 bytes per point of max_points;
+ * cvo_maps_create refuses when max_maps groups do not fit.
+ * Validation: CVO_ERR_INVALID, the message naming map, group, member and field: a null object; count / groups outside 1 .. max_maps; a map index
+ * outside 0 .. max_maps - 1 or given twice; sign not +1, -1 or -2; a null or negative stamp; everything cvo_check_fuse_clouds / cvo_check_fuse_frames
+ * checks on group_first, members, poses, cameras and the group's points against max_points; per extract output what cvo_check_fuse_clouds checks
+ * on its arrays (view_mask 8-byte aligned; cap outside 0 .. 65535); min_views outside 0 .. 64; drop and new_row not device memory of `rows`
+ * bytes / rows x 4 bytes.  At creation: max_maps outside 1 .. the reducer's max_clouds, max_rows outside 1 .. 1048575, voxel not finite or not
+ * > 0.  A refused call changes nothing and launches nothing that writes a map.  stream: the fuser's cloud_stream / image_stream rule.
+ * Destroy the maps before their reducer: cvo_reducer_destroy with live maps returns CVO_ERR_INVALID. */
+#define CVO_MAP_MAX_ROWS 1048575
+#define CVO_MAP_MAX_COUNT 16777215
+#define CVO_MAP_INTEGRATE 1
+#define CVO_MAP_REMOVE (-1)
+#define CVO_MAP_REMOVE_PRESENT (-2)
+typedef struct cvo_maps_s* cvo_maps;
+typedef struct cvo_map_filter { int min_points; int min_views; int min_last_stamp; int pad_; } cvo_map_filter;         /* 16 bytes */
+typedef struct cvo_map_keep { int min_last_stamp; int min_views; int probation_from; int pad_; } cvo_map_keep;         /* 16 bytes */
+typedef struct cvo_map_cloud { void *xyz, *feat, *count, *views, *view_mask, *last_stamp, *born, *row; int cap; int pad_; } cvo_map_cloud;   /* 72 bytes */
+int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out);
+int cvo_maps_destroy(cvo_maps m);
+/* the creation values and the device bytes the object holds (any pointer may be NULL) */
+int cvo_maps_info(cvo_maps m, int* max_maps, int* max_rows, float* voxel, long long* device_bytes);
+/* the listed maps become empty */
+int cvo_maps_clear(cvo_maps m, int count, const int* maps, void* stream);
+/* rows[k]: map k's rows, dead ones included; live_rows[k]: those with count >= 1 (host arrays, either may be NULL; one host wait) */
+int cvo_maps_rows(cvo_maps m, int count, const int* maps, int* rows, int* live_rows);
+/* the validation of the update calls alone: launches nothing */
+int cvo_check_maps_integrate_clouds(cvo_maps m, int groups, const int* maps /* groups */, const int* group_first /* groups + 1 */,
+                                    const cvo_fuse_member* members, const int* stamps /* one per member */, int sign);
+int cvo_check_maps_integrate_frames(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_frame* members, int width, int height,
+                                    int step, const cvo_camera* cams, const int* stamps, int sign);
+/* group g of the call goes into (sign +1) or out of (sign -1, or -2: what is still there) map maps[g] */
+int cvo_maps_integrate_clouds(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_member* members, const int* stamps, int sign,
+                              void* cloud_stream);
+int cvo_maps_integrate_frames(cvo_maps m, int groups, const int* maps, const int* group_first, const cvo_fuse_frame* members, int width, int height, int step,
+                              const cvo_camera* cams, const int* stamps, int sign, void* image_stream);
+int cvo_check_maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter /* count */, const cvo_map_cloud* dst /* count */);
+int cvo_maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* filter, const cvo_map_cloud* dst, int* n_out /* count, host */, void* stream);
+int cvo_check_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep /* count */, const void* const* drop /* NULL, or count of NULL or device bytes */,
+                           void* const* new_row /* NULL, or count of NULL or device int32 */);
+int cvo_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row,
+                     int* rows_out /* count, host, may be NULL */, void* stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
