@@ -225,6 +225,7 @@ ABI_SYMBOLS = [
     "cvo_maps_create", "cvo_maps_destroy", "cvo_maps_info", "cvo_maps_clear", "cvo_maps_rows", "cvo_check_maps_integrate_clouds",
     "cvo_check_maps_integrate_frames", "cvo_maps_integrate_clouds", "cvo_maps_integrate_frames", "cvo_check_maps_extract", "cvo_maps_extract",
     "cvo_check_maps_compact", "cvo_maps_compact",
+    "cvo_selftest_voxel_slots",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
 REDUCE_MEAN, REDUCE_CENTRAL = 0, 1       # CVO_REDUCE_MEAN, CVO_REDUCE_CENTRAL
@@ -343,6 +344,7 @@ def load_library():
                  "cvo_selftest_dist_se3_f32logm", "cvo_selftest_reset_initial"):
         getattr(L, name).argtypes = [C.c_int, C.c_int, fp, fp]
     L.cvo_selftest_pair_values.argtypes = [C.c_int, C.POINTER(Params), C.c_float, C.c_int, fp, fp, fp]
+    L.cvo_selftest_voxel_slots.argtypes = [C.c_int, C.c_int, fp, C.c_float, C.c_uint, ip, C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]
     L.cvo_function_inner_product_clouds.argtypes = [vp, fp, fp, C.c_int, fp, fp, C.c_int, C.POINTER(InnP)]
     L.cvo_se3_hessian_clouds.argtypes = [vp, fp, fp, C.c_int, fp, fp, C.c_int, dp, ip]
     L.cvo_batch_set_max_workgroups.argtypes = [vp, C.c_int]
@@ -569,6 +571,17 @@ def selftest_pair_values(y_g, ell: float, params: "Params | None" = None, device
     _check(load_library().cvo_selftest_pair_values(device, C.byref(params) if params is not None else None, float(ell), a.shape[0], a.ctypes.data_as(fp),
                                                    out.ctypes.data_as(fp), aux.ctypes.data_as(fp)))
     return out, aux[:, 0], aux[:, 1]
+
+
+def selftest_voxel_slots(xyz, voxel: float, slots: int, device: int = 0):
+    """The voxel table's two pure functions on the device (cell_of with zero features, home_slot) for n positions: (valid (n,) bool, key (n,) uint64,
+    home slot (n,) uint32); key and slot are 0 for an invalid point."""
+    a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3); n = a.shape[0]
+    valid = np.zeros(n, np.int32); key = np.zeros(n, np.uint64); slot = np.zeros(n, np.uint32)
+    _check(load_library().cvo_selftest_voxel_slots(device, n, a.ctypes.data_as(C.POINTER(C.c_float)), float(voxel), int(slots),
+                                                   valid.ctypes.data_as(C.POINTER(C.c_int)), key.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                   slot.ctypes.data_as(C.POINTER(C.c_uint))))
+    return valid != 0, key, slot
 
 
 def _check(rc: int):

@@ -124,6 +124,7 @@ hipError_t launch_adaptive(const AdaptiveArgs& A, int iterations, hipStream_t st
 int adaptive_partial_records(int nf, int nm);
 hipError_t launch_selftest(int kind, const float* in, float* out, int n, hipStream_t s);
 hipError_t launch_selftest_reset_initial(const float* in, float* out, int n, hipStream_t s);
+hipError_t launch_selftest_voxel_slots(const float* xyz, int n, float voxel, unsigned slots, int* valid, unsigned long long* key, unsigned* slot, hipStream_t s);
 hipError_t launch_track_link(const TrackLinkIn* in, const PairState* odo_states, PairState* key_states, TrackLinkOut* out, int n, hipStream_t s);
 hipError_t launch_selftest_pairs(const float* in, float* out, float* aux, int n, float ell, const DevParams& P, hipStream_t s);
 hipError_t launch_score(const ScoreBatch& B, const ScoreDesc* more, int nreq, int row_blocks, int chunks, const DevParams& P, double* partials,
@@ -2728,6 +2729,26 @@ int cvo_selftest_pair_values(int device, const cvo_params* params, float ell, in
     if (e == hipSuccess) e = hipMemcpy(a_out, dout.p, sizeof(float) * (size_t)n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && d2_d2c_out) e = hipMemcpy(d2_d2c_out, daux.p, sizeof(float) * (size_t)n * 2, hipMemcpyDeviceToHost);
     din.release(); dout.release(); daux.release();
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("self-test: ") + hipGetErrorString(e));
+    return CVO_OK;
+}
+int cvo_selftest_voxel_slots(int device, int n, const float* xyz, float voxel, unsigned slots, int* valid_out, unsigned long long* key_out, unsigned* slot_out) {
+    int rc = check_device(device, nullptr); if (rc) return rc;
+    if (n <= 0 || !xyz || !valid_out || !key_out || !slot_out || !(voxel > 0.f) || !std::isfinite(voxel) || slots == 0u) return fail(CVO_ERR_INVALID, "bad self-test arguments");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf din, dvalid, dkey, dslot;
+    if ((rc = din.ensure(sizeof(float) * (size_t)n * 3)) || (rc = dvalid.ensure(sizeof(int) * (size_t)n)) || (rc = dkey.ensure(sizeof(unsigned long long) * (size_t)n)) ||
+        (rc = dslot.ensure(sizeof(unsigned) * (size_t)n))) {
+        din.release(); dvalid.release(); dkey.release(); dslot.release(); return rc;
+    }
+    hipError_t e = hipMemcpy(din.p, xyz, sizeof(float) * (size_t)n * 3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_selftest_voxel_slots(static_cast<const float*>(din.p), n, voxel, slots, static_cast<int*>(dvalid.p), static_cast<unsigned long long*>(dkey.p),
+                                                         static_cast<unsigned*>(dslot.p), nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(valid_out, dvalid.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(key_out, dkey.p, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(slot_out, dslot.p, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToHost);
+    din.release(); dvalid.release(); dkey.release(); dslot.release();
     if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("self-test: ") + hipGetErrorString(e));
     return CVO_OK;
 }

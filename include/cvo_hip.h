@@ -274,6 +274,12 @@ int cvo_selftest_dist_se3_f32logm(int device, int n, const float* dR_dT, float* 
 int cvo_selftest_reset_initial(int device, int n, const float* transform_odometry, float* out);
 int cvo_selftest_libm(int device, int n, const float* x, float* out6);
 int cvo_selftest_pair_values(int device, const cvo_params* params /* NULL = defaults */, float ell, int n, const float* y_g, float* a_out, float* d2_d2c_out);
+/*   voxel_slots: the two pure functions of the voxel-grid kernels' table ("Reducing clouds" and what follows it below), as those kernels call them, for n
+ *               positions with features taken as zeros at voxel size `voxel` (finite, > 0) and a table of `slots` (>= 1) slots:   in: n x {x, y, z}
+ *               out: valid_out[i] = 1 where the point is valid (belongs to a cell), key_out[i] = its cell's key (cx + 2^20) << 42 | (cy + 2^20) << 21 |
+ *               (cz + 2^20), slot_out[i] = the slot at which the table starts to look for that key; 0 and 0 for an invalid point.
+ *               tests/test_gpu_table_cases.py: equal to the numpy mirror (tests/table_cases.py), which places the engineered clouds' cells. */
+int cvo_selftest_voxel_slots(int device, int n, const float* xyz, float voxel, unsigned slots, int* valid_out, unsigned long long* key_out, unsigned* slot_out);
 
 /* ======================= batched alignment (independent frame pairs) ===========
  * keyframe<->keyframe loop-closure candidates (keyframe_graph.cpp:622-731) and
