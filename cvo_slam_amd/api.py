@@ -134,6 +134,10 @@ class MapCloud(C.Structure):             # cvo_map_cloud: one map's extracted ar
                 ("last_stamp", C.c_void_p), ("born", C.c_void_p), ("row", C.c_void_p), ("cap", C.c_int), ("pad_", C.c_int)]
 
 
+class MapView(C.Structure):              # cvo_map_view: one resident map seen by one camera under one filter (pose: row-major 3 x 4, host memory)
+    _fields_ = [("map", C.c_int), ("cam", C.c_int), ("filter", MapFilter), ("pose", C.c_float * 12)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -224,7 +228,7 @@ ABI_SYMBOLS = [
     "cvo_check_view_clouds", "cvo_view_device_clouds",
     "cvo_maps_create", "cvo_maps_destroy", "cvo_maps_info", "cvo_maps_clear", "cvo_maps_rows", "cvo_check_maps_integrate_clouds",
     "cvo_check_maps_integrate_frames", "cvo_maps_integrate_clouds", "cvo_maps_integrate_frames", "cvo_check_maps_extract", "cvo_maps_extract",
-    "cvo_check_maps_compact", "cvo_maps_compact",
+    "cvo_check_maps_compact", "cvo_maps_compact", "cvo_check_maps_view", "cvo_maps_view",
     "cvo_selftest_voxel_slots",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
@@ -482,6 +486,9 @@ def load_library():
     L.cvo_maps_extract.argtypes = [vp, C.c_int, ip, mfp, mcp, ip, vp]
     L.cvo_check_maps_compact.argtypes = [vp, C.c_int, ip, mkp, vpp_, vpp_]
     L.cvo_maps_compact.argtypes = [vp, C.c_int, ip, mkp, vpp_, vpp_, ip, vp]
+    mvp = C.POINTER(MapView)
+    L.cvo_check_maps_view.argtypes = [vp, C.c_int, mvp, cap_, vpp, dip, vcp, vpp_]
+    L.cvo_maps_view.argtypes = [vp, C.c_int, mvp, cap_, vpp, dip, vcp, vpp_, ip, ip, vp]
     _lib = L
     return L
 
@@ -1159,8 +1166,9 @@ class CvoReducer:
         return DeviceImage(None, cd["data"][0], 0, td[0], 3, 0)
 
     @staticmethod
-    def _view_args(clouds, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index):
-        """what view refuses before it touches the library, and (View array, Camera array, ViewParams, DeviceImage array or None, points per view)"""
+    def _view_call(items, what, record, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index):
+        """what a viewing call refuses before it touches the library, over its `items` (`what`: "clouds", or "maps" for CvoMaps.view);
+        record(k, item, pose12, cam) makes view k's record.  (records, Camera array, ViewParams, DeviceImage array or None)"""
         bad = [w for w in want if w not in VIEW_WANT]
         if bad:
             raise ValueError(f"want: one of {VIEW_WANT} expected, got {bad[0]!r}")
@@ -1182,33 +1190,39 @@ class CvoReducer:
             raise ValueError(f"slack {slack}: a finite number, at least 0, expected")
         if not (np.isfinite(depth_tol) and depth_tol >= 0.0):
             raise ValueError(f"depth_tol {depth_tol}: a finite number, at least 0, expected")
-        clouds = list(clouds); poses = list(poses)
-        if not clouds:
-            raise ValueError("no clouds")
-        if len(poses) != len(clouds):
-            raise ValueError(f"{len(clouds)} clouds but {len(poses)} poses")
+        items = list(items); poses = list(poses)
+        if not items:
+            raise ValueError(f"no {what}")
+        if len(poses) != len(items):
+            raise ValueError(f"{len(items)} {what} but {len(poses)} poses")
         if len(cameras) == 5 and not hasattr(cameras[0], "__len__"):
             cameras = [cameras]
         cams = (Camera * len(cameras))(*[Camera(*[float(v) for v in c]) for c in cameras])
-        ci = np.zeros(len(clouds), np.int32) if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
-        if ci.shape[0] != len(clouds) or ci.min() < 0 or ci.max() >= len(cameras):
+        ci = np.zeros(len(items), np.int32) if cam_index is None else np.ascontiguousarray(cam_index, np.int32).reshape(-1)
+        if ci.shape[0] != len(items) or ci.min() < 0 or ci.max() >= len(cameras):
             raise ValueError("cam_index: one index into cameras per view")
         views = []
-        for k, (c, pose) in enumerate(zip(clouds, poses)):
+        for k, (c, pose) in enumerate(zip(items, poses)):
             M = np.asarray(pose, np.float32)
             if M.shape not in ((3, 4), (4, 4)):
                 raise ValueError(f"view {k}: a 3 x 4 or 4 x 4 pose expected, got shape {M.shape}")
             if not np.isfinite(M[:3]).all():
                 raise ValueError(f"view {k}: the pose is not finite")
-            d = c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS)
-            views.append(View(d, (C.c_float * 12)(*M[:3].reshape(-1).tolist()), int(ci[k]), 0))
+            views.append(record(k, c, (C.c_float * 12)(*M[:3].reshape(-1).tolist()), int(ci[k])))
         obs = None
         if observed is not None:
             observed = list(observed)
-            if len(observed) != len(clouds):
-                raise ValueError(f"{len(clouds)} clouds but {len(observed)} observed depth images")
+            if len(observed) != len(items):
+                raise ValueError(f"{len(items)} {what} but {len(observed)} observed depth images")
             obs = (DeviceImage * len(observed))(*[CvoReducer._observed_depth(o, w, h, k) for k, o in enumerate(observed)])
         prm = ViewParams(w, h, int(cell), int(VIEW_MODES.get(mode, mode)), near, far, float(slack), float(depth_tol))
+        return views, cams, prm, obs
+
+    @staticmethod
+    def _view_args(clouds, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index):
+        """what view refuses before it touches the library, and (View array, Camera array, ViewParams, DeviceImage array or None, points per view)"""
+        record = lambda k, c, pose, cam: View(c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS), pose, cam, 0)
+        views, cams, prm, obs = CvoReducer._view_call(clouds, "clouds", record, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index)
         return (View * len(views))(*views), cams, prm, obs, [int(v.cloud.n) for v in views]
 
     def check_view(self, clouds, poses, cameras, size, cell=1, mode="front", slack=0.0, z_range=(0.05, 30.0), observed=None, depth_tol=0.02,
@@ -1485,6 +1499,96 @@ class CvoMaps:
             k = over[0]
             raise CvoError(CVO_ERR_INVALID, f"map {int(ms[k])}: {int(n_out[k])} rows are more than cap {int(cap)}: filter harder, compact, or use a larger voxel")
         return [{key: t[:int(n_out[k])] for key, t in v.items()} | dict(n_out=int(n_out[k])) for k, v in enumerate(outs)]
+
+    def _view_records(self, maps, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, min_points, min_views, min_last_stamp, want, carve,
+                      cam_index):
+        """what view refuses before it touches the library, and (MapView array, Camera array, ViewParams, DeviceImage array or None, map numbers)"""
+        ms = [maps] if isinstance(maps, (int, np.integer)) else list(maps)
+        if any(int(k) != k for k in ms):
+            raise ValueError("maps: integers expected")
+        ms = [int(k) for k in ms]
+        bad = [k for k in ms if not 0 <= k < self.max_maps]
+        if bad:
+            raise ValueError(f"map {bad[0]}: 0 .. {self.max_maps - 1} expected")
+        if carve and observed is None:
+            raise ValueError("carve needs observed")
+        n = len(ms)
+        cols = (self._per_map(min_points, n, "min_points", 0, 2 ** 31 - 1), self._per_map(min_views, n, "min_views", 0, FUSE_MAX_MEMBERS),
+                self._per_map(min_last_stamp, n, "min_last_stamp", -2 ** 31, 2 ** 31 - 1))
+        record = lambda k, m, pose, cam: MapView(m, cam, MapFilter(cols[0][k], cols[1][k], cols[2][k], 0), pose)
+        views, cams, prm, obs = CvoReducer._view_call(ms, "maps", record, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, want, cam_index)
+        return (MapView * n)(*views), cams, prm, obs, ms
+
+    def check_view(self, maps, poses, cameras, size, cell=1, mode="front", slack=0.0, z_range=(0.05, 30.0), observed=None, depth_tol=0.02,
+                   min_points=1, min_views=1, min_last_stamp=0, cam_index=None):
+        """cvo_check_maps_view on the inputs of `view` with no output arrays (cap 0, no carve): the validation alone, nothing is launched"""
+        arr, cams, prm, obs, ms = self._view_records(maps, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, min_points, min_views,
+                                                     min_last_stamp, (), False, cam_index)
+        _check(self.L.cvo_check_maps_view(self.h, len(ms), arr, cams, C.byref(prm), obs, (ViewedCloud * len(ms))(), None))
+
+    def view(self, maps, poses, cameras, size, cell=1, mode="front", slack=0.0, z_range=(0.05, 30.0), observed=None, depth_tol=0.02, min_points=1,
+             min_views=1, min_last_stamp=0, cap=65535, want=("source",), carve=False, cam_index=None, stream=None):
+        """cvo_maps_view: every listed map seen from a camera where it lies -- CvoReducer.view of the map's extract, without the extract and
+        without its 65535-row ceiling.  maps: one map number per VIEW (a map may be listed for several views: K hypotheses, K filters);
+        poses, cameras, cam_index, size, cell, mode, slack, z_range, observed, depth_tol, cap, stream: CvoReducer.view's, the pose taking the
+        map's frame to the camera's.  min_points, min_views, min_last_stamp: extract's filter, each one value or one per view.  want: which of
+        "source" (the map's row number of each viewed row), "pixel", "relation", "map" (per map row: its viewed row, -1 hidden, -2 out of
+        view, -3 invalid, -4 filtered or dead), "depth" and "index" (the z-buffer; index holds map row numbers) to return beside xyz and feat.
+        carve = True (needs observed): each dict also has `carve`, a uint8 tensor of the map's rows, 1 where the camera saw through the row
+        (visible with relation 1): `compact`'s drop as it is.  Returns one dict per view, as CvoReducer.view does.  Raises CvoError when a view
+        comes to more than cap rows; cap = 0 counts only.  The maps are only read."""
+        import torch
+        observed = None if observed is None else list(observed)
+        arr, cams, prm, obs, ms = self._view_records(maps, poses, cameras, size, cell, mode, slack, z_range, observed, depth_tol, min_points, min_views,
+                                                     min_last_stamp, want, carve, cam_index)
+        if observed:
+            _settle_writer([(observed[0][1] if isinstance(observed[0], (tuple, list)) else observed[0], None)], stream)
+        n = len(ms)
+        uniq = sorted(set(ms))
+        have, _ = self.rows(uniq, live=False)
+        ns = [int(have[uniq.index(k)]) for k in ms]                    # each view's map rows, dead ones included
+        gw, gh = -(-prm.width // prm.cell), -(-prm.height // prm.cell)
+        most = [min(m, gw * gh) if prm.mode == VIEW_FRONT else m for m in ns]              # (the fronts alone: a row per z-cell at the most)
+        caps = [min(int(cap), m) if 0 <= int(cap) <= 65535 else int(cap) for m in most]   # (a cap out of range is the library's to refuse)
+        rows = [max(0, c) for c in caps]
+        dev = torch.device("cuda", self.device)
+        ts = None
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        per_row = dict(xyz=((3,), torch.float32), feat=((5,), torch.float32), source=((), torch.int32), pixel=((), torch.int32), relation=((), torch.int32))
+        with torch.cuda.stream(ts):                                   # (the arrays belong to the stream their readers will use)
+            whole = {k: torch.empty((sum(rows),) + sh, dtype=dt, device=dev) for k, (sh, dt) in per_row.items() if k in ("xyz", "feat") or k in want}
+            mp = torch.empty(sum(ns), dtype=torch.int32, device=dev) if "map" in want else None
+            cv = torch.empty(sum(ns), dtype=torch.uint8, device=dev) if carve else None
+            depth = torch.empty((n, gh, gw), dtype=torch.float32, device=dev) if "depth" in want else None
+            index = torch.empty((n, gh, gw), dtype=torch.int32, device=dev) if "index" in want else None
+        recs = (ViewedCloud * n)(); at = pt = 0; outs = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = {key: t[at:at + rows[k]] for key, t in whole.items()}
+            if mp is not None: v["map"] = mp[pt:pt + ns[k]]
+            if cv is not None: v["carve"] = cv[pt:pt + ns[k]]
+            if depth is not None: v["depth"] = depth[k]
+            if index is not None: v["index"] = index[k]
+            recs[k] = ViewedCloud(*[ptr(v.get(key)) for key in ("xyz", "feat", "source", "pixel", "relation", "map", "depth", "index")], caps[k], 0)
+            outs.append(v); at += rows[k]; pt += ns[k]
+        carves = (C.c_void_p * n)(*[ptr(v["carve"]) for v in outs]) if carve else None
+        n_out = np.zeros(n, np.int32); counts = np.zeros((n, 4), np.int32)
+        _check(self.L.cvo_maps_view(self.h, n, arr, cams, C.byref(prm), obs, recs, carves, self._ip(n_out), self._ip(counts) if obs is not None else None,
+                                    _stream_arg(stream)))
+        over = [k for k in range(n) if n_out[k] > caps[k]] if int(cap) != 0 else []      # (cap 0 counts only: n_out is the answer)
+        if over:
+            k = over[0]
+            raise CvoError(CVO_ERR_INVALID, f"view {k}: map {ms[k]}: {int(n_out[k])} rows at cell {prm.cell} are more than cap {int(cap)}: choose a larger cell (view_cell_for_budget)")
+        out = []
+        whole_map = ("map", "carve", "depth", "index")
+        for k, v in enumerate(outs):
+            m = int(n_out[k])
+            res = {key: (t if key in whole_map else t[:m]) for key, t in v.items()} | dict(n_out=m)
+            if obs is not None:
+                res["relation_counts"] = counts[k].copy()
+            out.append(res)
+        return out
 
     def _compact_args(self, maps, min_last_stamp, min_views, probation_from, drop):
         ms = self._maps(maps)

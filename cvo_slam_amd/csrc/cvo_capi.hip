@@ -107,6 +107,7 @@ hipError_t launch_fuse_frames(const FuseGroupDesc* groups, int n_groups, const F
 hipError_t launch_fuse_clouds(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, int n_members, int n_max, int slots_max, int rows_max,
                               float voxel, int mode, int min_points, int min_views, hipStream_t s);
 hipError_t launch_view_clouds(const ViewDesc* views, int n_views, int n_max, const ViewParams& P, bool observed, bool images, hipStream_t s);
+hipError_t launch_view_maps(const ViewDesc* views, const MapViewSrc* maps, int n_views, int n_max, const ViewParams& P, bool observed, bool images, hipStream_t s);
 hipError_t launch_fuse_cells(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n_max, int slots_max,
                              int rows_max, float voxel, hipStream_t s);
 hipError_t launch_map_lookup(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int n_max, hipStream_t s);
@@ -4378,12 +4379,16 @@ MapRows map_rows_at(char* base, const MapRowsLayout& L) {
     return R;
 }
 // record q of a call: map `k` as it stands, its figures at the reducer's counts 4 q ..; everything a single kind of call sets stays 0
+// map k's share of the object's memory
+char* map_base(cvo_maps m, int k) {
+    char* base = m->mem + up16(4 * (size_t)m->max_maps) + (size_t)k * m->map_bytes;
+    return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 127) & ~(uintptr_t)127);
+}
 MapDesc& maps_desc(cvo_maps m, int q, int k) {
     MapDesc& D = m->h_desc[q];
     std::memset(&D, 0, sizeof(D));
     const MapRowsLayout L = map_rows_layout(m->max_rows);
-    char* base = m->mem + up16(4 * (size_t)m->max_maps) + (size_t)k * m->map_bytes;
-    base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 127) & ~(uintptr_t)127);
+    char* base = map_base(m, k);
     D.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); D.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
     char* table = base + 2 * L.bytes;
     D.tkeys = reinterpret_cast<unsigned long long*>(table); D.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
@@ -4596,6 +4601,105 @@ int maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* kee
     }
     return CVO_OK;
 }
+// -- viewing maps (cvo_view_kernels.hip with the map as the point source; cvo_hip.h, "Viewing maps").  A list of views, not of maps: a map may
+// stand in several.  View q takes region q of the reducer's scratch, laid out from the call's own sizes -- the z-buffer of `cells` z-cells, and
+// for R = the most rows among the call's maps a code word per row and the counts of its ceil(R / 256) blocks -- and five of the reducer's
+// counts, as view_points does.  The maps are read only.
+// A region here is an equal share of the whole scratch (384 bytes per point of max_points), not the 120 bytes per point of a reduction's region:
+// a map may have many more rows than max_points.
+inline size_t map_view_region(cvo_reducer r) { return (r->scratch_bytes / (size_t)r->max_clouds) & ~(size_t)15; }
+struct MapViewLayout { size_t code, block_heads, block_relations, bytes; };   // (the z-buffer is at 0)
+MapViewLayout map_view_layout(long long cells, int rows_max) {
+    const size_t R = (size_t)rows_max, B = (R + 255) / 256;
+    MapViewLayout L;
+    L.code = up16(8 * (size_t)cells); L.block_heads = L.code + up16(4 * R); L.block_relations = L.block_heads + up16(4 * B); L.bytes = L.block_relations + up16(16 * B);
+    return L;
+}
+int maps_check_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                    const cvo_viewed_cloud* dst, void* const* carve) {
+    if (!m) return fail(CVO_ERR_INVALID, "null maps object");
+    cvo_reducer r = m->r;
+    if (views < 1 || views > r->max_clouds) return fail(CVO_ERR_INVALID, "views " + std::to_string(views) + " is outside 1 .. the reducer's max_clouds " + std::to_string(r->max_clouds));
+    if (!v || !cams || !p || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    int rc = view_check_params(r, *p); if (rc) return rc;
+    if (carve && !observed) return fail(CVO_ERR_INVALID, "carve is set but observed is null");
+    const long long cells = (long long)frame_sub(p->width, p->cell) * frame_sub(p->height, p->cell);
+    int rows_max = 0;
+    for (int k = 0; k < views; ++k) {
+        const std::string who = "view " + std::to_string(k) + ": ";
+        if (v[k].map < 0 || v[k].map >= m->max_maps) return fail(CVO_ERR_INVALID, who + "map " + std::to_string(v[k].map) + " is outside 0 .. " + std::to_string(m->max_maps - 1));
+        if (v[k].filter.min_views < 0 || v[k].filter.min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(v[k].filter.min_views) + " is outside 0 .. 64");
+        if ((rc = fuse_check_pose(v[k].pose, who)) || (rc = frames_check_camera(cams, v[k].cam, who))) return rc;
+        const long long rows = m->rows[v[k].map];
+        rows_max = std::max(rows_max, (int)rows);
+        const cvo_viewed_cloud& d = dst[k];
+        if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
+        if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
+        if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
+        if (d.relation && !observed) return fail(CVO_ERR_INVALID, who + "dst relation is set but observed is null");
+        if (observed && (rc = view_check_observed(r->device, observed[k], p->width, p->height, who))) return rc;
+        if ((rc = check_out_arrays(r->device, who, {{d.xyz, 12ll * d.cap, 4, "dst xyz", false}, {d.feat, 20ll * d.cap, 4, "dst feat", false},
+                                                    {d.source, 4ll * d.cap, 4, "dst source", false}, {d.pixel, 4ll * d.cap, 4, "dst pixel", false},
+                                                    {d.relation, 4ll * d.cap, 4, "dst relation", false}, {d.map, 4 * rows, 4, "dst map", false},
+                                                    {d.depth, 4 * cells, 4, "dst depth", false}, {d.index, 4 * cells, 4, "dst index", false},
+                                                    {carve ? carve[k] : nullptr, rows, 1, "carve", false}}))) return rc;
+    }
+    const size_t need = map_view_layout(cells, rows_max).bytes;
+    if (need > map_view_region(r))
+        return fail(CVO_ERR_INVALID, "a view of " + std::to_string(cells) + " z-cells over " + std::to_string(rows_max) + " rows takes " + std::to_string(need) +
+                                     " bytes of scratch, above the " + std::to_string(map_view_region(r)) + " bytes of a region of the reducer: create the reducer with a larger max_points");
+    if ((size_t)VIEW_COUNTS * views > (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "the reducer's counts have no room");   // (never: 5 of 16 per cloud)
+    return CVO_OK;
+}
+// every view gets a record, an empty map too: its depth and index images are written all the same
+int maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+              const cvo_viewed_cloud* dst, void* const* carve, int* n_out, int* relation_counts, void* stream) {
+    if (!n_out) return fail(CVO_ERR_INVALID, "null argument: n_out");
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    DescTable tab{r};
+    ViewDesc* h; const ViewDesc* d; MapViewSrc* hs; const MapViewSrc* ds;
+    int rc;
+    if ((rc = tab.take(views, &h, &d)) || (rc = tab.take(views, &hs, &ds))) return rc;
+    ViewParams P;
+    P.width = p->width; P.height = p->height; P.cell = p->cell; P.mode = p->mode; P.gw = frame_sub(p->width, p->cell); P.gh = frame_sub(p->height, p->cell);
+    P.z_near = p->z_near; P.z_far = p->z_far; P.slack = p->slack; P.depth_tol = p->depth_tol;
+    int n_max = 0; bool images = false;
+    for (int q = 0; q < views; ++q) n_max = std::max(n_max, m->rows[v[q].map]);
+    const MapViewLayout L = map_view_layout((long long)P.gw * P.gh, n_max);
+    const MapRowsLayout RL = map_rows_layout(m->max_rows);
+    for (int q = 0; q < views; ++q) {
+        ViewDesc& V = h[q]; MapViewSrc& S = hs[q];
+        std::memset(&V, 0, sizeof(V));                                // (no cloud: the rows are the points)
+        const int k = v[q].map;
+        const cvo_camera& c = cams[v[q].cam];
+        const MapRows rows = map_rows_at(map_base(m, k) + (m->side[k] ? RL.bytes : 0), RL);
+        S.sums = rows.sums; S.count = rows.count; S.mask = rows.mask; S.last_stamp = rows.last_stamp;
+        S.carve = carve ? static_cast<uint8_t*>(carve[q]) : nullptr;
+        S.min_points = v[q].filter.min_points; S.min_views = v[q].filter.min_views; S.min_last_stamp = v[q].filter.min_last_stamp; S.pad_ = 0;
+        std::memcpy(V.pose, v[q].pose, sizeof(V.pose));
+        V.fx = c.fx; V.fy = c.fy; V.cx = c.cx; V.cy = c.cy; V.scaling_factor = c.scaling_factor; V.n = m->rows[k];
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * map_view_region(r);
+        V.zbuf = reinterpret_cast<unsigned long long*>(base); V.code = reinterpret_cast<int*>(base + L.code); V.block_heads = reinterpret_cast<int*>(base + L.block_heads);
+        V.block_relations = reinterpret_cast<int*>(base + L.block_relations);
+        V.total = r->d_total + VIEW_COUNTS * q; V.relation_counts = V.total + 1;
+        V.observed = observed ? static_cast<const uint8_t*>(observed[q].depth16) : nullptr;
+        V.observed_pitch = observed && observed[q].depth_pitch ? observed[q].depth_pitch : 2ll * p->width;
+        const cvo_viewed_cloud& o = dst[q];
+        V.out_xyz = static_cast<float*>(o.xyz); V.out_feat = static_cast<float*>(o.feat); V.out_source = static_cast<int*>(o.source);
+        V.out_pixel = static_cast<int*>(o.pixel); V.out_relation = static_cast<int*>(o.relation); V.out_map = static_cast<int*>(o.map);
+        V.out_depth = static_cast<float*>(o.depth); V.out_index = static_cast<int*>(o.index);
+        V.cap = o.cap;
+        images = images || o.depth || o.index;
+    }
+    if ((rc = reducer_run(r, tab.used, VIEW_COUNTS * views, stream, [&] { return launch_view_maps(d, ds, views, n_max, P, observed != nullptr, images, r->stream); }))) return rc;
+    for (int q = 0; q < views; ++q) {
+        n_out[q] = r->h_total[VIEW_COUNTS * q];
+        if (relation_counts)
+            for (int k = 0; k < 4; ++k) relation_counts[4 * q + k] = observed ? r->h_total[VIEW_COUNTS * q + 1 + k] : 0;
+    }
+    return CVO_OK;
+}
 }  // namespace
 }  // extern "C++"
 int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out) {
@@ -4694,6 +4798,15 @@ int cvo_check_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map
 int cvo_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row, int* rows_out, void* stream) {
     int rc = maps_check_compact(m, count, maps, keep, drop, new_row); if (rc) return rc;
     return maps_compact(m, count, maps, keep, drop, new_row, rows_out, stream);
+}
+int cvo_check_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                        const cvo_viewed_cloud* dst, void* const* carve) {
+    return maps_check_view(m, views, v, cams, p, observed, dst, carve);
+}
+int cvo_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p, const cvo_device_image* observed,
+                  const cvo_viewed_cloud* dst, void* const* carve, int* n_out, int* relation_counts, void* stream) {
+    int rc = maps_check_view(m, views, v, cams, p, observed, dst, carve); if (rc) return rc;
+    return maps_view(m, views, v, cams, p, observed, dst, carve, n_out, relation_counts, stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

@@ -358,7 +358,7 @@ struct ViewDesc {
     float fx, fy, cx, cy, scaling_factor;
     int n;
     unsigned long long* zbuf;      // gw * gh: the z-cell's least (z' bits << 32) | index, all ones = empty
-    int* code;                     // n: the point's z-cell number; -2 valid but not in view; -3 invalid
+    int* code;                     // n: the point's z-cell number; -2 valid but not in view; -3 invalid; -4 a map's row that is filtered or dead
     int* block_heads;              // one per 256 points: the block's visible points, then their exclusive sum
     int* block_relations;          // four per 256 points: the block's rows of each relation value (with observed)
     int* total;                    // the full row count, and behind it ...
@@ -370,6 +370,18 @@ struct ViewDesc {
     int pad_;
 };
 static_assert(sizeof(ViewDesc) == 248, "ViewDesc layout");
+// the map a view of cvo_maps_view reads in place (cvo_hip.h, "Viewing maps"): one per view, behind the call's ViewDesc records, whose cloud
+// fields stay 0 and whose n is the map's rows, dead ones included.  Row r is point r when the filter keeps it.
+struct MapViewSrc {
+    const long long* sums;         // 8 per row (MapRows::sums)
+    const unsigned* count;
+    const unsigned long long* mask;
+    const int* last_stamp;
+    uint8_t* carve;                // n bytes, or null: 1 where the row is visible with relation 1
+    int min_points, min_views, min_last_stamp;   // extract's filter
+    int pad_;
+};
+static_assert(sizeof(MapViewSrc) == 56, "MapViewSrc layout");
 // what all views of a call share
 struct ViewParams {
     int width, height, cell, mode, gw, gh;

@@ -754,7 +754,8 @@ int cvo_view_device_clouds(cvo_reducer r, int views, const cvo_view* v, const cv
  *     it is NOT refused and subtracts what the row never received: sign -1 after such a compaction is unsupported.  Remove those members with
  *     sign -2, which skips what is gone.  Then a map is no longer the fusion of its window: it is that fusion minus the dropped rows' members.
  *   extract's ceiling: cap is at most 65535 (what a hand-over takes) and there is no paging: a map may hold up to max_rows rows, but one
- *     extract call returns a map's kept rows whole only when the filter keeps at most 65535 (n_out still says how many there are).
+ *     extract call returns a map's kept rows whole only when the filter keeps at most 65535 (n_out still says how many there are).  For the
+ *     part of a larger map that a camera sees, cvo_maps_view ("Viewing maps", below) reads the rows in place.
  *
  * Consequences (tests/map_reading.py restates the definition; the tests hold the kernels to it byte for byte).  Integrating one group in one
  * call with stamps 0 .. k-1 and extracting with (min_points, min_views) gives cvo_fuse_device_clouds' MEAN result for that group byte for byte
@@ -807,6 +808,58 @@ int cvo_check_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map
                            void* const* new_row /* NULL, or count of NULL or device int32 */);
 int cvo_maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* keep, const void* const* drop, void* const* new_row,
                      int* rows_out /* count, host, may be NULL */, void* stream);
+/* ---- Viewing maps (not in the reference): a resident map seen from a camera where it lies -- "Viewing clouds" with the map's rows as the
+ * points, so that a tracker stream gets the part of its map a camera can see without cvo_maps_extract in between: no cloud of the whole
+ * filtered map is written and read back, the filter may keep more than 65535 rows (the view's own output is what cap bounds), and free-space
+ * carving is one byte array that cvo_maps_compact takes as it is.
+ *
+ * The definition.  A call is a list of VIEWS, not of maps: a cvo_map_view is a map number, a camera index into cams, a cvo_map_filter and a
+ * pose (12 f32, row-major 3 x 4, HOST memory) taking the map's frame to the camera's frame.  The same map may stand in several views of one
+ * call (one map under K hypotheses, or under K filters).  The call only reads the maps.  cvo_view_params and cvo_viewed_cloud are "Viewing
+ * clouds"' as they stand.  Per view, with rows the map's row count, dead rows included:
+ *   point index: the map's row number r in 0 .. rows - 1: the low word of the z-buffer key, the value in source and in the index image.
+ *   filtered: row r takes part only if extract's rule keeps it under the view's filter: count >= max(1, min_points), popcount(view_mask) >=
+ *     min_views, last_stamp >= min_last_stamp.  A row that is not kept has map[r] = -4 ("filtered or dead"); it is never divided, projected
+ *     or counted.
+ *   point: its eight floats are (float)((double)sum / ((double)count * 16777216.0)), extract's expression.
+ *   valid point: the three mean position floats and the three moved floats are finite and below 2^15 in magnitude; otherwise map[r] = -3.
+ *     The five feature means are NOT examined: in every supported map state a sum is the sum of llrint((double)v * 2^24) over `count` members
+ *     with |v| < 2^15 (the fuser's validity).  The largest such f32 is 32768 - 2^-9, its llrint(v * 2^24) is exact, so |sum| <= count *
+ *     (2^39 - 2^15) < 2^63.  The conversion of sum to f64, the division by the exact count * 2^24 and the conversion to f32 are each rounded
+ *     to nearest and monotone; the first two move the bound 32768 - 2^-9 by a few units of 2^-38 at the most, and the last takes anything
+ *     nearer than 2^-10 to that f32 back to it: the mean is below 2^15.  (A sign -1 removal after a
+ *     compaction that dropped live rows is unsupported above and may break this.)  Project and count therefore read 24 of a row's 64 bytes of
+ *     sums.  tests/map_view_reading.py asserts the condition on every kept row of every test.
+ *   everything else is "Viewing clouds" word for word: the moved position, in view, z-cell, front (a tie in z' goes to the lowest row number),
+ *     FRONT / SURFACE, rows in ascending index, pixel, relation, relation_counts, depth, index, n_out as the FULL count, cap in 0 .. 65535 with
+ *     no byte touched behind row cap - 1, cap == 0 counting only.  dst.map has rows int32 entries.
+ *   carve[k] (optional, needs observed): a device uint8 array of rows bytes.  Byte r is 1 when row r is visible in this view and its relation
+ *     is 1 (the camera saw through it), 0 otherwise.  All rows bytes are written, computed over all visible rows, those at or above cap
+ *     included.  It is cvo_maps_compact's drop as it is.
+ * Consequence (tests/map_view_reading.py): with E the uncapped extract of the map under the view's filter and V the view of (E.xyz, E.feat),
+ * n_out, xyz, feat, pixel, relation, relation_counts and depth are V's bytes; source = E.row[V.source]; index = E.row[V.index] where
+ * V.index >= 0; map is -4 everywhere except map[E.row] = V.map; carve is 1 exactly at E.row[V.source[V.relation == 1]].  E.row is ascending,
+ * so the front is the same: a view of a map is the view of its extract, without the extract and without its cap.
+ *
+ * Scratch: view q takes region q of the reducer's scratch, laid out from the call's own sizes, each array rounded up to 16 bytes: the z-buffer
+ * 8 x gw * gh, a code word 4 x R, block counts 4 x B and block relation counts 16 x B, with R the most rows among the call's maps and
+ * B = ceil(R / 256).  A region is an equal share of the scratch, cvo_reducer_info's scratch_bytes / max_clouds (384 bytes per point of
+ * max_points), rounded down to 16.  A call whose layout is above it is refused, the message
+ * naming both figures; a map may well have more rows than max_points.  Five of the reducer's counts per view.
+ * Validation: CVO_ERR_INVALID, the message naming the view and the field: a null object or argument; views outside 1 .. the reducer's
+ * max_clouds; a map index outside 0 .. max_maps - 1 (repeats are allowed); min_views outside 0 .. 64; everything cvo_check_view_clouds checks
+ * on the parameters, poses, cameras, observed and, per output array, on dst (map: rows x 4 bytes); carve without observed; carve[k] that is
+ * not device memory of rows bytes.  A refused call changes nothing and launches nothing; a successful call leaves every map byte-identical.
+ * stream: the maps' rule -- the call is queued on the reducer's stream behind every earlier map write; with a stream one event edge in and
+ * one out, with NULL everything is done on return; one host wait, for the counts.  observed, the output arrays and carve fall under that rule
+ * as in cvo_view_device_clouds. */
+typedef struct cvo_map_view { int map; int cam; cvo_map_filter filter; float pose[12]; } cvo_map_view;   /* 72 bytes */
+/* the validation of cvo_maps_view alone: launches nothing.  cams holds max(v[].cam) + 1 cameras */
+int cvo_check_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p,
+                        const cvo_device_image* observed /* NULL or views */, const cvo_viewed_cloud* dst, void* const* carve /* NULL, or views of NULL or device bytes */);
+int cvo_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p /* one for all */,
+                  const cvo_device_image* observed, const cvo_viewed_cloud* dst, void* const* carve,
+                  int* n_out /* views, host */, int* relation_counts /* views x 4, host, may be NULL */, void* stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
