@@ -2512,6 +2512,34 @@ static __device__ __noinline__ void phase_tail_scores(const PairDesc* Dp_in, int
         // the final transform while another's are not.  They exchange partial sums below, so they have to take the same branch: one more exchange, of the
         // "my lists are stale" flags, and everybody walks only when nobody's are.  (One workgroup per pair: its own flag.)
         bool lists_ok = sh->rebuild == 0;
+        const int rebuilds_before = sh->rebuilds;                                       // (the culls below are not the alignment's: restored at the end)
+        // the raw lists of a cull (jT4, by row) against the cloud in ylds: a thread per row; a row longer than the lists hold is skipped and says so
+        auto raw_walk = [&](double& sumA, int& count, float (&H)[21], int& overflow) {
+            int hcount = 0;
+            for (int li = tid; li < c.nrows; li += nthreads) {
+                const int len = L.rowlen[li];
+                if (len > c.capn) { overflow = 1; continue; }
+                const int gi = global_row(c, li);
+                const float4 flo = ld4(c.fixed + lo_off(gi)), fhi = ld4(c.fixed + hi_off(c.nf, gi));
+                const float xi[3] = {flo.x, flo.y, flo.z};
+                const float fb[5] = {flo.w, fhi.x, fhi.y, fhi.z, fhi.w};
+                const gv2u* jp = c.jT4 + li;
+                for (int n = 0; n < len; ++n) {
+                    const v2u w = jp[(size_t)(n >> 2) * c.rows_pad];
+                    const unsigned half = (n & 2) ? w.y : w.x;
+                    const int j = (int)((n & 1) ? (half >> 16) : (half & 0xFFFFu));
+                    const float4 y = L.ylds[j];
+                    const float pa[3] = {y.x, y.y, y.z};
+                    const float e0 = pa[0] - xi[0], e1 = pa[1] - xi[1], e2 = pa[2] - xi[2];
+                    float d2 = e0 * e0; d2 = d2 + e1 * e1; d2 = d2 + e2 * e2;
+                    if (d2 < d2_thres) {
+                        const float4 ghi = ld4(c.moving + hi_off(c.nm, j));
+                        const float fa[5] = {y.w, ghi.x, ghi.y, ghi.z, ghi.w};
+                        score_pair_terms(pa, fa, xi, fb, d2, d2c_thres, sig2, csig2, den_l, den_c, il2, sumA, count, H, hcount);
+                    }
+                }
+            }
+        };
         if (G > 1) {
             double fl[8] = {(tid == 0 && sh->rebuild != 0) ? 1.0 : 0.0, 0, 0, 0, 0, 0, 0, 0};
             const double stale = tail_reduce8(fl, sh, c, G, g, ep0, tid, nwaves);
@@ -2520,11 +2548,27 @@ static __device__ __noinline__ void phase_tail_scores(const PairDesc* Dp_in, int
             lists_ok = sh->cull_next != 0;
             __syncthreads();
         }
-        if (lists_ok) {
+        // With a list margin of zero (skin 0: the launch culls in every iteration) the lists hold for no transform but the one they were built at --
+        // (r_c + reach) * 1.00001 > Rb = r_c in phase T, whatever the reach -- so they are never valid for the final one: such a launch culls the
+        // transformed cloud once more, at r_c, as it would in its next iteration, and walks the raw lists like those of inn_pre below.  The margin is the
+        // launch's (every member of a pair has the same): the members take the same branch without another exchange.
+        const bool recull = !lists_ok && P.skin == 0.f;
+        if (lists_ok || recull) {
             ep_pre = ep0 + 4u;
             double sumA = 0; int count = 0, hcount = 0; float H[21];
+            double decline = 0.0;                                                       // the last reduction's spare slot: somebody has no lists to answer from
 #pragma unroll
             for (int q = 0; q < 21; ++q) H[q] = 0.f;
+            if (recull) {
+                if (tid == 0) { sh->list_valid = 0; sh->P.skin_alpha = 0.f; sh->twist_ok = 0; }   // (skin is 0 already; nothing moves any more: restored below)
+                __syncthreads();
+                transform_body_t<1>(c, L, sh, none, false);                             // y = FINAL transform * p once more, without lists to test
+                phase_cull(Dp, g, G, tgeo, y_lds);                                      // the rows' neighbours within r_c of the transformed cloud, by row
+                int overflow = 0;
+                raw_walk(sumA, count, H, overflow);
+                decline = (double)overflow;
+            } else {
+            if (dense && tid == 0) decline = 1.0;
             const bool x_lds = sh->x_lds != 0;
             const int nb = dense ? 0 : sh->wnb[wave];
             for (int bi = 0; bi < nb; ++bi) {
@@ -2557,6 +2601,7 @@ static __device__ __noinline__ void phase_tail_scores(const PairDesc* Dp_in, int
                     }
                 }
             }
+            }
             double v[8];
             v[0] = sumA; v[1] = (double)count;
 #pragma unroll
@@ -2569,7 +2614,7 @@ static __device__ __noinline__ void phase_tail_scores(const PairDesc* Dp_in, int
             r0 = tail_reduce8(v, sh, c, G, g, ep0 + 2u, tid, nwaves);
             if (own && tid < 8) out[4 * 24 + 8 + tid] = r0;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = q < 7 ? (double)H[14 + q] : ((dense && tid == 0) ? 1.0 : 0.0);
+            for (int q = 0; q < 8; ++q) v[q] = q < 7 ? (double)H[14 + q] : decline;
             r0 = tail_reduce8(v, sh, c, G, g, ep0 + 3u, tid, nwaves);
             if (own && tid < 7) out[4 * 24 + 16 + tid] = r0;
             const double no_lists = __shfl(r0, 7, 64);                                  // (wave 0 holds the totals; thread 0 decides)
@@ -2588,37 +2633,14 @@ static __device__ __noinline__ void phase_tail_scores(const PairDesc* Dp_in, int
         }
         __syncthreads();
         transform_body_t<1>(c, L, sh, none, false);                                     // y = p
-        const int rebuilds_before = sh->rebuilds;
         phase_cull(Dp, g, G, tgeo, y_lds);                                              // the rows' neighbours within (1 + skin) r_c of the untransformed cloud, by row
         tt2 = CVO_NOW();
         {
-            double sumA = 0; int count = 0, hcount = 0; float H[21];
+            double sumA = 0; int count = 0; float H[21];
 #pragma unroll
             for (int q = 0; q < 21; ++q) H[q] = 0.f;
             int overflow = 0;
-            for (int li = tid; li < c.nrows; li += nthreads) {
-                const int len = L.rowlen[li];
-                if (len > c.capn) { overflow = 1; continue; }
-                const int gi = global_row(c, li);
-                const float4 flo = ld4(c.fixed + lo_off(gi)), fhi = ld4(c.fixed + hi_off(c.nf, gi));
-                const float xi[3] = {flo.x, flo.y, flo.z};
-                const float fb[5] = {flo.w, fhi.x, fhi.y, fhi.z, fhi.w};
-                const gv2u* jp = c.jT4 + li;
-                for (int n = 0; n < len; ++n) {
-                    const v2u w = jp[(size_t)(n >> 2) * c.rows_pad];
-                    const unsigned half = (n & 2) ? w.y : w.x;
-                    const int j = (int)((n & 1) ? (half >> 16) : (half & 0xFFFFu));
-                    const float4 y = L.ylds[j];
-                    const float pa[3] = {y.x, y.y, y.z};
-                    const float e0 = pa[0] - xi[0], e1 = pa[1] - xi[1], e2 = pa[2] - xi[2];
-                    float d2 = e0 * e0; d2 = d2 + e1 * e1; d2 = d2 + e2 * e2;
-                    if (d2 < d2_thres) {
-                        const float4 ghi = ld4(c.moving + hi_off(c.nm, j));
-                        const float fa[5] = {y.w, ghi.x, ghi.y, ghi.z, ghi.w};
-                        score_pair_terms(pa, fa, xi, fb, d2, d2c_thres, sig2, csig2, den_l, den_c, il2, sumA, count, H, hcount);
-                    }
-                }
-            }
+            raw_walk(sumA, count, H, overflow);
             double v[8] = {sumA, (double)count, (double)overflow, 0, 0, 0, 0, 0};
             const double r0 = tail_reduce8(v, sh, c, G, g, ep_pre, tid, nwaves);       // (with or without the lists of the first part: the members all took the same branch)
             if (own && tid < 2) out[tid] = r0;
