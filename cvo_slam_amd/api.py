@@ -138,6 +138,14 @@ class MapView(C.Structure):              # cvo_map_view: one resident map seen b
     _fields_ = [("map", C.c_int), ("cam", C.c_int), ("filter", MapFilter), ("pose", C.c_float * 12)]
 
 
+class MapProbe(C.Structure):             # cvo_map_probe: which resident map one posed member is looked up in, how far around each point, under which filter
+    _fields_ = [("map", C.c_int), ("reach", C.c_int), ("filter", MapFilter)]
+
+
+class ProbedPoints(C.Structure):         # cvo_probed_points: one probe's output arrays in caller-owned device memory
+    _fields_ = [("row", C.c_void_p), ("dist2", C.c_void_p), ("count", C.c_void_p), ("views", C.c_void_p), ("last_stamp", C.c_void_p), ("hit", C.c_void_p)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -229,6 +237,7 @@ ABI_SYMBOLS = [
     "cvo_maps_create", "cvo_maps_destroy", "cvo_maps_info", "cvo_maps_clear", "cvo_maps_rows", "cvo_check_maps_integrate_clouds",
     "cvo_check_maps_integrate_frames", "cvo_maps_integrate_clouds", "cvo_maps_integrate_frames", "cvo_check_maps_extract", "cvo_maps_extract",
     "cvo_check_maps_compact", "cvo_maps_compact", "cvo_check_maps_view", "cvo_maps_view",
+    "cvo_check_maps_probe_clouds", "cvo_maps_probe_clouds", "cvo_check_maps_probe_frames", "cvo_maps_probe_frames",
     "cvo_selftest_voxel_slots",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
@@ -248,6 +257,8 @@ MAP_MAX_ROWS = 1048575                   # CVO_MAP_MAX_ROWS
 MAP_MAX_COUNT = 16777215                 # CVO_MAP_MAX_COUNT
 MAP_INTEGRATE, MAP_REMOVE, MAP_REMOVE_PRESENT = 1, -1, -2      # CVO_MAP_*: the sign of an update
 MAP_WANT = ("count", "views", "view_mask", "last_stamp", "born", "row")
+PROBE_WANT = ("dist2", "count", "views", "last_stamp")      # what a probe returns beside row, one entry per point
+PROBE_ABSENT, PROBE_INVALID, PROBE_FILTERED = -1, -3, -4     # a probed point's row when it has none
 
 _lib = None
 
@@ -489,6 +500,11 @@ def load_library():
     mvp = C.POINTER(MapView)
     L.cvo_check_maps_view.argtypes = [vp, C.c_int, mvp, cap_, vpp, dip, vcp, vpp_]
     L.cvo_maps_view.argtypes = [vp, C.c_int, mvp, cap_, vpp, dip, vcp, vpp_, ip, ip, vp]
+    mpp = C.POINTER(MapProbe); ppp = C.POINTER(ProbedPoints)
+    L.cvo_check_maps_probe_clouds.argtypes = [vp, C.c_int, mpp, fmp, ppp]
+    L.cvo_maps_probe_clouds.argtypes = [vp, C.c_int, mpp, fmp, ppp, ip, vp]
+    L.cvo_check_maps_probe_frames.argtypes = [vp, C.c_int, mpp, ffp, C.c_int, C.c_int, C.c_int, cap_, ppp]
+    L.cvo_maps_probe_frames.argtypes = [vp, C.c_int, mpp, ffp, C.c_int, C.c_int, C.c_int, cap_, ppp, ip, vp]
     _lib = L
     return L
 
@@ -1589,6 +1605,120 @@ class CvoMaps:
                 res["relation_counts"] = counts[k].copy()
             out.append(res)
         return out
+
+    # ---- probing maps (cvo_hip.h, "Probing maps"): where a posed member's points fall in a map
+    def _probe_records(self, maps, items, what, poses, reach, min_points, min_views, min_last_stamp, want):
+        """what a probing call refuses before it touches the library, and (map numbers, MapProbe array, one (C.c_float * 12) pose per probe)"""
+        ms = [maps] if isinstance(maps, (int, np.integer)) else list(maps)
+        if not ms:
+            raise ValueError("no maps")
+        if any(int(k) != k for k in ms):
+            raise ValueError("maps: integers expected")
+        ms = [int(k) for k in ms]
+        bad = [k for k in ms if not 0 <= k < self.max_maps]
+        if bad:
+            raise ValueError(f"map {bad[0]}: 0 .. {self.max_maps - 1} expected")
+        bad = [w for w in (want or ()) if w not in PROBE_WANT]
+        if bad:
+            raise ValueError(f"want: None or some of {PROBE_WANT} expected, got {bad[0]!r}")
+        n = len(ms)
+        poses = list(poses)
+        if len(items) != n:
+            raise ValueError(f"{n} maps but {len(items)} {what}")
+        if len(poses) != n:
+            raise ValueError(f"{n} maps but {len(poses)} poses")
+        cols = (self._per_map(reach, n, "reach", 0, 1), self._per_map(min_points, n, "min_points", 0, 2 ** 31 - 1),
+                self._per_map(min_views, n, "min_views", 0, FUSE_MAX_MEMBERS), self._per_map(min_last_stamp, n, "min_last_stamp", -2 ** 31, 2 ** 31 - 1))
+        Ms = []
+        for k, pose in enumerate(poses):
+            M = np.asarray(pose, np.float32)
+            if M.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"probe {k}: a 3 x 4 or 4 x 4 pose expected, got shape {M.shape}")
+            if not np.isfinite(M[:3]).all():
+                raise ValueError(f"probe {k}: the pose is not finite")
+            Ms.append((C.c_float * 12)(*M[:3].reshape(-1).tolist()))
+        return ms, (MapProbe * n)(*[MapProbe(m, r, MapFilter(a, b, c, 0)) for m, r, a, b, c in zip(ms, *cols)]), Ms
+
+    def _cloud_probes(self, maps, clouds, poses, reach, min_points, min_views, min_last_stamp, want):
+        clouds = list(clouds)
+        ms, prb, Ms = self._probe_records(maps, clouds, "clouds", poses, reach, min_points, min_views, min_last_stamp, want)
+        ds = [c if isinstance(c, DeviceCloud) else device_cloud(*c, max_n=REDUCE_MAX_POINTS) for c in clouds]
+        return ms, prb, (FuseMember * len(ds))(*[FuseMember(d, M) for d, M in zip(ds, Ms)]), [int(d.n) for d in ds], clouds
+
+    def _frame_probes(self, maps, frames, poses, cameras, cam_index, step, swap_rb, reach, min_points, min_views, min_last_stamp, want):
+        frames = list(frames)
+        ms, prb, Ms = self._probe_records(maps, frames, "frames", poses, reach, min_points, min_views, min_last_stamp, want)
+        descs, w, h, step, cams, ci = CvoReducer._frame_list(frames, cameras, cam_index, step, swap_rb)
+        arr = (FuseFrame * len(descs))(*[FuseFrame(d, M, int(c), 0) for d, M, c in zip(descs, Ms, ci)])
+        return ms, prb, arr, (w, h, step, cams), [-(-w // step) * -(-h // step)] * len(descs), frames
+
+    def check_probe(self, maps, clouds, poses, reach=0, min_points=1, min_views=1, min_last_stamp=0):
+        """cvo_check_maps_probe_clouds on the inputs of `probe` with no output arrays: the validation alone, nothing is launched"""
+        ms, prb, arr, ns, clouds = self._cloud_probes(maps, clouds, poses, reach, min_points, min_views, min_last_stamp, None)
+        _check(self.L.cvo_check_maps_probe_clouds(self.h, len(ms), prb, arr, (ProbedPoints * len(ms))()))
+
+    def check_probe_frames(self, maps, frames, poses, cameras, cam_index=None, step: int = 1, swap_rb=False, reach=0, min_points=1, min_views=1,
+                           min_last_stamp=0):
+        """cvo_check_maps_probe_frames on the inputs of `probe_frames` with no output arrays: the validation alone"""
+        ms, prb, arr, (w, h, step, cams), ns, frames = self._frame_probes(maps, frames, poses, cameras, cam_index, step, swap_rb, reach, min_points, min_views,
+                                                                          min_last_stamp, None)
+        _check(self.L.cvo_check_maps_probe_frames(self.h, len(ms), prb, arr, w, h, step, cams, (ProbedPoints * len(ms))()))
+
+    def _run_probe(self, call, ms, ns, want, hit, counts, stream):
+        """the output arrays of len(ms) probes of ns points, the call, and the per-probe dicts"""
+        import torch
+        n = len(ms)
+        rows = [0] * n
+        if hit:
+            uniq = sorted(set(ms))
+            have, _ = self.rows(uniq, live=False)
+            rows = [int(have[uniq.index(k)]) for k in ms]              # each probe's map rows, dead ones included
+        dev = torch.device("cuda", self.device)
+        ts = None
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        keys = () if want is None else ("row",) + tuple(k for k in PROBE_WANT if k in want)
+        with torch.cuda.stream(ts):                                   # (the arrays belong to the stream their readers will use)
+            whole = {k: torch.empty(sum(ns), dtype=torch.float32 if k == "dist2" else torch.int32, device=dev) for k in keys}
+            hits = torch.empty(sum(rows), dtype=torch.uint8, device=dev) if hit else None
+        recs = (ProbedPoints * n)(); at = ht = 0; outs = []
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        for k in range(n):
+            v = {key: t[at:at + ns[k]] for key, t in whole.items()}
+            if hits is not None: v["hit"] = hits[ht:ht + rows[k]]
+            recs[k] = ProbedPoints(*[ptr(v.get(key)) for key in ("row", "dist2", "count", "views", "last_stamp", "hit")])
+            outs.append(v); at += ns[k]; ht += rows[k]
+        cnt = np.zeros((n, 4), np.int32) if counts else None
+        _check(call(recs, self._ip(cnt) if counts else None))
+        return [v | (dict(counts=cnt[k].copy()) if counts else {}) for k, v in enumerate(outs)]
+
+    def probe(self, maps, clouds, poses, reach=0, min_points=1, min_views=1, min_last_stamp=0, want=("dist2",), hit=False, counts=True, cloud_stream=None):
+        """cvo_maps_probe_clouds: for every point of a posed cloud, the map row it falls into (reach 0) or lies nearest to among the 27 cells
+        around it (reach 1).  maps: one map number per PROBE (a map may be listed for several: K pose hypotheses, K filters); clouds: one of
+        what CvoReducer.reduce takes per probe, of any size up to REDUCE_MAX_POINTS; poses: one 3 x 4 or 4 x 4 array-like per probe, the
+        cloud's frame to the map's.  reach, min_points, min_views, min_last_stamp (extract's filter): each one value or one per probe.
+        Returns one dict per probe: `row` (n,) int32 -- the row number, or -1 absent (no row for the cell, at reach 1 for none of the 27),
+        -4 filtered or dead, -3 invalid point -- and of want: "dist2" (float32: the squared distance to the row's mean position, inf where
+        row < 0), "count", "views", "last_stamp" (int32: the row's, 0 where row < 0).  hit = True: `hit`, a uint8 tensor of the map's rows,
+        1 where some point of the probe has that row.  counts = True: `counts`, numpy int32 (found, absent, filtered, invalid), at the cost
+        of the call's one host wait (voxels.probe_shares makes the novelty of them); counts = False with a cloud_stream: no host wait at
+        all.  want = None: no per-point arrays, the probe counts only.  The maps are only read."""
+        ms, prb, arr, ns, clouds = self._cloud_probes(maps, clouds, poses, reach, min_points, min_views, min_last_stamp, want)
+        _settle_cloud_writer(clouds, cloud_stream)
+        call = lambda recs, cnt: self.L.cvo_maps_probe_clouds(self.h, len(ms), prb, arr, recs, cnt, _stream_arg(cloud_stream))
+        return self._run_probe(call, ms, ns, want, hit, counts, cloud_stream)
+
+    def probe_frames(self, maps, frames, poses, cameras, cam_index=None, step: int = 1, swap_rb=False, reach=0, min_points=1, min_views=1,
+                     min_last_stamp=0, want=("dist2",), hit=False, counts=True, image_stream=None):
+        """cvo_maps_probe_frames: `probe` of the frames' dense clouds (CvoReducer.dense_frames), read in place.  frames: one (bgr, depth)
+        device image per probe, all of one size; cameras: one camera or a list, with cam_index one index per probe; step, swap_rb:
+        dense_frames'.  Every array has one entry per sub-grid pixel (voxels.probe_pixels makes the per-pixel image of `row`); a pixel
+        without depth is an invalid point."""
+        ms, prb, arr, (w, h, step, cams), ns, frames = self._frame_probes(maps, frames, poses, cameras, cam_index, step, swap_rb, reach, min_points, min_views,
+                                                                          min_last_stamp, want)
+        _settle_writer(frames, image_stream)
+        call = lambda recs, cnt: self.L.cvo_maps_probe_frames(self.h, len(ms), prb, arr, w, h, step, cams, recs, cnt, _stream_arg(image_stream))
+        return self._run_probe(call, ms, ns, want, hit, counts, image_stream)
 
     def _compact_args(self, maps, min_last_stamp, min_views, probation_from, drop):
         ms = self._maps(maps)

@@ -115,6 +115,8 @@ hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc
 hipError_t launch_map_extract(const MapDesc* maps, int n_maps, int rows_max, bool write, hipStream_t s);
 hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hipStream_t s);
 hipError_t launch_map_clear(const MapDesc* maps, int n_maps, int slots, hipStream_t s);
+hipError_t launch_probe_clouds(const ProbeDesc* probes, int n_probes, int n_max, float voxel, hipStream_t s);
+hipError_t launch_probe_frames(const ProbeDesc* probes, const FrameDesc* frames, int n_probes, int n, float voxel, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -3708,6 +3710,7 @@ struct cvo_reducer_s {
     void* h_desc = nullptr; int* h_total = nullptr;                   // their pinned twins: written before the launches, read after the call's one wait
     size_t table_bytes = 0;                                           // the size of d_desc and of h_desc
     int live_maps = 0;                                                // cvo_maps objects created on this reducer and not yet destroyed
+    bool table_in_flight = false;                                     // a call without a host wait (a probe without counts) left h_desc's copy queued
 };
 extern "C++" {                                                        // (the helpers below have templates among them)
 namespace {
@@ -3768,6 +3771,10 @@ int reducer_alloc(cvo_reducer r) {
 struct DescTable {
     cvo_reducer r; size_t used = 0;                                   // used: what the call copies to the device (reducer_run)
     template <class T> int take(size_t count, T** host, const T** dev) {
+        if (r->table_in_flight) {                                     // (the pinned table is about to be written: its last copy must have left)
+            HIP_TRY(hipEventSynchronize(r->ev_out));
+            r->table_in_flight = false;
+        }
         *host = reinterpret_cast<T*>(static_cast<char*>(r->h_desc) + used);
         *dev = reinterpret_cast<const T*>(static_cast<const char*>(r->d_desc) + used);
         used += sizeof(T) * count;
@@ -4700,6 +4707,123 @@ int maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* ca
     }
     return CVO_OK;
 }
+// -- probing maps (cvo_probe_kernels.hip; cvo_hip.h, "Probing maps").  A list of probes, not of maps: a map may stand in several.  Probe q takes
+// region q of the reducer's scratch (map_view_region: an equal share) for the four counts of each of its member's 256-point blocks, and four of
+// the reducer's counts.  A member is not bound by max_points: nothing of the scratch grows with it but those 16 bytes per block.  The maps are
+// read only, where they lie: the table, and the rows of the side that holds them.
+constexpr int PROBE_COUNTS = 4;
+inline size_t probe_blocks_bytes(long long n) { return 16 * (size_t)((n + 255) / 256); }
+int maps_check_probe_head(cvo_maps m, int probes, const cvo_map_probe* p, const void* members, const cvo_probed_points* dst) {
+    if (!m) return fail(CVO_ERR_INVALID, "null maps object");
+    if (probes < 1 || probes > m->r->max_clouds)
+        return fail(CVO_ERR_INVALID, "probes " + std::to_string(probes) + " is outside 1 .. the reducer's max_clouds " + std::to_string(m->r->max_clouds));
+    if (!p || !members || !dst) return fail(CVO_ERR_INVALID, "null argument");
+    return CVO_OK;
+}
+// what both probing calls check behind their members; n_of(k): the points of probe k's member
+int maps_check_probe_tail(cvo_maps m, int probes, const cvo_map_probe* p, const std::function<long long(int)>& n_of, const cvo_probed_points* dst) {
+    cvo_reducer r = m->r;
+    long long n_max = 0;
+    int rc;
+    for (int k = 0; k < probes; ++k) {
+        const std::string who = "probe " + std::to_string(k) + ": ";
+        if (p[k].map < 0 || p[k].map >= m->max_maps) return fail(CVO_ERR_INVALID, who + "map " + std::to_string(p[k].map) + " is outside 0 .. " + std::to_string(m->max_maps - 1));
+        if (p[k].reach != 0 && p[k].reach != 1) return fail(CVO_ERR_INVALID, who + "reach " + std::to_string(p[k].reach) + " is neither 0 nor 1");
+        if (p[k].filter.min_views < 0 || p[k].filter.min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(p[k].filter.min_views) + " is outside 0 .. 64");
+        const long long n = n_of(k), rows = m->rows[p[k].map];
+        const cvo_probed_points& d = dst[k];
+        const struct { const void* ptr; const char* name; } needs_row[4] = {{d.dist2, "dist2"}, {d.count, "count"}, {d.views, "views"}, {d.last_stamp, "last_stamp"}};
+        for (const auto& x : needs_row)
+            if (x.ptr && !d.row) return fail(CVO_ERR_INVALID, who + "dst " + x.name + " is set but dst row is null");
+        if ((rc = check_out_arrays(r->device, who, {{d.row, 4 * n, 4, "dst row", false}, {d.dist2, 4 * n, 4, "dst dist2", false}, {d.count, 4 * n, 4, "dst count", false},
+                                                    {d.views, 4 * n, 4, "dst views", false}, {d.last_stamp, 4 * n, 4, "dst last_stamp", false},
+                                                    {d.hit, rows, 1, "dst hit", false}}))) return rc;
+        n_max = std::max(n_max, n);
+    }
+    if (probe_blocks_bytes(n_max) > map_view_region(r))
+        return fail(CVO_ERR_INVALID, "a probe of " + std::to_string(n_max) + " points takes " + std::to_string(probe_blocks_bytes(n_max)) + " bytes of scratch, above the " +
+                                     std::to_string(map_view_region(r)) + " bytes of a region of the reducer: create the reducer with a larger max_points");
+    if ((size_t)PROBE_COUNTS * probes > (size_t)r->max_clouds * CVO_REDUCE_MAX_VOXELS) return fail(CVO_ERR_INVALID, "the reducer's counts have no room");   // (never: 4 of 16 per cloud)
+    return CVO_OK;
+}
+int maps_check_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_member* members, const cvo_probed_points* dst) {
+    int rc = maps_check_probe_head(m, probes, p, members, dst); if (rc) return rc;
+    std::vector<cvo_device_cloud> clouds(probes); std::vector<std::string> names(probes);
+    for (int k = 0; k < probes; ++k) {
+        clouds[k] = members[k].cloud;
+        names[k] = "probe " + std::to_string(k) + ": ";
+        if ((rc = fuse_check_pose(members[k].pose, names[k]))) return rc;
+    }
+    if ((rc = check_device_clouds(m->r->device, probes, clouds.data(), CVO_REDUCE_MAX_POINTS, names.data()))) return rc;
+    return maps_check_probe_tail(m, probes, p, [&](int k) { return (long long)members[k].cloud.n; }, dst);
+}
+int maps_check_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                            const cvo_probed_points* dst) {
+    int rc = maps_check_probe_head(m, probes, p, members, dst); if (rc) return rc;
+    std::vector<cvo_device_image> images(probes);
+    for (int k = 0; k < probes; ++k) images[k] = members[k].image;
+    if ((rc = check_device_images(m->r->device, probes, images.data(), width, height))) return rc;   // ("image k": the probe's place in the call)
+    if (step < 1 || step > 16) return fail(CVO_ERR_INVALID, "step " + std::to_string(step) + " is outside 1 .. 16");
+    const long long n = (long long)frame_sub(width, step) * frame_sub(height, step);
+    if (n > CVO_REDUCE_MAX_POINTS) return fail(CVO_ERR_INVALID, "a frame's " + std::to_string(n) + " points at step " + std::to_string(step) + " are above " + std::to_string(CVO_REDUCE_MAX_POINTS));
+    if (!cams) return fail(CVO_ERR_INVALID, "null argument: cams");
+    for (int k = 0; k < probes; ++k) {
+        const std::string who = "probe " + std::to_string(k) + ": ";
+        if ((rc = fuse_check_pose(members[k].pose, who)) || (rc = frames_check_camera(cams, members[k].cam, who))) return rc;
+    }
+    return maps_check_probe_tail(m, probes, p, [&](int) { return n; }, dst);
+}
+// every probe gets a record, an empty member too: its four counts are 0 and its hit bytes are cleared all the same.  src's item k is probe k's
+// member, pose(k) its 12 floats.  counts == nullptr and a stream: no host wait -- the table's copy is still queued when the call returns, which
+// the next DescTable::take settles.
+int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource& src, const std::function<const float*(int)>& pose, const cvo_probed_points* dst,
+               int* counts, void* stream) {
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    DescTable tab{r};
+    ProbeDesc* h; const ProbeDesc* d; FrameDesc* hf = nullptr; const FrameDesc* df = nullptr;
+    int rc;
+    if ((rc = tab.take(probes, &h, &d))) return rc;
+    if (src.frames() && (rc = tab.take(probes, &hf, &df))) return rc;
+    const MapRowsLayout RL = map_rows_layout(m->max_rows);
+    int n_max = 0;
+    for (int q = 0; q < probes; ++q) {
+        ProbeDesc& D = h[q];
+        std::memset(&D, 0, sizeof(D));
+        src.fill(q, D, hf, q);
+        std::memcpy(D.pose, pose(q), sizeof(D.pose));
+        D.n = src.n(q); D.reach = p[q].reach;
+        const int k = p[q].map;
+        char* base = map_base(m, k);
+        const MapRows rows = map_rows_at(base + (m->side[k] ? RL.bytes : 0), RL);
+        char* table = base + 2 * RL.bytes;
+        D.tkeys = reinterpret_cast<const unsigned long long*>(table); D.trow = reinterpret_cast<const int*>(table + map_table_keys(m->max_rows));
+        D.sums = rows.sums; D.count = rows.count; D.mask = rows.mask; D.last_stamp = rows.last_stamp;
+        D.slots = 2 * m->max_rows; D.rows = m->rows[k];
+        D.min_points = p[q].filter.min_points; D.min_views = p[q].filter.min_views; D.min_last_stamp = p[q].filter.min_last_stamp;
+        const cvo_probed_points& o = dst[q];
+        D.out_row = static_cast<int*>(o.row); D.out_dist2 = static_cast<float*>(o.dist2); D.out_count = static_cast<int*>(o.count);
+        D.out_views = static_cast<int*>(o.views); D.out_last_stamp = static_cast<int*>(o.last_stamp);
+        D.out_hit = D.rows > 0 ? static_cast<uint8_t*>(o.hit) : nullptr;
+        D.block_counts = reinterpret_cast<int*>(static_cast<char*>(r->scratch) + (size_t)q * map_view_region(r));
+        D.totals = r->d_total + PROBE_COUNTS * q;
+        n_max = std::max(n_max, D.n);
+    }
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
+    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
+    for (int q = 0; q < probes; ++q)
+        if (h[q].out_hit) HIP_TRY(hipMemsetAsync(h[q].out_hit, 0, (size_t)h[q].rows, r->stream));
+    const hipError_t e = src.frames() ? launch_probe_frames(d, df, probes, n_max, m->voxel, r->stream) : launch_probe_clouds(d, probes, n_max, m->voxel, r->stream);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map probe kernel launch: ") + hipGetErrorString(e));
+    if (counts) HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * PROBE_COUNTS * (size_t)probes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
+    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
+    if (!counts && cs) { r->table_in_flight = true; return CVO_OK; }   // (no host wait: the outputs are ordered on the caller's stream)
+    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    if (counts) std::memcpy(counts, r->h_total, sizeof(int) * PROBE_COUNTS * (size_t)probes);
+    return CVO_OK;
+}
 }  // namespace
 }  // extern "C++"
 int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out) {
@@ -4807,6 +4931,26 @@ int cvo_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera
                   const cvo_viewed_cloud* dst, void* const* carve, int* n_out, int* relation_counts, void* stream) {
     int rc = maps_check_view(m, views, v, cams, p, observed, dst, carve); if (rc) return rc;
     return maps_view(m, views, v, cams, p, observed, dst, carve, n_out, relation_counts, stream);
+}
+int cvo_check_maps_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_member* members, const cvo_probed_points* dst) {
+    return maps_check_probe_clouds(m, probes, p, members, dst);
+}
+int cvo_check_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                                const cvo_probed_points* dst) {
+    return maps_check_probe_frames(m, probes, p, members, width, height, step, cams, dst);
+}
+int cvo_maps_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_member* members, const cvo_probed_points* dst, int* counts, void* cloud_stream) {
+    int rc = maps_check_probe_clouds(m, probes, p, members, dst); if (rc) return rc;
+    PointSource src; src.cloud = [&](int k) { return &members[k].cloud; };
+    return maps_probe(m, probes, p, src, [&](int k) { return members[k].pose; }, dst, counts, cloud_stream);
+}
+int cvo_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members, int width, int height, int step, const cvo_camera* cams,
+                          const cvo_probed_points* dst, int* counts, void* image_stream) {
+    int rc = maps_check_probe_frames(m, probes, p, members, width, height, step, cams, dst); if (rc) return rc;
+    PointSource src;
+    src.frame = [&](int k, FrameDesc& F) { frame_desc(members[k].image, width, height, step, cams[members[k].cam], F); };
+    src.frame_n = frame_sub(width, step) * frame_sub(height, step);
+    return maps_probe(m, probes, p, src, [&](int k) { return members[k].pose; }, dst, counts, image_stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

@@ -382,6 +382,29 @@ struct MapViewSrc {
     int pad_;
 };
 static_assert(sizeof(MapViewSrc) == 56, "MapViewSrc layout");
+// one probe of a probing call (cvo_probe_kernels.hip; not in the reference; cvo_hip.h, "Probing maps"): a posed member -- a cloud with the
+// strides resolved, or a frame read in place (its FrameDesc behind the records, the cloud fields 0) -- and the map it is looked up in, read
+// where it lies: the table, and of the rows what the filter and the distance need.  The grid's second dimension.
+struct ProbeDesc {
+    const float* xyz; const float* feat;
+    long long xyz_stride, feat_point_stride, feat_channel_stride;
+    float pose[12];                // row-major 3 x 4: the member's frame to the map's
+    int n;                         // the member's points
+    int reach;                     // 0: the point's own cell; 1: the 27 cells around it
+    const unsigned long long* tkeys; const int* trow;   // MapDesc's table: key (all ones = empty) and row
+    const long long* sums;         // 8 per row (MapRows::sums)
+    const unsigned* count;
+    const unsigned long long* mask;
+    const int* last_stamp;
+    int slots, rows;
+    int min_points, min_views, min_last_stamp;   // extract's filter
+    int pad_;
+    int* out_row; float* out_dist2; int* out_count; int* out_views; int* out_last_stamp;   // n each, any may be null
+    uint8_t* out_hit;              // rows bytes, cleared by the call, or null
+    int* block_counts;             // four per 256 points: the block's found, absent, filtered and invalid points
+    int* totals;                   // their four sums over the member
+};
+static_assert(sizeof(ProbeDesc) == 232, "ProbeDesc layout");
 // what all views of a call share
 struct ViewParams {
     int width, height, cell, mode, gw, gh;

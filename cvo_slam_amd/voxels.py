@@ -125,6 +125,43 @@ def carve_mask(rows: int, row, source, relation, relations=(1,)):
     return out
 
 
+def probe_shares(counts):
+    """A probe's `counts` (found, absent, filtered, invalid; one probe's four, or (probes, 4)) as shares of its VALID points: dict(found,
+    absent, filtered, novelty, valid), each a float64 array over the probes (a scalar for one).  novelty = 1 - found: the share of the
+    member's valid points that the map does not hold under the probe's filter -- with min_views = 2, not yet confirmed.  A member without
+    a valid point has novelty 0: it has nothing to add."""
+    c = np.asarray(counts)
+    if c.shape[-1:] != (4,) or c.ndim > 2:
+        raise ValueError(f"probe_shares: four counts per probe expected, got shape {c.shape}")
+    if (c < 0).any():
+        raise ValueError("probe_shares: a negative count")
+    c = c.astype(np.float64)
+    valid = c[..., 0] + c[..., 1] + c[..., 2]
+    den = np.where(valid > 0, valid, 1.0)
+    found, absent, filtered = c[..., 0] / den, c[..., 1] / den, c[..., 2] / den
+    return dict(found=found, absent=absent, filtered=filtered, novelty=np.where(valid > 0, 1.0 - found, 0.0), valid=valid)
+
+
+def probe_pixels(row, width: int, height: int, step: int = 1):
+    """The per-pixel image of a frame probe's `row` (CvoMaps.probe_frames): int32 (height, width), pixel ((i % ws) * step, (i // ws) * step)
+    holding row[i], and -3 (no point) at every pixel off the sub-grid.  image >= 0 is the known mask of the probe's filter.  row: a numpy
+    array or a torch tensor of ceil(width / step) * ceil(height / step) entries; the image is of its kind."""
+    w, h, step = int(width), int(height), int(step)
+    if w < 1 or h < 1 or not 1 <= step <= 16:
+        raise ValueError(f"probe_pixels: size {(w, h)} and step {step}: a positive size and a step in 1 .. 16 expected")
+    ws, hs = -(-w // step), -(-h // step)
+    if len(row) != ws * hs:
+        raise ValueError(f"probe_pixels: {len(row)} entries for the {ws} x {hs} sub-grid of step {step}")
+    if isinstance(row, np.ndarray) or not hasattr(row, "device"):
+        out = np.full((h, w), -3, np.int32)
+        out[::step, ::step] = np.asarray(row).astype(np.int32).reshape(hs, ws)
+        return out
+    import torch
+    out = torch.full((h, w), -3, dtype=torch.int32, device=row.device)
+    out[::step, ::step] = row.to(torch.int32).reshape(hs, ws)
+    return out
+
+
 def lift(map, per_row_values, fill):
     """per_row_values[map[i]] for every point i of the dense cloud, `fill` where map[i] == -1 (an invalid point or a dropped cell).  map and
     per_row_values are both numpy arrays or both torch tensors (of one device); values may have trailing dimensions."""

@@ -860,6 +860,62 @@ int cvo_check_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_
 int cvo_maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* cams, const cvo_view_params* p /* one for all */,
                   const cvo_device_image* observed, const cvo_viewed_cloud* dst, void* const* carve,
                   int* n_out /* views, host */, int* relation_counts /* views x 4, host, may be NULL */, void* stream);
+/* ---- Probing maps (not in the reference): a resident map asked from the points' side -- for every point of a new cloud or frame under a pose,
+ * the map row it falls into (reach 0) or lies nearest to among the 27 cells around it (reach 1).  One call answers what a frame-to-model front
+ * end asks before it integrates a frame: how much of the frame is new to the map (the keyframe decision), which of its pixels land in a
+ * confirmed cell (a static / known mask), and which row each point re-observes at what squared distance (association without an alignment).
+ *
+ * The definition.  A call is a list of PROBES, as a viewing call is a list of views: a cvo_map_probe is a map number, a cvo_map_filter and a
+ * reach (0 or 1), and with it goes one posed member: a cvo_fuse_member (cvo_maps_probe_clouds), or a cvo_fuse_frame with the call's width,
+ * height, step and cameras (cvo_maps_probe_frames); the pose takes the member's frame to the map's.  The same map may stand in several probes
+ * of one call (one map under K pose hypotheses, one frame against K filters).  The call only reads the maps.  Per point i of the member (for a
+ * frame: the fuser's sub-grid pixel index), with rows the map's row count, dead rows included:
+ *   moved position, validity, cell: the fuser's rules, bit for bit: x' = (M[r,0]*x + (M[r,1]*y + M[r,2]*z)) + M[r,3] per row r, f32, un-fused;
+ *     a point is valid when its source floats and its three moved floats are finite and below 2^15 in magnitude and each cell coordinate
+ *     floorf(x' / voxel), at the maps' voxel, has magnitude below 2^20.  For a frame the source floats are the position alone, as in "Reducing
+ *     frames".  An invalid point has row[i] = -3.
+ *   reach 0: the point's own cell alone is examined.  Its key is absent from the map's table: row[i] = -1.  Present, but extract's rule under
+ *     the probe's filter drops the row (count >= max(1, min_points), popcount(view_mask) >= min_views, last_stamp >= min_last_stamp; a dead
+ *     row is always dropped): -4.  Otherwise row[i] is the row number.
+ *   reach 1: the 27 cells c + d, d in {-1, 0, 1}^3, are examined.  A neighbour with a coordinate of magnitude 2^20 or more is in no map and is
+ *     skipped; its key is never formed.  Among the examined cells whose row the filter keeps, the winner has the least (d2 bits, row number):
+ *     CENTRAL's tie rule, a tie in d2 goes to the lowest row.  d2 = (dx*dx + dy*dy) + dz*dz in f32, every product and sum rounded, never
+ *     contracted; dx = x' - mean_x with the mean extract's expression (float)((double)sum / ((double)count * 16777216.0)).  d2 >= 0, so its
+ *     bits order as the floats do.  No cell kept: row[i] = -4 if at least one examined cell has a row in the table, -1 if none has.
+ *   outputs per probe, caller-owned device memory, one entry per point, all optional: row (int32); dist2 (float32: the winner's d2, at reach 0
+ *     the distance to the own cell's mean; bits 0x7F800000 where row < 0); count, views, last_stamp (int32: the winner row's count,
+ *     popcount(view_mask) and last_stamp; 0 where row < 0); and hit (uint8), one byte per MAP row, `rows` bytes, dead rows included: byte r is 1
+ *     when some point of this probe has row == r, else 0; all bytes are written.  dist2, count, views and last_stamp cannot stand without
+ *     row; hit can.  With every array NULL the probe counts only.
+ *   counts (host, 4 ints per probe, may be NULL): counts[4 * probe + k] is the number of points that are found (k = 0), absent (-1), filtered
+ *     (-4) and invalid (-3); the four sum to the member's n.
+ * The validity of a kept row's mean needs no test: the argument under "Viewing maps" applies unchanged (tests/map_probe_reading.py asserts it).
+ *
+ * A call runs on the maps' reducer and allocates nothing.  Probe q takes region q of the reducer's scratch -- an equal share,
+ * cvo_reducer_info's scratch_bytes / max_clouds rounded down to 16 -- for its block counts, 16 bytes per 256 points; four of the reducer's
+ * counts per probe.  Probes lie in 1 .. the reducer's max_clouds.  A member's n goes up to 1048575 and is not bound by max_points; a call
+ * whose block counts are above a region is refused, the message naming both figures.  All probes go through the same two launches, the
+ * probe in the grid's second dimension; no atomics: hit is cleared on the stream and set by byte stores of 1.
+ * Validation: CVO_ERR_INVALID, the message naming the probe and the field: a null object or argument; probes outside 1 .. max_clouds; a map
+ * index outside 0 .. max_maps - 1 (repeats are allowed); reach outside {0, 1}; min_views outside 0 .. 64; everything cvo_check_fuse_clouds /
+ * cvo_check_fuse_frames checks on a member, its pose and its camera (n up to 1048575; a frame's ws * hs up to 1048575); per output array
+ * 4-byte aligned device memory of n x 4 bytes, for hit of rows bytes; dist2, count, views or last_stamp without row.  A refused call
+ * launches nothing; after any call every map is byte-identical.
+ * stream: the maps' rule -- the call is queued on the reducer's stream behind every earlier map write; with a stream one event edge in and
+ * one out, with NULL everything is done on return.  With counts the call has one host wait, for them.  With counts NULL and a stream it has
+ * no host wait at all: the outputs are ordered on that stream.  (With counts NULL and a NULL stream the call waits for its own launches:
+ * "done on return" is the only ordering such a caller has.) */
+typedef struct cvo_map_probe { int map; int reach; cvo_map_filter filter; } cvo_map_probe;   /* 24 bytes */
+typedef struct cvo_probed_points { void *row, *dist2, *count, *views, *last_stamp, *hit; } cvo_probed_points;   /* 48 bytes */
+/* the validation of the probing calls alone: launches nothing.  cams holds max(members[].cam) + 1 cameras */
+int cvo_check_maps_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_member* members /* probes */,
+                                const cvo_probed_points* dst /* probes */);
+int cvo_check_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members /* probes */, int width, int height,
+                                int step, const cvo_camera* cams, const cvo_probed_points* dst);
+int cvo_maps_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_member* members, const cvo_probed_points* dst,
+                          int* counts /* probes x 4, host, may be NULL */, void* cloud_stream);
+int cvo_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members, int width, int height, int step,
+                          const cvo_camera* cams, const cvo_probed_points* dst, int* counts /* probes x 4, host, may be NULL */, void* image_stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
