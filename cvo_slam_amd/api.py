@@ -146,6 +146,11 @@ class ProbedPoints(C.Structure):         # cvo_probed_points: one probe's output
     _fields_ = [("row", C.c_void_p), ("dist2", C.c_void_p), ("count", C.c_void_p), ("views", C.c_void_p), ("last_stamp", C.c_void_p), ("hit", C.c_void_p)]
 
 
+class MapSnapshot(C.Structure):          # cvo_map_snapshot: one map's rows as six caller-owned device arrays; rows: the capacity (snapshot) or the rows to put in (restore)
+    _fields_ = [("keys", C.c_void_p), ("sums", C.c_void_p), ("count", C.c_void_p), ("view_mask", C.c_void_p), ("last_stamp", C.c_void_p),
+                ("born", C.c_void_p), ("rows", C.c_int), ("pad_", C.c_int)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -238,6 +243,7 @@ ABI_SYMBOLS = [
     "cvo_check_maps_integrate_frames", "cvo_maps_integrate_clouds", "cvo_maps_integrate_frames", "cvo_check_maps_extract", "cvo_maps_extract",
     "cvo_check_maps_compact", "cvo_maps_compact", "cvo_check_maps_view", "cvo_maps_view",
     "cvo_check_maps_probe_clouds", "cvo_maps_probe_clouds", "cvo_check_maps_probe_frames", "cvo_maps_probe_frames",
+    "cvo_check_maps_snapshot", "cvo_maps_snapshot", "cvo_check_maps_restore", "cvo_maps_restore",
     "cvo_selftest_voxel_slots",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
@@ -259,6 +265,9 @@ MAP_INTEGRATE, MAP_REMOVE, MAP_REMOVE_PRESENT = 1, -1, -2      # CVO_MAP_*: the 
 MAP_WANT = ("count", "views", "view_mask", "last_stamp", "born", "row")
 PROBE_WANT = ("dist2", "count", "views", "last_stamp")      # what a probe returns beside row, one entry per point
 PROBE_ABSENT, PROBE_INVALID, PROBE_FILTERED = -1, -3, -4     # a probed point's row when it has none
+SNAPSHOT_FIELDS = (("keys", 8, "iu", ()), ("sums", 8, "i", (8,)), ("count", 4, "iu", ()), ("view_mask", 8, "iu", ()), ("last_stamp", 4, "i", ()),
+                   ("born", 4, "i", ()))    # a snapshot's arrays: name, item bytes, integer kinds that carry it, a row's shape
+RESTORE_BAD_KEY, RESTORE_BAD_COUNT, RESTORE_BAD_STAMP, RESTORE_BAD_SUM, RESTORE_DUPLICATE = 1, 2, 4, 8, 16   # a refused restore's bits
 
 _lib = None
 
@@ -505,6 +514,11 @@ def load_library():
     L.cvo_maps_probe_clouds.argtypes = [vp, C.c_int, mpp, fmp, ppp, ip, vp]
     L.cvo_check_maps_probe_frames.argtypes = [vp, C.c_int, mpp, ffp, C.c_int, C.c_int, C.c_int, cap_, ppp]
     L.cvo_maps_probe_frames.argtypes = [vp, C.c_int, mpp, ffp, C.c_int, C.c_int, C.c_int, cap_, ppp, ip, vp]
+    msp = C.POINTER(MapSnapshot)
+    L.cvo_check_maps_snapshot.argtypes = [vp, C.c_int, ip, msp]
+    L.cvo_maps_snapshot.argtypes = [vp, C.c_int, ip, msp, ip, vp]
+    L.cvo_check_maps_restore.argtypes = [vp, C.c_int, ip, msp, C.c_float]
+    L.cvo_maps_restore.argtypes = [vp, C.c_int, ip, msp, C.c_float, vp]
     _lib = L
     return L
 
@@ -1777,6 +1791,126 @@ class CvoMaps:
             sys.modules["torch"].cuda.current_stream(self.device).synchronize()          # (the masks' writer: torch's current stream)
         _check(self.L.cvo_maps_compact(self.h, n, self._ip(ms), keep, drops, ptrs, self._ip(out), _stream_arg(stream)))
         return (out, news) if new_row else out
+
+    # -- saving and restoring (cvo_hip.h, "Saving and restoring maps")
+    @staticmethod
+    def _device_array(a):
+        """(pointer, shape, item bytes, kind letter, contiguous) of a device array, or None when `a` is none.  A torch tensor is asked
+        directly: its __cuda_array_interface__ costs microseconds a look, and a call over 64 maps looks at 384 arrays."""
+        if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):
+            if not a.is_cuda:
+                return None
+            name = str(a.dtype)
+            kind = "f" if a.is_floating_point() or a.is_complex() else "b" if name == "torch.bool" else "u" if name.startswith("torch.uint") else "i"
+            return a.data_ptr(), tuple(int(v) for v in a.shape), a.element_size(), kind, a.is_contiguous()
+        cai = getattr(a, "__cuda_array_interface__", None)
+        if cai is None:
+            return None
+        shape = tuple(int(v) for v in cai["shape"])
+        ts = cai["typestr"]
+        item = int(ts[2:])
+        dense = tuple(item * int(np.prod(shape[j + 1:])) for j in range(len(shape)))
+        return cai["data"][0], shape, item, ts[1] if ts[0] in "<|=" else "?", cai.get("strides") in (None, dense)
+
+    def _snap_records(self, ms, snaps, what):
+        """what a snapshot or a restore refuses before it touches the library, and the MapSnapshot array: one dict per map with the six device
+        arrays (anything with __cuda_array_interface__) and optionally `rows` (default: the arrays' length)"""
+        snaps = [snaps] if isinstance(snaps, dict) else list(snaps)
+        if len(snaps) != len(ms):
+            raise ValueError(f"{len(ms)} maps but {len(snaps)} snapshots")
+        recs = (MapSnapshot * len(ms))()
+        for k, sn in enumerate(snaps):
+            if not isinstance(sn, dict):
+                raise ValueError(f"{what} {k}: a dict of device arrays expected")
+            ptrs, lens = [], []
+            for name, size, kinds, tail in SNAPSHOT_FIELDS:
+                a = sn.get(name)
+                if a is None:
+                    ptrs.append(None); lens.append(None); continue
+                info = self._device_array(a)
+                if info is None:
+                    raise ValueError(f"{what} {k}: {name}: a device array (__cuda_array_interface__) expected")
+                ptr, shape, item, kind, contiguous = info
+                if kind not in kinds or item != size or shape[1:] != tail or len(shape) != 1 + len(tail) or not contiguous:
+                    raise ValueError(f"{what} {k}: {name}: a contiguous {size}-byte integer array of shape (rows{', 8' if tail else ''}) expected, got {kind}{item} {shape}")
+                ptrs.append(ptr if shape[0] else None); lens.append(shape[0])
+            have = [v for v in lens if v is not None]
+            rows = sn.get("rows", min(have) if have else 0)
+            if int(rows) != rows or not 0 <= int(rows) < 2 ** 31:
+                raise ValueError(f"{what} {k}: rows {rows!r}: an integer in 0 .. 2^31 - 1 expected")
+            rows = int(rows)
+            for (name, _, _, _), n in zip(SNAPSHOT_FIELDS, lens):
+                if (n is None and rows > 0) or (n is not None and n < rows):
+                    raise ValueError(f"{what} {k}: {name} has {0 if n is None else n} rows, below rows {rows}")
+            recs[k] = MapSnapshot(*ptrs, rows, 0)
+        return recs, snaps
+
+    def empty_snapshots(self, rows, stream=None):
+        """one dict of uninitialised device tensors per entry of `rows`, each with room for that many rows: what snapshot_into fills"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ts = None
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+        kinds = dict(keys=torch.int64, sums=torch.int64, count=torch.int32, view_mask=torch.int64, last_stamp=torch.int32, born=torch.int32)
+        with torch.cuda.stream(ts):                                    # (keys, count, view_mask: unsigned bits in torch's signed carriers)
+            return [{name: torch.empty((int(n),) + tail, dtype=kinds[name], device=dev) for name, _, _, tail in SNAPSHOT_FIELDS} | dict(rows=int(n)) for n in rows]
+
+    def check_snapshot(self, maps, snaps):
+        """cvo_check_maps_snapshot on what snapshot_into takes: the validation alone, nothing is launched"""
+        ms = self._maps(maps)
+        recs, snaps = self._snap_records(ms, snaps, "snapshot")
+        _check(self.L.cvo_check_maps_snapshot(self.h, len(ms), self._ip(ms), recs))
+
+    def snapshot_into(self, maps, snaps, stream=None):
+        """cvo_maps_snapshot into arrays the caller has: snaps[k]'s six device arrays (empty_snapshots' dicts; `rows`: their capacity) take map
+        maps[k]'s rows 0 .. rows - 1 as they stand, dead ones included; nothing behind them is touched.  A capacity below a map's rows refuses
+        the call.  Returns the maps' row counts (int32 array).  With a stream there is no host wait."""
+        ms = self._maps(maps)
+        recs, snaps = self._snap_records(ms, snaps, "snapshot")
+        out = np.zeros(len(ms), np.int32)
+        _check(self.L.cvo_maps_snapshot(self.h, len(ms), self._ip(ms), recs, self._ip(out), _stream_arg(stream)))
+        return out
+
+    def snapshot(self, maps=None, stream=None):
+        """cvo_maps_snapshot: the rows of every listed map (None: all) as they stand, dead ones included.  Returns one dict per map of device
+        tensors with one entry per row -- keys (int64 carrier of the 64 bits), sums (rows, 8) int64, count (int32 carrier), view_mask (int64
+        carrier), last_stamp, born (int32) -- and rows.  `restore` on any CvoMaps of the same voxel makes the same map of them; voxels.save_maps
+        writes them to a file.  The maps are only read; with a stream there is no host wait."""
+        ms = self._maps(maps)
+        have, _ = self.rows(ms, live=False)
+        snaps = self.empty_snapshots(have, stream)
+        self.snapshot_into(ms, snaps, stream)
+        return snaps
+
+    def check_restore(self, maps, snaps, voxel=None):
+        """cvo_check_maps_restore: the validation of `restore` alone, nothing is launched"""
+        ms = self._maps(maps)
+        recs, snaps = self._snap_records(ms, snaps, "snapshot")
+        _check(self.L.cvo_check_maps_restore(self.h, len(ms), self._ip(ms), recs, self.voxel if voxel is None else float(voxel)))
+
+    def restore(self, maps, snaps, voxel=None, stream=None):
+        """cvo_maps_restore: map maps[k] becomes exactly the rows of snaps[k] (a `snapshot`'s dict, or any six device arrays of that layout with
+        `rows`, default their length); what it held before is gone.  voxel: the size the keys were made at (None: this object's); it must have
+        the bits of this object's voxel.  The rows are untrusted: each is tested on the device first, and a bad key (bit 1), a count above
+        16777215 (2), a negative stamp (4), a sum out of bound (8) or a duplicate key (16) raises CvoError naming the map and its bits, with
+        every listed map unchanged.  stream None: the arrays are taken as written on torch's current stream."""
+        ms = self._maps(maps)
+        recs, snaps = self._snap_records(ms, snaps, "snapshot")
+        if stream is None and "torch" in sys.modules:
+            sys.modules["torch"].cuda.current_stream(self.device).synchronize()          # (the arrays' writer: torch's current stream)
+        _check(self.L.cvo_maps_restore(self.h, len(ms), self._ip(ms), recs, self.voxel if voxel is None else float(voxel), _stream_arg(stream)))
+
+    def grown(self, max_rows: int):
+        """A new CvoMaps on the same reducer with max_rows rows per map and every map restored from this one: the remedy for a map that an
+        integration would take above max_rows.  This object stays as it is; close it when the new one has taken over."""
+        new = CvoMaps(self.reducer, self.max_maps, int(max_rows), self.voxel)
+        try:
+            new.restore(None, self.snapshot(None))
+        except Exception:
+            new.close()
+            raise
+        return new
 
 
 # ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms

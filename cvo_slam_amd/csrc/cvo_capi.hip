@@ -117,6 +117,9 @@ hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hip
 hipError_t launch_map_clear(const MapDesc* maps, int n_maps, int slots, hipStream_t s);
 hipError_t launch_probe_clouds(const ProbeDesc* probes, int n_probes, int n_max, float voxel, hipStream_t s);
 hipError_t launch_probe_frames(const ProbeDesc* probes, const FrameDesc* frames, int n_probes, int n, float voxel, hipStream_t s);
+hipError_t launch_map_snapshot(const MapSnapDesc* maps, int n_maps, int rows_max, hipStream_t s);
+hipError_t launch_map_restore(const MapSnapDesc* maps, int n_maps, int rows_max, hipStream_t s);
+hipError_t launch_map_restore_undo(const MapSnapDesc* maps, int n_maps, int rows_max, int slots, hipStream_t s);
 int score_nout();
 int score_row_blocks(int na);
 int score_groups(int n);
@@ -4824,6 +4827,123 @@ int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource
     if (counts) std::memcpy(counts, r->h_total, sizeof(int) * PROBE_COUNTS * (size_t)probes);
     return CVO_OK;
 }
+// -- saving and restoring maps (cvo_map_snapshot_kernels.hip; cvo_hip.h, "Saving and restoring maps").  The records are MapSnapDescs in the
+// reducer's descriptor table (max_maps <= max_clouds of them: reducer_alloc's first term covers them), a restore's figures four ints per map of
+// the call in the reducer's counts, as an update's.
+static_assert(sizeof(MapSnapDesc) <= sizeof(ReduceDesc) + sizeof(FrameDesc), "a MapSnapDesc per map fits the reducer's descriptor table");
+int maps_check_snap_arrays(cvo_maps m, const std::string& who, const char* side, const cvo_map_snapshot& x, long long rows) {
+    const bool need = rows > 0;
+    const std::string s(side);
+    const std::string names[6] = {s + " keys", s + " sums", s + " count", s + " view_mask", s + " last_stamp", s + " born"};
+    return check_out_arrays(m->r->device, who, {{x.keys, 8 * rows, 8, names[0].c_str(), need}, {x.sums, 64 * rows, 8, names[1].c_str(), need},
+                                                {x.count, 4 * rows, 4, names[2].c_str(), need}, {x.view_mask, 8 * rows, 8, names[3].c_str(), need},
+                                                {x.last_stamp, 4 * rows, 4, names[4].c_str(), need}, {x.born, 4 * rows, 4, names[5].c_str(), need}});
+}
+int maps_check_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    if (!dst) return fail(CVO_ERR_INVALID, "null argument: dst");
+    for (int q = 0; q < count; ++q) {
+        const std::string who = "map " + std::to_string(maps[q]) + ": ";
+        const int rows = m->rows[maps[q]];
+        if (dst[q].rows < rows)
+            return fail(CVO_ERR_INVALID, who + "dst rows " + std::to_string(dst[q].rows) + " (the arrays' capacity) is below the map's " + std::to_string(rows) + " rows: there are no partial snapshots");
+        if ((rc = maps_check_snap_arrays(m, who, "dst", dst[q], rows))) return rc;
+    }
+    return CVO_OK;
+}
+int maps_check_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel) {
+    int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
+    if (!src) return fail(CVO_ERR_INVALID, "null argument: src");
+    if (std::memcmp(&voxel, &m->voxel, sizeof(float)) != 0)
+        return fail(CVO_ERR_INVALID, "voxel " + std::to_string(voxel) + " has not the bits of the object's voxel " + std::to_string(m->voxel) + ": a key means nothing at another cell size");
+    for (int q = 0; q < count; ++q) {
+        const std::string who = "map " + std::to_string(maps[q]) + ": ";
+        if (src[q].rows < 0 || src[q].rows > m->max_rows)
+            return fail(CVO_ERR_INVALID, who + "src rows " + std::to_string(src[q].rows) + " is outside 0 .. max_rows " + std::to_string(m->max_rows));
+        if ((rc = maps_check_snap_arrays(m, who, "src", src[q], src[q].rows))) return rc;
+    }
+    return CVO_OK;
+}
+// record q of a call: map k as it stands and the caller's arrays x
+void maps_snap_desc(cvo_maps m, MapSnapDesc& D, int q, int k, const cvo_map_snapshot& x) {
+    std::memset(&D, 0, sizeof(D));
+    const MapRowsLayout L = map_rows_layout(m->max_rows);
+    char* base = map_base(m, k);
+    D.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); D.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
+    D.ext.keys = static_cast<unsigned long long*>(x.keys); D.ext.sums = static_cast<long long*>(x.sums); D.ext.count = static_cast<unsigned*>(x.count);
+    D.ext.mask = static_cast<unsigned long long*>(x.view_mask); D.ext.last_stamp = static_cast<int*>(x.last_stamp); D.ext.born = static_cast<int*>(x.born);
+    char* table = base + 2 * L.bytes;
+    D.tkeys = reinterpret_cast<unsigned long long*>(table); D.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
+    D.live = m->d_live + k;
+    D.figures = m->r->d_total + MAP_FIGURES * q;
+    D.rows = m->rows[k]; D.slots = 2 * m->max_rows;
+}
+// with a stream: no host wait -- the table's copy is still queued when the call returns, which the next DescTable::take settles
+int maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst, int* rows_out, void* stream) {
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    int rows_max = 0;
+    for (int q = 0; q < count; ++q) {
+        if (rows_out) rows_out[q] = m->rows[maps[q]];
+        rows_max = std::max(rows_max, m->rows[maps[q]]);
+    }
+    if (rows_max == 0) return CVO_OK;
+    DescTable tab{r};
+    MapSnapDesc* h; const MapSnapDesc* d;
+    int rc;
+    if ((rc = tab.take(count, &h, &d))) return rc;
+    for (int q = 0; q < count; ++q) maps_snap_desc(m, h[q], q, maps[q], dst[q]);
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
+    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
+    const hipError_t e = launch_map_snapshot(d, count, rows_max, r->stream);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map snapshot kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
+    if (cs) { HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0)); r->table_in_flight = true; return CVO_OK; }   // (the arrays are ordered on the caller's stream)
+    HIP_TRY(hipEventSynchronize(r->ev_out));
+    return CVO_OK;
+}
+// Two steps, as an update: the rows written and tested on the side the map is not on, the table emptied and filled from them with the duplicate
+// test; the call's one host wait, for the refusal bits; then the host flips the side -- or, on a refusal, queues the launches that make every
+// listed map's table again from the rows it still has.  The caller's arrays are read in the first step only.
+int maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, void* stream) {
+    cvo_reducer r = m->r;
+    HIP_TRY(hipSetDevice(r->device));
+    DescTable tab{r};
+    MapSnapDesc* h; const MapSnapDesc* d;
+    int rc;
+    if ((rc = tab.take(count, &h, &d))) return rc;
+    int new_max = 0, old_max = 0;
+    for (int q = 0; q < count; ++q) {
+        maps_snap_desc(m, h[q], q, maps[q], src[q]);
+        h[q].ext_rows = src[q].rows;
+        new_max = std::max(new_max, src[q].rows); old_max = std::max(old_max, h[q].rows);
+    }
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
+    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_total, 0, sizeof(int) * MAP_FIGURES * (size_t)count, r->stream));
+    hipError_t e = launch_map_restore(d, count, new_max, r->stream);
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map restore kernel launch: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * MAP_FIGURES * (size_t)count, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
+    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
+    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    for (int q = 0; q < count; ++q) {
+        const int bits = r->h_total[MAP_FIGURES * q + 1];
+        if (!bits) continue;
+        e = launch_map_restore_undo(d, count, old_max, 2 * m->max_rows, r->stream);   // behind it runs every later call on the reducer
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map restore kernel launch: ") + hipGetErrorString(e));
+        std::string what;
+        const char* names[5] = {"a bad key", "a count above 16777215", "a negative stamp", "a sum out of bound", "a duplicate key"};
+        for (int b = 0; b < 5; ++b)
+            if (bits & (1 << b)) what += std::string(what.empty() ? "" : ", ") + names[b];
+        return fail(CVO_ERR_INVALID, "map " + std::to_string(maps[q]) + " (entry " + std::to_string(q) + "): the rows are refused, bits " + std::to_string(bits) + ": " + what +
+                                     "; every listed map is unchanged");
+    }
+    for (int q = 0; q < count; ++q) { m->rows[maps[q]] = src[q].rows; m->side[maps[q]] ^= 1; }
+    return CVO_OK;
+}
 }  // namespace
 }  // extern "C++"
 int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out) {
@@ -4951,6 +5071,16 @@ int cvo_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const 
     src.frame = [&](int k, FrameDesc& F) { frame_desc(members[k].image, width, height, step, cams[members[k].cam], F); };
     src.frame_n = frame_sub(width, step) * frame_sub(height, step);
     return maps_probe(m, probes, p, src, [&](int k) { return members[k].pose; }, dst, counts, image_stream);
+}
+int cvo_check_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst) { return maps_check_snapshot(m, count, maps, dst); }
+int cvo_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst, int* rows_out, void* stream) {
+    int rc = maps_check_snapshot(m, count, maps, dst); if (rc) return rc;
+    return maps_snapshot(m, count, maps, dst, rows_out, stream);
+}
+int cvo_check_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel) { return maps_check_restore(m, count, maps, src, voxel); }
+int cvo_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel, void* stream) {
+    int rc = maps_check_restore(m, count, maps, src, voxel); if (rc) return rc;
+    return maps_restore(m, count, maps, src, stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

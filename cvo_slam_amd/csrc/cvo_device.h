@@ -405,6 +405,19 @@ struct ProbeDesc {
     int* totals;                   // their four sums over the member
 };
 static_assert(sizeof(ProbeDesc) == 232, "ProbeDesc layout");
+// one map of a snapshot or a restore (cvo_map_snapshot_kernels.hip; not in the reference; cvo_hip.h, "Saving and restoring maps"): the map's rows
+// on the side that holds them (`at`) and on the other (`to`: where a restore writes), the caller's arrays (`ext`: a snapshot's destination, a
+// restore's source), the table and the call's two figures.  The grid's second dimension.  MapDesc stays as it is.
+struct MapSnapDesc {
+    MapRows at, to, ext;
+    unsigned long long* tkeys; int* trow;   // MapDesc's table: key (all ones = empty) and row
+    int* live;                     // the map's rows with count >= 1
+    int* figures;                  // a restore: [1] the refusal bits
+    int rows;                      // the map's rows as it stands, dead ones included
+    int ext_rows;                  // a restore: the rows to put in
+    int slots, pad_;
+};
+static_assert(sizeof(MapSnapDesc) == 192, "MapSnapDesc layout");
 // what all views of a call share
 struct ViewParams {
     int width, height, cell, mode, gw, gh;

@@ -177,3 +177,49 @@ def lift(map, per_row_values, fill):
     ok = m >= 0
     out[ok] = per_row_values[m[ok]]
     return out
+
+
+SNAPSHOT_ARRAYS = (("keys", np.uint64), ("sums", np.int64), ("count", np.uint32), ("view_mask", np.uint64), ("last_stamp", np.int32), ("born", np.int32))
+
+
+def save_maps(path, snaps, voxel: float):
+    """Write resident maps' snapshots (CvoMaps.snapshot's list of dicts, or the same of numpy arrays) to ONE .npz file at `path`, with the
+    bits of the voxel size the keys were made at: m<k>_keys, m<k>_sums, ... per map, `maps` and `voxel_bits`.  Device tensors are copied to
+    the host here; the unsigned fields are stored unsigned."""
+    out = dict(maps=np.int32(len(snaps)), voxel_bits=np.float32(voxel).view(np.uint32))
+    for k, sn in enumerate(snaps):
+        rows = None
+        for name, dt in SNAPSHOT_ARRAYS:
+            a = sn[name]
+            a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+            if a.dtype.kind not in "iu" or a.dtype.itemsize != np.dtype(dt).itemsize:
+                raise ValueError(f"save_maps: map {k}: {name}: a {np.dtype(dt).itemsize}-byte integer array expected, got {a.dtype}")
+            rows = int(sn.get("rows", a.shape[0])) if rows is None else rows
+            if a.shape[0] < rows or a.shape[1:] != ((8,) if name == "sums" else ()):
+                raise ValueError(f"save_maps: map {k}: {name} of shape {a.shape} for {rows} rows")
+            out[f"m{k}_{name}"] = np.ascontiguousarray(a[:rows]).view(dt)
+    with open(path, "wb") as f:
+        np.savez(f, **out)
+
+
+def load_maps(path, device=None):
+    """(snaps, voxel) from a save_maps file: one dict per map with the six arrays and rows -- torch tensors on `device` (a torch device or a
+    GPU number; the unsigned fields in torch's signed carriers, as CvoMaps.snapshot gives them), or numpy arrays with device None -- and the
+    voxel size as a float with the saved bits.  CvoMaps.restore(maps, snaps, voxel) takes them as they are."""
+    with np.load(path) as z:
+        n = int(z["maps"])
+        voxel = float(np.asarray(z["voxel_bits"], np.uint32).reshape(1).view(np.float32)[0])
+        snaps = [{name: np.ascontiguousarray(z[f"m{k}_{name}"]).astype(dt, copy=False) for name, dt in SNAPSHOT_ARRAYS} for k in range(n)]
+    for sn in snaps:
+        sn["rows"] = int(sn["keys"].shape[0])
+        if any(sn[name].shape != ((sn["rows"], 8) if name == "sums" else (sn["rows"],)) for name, _ in SNAPSHOT_ARRAYS):
+            raise ValueError("load_maps: the arrays of a map differ in length")
+    if device is None:
+        return snaps, voxel
+    import torch
+    dev = torch.device("cuda", device) if isinstance(device, (int, np.integer)) else torch.device(device)
+    signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32}
+    for sn in snaps:
+        for name, dt in SNAPSHOT_ARRAYS:
+            sn[name] = torch.from_numpy(sn[name].view(signed.get(np.dtype(dt), dt))).to(dev)
+    return snaps, voxel

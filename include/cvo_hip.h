@@ -916,6 +916,52 @@ int cvo_maps_probe_clouds(cvo_maps m, int probes, const cvo_map_probe* p, const 
                           int* counts /* probes x 4, host, may be NULL */, void* cloud_stream);
 int cvo_maps_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, const cvo_fuse_frame* members, int width, int height, int step,
                           const cvo_camera* cams, const cvo_probed_points* dst, int* counts /* probes x 4, host, may be NULL */, void* image_stream);
+/* ---- Saving and restoring maps (not in the reference): a resident map's rows copied out as they stand, and a map made of rows the caller
+ * gives -- so that a map can grow (a new object with a larger max_rows, every map restored from the old one), outlast its process, move to
+ * another reducer or another GPU, be forked into another slot to try something on a copy, and be put into a chosen state by a test.
+ *
+ * The statement.  The sums are integers and nothing about the table reaches an output, so a map IS its ordered rows: restoring the snapshot of
+ * a map gives a map on which every later call -- integrate, remove, extract, compact, view, probe, snapshot -- returns the same bytes as on the
+ * original (tests/map_snapshot_reading.py restates the definition; the tests hold the kernels to it byte for byte).
+ *
+ * A cvo_map_snapshot is six caller-owned DEVICE arrays, one set per map, a structure of arrays with row r at index r: keys (uint64), sums
+ * (int64, 8 per row, row-major: a row's 64 bytes), count (uint32), view_mask (uint64), last_stamp and born (int32) -- 92 bytes a row -- and
+ * rows: for a snapshot the arrays' capacity in rows, for a restore the rows to put in.
+ *   snapshot: map maps[k]'s rows 0 .. rows - 1 are written to dst[k] as they stand, in row order, dead rows included (they keep their place
+ *     and their key: a revival must find them).  dst[k].rows must be at least the map's rows, otherwise the call is refused with both
+ *     figures: there are no partial snapshots.  No byte behind row rows - 1 of any array is touched.  rows_out[k] is the map's rows.  The
+ *     call only reads the maps.  One launch for all listed maps.  The host knows every map's rows, so there is no host wait: with a stream
+ *     one event edge in and one out (the maps' rule), with NULL everything is done on return.
+ *   restore: map maps[k] becomes exactly the rows of src[k]: src[k].rows rows in order, the table built from their keys, the live count
+ *     the rows with count >= 1.  What the map held before is gone.  voxel must have the bits of the object's voxel: a key means nothing at
+ *     another cell size.  Source and destination may be different cvo_maps objects, on different reducers, with different max_rows.
+ *   the rows are untrusted (they may come from a file): every row is tested on the device before any map changes, against the conditions of
+ *     "every supported map state", so that a restored map is one that the arguments under "Viewing maps" and "Probing maps" cover.  The
+ *     refusal bits, OR-ed over a map's rows:
+ *        1  bad key: bit 63 set, or one of the three 21-bit fields 0.  A key is (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20) with
+ *           |c| < 2^20, so every field lies in 1 .. 2^21 - 1.  (All ones is the table's empty mark.)
+ *        2  count above CVO_MAP_MAX_COUNT.
+ *        4  stamp: last_stamp < 0 or born < 0.
+ *        8  sum out of bound: some |sum_k| > count * (2^39 - 2^15), as exact integers (the bound of "Viewing maps"; it implies eight zero
+ *           sums in a dead row, and with a count that passes bit 2 the product is below 2^63).
+ *       16  duplicate key: two rows of one map with the same key, among the rows whose key passes bit 1.
+ *     A refusal is CVO_ERR_INVALID naming the first offending map in the call's order and its bits ("bits N"), and leaves EVERY listed map
+ *     unchanged for every later call.  For this a restore runs in two steps, as an update does: the rows are written and tested on the side
+ *     of the rows' memory that the map is not on, the table is emptied and the keys are inserted with the duplicate test; the call's one host
+ *     wait, for the bits; then either the host flips the side and sets rows, or the launches that build every listed map's table again from
+ *     the rows it still has (dead rows included, the live count counted again) are queued on the reducer's stream, behind which every later
+ *     call on the reducer runs.  The caller's arrays are read in the first step only.
+ * Validation: CVO_ERR_INVALID, launching nothing, the message naming map and field: everything the other map calls check on m, count and maps
+ * (each map at most once); a null dst / src; an array that is null with rows to hold, is not device memory of the needed bytes (rows x 8, 64,
+ * 4, 8, 4, 4; for a snapshot the MAP's rows) or is not aligned (keys, sums, view_mask 8 bytes, the others 4); a restore's rows outside 0 ..
+ * max_rows of the destination (both figures in the message); voxel not the object's bits; a snapshot's capacity below the map's rows.
+ * rows == 0 with NULL arrays restores an empty map and is legal. */
+typedef struct cvo_map_snapshot { void *keys, *sums, *count, *view_mask, *last_stamp, *born; int rows; int pad_; } cvo_map_snapshot;   /* 56 bytes */
+/* the validation of the two calls alone: launches nothing */
+int cvo_check_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst /* count */);
+int cvo_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst, int* rows_out /* count, host, may be NULL */, void* stream);
+int cvo_check_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src /* count */, float voxel);
+int cvo_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel, void* stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
