@@ -114,7 +114,7 @@ hipError_t launch_map_lookup(const MapDesc* maps, int n_maps, const FuseGroupDes
 hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, hipStream_t s);
 hipError_t launch_map_extract(const MapDesc* maps, int n_maps, int rows_max, bool write, hipStream_t s);
 hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hipStream_t s);
-hipError_t launch_map_clear(const MapDesc* maps, int n_maps, int slots, hipStream_t s);
+hipError_t launch_map_clear(const void* records, size_t stride, int n_maps, int slots, hipStream_t s);
 hipError_t launch_probe_clouds(const ProbeDesc* probes, int n_probes, int n_max, float voxel, hipStream_t s);
 hipError_t launch_probe_frames(const ProbeDesc* probes, const FrameDesc* frames, int n_probes, int n, float voxel, hipStream_t s);
 hipError_t launch_map_snapshot(const MapSnapDesc* maps, int n_maps, int rows_max, hipStream_t s);
@@ -3713,7 +3713,7 @@ struct cvo_reducer_s {
     void* h_desc = nullptr; int* h_total = nullptr;                   // their pinned twins: written before the launches, read after the call's one wait
     size_t table_bytes = 0;                                           // the size of d_desc and of h_desc
     int live_maps = 0;                                                // cvo_maps objects created on this reducer and not yet destroyed
-    bool table_in_flight = false;                                     // a call without a host wait (a probe without counts) left h_desc's copy queued
+    bool table_in_flight = false;                                     // a call without a host wait (CallEdges::may_return_early) left h_desc's copy queued
 };
 extern "C++" {                                                        // (the helpers below have templates among them)
 namespace {
@@ -3991,19 +3991,35 @@ void desc_scratch_out(cvo_reducer r, const ReduceLayout& L, int q, const Dst& d,
     D.total = r->d_total + q;
     D.n = n; D.slots = 2 * n; D.cap = d.cap; D.rows_cap = std::min(d.cap, n);
 }
-// The edges of a call: the reducer's stream behind the caller's, the launches (queue), their counts to pinned memory, the caller's stream behind
-// the reducer's, and the call's one host wait.
-int reducer_run(cvo_reducer r, size_t table_bytes, int n_totals, void* cloud_stream, const std::function<hipError_t()>& queue) {
-    hipStream_t cs = static_cast<hipStream_t>(cloud_stream);
+// The edges of every call on the reducer's stream, written once: the reducer's stream behind the caller's, the call's tables to the device, its
+// figures zeroed, the launches (queue), the figures to pinned memory, the caller's stream behind the reducer's, and the call's one host wait --
+// or none: a call with a stream and nothing to read back may return with its table's copy still queued, which the next DescTable::take settles.
+struct CallEdges {
+    const char* name;                                                 // of the kernels, for the launch-failure message
+    size_t table_bytes = 0;                                           // of the reducer's descriptor table (0: none)
+    const void* own_host = nullptr; void* own_dev = nullptr; size_t own_bytes = 0;   // a table of the caller's own copied beside it (a maps object's MapDescs)
+    int zero_figures = 0, read_figures = 0;                           // ints of the reducer's counts zeroed first / copied to h_total behind the launches
+    bool may_return_early = false;
+};
+int run_call(cvo_reducer r, const CallEdges& c, void* stream, const std::function<hipError_t()>& queue) {
+    hipStream_t cs = static_cast<hipStream_t>(stream);
     if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
-    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, table_bytes, hipMemcpyHostToDevice, r->stream));
+    if (c.table_bytes) HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, c.table_bytes, hipMemcpyHostToDevice, r->stream));
+    if (c.own_bytes) HIP_TRY(hipMemcpyAsync(c.own_dev, c.own_host, c.own_bytes, hipMemcpyHostToDevice, r->stream));
+    if (c.zero_figures > 0) HIP_TRY(hipMemsetAsync(r->d_total, 0, sizeof(int) * (size_t)c.zero_figures, r->stream));
     const hipError_t e = queue();
-    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("cloud reduce kernel launch: ") + hipGetErrorString(e));
-    if (n_totals > 0) HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * (size_t)n_totals, hipMemcpyDeviceToHost, r->stream));
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string(c.name) + " kernel launch: " + hipGetErrorString(e));
+    if (c.read_figures > 0) HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * (size_t)c.read_figures, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipEventRecord(r->ev_out, r->stream));
     if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
+    if (c.may_return_early && cs && c.read_figures == 0) { r->table_in_flight = true; return CVO_OK; }   // (the outputs are ordered on the caller's stream)
     HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
     return CVO_OK;
+}
+int reducer_run(cvo_reducer r, size_t table_bytes, int n_totals, void* cloud_stream, const std::function<hipError_t()>& queue) {
+    CallEdges c{"cloud reduce"};
+    c.table_bytes = table_bytes; c.read_figures = n_totals;
+    return run_call(r, c, cloud_stream, queue);
 }
 
 // -- reduce, count and fuse, each once over a point source: the checked call's items with points (a frame always has some) get records, in order
@@ -4388,26 +4404,39 @@ MapRows map_rows_at(char* base, const MapRowsLayout& L) {
     R.last_stamp = reinterpret_cast<int*>(base + L.last_stamp); R.born = reinterpret_cast<int*>(base + L.born);
     return R;
 }
-// record q of a call: map `k` as it stands, its figures at the reducer's counts 4 q ..; everything a single kind of call sets stays 0
 // map k's share of the object's memory
 char* map_base(cvo_maps m, int k) {
     char* base = m->mem + up16(4 * (size_t)m->max_maps) + (size_t)k * m->map_bytes;
     return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 127) & ~(uintptr_t)127);
 }
+// Where map k lies now -- the side that holds its rows and the other, the table behind both, `live`, the rows and the slots -- for every record
+// that names a map; block_heads: the block counts behind the table, if asked for.  Compact and restore flip the side; nothing else reads it.
+MapPlace map_place(cvo_maps m, int k, int** block_heads = nullptr) {
+    const MapRowsLayout L = map_rows_layout(m->max_rows);
+    char* base = map_base(m, k);
+    char* table = base + 2 * L.bytes;
+    MapPlace P;
+    P.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); P.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
+    P.tkeys = reinterpret_cast<unsigned long long*>(table); P.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
+    P.live = m->d_live + k;
+    P.rows = m->rows[k]; P.slots = 2 * m->max_rows;
+    if (block_heads) *block_heads = reinterpret_cast<int*>(table + map_table_keys(m->max_rows) + map_table_rows(m->max_rows));
+    return P;
+}
+// record q of a call: map `k` as it stands, its figures at the reducer's counts 4 q ..; everything a single kind of call sets stays 0
 MapDesc& maps_desc(cvo_maps m, int q, int k) {
     MapDesc& D = m->h_desc[q];
     std::memset(&D, 0, sizeof(D));
-    const MapRowsLayout L = map_rows_layout(m->max_rows);
-    char* base = map_base(m, k);
-    D.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); D.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
-    char* table = base + 2 * L.bytes;
-    D.tkeys = reinterpret_cast<unsigned long long*>(table); D.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
-    D.block_heads = reinterpret_cast<int*>(table + map_table_keys(m->max_rows) + map_table_rows(m->max_rows));
-    D.live = m->d_live + k;
+    static_cast<MapPlace&>(D) = map_place(m, k, &D.block_heads);
     D.total = m->r->d_total + MAP_FIGURES * q;
-    D.rows = m->rows[k]; D.slots = 2 * m->max_rows;
     return D;
 }
+// the range of a row filter's min_views (extract's, compact's keep rule, a view's and a probe's), `who`: "map 3: "
+int maps_check_filter(const std::string& who, int min_views) {
+    if (min_views < 0 || min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(min_views) + " is outside 0 .. 64");
+    return CVO_OK;
+}
+inline MapRowFilter map_row_filter(const cvo_map_filter& f) { return MapRowFilter{f.min_points, f.min_views, f.min_last_stamp}; }
 int maps_check_list(cvo_maps m, int count, const int* maps, const char* what) {
     if (!m) return fail(CVO_ERR_INVALID, "null maps object");
     if (count < 1 || count > m->max_maps) return fail(CVO_ERR_INVALID, std::string(what) + " " + std::to_string(count) + " is outside 1 .. max_maps " + std::to_string(m->max_maps));
@@ -4449,21 +4478,12 @@ int maps_check_frames(cvo_maps m, int groups, const int* maps, const int* group_
     if ((rc = fuse_frames_check(m->r, groups, group_first, members, width, height, step, cams, &P, none.data()))) return rc;
     return maps_check_stamps(groups, group_first, stamps);
 }
-// the edges of a maps call: reducer_run's, with the call's MapDesc records copied beside the reducer's table (fuse_bytes of it; 0: none)
+// the edges of a call over MapDesc records: they are copied beside the reducer's table (fuse_bytes of it; 0: none), four figures per map
 int maps_run(cvo_maps m, int n_maps, size_t fuse_bytes, void* stream, const std::function<hipError_t()>& queue) {
-    cvo_reducer r = m->r;
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
-    if (fuse_bytes) HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, fuse_bytes, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipMemcpyAsync(m->d_desc, m->h_desc, sizeof(MapDesc) * (size_t)n_maps, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_total, 0, sizeof(int) * MAP_FIGURES * (size_t)n_maps, r->stream));
-    const hipError_t e = queue();
-    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("resident maps kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * MAP_FIGURES * (size_t)n_maps, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
-    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
-    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
-    return CVO_OK;
+    CallEdges c{"resident maps"};
+    c.table_bytes = fuse_bytes; c.own_host = m->h_desc; c.own_dev = m->d_desc; c.own_bytes = sizeof(MapDesc) * (size_t)n_maps;
+    c.zero_figures = c.read_figures = MAP_FIGURES * n_maps;
+    return run_call(m->r, c, stream, queue);
 }
 // src's item k is member k of the call, pose(k) its 12 floats.  A group with points gets a FuseGroupDesc, its members with points FuseMemberDescs
 // behind them (fuse_points' tables), and its map a MapDesc; a group without points changes nothing.
@@ -4549,7 +4569,7 @@ int maps_check_extract(cvo_maps m, int count, const int* maps, const cvo_map_fil
     for (int q = 0; q < count; ++q) {
         const std::string who = "map " + std::to_string(maps[q]) + ": ";
         const cvo_map_cloud& d = dst[q];
-        if (filter[q].min_views < 0 || filter[q].min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(filter[q].min_views) + " is outside 0 .. 64");
+        if ((rc = maps_check_filter(who, filter[q].min_views))) return rc;
         if (d.cap < 0 || d.cap > 65535) return fail(CVO_ERR_INVALID, who + "cap " + std::to_string(d.cap) + " is outside 0 .. 65535");
         if (d.cap > 0 && !d.xyz) return fail(CVO_ERR_INVALID, who + "dst xyz is null with cap " + std::to_string(d.cap));
         if (d.cap > 0 && !d.feat) return fail(CVO_ERR_INVALID, who + "dst feat is null with cap " + std::to_string(d.cap));
@@ -4571,7 +4591,7 @@ int maps_extract(cvo_maps m, int count, const int* maps, const cvo_map_filter* f
         D.out_xyz = static_cast<float*>(d.xyz); D.out_feat = static_cast<float*>(d.feat); D.out_count = static_cast<int*>(d.count);
         D.out_views = static_cast<int*>(d.views); D.out_view_mask = static_cast<unsigned long long*>(d.view_mask);
         D.out_last_stamp = static_cast<int*>(d.last_stamp); D.out_born = static_cast<int*>(d.born); D.out_row = static_cast<int*>(d.row);
-        D.cap = d.cap; D.min_points = filter[q].min_points; D.min_views = filter[q].min_views; D.min_last_stamp = filter[q].min_last_stamp;
+        D.cap = d.cap; D.filter = map_row_filter(filter[q]);
         rows_max = std::max(rows_max, D.rows); cap_max = std::max(cap_max, d.cap);
     }
     if (rows_max == 0) return CVO_OK;
@@ -4585,7 +4605,7 @@ int maps_check_compact(cvo_maps m, int count, const int* maps, const cvo_map_kee
     if (!keep) return fail(CVO_ERR_INVALID, "null argument: keep");
     for (int q = 0; q < count; ++q) {
         const std::string who = "map " + std::to_string(maps[q]) + ": ";
-        if (keep[q].min_views < 0 || keep[q].min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(keep[q].min_views) + " is outside 0 .. 64");
+        if ((rc = maps_check_filter(who, keep[q].min_views))) return rc;
         const long long rows = m->rows[maps[q]];
         if ((rc = check_out_arrays(m->r->device, who, {{drop ? drop[q] : nullptr, rows, 1, "drop", false}, {new_row ? new_row[q] : nullptr, 4 * rows, 4, "new_row", false}}))) return rc;
     }
@@ -4598,7 +4618,7 @@ int maps_compact(cvo_maps m, int count, const int* maps, const cvo_map_keep* kee
         if (rows_out) rows_out[q] = 0;
         MapDesc& D = maps_desc(m, q, maps[q]);
         D.drop = drop ? static_cast<const uint8_t*>(drop[q]) : nullptr; D.new_row = new_row ? static_cast<int*>(new_row[q]) : nullptr;
-        D.min_last_stamp = keep[q].min_last_stamp; D.min_views = keep[q].min_views; D.probation_from = keep[q].probation_from;
+        D.filter.min_last_stamp = keep[q].min_last_stamp; D.filter.min_views = keep[q].min_views; D.probation_from = keep[q].probation_from;
         rows_max = std::max(rows_max, D.rows);
     }
     if (rows_max == 0) return CVO_OK;
@@ -4638,7 +4658,7 @@ int maps_check_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_came
     for (int k = 0; k < views; ++k) {
         const std::string who = "view " + std::to_string(k) + ": ";
         if (v[k].map < 0 || v[k].map >= m->max_maps) return fail(CVO_ERR_INVALID, who + "map " + std::to_string(v[k].map) + " is outside 0 .. " + std::to_string(m->max_maps - 1));
-        if (v[k].filter.min_views < 0 || v[k].filter.min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(v[k].filter.min_views) + " is outside 0 .. 64");
+        if ((rc = maps_check_filter(who, v[k].filter.min_views))) return rc;
         if ((rc = fuse_check_pose(v[k].pose, who)) || (rc = frames_check_camera(cams, v[k].cam, who))) return rc;
         const long long rows = m->rows[v[k].map];
         rows_max = std::max(rows_max, (int)rows);
@@ -4677,18 +4697,16 @@ int maps_view(cvo_maps m, int views, const cvo_map_view* v, const cvo_camera* ca
     int n_max = 0; bool images = false;
     for (int q = 0; q < views; ++q) n_max = std::max(n_max, m->rows[v[q].map]);
     const MapViewLayout L = map_view_layout((long long)P.gw * P.gh, n_max);
-    const MapRowsLayout RL = map_rows_layout(m->max_rows);
     for (int q = 0; q < views; ++q) {
         ViewDesc& V = h[q]; MapViewSrc& S = hs[q];
         std::memset(&V, 0, sizeof(V));                                // (no cloud: the rows are the points)
         const int k = v[q].map;
         const cvo_camera& c = cams[v[q].cam];
-        const MapRows rows = map_rows_at(map_base(m, k) + (m->side[k] ? RL.bytes : 0), RL);
-        S.sums = rows.sums; S.count = rows.count; S.mask = rows.mask; S.last_stamp = rows.last_stamp;
+        S.map = map_place(m, k);
         S.carve = carve ? static_cast<uint8_t*>(carve[q]) : nullptr;
-        S.min_points = v[q].filter.min_points; S.min_views = v[q].filter.min_views; S.min_last_stamp = v[q].filter.min_last_stamp; S.pad_ = 0;
+        S.filter = map_row_filter(v[q].filter); S.pad_ = 0;
         std::memcpy(V.pose, v[q].pose, sizeof(V.pose));
-        V.fx = c.fx; V.fy = c.fy; V.cx = c.cx; V.cy = c.cy; V.scaling_factor = c.scaling_factor; V.n = m->rows[k];
+        V.fx = c.fx; V.fy = c.fy; V.cx = c.cx; V.cy = c.cy; V.scaling_factor = c.scaling_factor; V.n = S.map.rows;
         char* base = static_cast<char*>(r->scratch) + (size_t)q * map_view_region(r);
         V.zbuf = reinterpret_cast<unsigned long long*>(base); V.code = reinterpret_cast<int*>(base + L.code); V.block_heads = reinterpret_cast<int*>(base + L.block_heads);
         V.block_relations = reinterpret_cast<int*>(base + L.block_relations);
@@ -4732,7 +4750,7 @@ int maps_check_probe_tail(cvo_maps m, int probes, const cvo_map_probe* p, const 
         const std::string who = "probe " + std::to_string(k) + ": ";
         if (p[k].map < 0 || p[k].map >= m->max_maps) return fail(CVO_ERR_INVALID, who + "map " + std::to_string(p[k].map) + " is outside 0 .. " + std::to_string(m->max_maps - 1));
         if (p[k].reach != 0 && p[k].reach != 1) return fail(CVO_ERR_INVALID, who + "reach " + std::to_string(p[k].reach) + " is neither 0 nor 1");
-        if (p[k].filter.min_views < 0 || p[k].filter.min_views > FUSE_MAX_MEMBERS) return fail(CVO_ERR_INVALID, who + "min_views " + std::to_string(p[k].filter.min_views) + " is outside 0 .. 64");
+        if ((rc = maps_check_filter(who, p[k].filter.min_views))) return rc;
         const long long n = n_of(k), rows = m->rows[p[k].map];
         const cvo_probed_points& d = dst[k];
         const struct { const void* ptr; const char* name; } needs_row[4] = {{d.dist2, "dist2"}, {d.count, "count"}, {d.views, "views"}, {d.last_stamp, "last_stamp"}};
@@ -4777,8 +4795,7 @@ int maps_check_probe_frames(cvo_maps m, int probes, const cvo_map_probe* p, cons
     return maps_check_probe_tail(m, probes, p, [&](int) { return n; }, dst);
 }
 // every probe gets a record, an empty member too: its four counts are 0 and its hit bytes are cleared all the same.  src's item k is probe k's
-// member, pose(k) its 12 floats.  counts == nullptr and a stream: no host wait -- the table's copy is still queued when the call returns, which
-// the next DescTable::take settles.
+// member, pose(k) its 12 floats.  counts == nullptr and a stream: no host wait (run_call).
 int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource& src, const std::function<const float*(int)>& pose, const cvo_probed_points* dst,
                int* counts, void* stream) {
     cvo_reducer r = m->r;
@@ -4788,7 +4805,6 @@ int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource
     int rc;
     if ((rc = tab.take(probes, &h, &d))) return rc;
     if (src.frames() && (rc = tab.take(probes, &hf, &df))) return rc;
-    const MapRowsLayout RL = map_rows_layout(m->max_rows);
     int n_max = 0;
     for (int q = 0; q < probes; ++q) {
         ProbeDesc& D = h[q];
@@ -4796,34 +4812,23 @@ int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource
         src.fill(q, D, hf, q);
         std::memcpy(D.pose, pose(q), sizeof(D.pose));
         D.n = src.n(q); D.reach = p[q].reach;
-        const int k = p[q].map;
-        char* base = map_base(m, k);
-        const MapRows rows = map_rows_at(base + (m->side[k] ? RL.bytes : 0), RL);
-        char* table = base + 2 * RL.bytes;
-        D.tkeys = reinterpret_cast<const unsigned long long*>(table); D.trow = reinterpret_cast<const int*>(table + map_table_keys(m->max_rows));
-        D.sums = rows.sums; D.count = rows.count; D.mask = rows.mask; D.last_stamp = rows.last_stamp;
-        D.slots = 2 * m->max_rows; D.rows = m->rows[k];
-        D.min_points = p[q].filter.min_points; D.min_views = p[q].filter.min_views; D.min_last_stamp = p[q].filter.min_last_stamp;
+        D.map = map_place(m, p[q].map);
+        D.filter = map_row_filter(p[q].filter);
         const cvo_probed_points& o = dst[q];
         D.out_row = static_cast<int*>(o.row); D.out_dist2 = static_cast<float*>(o.dist2); D.out_count = static_cast<int*>(o.count);
         D.out_views = static_cast<int*>(o.views); D.out_last_stamp = static_cast<int*>(o.last_stamp);
-        D.out_hit = D.rows > 0 ? static_cast<uint8_t*>(o.hit) : nullptr;
+        D.out_hit = D.map.rows > 0 ? static_cast<uint8_t*>(o.hit) : nullptr;
         D.block_counts = reinterpret_cast<int*>(static_cast<char*>(r->scratch) + (size_t)q * map_view_region(r));
         D.totals = r->d_total + PROBE_COUNTS * q;
         n_max = std::max(n_max, D.n);
     }
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
-    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
-    for (int q = 0; q < probes; ++q)
-        if (h[q].out_hit) HIP_TRY(hipMemsetAsync(h[q].out_hit, 0, (size_t)h[q].rows, r->stream));
-    const hipError_t e = src.frames() ? launch_probe_frames(d, df, probes, n_max, m->voxel, r->stream) : launch_probe_clouds(d, probes, n_max, m->voxel, r->stream);
-    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map probe kernel launch: ") + hipGetErrorString(e));
-    if (counts) HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * PROBE_COUNTS * (size_t)probes, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
-    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
-    if (!counts && cs) { r->table_in_flight = true; return CVO_OK; }   // (no host wait: the outputs are ordered on the caller's stream)
-    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    CallEdges c{"map probe"};
+    c.table_bytes = tab.used; c.read_figures = counts ? PROBE_COUNTS * probes : 0; c.may_return_early = true;
+    if ((rc = run_call(r, c, stream, [&] {
+            for (int q = 0; q < probes; ++q)                          // (the hit bytes cleared on the stream, in front of the kernels)
+                if (h[q].out_hit) { const hipError_t e = hipMemsetAsync(h[q].out_hit, 0, (size_t)h[q].map.rows, r->stream); if (e != hipSuccess) return e; }
+            return src.frames() ? launch_probe_frames(d, df, probes, n_max, m->voxel, r->stream) : launch_probe_clouds(d, probes, n_max, m->voxel, r->stream); })))
+        return rc;
     if (counts) std::memcpy(counts, r->h_total, sizeof(int) * PROBE_COUNTS * (size_t)probes);
     return CVO_OK;
 }
@@ -4831,6 +4836,9 @@ int maps_probe(cvo_maps m, int probes, const cvo_map_probe* p, const PointSource
 // reducer's descriptor table (max_maps <= max_clouds of them: reducer_alloc's first term covers them), a restore's figures four ints per map of
 // the call in the reducer's counts, as an update's.
 static_assert(sizeof(MapSnapDesc) <= sizeof(ReduceDesc) + sizeof(FrameDesc), "a MapSnapDesc per map fits the reducer's descriptor table");
+// max_clouds probes with a FrameDesc each, and max_clouds views with a MapViewSrc each: reducer_alloc's second term (16 CountDescs per cloud)
+static_assert(sizeof(ProbeDesc) + sizeof(FrameDesc) <= CVO_REDUCE_MAX_VOXELS * sizeof(CountDesc), "a ProbeDesc and a FrameDesc per probe fit the reducer's descriptor table");
+static_assert(sizeof(ViewDesc) + sizeof(MapViewSrc) <= CVO_REDUCE_MAX_VOXELS * sizeof(CountDesc), "a ViewDesc and a MapViewSrc per view fit the reducer's descriptor table");
 int maps_check_snap_arrays(cvo_maps m, const std::string& who, const char* side, const cvo_map_snapshot& x, long long rows) {
     const bool need = rows > 0;
     const std::string s(side);
@@ -4867,18 +4875,12 @@ int maps_check_restore(cvo_maps m, int count, const int* maps, const cvo_map_sna
 // record q of a call: map k as it stands and the caller's arrays x
 void maps_snap_desc(cvo_maps m, MapSnapDesc& D, int q, int k, const cvo_map_snapshot& x) {
     std::memset(&D, 0, sizeof(D));
-    const MapRowsLayout L = map_rows_layout(m->max_rows);
-    char* base = map_base(m, k);
-    D.at = map_rows_at(base + (m->side[k] ? L.bytes : 0), L); D.to = map_rows_at(base + (m->side[k] ? 0 : L.bytes), L);
+    static_cast<MapPlace&>(D) = map_place(m, k);
     D.ext.keys = static_cast<unsigned long long*>(x.keys); D.ext.sums = static_cast<long long*>(x.sums); D.ext.count = static_cast<unsigned*>(x.count);
     D.ext.mask = static_cast<unsigned long long*>(x.view_mask); D.ext.last_stamp = static_cast<int*>(x.last_stamp); D.ext.born = static_cast<int*>(x.born);
-    char* table = base + 2 * L.bytes;
-    D.tkeys = reinterpret_cast<unsigned long long*>(table); D.trow = reinterpret_cast<int*>(table + map_table_keys(m->max_rows));
-    D.live = m->d_live + k;
     D.figures = m->r->d_total + MAP_FIGURES * q;
-    D.rows = m->rows[k]; D.slots = 2 * m->max_rows;
 }
-// with a stream: no host wait -- the table's copy is still queued when the call returns, which the next DescTable::take settles
+// with a stream: no host wait (run_call)
 int maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst, int* rows_out, void* stream) {
     cvo_reducer r = m->r;
     HIP_TRY(hipSetDevice(r->device));
@@ -4893,15 +4895,9 @@ int maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot
     int rc;
     if ((rc = tab.take(count, &h, &d))) return rc;
     for (int q = 0; q < count; ++q) maps_snap_desc(m, h[q], q, maps[q], dst[q]);
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
-    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
-    const hipError_t e = launch_map_snapshot(d, count, rows_max, r->stream);
-    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map snapshot kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
-    if (cs) { HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0)); r->table_in_flight = true; return CVO_OK; }   // (the arrays are ordered on the caller's stream)
-    HIP_TRY(hipEventSynchronize(r->ev_out));
-    return CVO_OK;
+    CallEdges c{"map snapshot"};
+    c.table_bytes = tab.used; c.may_return_early = true;
+    return run_call(r, c, stream, [&] { return launch_map_snapshot(d, count, rows_max, r->stream); });
 }
 // Two steps, as an update: the rows written and tested on the side the map is not on, the table emptied and filled from them with the duplicate
 // test; the call's one host wait, for the refusal bits; then the host flips the side -- or, on a refusal, queues the launches that make every
@@ -4919,20 +4915,13 @@ int maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot*
         h[q].ext_rows = src[q].rows;
         new_max = std::max(new_max, src[q].rows); old_max = std::max(old_max, h[q].rows);
     }
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    if (cs) { HIP_TRY(hipEventRecord(r->ev_in, cs)); HIP_TRY(hipStreamWaitEvent(r->stream, r->ev_in, 0)); }
-    HIP_TRY(hipMemcpyAsync(r->d_desc, r->h_desc, tab.used, hipMemcpyHostToDevice, r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_total, 0, sizeof(int) * MAP_FIGURES * (size_t)count, r->stream));
-    hipError_t e = launch_map_restore(d, count, new_max, r->stream);
-    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map restore kernel launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpyAsync(r->h_total, r->d_total, sizeof(int) * MAP_FIGURES * (size_t)count, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipEventRecord(r->ev_out, r->stream));
-    if (cs) HIP_TRY(hipStreamWaitEvent(cs, r->ev_out, 0));
-    HIP_TRY(hipEventSynchronize(r->ev_out));                          // (the call's one host wait)
+    CallEdges c{"map restore"};
+    c.table_bytes = tab.used; c.zero_figures = c.read_figures = MAP_FIGURES * count;
+    if ((rc = run_call(r, c, stream, [&] { return launch_map_restore(d, count, new_max, r->stream); }))) return rc;
     for (int q = 0; q < count; ++q) {
         const int bits = r->h_total[MAP_FIGURES * q + 1];
         if (!bits) continue;
-        e = launch_map_restore_undo(d, count, old_max, 2 * m->max_rows, r->stream);   // behind it runs every later call on the reducer
+        const hipError_t e = launch_map_restore_undo(d, count, old_max, 2 * m->max_rows, r->stream);   // behind it runs every later call on the reducer
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("map restore kernel launch: ") + hipGetErrorString(e));
         std::string what;
         const char* names[5] = {"a bad key", "a count above 16777215", "a negative stamp", "a sum out of bound", "a duplicate key"};
@@ -4970,7 +4959,7 @@ int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_
     if (e == hipSuccess) {                                            // every table empty (all ones), every live count 0
         m->d_live = reinterpret_cast<int*>(m->mem);
         e = hipMemsetAsync(m->mem, 0, up16(4 * (size_t)max_maps), r->stream);
-        for (int k = 0; k < max_maps && e == hipSuccess; ++k) e = hipMemsetAsync(maps_desc(m, 0, k).tkeys, 0xFF, 16 * (size_t)max_rows, r->stream);
+        for (int k = 0; k < max_maps && e == hipSuccess; ++k) e = hipMemsetAsync(map_place(m, k).tkeys, 0xFF, 16 * (size_t)max_rows, r->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
     }
     if (e != hipSuccess) { maps_release(m); return fail(CVO_ERR_HIP, std::string("cvo_maps_create: ") + hipGetErrorString(e)); }
@@ -4993,7 +4982,7 @@ int cvo_maps_clear(cvo_maps m, int count, const int* maps, void* stream) {
     int rc = maps_check_list(m, count, maps, "count"); if (rc) return rc;
     HIP_TRY(hipSetDevice(m->r->device));
     for (int q = 0; q < count; ++q) maps_desc(m, q, maps[q]);
-    if ((rc = maps_run(m, count, 0, stream, [&] { return launch_map_clear(m->d_desc, count, 2 * m->max_rows, m->r->stream); }))) return rc;
+    if ((rc = maps_run(m, count, 0, stream, [&] { return launch_map_clear(m->d_desc, sizeof(MapDesc), count, 2 * m->max_rows, m->r->stream); }))) return rc;
     for (int q = 0; q < count; ++q) m->rows[maps[q]] = 0;
     return CVO_OK;
 }

@@ -322,8 +322,8 @@ struct FuseMemberDesc {
 static_assert(sizeof(FuseMemberDesc) == 112, "FuseMemberDesc layout");
 // one map of a resident-maps call (cvo_map_kernels.hip; not in the reference; cvo_hip.h, "Resident maps"): the grid's second dimension in every
 // pass.  A map's rows are a structure of arrays, one array per field, except the 8 sums of a row, which lie together (64 bytes: a wave's rows
-// are whole cache lines in the merge's scattered reads and in the extract's dense ones).  The rows exist twice: `to` is where a compaction
-// moves them (the call's host side then swaps the two).  The table maps a cell key to its row: 2 x max_rows slots, open addressing.
+// are whole cache lines in the merge's scattered reads and in the extract's dense ones).  The rows exist twice: `to` is where a compaction or a
+// restore writes them (the call's host side then swaps the two).  The table maps a cell key to its row: 2 x max_rows slots, open addressing.
 struct MapRows {
     unsigned long long* keys;      // the row's cell key
     long long* sums;               // 8 per row
@@ -331,24 +331,34 @@ struct MapRows {
     unsigned long long* mask;      // view_mask
     int* last_stamp; int* born;
 };
-struct MapDesc {
-    MapRows at, to;
+// where a map lies now: what every kernel that reads or writes a map takes of it (cvo_capi.hip's map_place fills it; the rules that read it
+// are cvo_voxel_table.hpp's "a resident map read in place").  A reader that does not use a field leaves it filled; what only a writer uses (`to`)
+// lies last, so a reader's uniform loads stay within the record's first 80 bytes.
+struct MapPlace {
+    MapRows at;                    // the side that holds the rows
     unsigned long long* tkeys; int* trow;   // slots: key (all ones = empty) and row
     int* live;                     // the map's rows with count >= 1
+    int rows, slots;               // the map's rows as it stands, dead ones included; the table's size
+    MapRows to;                    // the other side: where a compaction or a restore writes the rows
+};
+// extract's filter (row_kept), which the views and the probes of a map apply as well
+struct MapRowFilter { int min_points, min_views, min_last_stamp; };
+struct MapDesc : MapPlace {
     int* block_heads;              // one per 256 rows (extract, compact) or per 256 call-cells (an update's births), then their exclusive sum
     int* cell_row;                 // an update: the map row of the call-cell of rank r; -1: absent; after the merge -(row) - 1 for a cell born there
     int* total;                    // the call's figures: [0] rows out (extract, compact) / call-cells, [1] an update's births, [2] its refusal bits
     float* out_xyz; float* out_feat; int* out_count; int* out_views; unsigned long long* out_view_mask;   // extract's arrays, all but xyz, feat may be null
     int* out_last_stamp; int* out_born; int* out_row;
     const uint8_t* drop; int* new_row;   // compact's, either may be null
-    int rows, slots, cap;
+    int cap;
     int group;                     // an update: its group in the launch's FuseGroupDesc table
     int sign;                      // +1 integrate, -1 remove, -2 remove what is still there (CVO_MAP_*)
-    int min_points, min_views, min_last_stamp, probation_from;   // extract's filter / compact's keep rule
+    MapRowFilter filter; int probation_from;   // extract's filter / with it compact's keep rule (row_stays)
     int pad_;
     int stamps[64];                // an update: the stamp of member number m of the group
 };
-static_assert(sizeof(MapRows) == 48 && sizeof(MapDesc) == 520, "MapDesc layout");
+static_assert(sizeof(MapRows) == 48 && sizeof(MapPlace) == 128 && sizeof(MapRowFilter) == 12, "MapPlace layout");
+static_assert(sizeof(MapDesc) == 520, "MapDesc layout");              // (128 + 24 + 64 + 16 + 32 + 256)
 // one view of a viewing call (cvo_view_kernels.hip; not in the reference; cvo_hip.h, "Viewing clouds"): a cloud (n may be 0: its images are
 // still written), its pose and camera, its part of the reducer's scratch and the caller's arrays.  The grid's second dimension in every pass.
 struct ViewDesc {
@@ -373,49 +383,37 @@ static_assert(sizeof(ViewDesc) == 248, "ViewDesc layout");
 // the map a view of cvo_maps_view reads in place (cvo_hip.h, "Viewing maps"): one per view, behind the call's ViewDesc records, whose cloud
 // fields stay 0 and whose n is the map's rows, dead ones included.  Row r is point r when the filter keeps it.
 struct MapViewSrc {
-    const long long* sums;         // 8 per row (MapRows::sums)
-    const unsigned* count;
-    const unsigned long long* mask;
-    const int* last_stamp;
     uint8_t* carve;                // n bytes, or null: 1 where the row is visible with relation 1
-    int min_points, min_views, min_last_stamp;   // extract's filter
+    MapRowFilter filter;
     int pad_;
+    MapPlace map;
 };
-static_assert(sizeof(MapViewSrc) == 56, "MapViewSrc layout");
+static_assert(sizeof(MapViewSrc) == 152, "MapViewSrc layout");
 // one probe of a probing call (cvo_probe_kernels.hip; not in the reference; cvo_hip.h, "Probing maps"): a posed member -- a cloud with the
 // strides resolved, or a frame read in place (its FrameDesc behind the records, the cloud fields 0) -- and the map it is looked up in, read
-// where it lies: the table, and of the rows what the filter and the distance need.  The grid's second dimension.
+// where it lies.  The grid's second dimension.
 struct ProbeDesc {
     const float* xyz; const float* feat;
     long long xyz_stride, feat_point_stride, feat_channel_stride;
     float pose[12];                // row-major 3 x 4: the member's frame to the map's
     int n;                         // the member's points
     int reach;                     // 0: the point's own cell; 1: the 27 cells around it
-    const unsigned long long* tkeys; const int* trow;   // MapDesc's table: key (all ones = empty) and row
-    const long long* sums;         // 8 per row (MapRows::sums)
-    const unsigned* count;
-    const unsigned long long* mask;
-    const int* last_stamp;
-    int slots, rows;
-    int min_points, min_views, min_last_stamp;   // extract's filter
+    MapRowFilter filter;
     int pad_;
     int* out_row; float* out_dist2; int* out_count; int* out_views; int* out_last_stamp;   // n each, any may be null
-    uint8_t* out_hit;              // rows bytes, cleared by the call, or null
+    uint8_t* out_hit;              // map.rows bytes, cleared by the call, or null
     int* block_counts;             // four per 256 points: the block's found, absent, filtered and invalid points
     int* totals;                   // their four sums over the member
+    MapPlace map;                  // (last: what the kernel reads of the record ends 256 bytes in, as before the map had a record of its own)
 };
-static_assert(sizeof(ProbeDesc) == 232, "ProbeDesc layout");
-// one map of a snapshot or a restore (cvo_map_snapshot_kernels.hip; not in the reference; cvo_hip.h, "Saving and restoring maps"): the map's rows
-// on the side that holds them (`at`) and on the other (`to`: where a restore writes), the caller's arrays (`ext`: a snapshot's destination, a
-// restore's source), the table and the call's two figures.  The grid's second dimension.  MapDesc stays as it is.
-struct MapSnapDesc {
-    MapRows at, to, ext;
-    unsigned long long* tkeys; int* trow;   // MapDesc's table: key (all ones = empty) and row
-    int* live;                     // the map's rows with count >= 1
+static_assert(sizeof(ProbeDesc) == 304, "ProbeDesc layout");
+// one map of a snapshot or a restore (cvo_map_snapshot_kernels.hip; not in the reference; cvo_hip.h, "Saving and restoring maps"): the map where
+// it lies, the caller's arrays (`ext`: a snapshot's destination, a restore's source) and the call's two figures.  The grid's second dimension.
+struct MapSnapDesc : MapPlace {
+    MapRows ext;
     int* figures;                  // a restore: [1] the refusal bits
-    int rows;                      // the map's rows as it stands, dead ones included
     int ext_rows;                  // a restore: the rows to put in
-    int slots, pad_;
+    int pad_;
 };
 static_assert(sizeof(MapSnapDesc) == 192, "MapSnapDesc layout");
 // what all views of a call share

@@ -10,7 +10,7 @@
 // groups and members.
 //
 // A point's moved position is x' = (M[r,0]*x + (M[r,1]*y + M[r,2]*z)) + M[r,3] by __fmul_rn / __fadd_rn: no contraction, the same bits wherever it
-// is computed again (insert, gather, and the CENTRAL write of the winner).  Valid: the 8 source floats and the 3 moved ones finite and below
+// is computed again (move_row of cvo_voxel_table.hpp: insert, gather, and the CENTRAL write of the winner).  Valid: the 8 source floats and the 3 moved ones finite and below
 // 2^15, the cell coordinates of the moved position below 2^20.
 //
 // View masks: a cell's mask is the OR of 1 << member number over its members -- cleared with the table, set by insert once per run of lanes
@@ -25,10 +25,6 @@
 
 namespace cvohip {
 namespace {
-// rows 0 .. 2 of the moved position; the features pass through
-__device__ __forceinline__ float move_row(const float* M, int r, float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], x), __fadd_rn(__fmul_rn(M[4 * r + 1], y), __fmul_rn(M[4 * r + 2], z))), M[4 * r + 3]);
-}
 // member point i (i < n): its source floats v, and w = (moved position, features); for_cell: what validity and cell need (point_for_cell)
 template <class Src>
 __device__ __forceinline__ void load_moved(const FuseMemberDesc& M, typename Src::Table T, int which, int i, bool for_cell, float v[8], float w[8]) {

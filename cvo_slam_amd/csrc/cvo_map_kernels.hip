@@ -4,7 +4,9 @@
 //
 // An update's own cells are a fusion's (cvo_fuse_kernels.hip, the passes clear .. gather as they stand, MEAN, every cell kept): they leave, per
 // group, the cells in rank order (row_slot), and per cell its key, member count, member mask and undivided sums.  This file adds what works on
-// the maps.  The map is the grid's second dimension everywhere; a MapDesc (cvo_device.h) says where its rows and its table are.
+// the maps.  The map is the grid's second dimension everywhere; a MapDesc (cvo_device.h) starts with the MapPlace that says where its rows and
+// its table are, and the table's walk, extract's filter, a row's mean and the table's emptying are cvo_voxel_table.hpp's ("a resident map
+// read in place"), shared with the views, the probes and the snapshots.
 //   an update    lookup   a lane per call-cell: its row in the map (cell_row; -1: absent), the block's births, the refusal bits
 //                         (sign -2, "remove what is still there": a cell whose row has none of its members' stamp bits counts as absent
 //                         and is skipped, one with some of them is a refusal)
@@ -16,7 +18,7 @@
 //                sums     a lane per (call-cell, value): the 8 sums added, subtracted or (born) stored: whole cache lines per wave
 //   extract      count, offsets, write: a block's 256 rows are ranked by ballot; the 8 values of a row are written by 8 lanes
 //   compact      mark, offsets, move (to the rows' other side; it also empties the table), rebuild (a lane per surviving row inserts its key)
-//   clear        the table's keys to empty
+//   clear        the table's keys to empty, `live` to 0: of any record that starts with a MapPlace (a refused restore's undo uses it too)
 // Integer atomics only (the key's compare-and-swap, a ballot's count added to `live`, an OR of refusal bits); no float atomics; no lane waits
 // for another.  Row order never depends on arrival: ranks come from block counts and ballots.
 #include <hip/hip_runtime.h>
@@ -27,16 +29,6 @@
 namespace cvohip {
 namespace {
 constexpr unsigned MAP_MAX_COUNT = 16777215u;                         // CVO_MAP_MAX_COUNT
-// the row of `key` in the map, -1: absent.  The table is at most half full, and a slot's key never changes between two rebuilds.
-__device__ __forceinline__ int map_lookup(const MapDesc& M, u64 key) {
-    unsigned s = home_slot(key, (unsigned)M.slots);
-    for (;;) {
-        const u64 k = M.tkeys[s];
-        if (k == key) return M.trow[s];
-        if (k == KEY_EMPTY) return -1;
-        s = s + 1 == (unsigned)M.slots ? 0u : s + 1;
-    }
-}
 // the rank of this lane among the block's lanes with `flag`, all 256 threads take part.  The barrier behind the reads lets a kernel call it again
 // (the waves' counts are one array per block)
 __device__ __forceinline__ int block_rank(bool flag) {
@@ -61,14 +53,10 @@ __device__ __forceinline__ u64 cell_stamps(const MapDesc& M, const FuseGroupDesc
 }
 // what offsets_pass needs of a record
 struct BlockCounts { int* block_heads; int* total; };
-// extract's filter and compact's keep rule on row r
-__device__ __forceinline__ bool row_kept(const MapDesc& M, int r) {
-    const unsigned c = M.at.count[r];
-    return c >= (unsigned)max(1, M.min_points) && __popcll(M.at.mask[r]) >= M.min_views && M.at.last_stamp[r] >= M.min_last_stamp;
-}
+// compact's keep rule on row r
 __device__ __forceinline__ bool row_stays(const MapDesc& M, int r) {
-    if (M.at.count[r] < 1u || M.at.last_stamp[r] < M.min_last_stamp) return false;
-    if (__popcll(M.at.mask[r]) < M.min_views && M.at.born[r] < M.probation_from) return false;
+    if (M.at.count[r] < 1u || M.at.last_stamp[r] < M.filter.min_last_stamp) return false;
+    if (__popcll(M.at.mask[r]) < M.filter.min_views && M.at.born[r] < M.probation_from) return false;
     return !M.drop || M.drop[r] == 0;
 }
 }  // namespace
@@ -164,7 +152,7 @@ __global__ __launch_bounds__(RB) void cvo_map_xcount_kernel(const MapDesc* __res
     const MapDesc& M = maps[blockIdx.y];
     const int r = blockIdx.x * RB + threadIdx.x;
     if ((int)blockIdx.x * RB >= M.rows) return;                       // (uniform over the block)
-    const int k = __syncthreads_count(r < M.rows && row_kept(M, r));
+    const int k = __syncthreads_count(r < M.rows && row_kept(M.at, M.filter, r));
     if (threadIdx.x == 0) M.block_heads[blockIdx.x] = k;
 }
 __global__ __launch_bounds__(RB) void cvo_map_xwrite_kernel(const MapDesc* __restrict__ maps) {
@@ -172,7 +160,7 @@ __global__ __launch_bounds__(RB) void cvo_map_xwrite_kernel(const MapDesc* __res
     const MapDesc& M = maps[blockIdx.y];
     const int first = blockIdx.x * RB, r = first + threadIdx.x;
     if (first >= M.rows) return;                                      // (uniform over the block)
-    const bool kept = r < M.rows && row_kept(M, r);
+    const bool kept = r < M.rows && row_kept(M.at, M.filter, r);
     int o = M.block_heads[blockIdx.x] + block_rank(kept);
     if (!kept || o >= M.cap) o = -1;                                  // rows at or above cap are not written
     out_of[threadIdx.x] = o;
@@ -192,7 +180,7 @@ __global__ __launch_bounds__(RB) void cvo_map_xwrite_kernel(const MapDesc* __res
         const int at = out_of[t];
         if (at < 0) continue;
         const int row = first + t;
-        const float val = (float)((double)M.at.sums[8 * (size_t)row + k] / ((double)M.at.count[row] * 16777216.0));
+        const float val = row_mean(M.at.sums[8 * (size_t)row + k], M.at.count[row]);
         if (k < 3) M.out_xyz[3 * (size_t)at + k] = val; else M.out_feat[5 * (size_t)at + (k - 3)] = val;
     }
 }
@@ -209,7 +197,7 @@ __global__ __launch_bounds__(RB) void cvo_map_move_kernel(const MapDesc* __restr
     __shared__ int out_of[RB];
     const MapDesc& M = maps[blockIdx.y];
     const int first = blockIdx.x * RB, r = first + threadIdx.x;
-    for (long long g = r; g < M.slots; g += (long long)gridDim.x * RB) M.tkeys[g] = KEY_EMPTY;   // (nothing reads the table before rebuild)
+    table_empty(M, r, (int)gridDim.x * RB);                           // (nothing reads the table before rebuild, which sets `live`)
     if (first >= M.rows) return;                                      // (uniform over the block)
     const bool stays = r < M.rows && row_stays(M, r);
     const int rank = block_rank(stays);                               // (every thread of the block: it has a barrier)
@@ -238,11 +226,9 @@ __global__ __launch_bounds__(RB) void cvo_map_rebuild_kernel(const MapDesc* __re
     const unsigned t = table_insert(M.tkeys, (unsigned)M.slots, M.to.keys[r], &fresh);
     M.trow[t] = r;
 }
-__global__ __launch_bounds__(RB) void cvo_map_clear_kernel(const MapDesc* __restrict__ maps) {
-    const MapDesc& M = maps[blockIdx.y];
-    const long long g = (long long)blockIdx.x * RB + threadIdx.x;
-    if (g == 0) *M.live = 0;
-    if (g < M.slots) M.tkeys[g] = KEY_EMPTY;
+// records: MapDescs or MapSnapDescs, `stride` bytes each: the MapPlace a record starts with
+__global__ __launch_bounds__(RB) void cvo_map_clear_kernel(const char* __restrict__ records, size_t stride) {
+    table_empty(*reinterpret_cast<const MapPlace*>(records + blockIdx.y * stride), blockIdx.x * RB + threadIdx.x, gridDim.x * RB);
 }
 
 // maps, groups: the device's copies of the call's tables; n_max: the most call-cells a group can have (its points)
@@ -275,8 +261,9 @@ hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hip
     hipLaunchKernelGGL(cvo_map_rebuild_kernel, grid, dim3(RB), 0, s, maps);
     return hipGetLastError();
 }
-hipError_t launch_map_clear(const MapDesc* maps, int n_maps, int slots, hipStream_t s) {
-    hipLaunchKernelGGL(cvo_map_clear_kernel, dim3((slots + RB - 1) / RB, n_maps), dim3(RB), 0, s, maps);
+// records: the device's copy of a table of records that start with a MapPlace, `stride` bytes each; slots: the tables' size
+hipError_t launch_map_clear(const void* records, size_t stride, int n_maps, int slots, hipStream_t s) {
+    hipLaunchKernelGGL(cvo_map_clear_kernel, dim3((slots + RB - 1) / RB, n_maps), dim3(RB), 0, s, static_cast<const char*>(records), stride);
     return hipGetLastError();
 }
 }  // namespace cvohip

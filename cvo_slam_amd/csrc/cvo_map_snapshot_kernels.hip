@@ -1,16 +1,16 @@
 // cvo_map_snapshot_kernels.hip -- saving and restoring resident maps (NOT in the reference): a map's rows copied out as they stand, and a map
 // made of rows that the caller gives.  The definition is include/cvo_hip.h's "Saving and restoring maps" (tests/map_snapshot_reading.py restates
-// it in numpy); every byte is held to it.  The map is the grid's second dimension everywhere; a MapSnapDesc (cvo_device.h) says where the map's
-// rows, its table and the caller's arrays are.  MapDesc and the kernels of cvo_map_kernels.hip are not touched.
+// it in numpy); every byte is held to it.  The map is the grid's second dimension everywhere; a MapSnapDesc (cvo_device.h) starts with the
+// MapPlace that says where the map's rows and its table are, and adds the caller's arrays.
 //   snapshot   copy     a lane per row: key, count, mask and the two stamps; a row's 64 bytes of sums by 8 lanes.  Rows 0 .. rows - 1, dead ones
 //                       included; nothing behind them
 //   restore    write    the caller's rows are untrusted.  A lane per row reads its fields ONCE, tests them (key, count, stamps), and writes them
 //                       to the side the map is not on; 8 lanes a row do the same with the sums, against the count the block has just read.  The
-//                       refusal bits are OR-ed into the call's figures.  The launch also empties the table and zeroes `live` (what move does)
+//                       refusal bits are OR-ed into the call's figures.  The launch also empties the table and zeroes `live` (table_empty, as move does)
 //              insert   a lane per row inserts the key it reads from the map's OWN copy (a bad key is not inserted): a lane that is not `fresh`
 //                       has met its key's twin -- the duplicate bit.  A ballot's count of the rows with count >= 1 is added to `live`
 //              -- the host waits; on success it flips the side and sets rows; on a refusal, for EVERY listed map: --
-//              empty    the table's keys to empty, `live` to 0
+//              clear    cvo_map_kernels.hip's, over these records: the table's keys to empty, `live` to 0
 //              insert   the same kernel over the rows the map still has on its old side, dead ones included, `live` counted again
 // Integer atomics only (the key's compare-and-swap, a ballot's count added to `live`, an OR of refusal bits); no lane waits for another.
 #include <hip/hip_runtime.h>
@@ -54,8 +54,7 @@ __global__ __launch_bounds__(RB) void cvo_map_restore_write_kernel(const MapSnap
     __shared__ unsigned count_of[RB];
     const MapSnapDesc& M = maps[blockIdx.y];
     const int first = blockIdx.x * RB, r = first + threadIdx.x;
-    for (long long g = r; g < M.slots; g += (long long)gridDim.x * RB) M.tkeys[g] = KEY_EMPTY;   // (nothing reads the table before insert)
-    if (r == 0) *M.live = 0;
+    table_empty(M, r, (int)gridDim.x * RB);                           // (nothing reads the table before insert)
     if (first >= M.ext_rows) return;                                  // (uniform over the block)
     int bad = 0;
     unsigned c = 0u;
@@ -101,13 +100,8 @@ __global__ __launch_bounds__(RB) void cvo_map_restore_insert_kernel(const MapSna
     const int k = __popcll(__ballot(alive));
     if ((threadIdx.x & 63) == 0 && k != 0) atomicAdd(M.live, k);
 }
-__global__ __launch_bounds__(RB) void cvo_map_restore_empty_kernel(const MapSnapDesc* __restrict__ maps) {
-    const MapSnapDesc& M = maps[blockIdx.y];
-    const long long g = (long long)blockIdx.x * RB + threadIdx.x;
-    if (g == 0) *M.live = 0;
-    if (g < M.slots) M.tkeys[g] = KEY_EMPTY;
-}
 
+hipError_t launch_map_clear(const void* records, size_t stride, int n_maps, int slots, hipStream_t s);   // cvo_map_kernels.hip
 // maps: the device's copy of the call's table; rows_max: the most rows among the maps (> 0)
 hipError_t launch_map_snapshot(const MapSnapDesc* maps, int n_maps, int rows_max, hipStream_t s) {
     hipLaunchKernelGGL(cvo_map_snapshot_kernel, dim3((rows_max + RB - 1) / RB, n_maps), dim3(RB), 0, s, maps);
@@ -122,7 +116,8 @@ hipError_t launch_map_restore(const MapSnapDesc* maps, int n_maps, int rows_max,
 }
 // a refused restore: every listed map's table again from the rows it has; rows_max: the most such rows (may be 0), slots: the table's size
 hipError_t launch_map_restore_undo(const MapSnapDesc* maps, int n_maps, int rows_max, int slots, hipStream_t s) {
-    hipLaunchKernelGGL(cvo_map_restore_empty_kernel, dim3((slots + RB - 1) / RB, n_maps), dim3(RB), 0, s, maps);
+    const hipError_t e = launch_map_clear(maps, sizeof(MapSnapDesc), n_maps, slots, s);
+    if (e != hipSuccess) return e;
     if (rows_max > 0) hipLaunchKernelGGL(cvo_map_restore_insert_kernel, dim3((rows_max + RB - 1) / RB, n_maps), dim3(RB), 0, s, maps, 1);
     return hipGetLastError();
 }

@@ -4,9 +4,9 @@
 //
 // All probes of a call go through the same two launches, the PROBE in the grid's second dimension: all lanes of a block belong to one probe,
 // read one pose and one map (uniform loads) and never search for their probe.
-//   probe    a lane per point: move, validity and cell by the fuser's rules (cvo_fuse_kernels.hip's insert, bit for bit); the walk of the map's
-//            table (cvo_map_kernels.hip's map_lookup) for the point's own cell (reach 0) or for the 27 cells around it (reach 1); extract's
-//            filter on the rows found; the squared distance to a kept row's mean position; the least (d2 bits, row) wins.  The lane writes
+//   probe    a lane per point: move, validity and cell by the fuser's rules (move_row, cell_of); the walk of the map's table (map_lookup) for
+//            the point's own cell (reach 0) or for the 27 cells around it (reach 1); extract's filter on the rows found (row_kept); the squared
+//            distance to a kept row's mean position (row_mean); the least (d2 bits, row) wins -- each rule cvo_voxel_table.hpp's.  The lane writes
 //            its point's outputs and a byte of 1 into `hit` at its row; the block stores its four class counts
 //   sum      a block per probe adds the blocks' counts up and stores the probe's four
 // The points come from the kernel's template parameter, as in the reducer: a cvo_device_cloud (CloudSource) or an RGB-D frame read in place
@@ -23,31 +23,11 @@ namespace cvohip {
 namespace {
 constexpr int ROW_ABSENT = -1, ROW_INVALID = -3, ROW_FILTERED = -4;
 constexpr int ROW_NO_POINT = -2;                                      // a lane past the member's points: in no class
-// row r of the moved position: the fuser's move_row, bit for bit
-__device__ __forceinline__ float probe_move_row(const float* M, int r, float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], x), __fadd_rn(__fmul_rn(M[4 * r + 1], y), __fmul_rn(M[4 * r + 2], z))), M[4 * r + 3]);
-}
-// the row of `key` in the probe's map, -1: absent (map_lookup's walk: the table is at most half full, and nothing writes it during the call)
-__device__ __forceinline__ int probe_lookup(const ProbeDesc& P, u64 key) {
-    unsigned s = home_slot(key, (unsigned)P.slots);
-    for (;;) {
-        const u64 k = P.tkeys[s];
-        if (k == key) return P.trow[s];
-        if (k == KEY_EMPTY) return -1;
-        s = s + 1 == (unsigned)P.slots ? 0u : s + 1;
-    }
-}
-// extract's filter on row r (row_kept of cvo_map_kernels.hip)
-__device__ __forceinline__ bool probe_row_kept(const ProbeDesc& P, int r) {
-    const unsigned c = P.count[r];
-    return c >= (unsigned)max(1, P.min_points) && __popcll(P.mask[r]) >= P.min_views && P.last_stamp[r] >= P.min_last_stamp;
-}
-// the squared distance of the moved position w to the mean position of kept row r (count >= 1): extract's expression, then every product and
-// sum rounded
-__device__ __forceinline__ float probe_dist2(const ProbeDesc& P, int r, const float w[3]) {
-    const long long* q = P.sums + 8 * (size_t)r;
-    const double den = (double)P.count[r] * 16777216.0;
-    const float dx = __fsub_rn(w[0], (float)((double)q[0] / den)), dy = __fsub_rn(w[1], (float)((double)q[1] / den)), dz = __fsub_rn(w[2], (float)((double)q[2] / den));
+// the squared distance of the moved position w to the mean position of kept row r (count >= 1): every product and sum rounded
+__device__ __forceinline__ float probe_dist2(const MapRows& R, int r, const float w[3]) {
+    const long long* q = R.sums + 8 * (size_t)r;
+    const unsigned c = R.count[r];
+    const float dx = __fsub_rn(w[0], row_mean(q[0], c)), dy = __fsub_rn(w[1], row_mean(q[1], c)), dz = __fsub_rn(w[2], row_mean(q[2], c));
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 }  // namespace
@@ -56,6 +36,7 @@ template <class Src>
 __global__ __launch_bounds__(RB) void cvo_probe_kernel(const ProbeDesc* __restrict__ probes, typename Src::Table T, float voxel) {
     __shared__ int wave_class[RB / 64][4];
     const ProbeDesc& P = probes[blockIdx.y];
+    const MapRows& R = P.map.at;
     const int i = blockIdx.x * RB + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if ((int)blockIdx.x * RB >= P.n) return;                          // (uniform over the block; past that every lane stays for the ballots)
     int row = ROW_NO_POINT;
@@ -65,17 +46,17 @@ __global__ __launch_bounds__(RB) void cvo_probe_kernel(const ProbeDesc* __restri
         u64 key;
         point_for_cell<Src>(P, T, blockIdx.y, i, v);
 #pragma unroll
-        for (int r = 0; r < 3; ++r) w[r] = probe_move_row(P.pose, r, v[0], v[1], v[2]);
+        for (int r = 0; r < 3; ++r) w[r] = move_row(P.pose, r, v[0], v[1], v[2]);
 #pragma unroll
         for (int k = 3; k < 8; ++k) w[k] = v[k];
         const bool src_ok = fabsf(v[0]) < 32768.f && fabsf(v[1]) < 32768.f && fabsf(v[2]) < 32768.f;   // (the features are w's)
         if (!cell_of(w, voxel, c, &key) || !src_ok) {
             row = ROW_INVALID;
         } else if (P.reach == 0) {
-            const int r = probe_lookup(P, key);
+            const int r = map_lookup(P.map, key);
             if (r < 0) row = ROW_ABSENT;
-            else if (!probe_row_kept(P, r)) row = ROW_FILTERED;
-            else { row = r; d2 = probe_dist2(P, r, w); }
+            else if (!row_kept(R, P.filter, r)) row = ROW_FILTERED;
+            else { row = r; d2 = probe_dist2(R, r, w); }
         } else {
             const int cx = (int)c[0], cy = (int)c[1], cz = (int)c[2];
             u64 best = KEY_EMPTY;                                     // the least (d2 bits << 32) | row: d2 >= 0, so the bits order as the floats do
@@ -84,11 +65,11 @@ __global__ __launch_bounds__(RB) void cvo_probe_kernel(const ProbeDesc* __restri
                 const int nx = cx + j / 9 - 1, ny = cy + (j / 3) % 3 - 1, nz = cz + j % 3 - 1;
                 if (abs(nx) >= 1048576 || abs(ny) >= 1048576 || abs(nz) >= 1048576) continue;   // in no map: its key is never formed
                 const u64 k = ((u64)(unsigned)(nx + 1048576) << 42) | ((u64)(unsigned)(ny + 1048576) << 21) | (u64)(unsigned)(nz + 1048576);
-                const int r = probe_lookup(P, k);
+                const int r = map_lookup(P.map, k);
                 if (r < 0) continue;
                 any = true;
-                if (!probe_row_kept(P, r)) continue;
-                const u64 cand = ((u64)__float_as_uint(probe_dist2(P, r, w)) << 32) | (u64)(unsigned)r;
+                if (!row_kept(R, P.filter, r)) continue;
+                const u64 cand = ((u64)__float_as_uint(probe_dist2(R, r, w)) << 32) | (u64)(unsigned)r;
                 if (cand < best) best = cand;
             }
             if (best != KEY_EMPTY) { row = (int)(unsigned)(best & 0xFFFFFFFFull); d2 = __uint_as_float((unsigned)(best >> 32)); }
@@ -96,9 +77,9 @@ __global__ __launch_bounds__(RB) void cvo_probe_kernel(const ProbeDesc* __restri
         }
         if (P.out_row) P.out_row[i] = row;
         if (P.out_dist2) P.out_dist2[i] = d2;                         // (0x7F800000 where row < 0)
-        if (P.out_count) P.out_count[i] = row >= 0 ? (int)P.count[row] : 0;
-        if (P.out_views) P.out_views[i] = row >= 0 ? __popcll(P.mask[row]) : 0;
-        if (P.out_last_stamp) P.out_last_stamp[i] = row >= 0 ? P.last_stamp[row] : 0;
+        if (P.out_count) P.out_count[i] = row >= 0 ? (int)R.count[row] : 0;
+        if (P.out_views) P.out_views[i] = row >= 0 ? __popcll(R.mask[row]) : 0;
+        if (P.out_last_stamp) P.out_last_stamp[i] = row >= 0 ? R.last_stamp[row] : 0;
         if (P.out_hit && row >= 0) P.out_hit[row] = 1;                // (row < rows: the table's own; every writer stores the same byte)
     }
     // the block's four counts: found, absent, filtered, invalid

@@ -18,8 +18,8 @@
 //   images   a lane per z-cell: depth and index (only when a view asked for one of them)
 // The points come from the passes' template parameter, as in the reducer: a cvo_device_cloud (ViewCloudSource: "Viewing clouds"), or the rows
 // of a resident map where they lie (ViewMapSource: "Viewing maps"; a MapViewSrc per view behind the ViewDesc records).  A map's row is a
-// point when its filter keeps it (code -4 otherwise: never divided, projected or counted); its floats are extract's expression on the row's
-// sums and count, its index the row number.  project, count and write read points and are instantiated per source; clear, offsets, relation
+// point when its filter keeps it (row_kept; code -4 otherwise: never divided, projected or counted); its floats are extract's expression on the
+// row's sums and count (row_mean), its index the row number; the rules are cvo_voxel_table.hpp's, as the move is (move_row).  project, count and write read points and are instantiated per source; clear, offsets, relation
 // and images read the z-buffer, the codes and the counts alone and are shared.  A lane takes a row: the visible rows, whose 64 bytes of sums
 // are read whole, are a small share of a map, and project and count read a row's 24 bytes of position sums.
 // z' is never stored: count and write compute it again by the same __fmul_rn / __fadd_rn sequence (move_z), as the fuser recomputes moved
@@ -36,10 +36,6 @@
 namespace cvohip {
 namespace {
 constexpr int CODE_OUTSIDE = -2, CODE_INVALID = -3, CODE_FILTERED = -4;
-// row r of the moved position: the fuser's move_row, bit for bit
-__device__ __forceinline__ float view_move_row(const float* M, int r, float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], x), __fadd_rn(__fmul_rn(M[4 * r + 1], y), __fmul_rn(M[4 * r + 2], z))), M[4 * r + 3]);
-}
 // ---- Where a view's points come from: `which` is the view's place in the call (its ViewDesc and, for a map, its MapViewSrc).
 struct ViewCloudSource {                                              // a cvo_device_cloud: the arrays are the record's own, no table
     struct Table {};
@@ -54,30 +50,29 @@ struct ViewCloudSource {                                              // a cvo_d
     }
     static __device__ __forceinline__ void carve(Table, int, int, bool) {}
 };
-// A resident map's rows read in place: row i is a point when the view's filter keeps it (extract's rule, so count >= 1), and then its floats are
-// extract's expression.  bounded_features: the feature means are means of floats below 2^15 in every supported map state (cvo_hip.h, "Viewing
+// A resident map's rows read in place: row i is a point when the view's filter keeps it (row_kept, so count >= 1), and then its floats are
+// row_mean's.  bounded_features: the feature means are means of floats below 2^15 in every supported map state (cvo_hip.h, "Viewing
 // maps"), so validity needs the position alone: 24 of a row's 64 bytes of sums.
 struct ViewMapSource {
     struct Table { const MapViewSrc* maps; };
     static constexpr bool bounded_features = true;
-    static __device__ __forceinline__ float mean(long long sum, unsigned count) { return (float)((double)sum / ((double)count * 16777216.0)); }
     static __device__ __forceinline__ bool takes_part(const ViewDesc&, Table T, int which, int i) {
         const MapViewSrc& S = T.maps[which];
-        return S.count[i] >= (unsigned)max(1, S.min_points) && __popcll(S.mask[i]) >= S.min_views && S.last_stamp[i] >= S.min_last_stamp;
+        return row_kept(S.map.at, S.filter, i);
     }
     static __device__ __forceinline__ void position(const ViewDesc&, Table T, int which, int i, float p[3]) {
         const MapViewSrc& S = T.maps[which];
-        const long long* q = S.sums + 8 * (size_t)i;
-        const unsigned c = S.count[i];
+        const long long* q = S.map.at.sums + 8 * (size_t)i;
+        const unsigned c = S.map.at.count[i];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = mean(q[k], c);
+        for (int k = 0; k < 3; ++k) p[k] = row_mean(q[k], c);
     }
     static __device__ __forceinline__ void point(const ViewDesc&, Table T, int which, int i, float v[8]) {
         const MapViewSrc& S = T.maps[which];
-        const long long* q = S.sums + 8 * (size_t)i;
-        const unsigned c = S.count[i];
+        const long long* q = S.map.at.sums + 8 * (size_t)i;
+        const unsigned c = S.map.at.count[i];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = mean(q[k], c);
+        for (int k = 0; k < 8; ++k) v[k] = row_mean(q[k], c);
     }
     static __device__ __forceinline__ void carve(Table T, int which, int i, bool seen_through) {
         uint8_t* out = T.maps[which].carve;
@@ -89,7 +84,7 @@ template <class Src>
 __device__ __forceinline__ float move_z(const ViewDesc& V, typename Src::Table T, int which, int i) {
     float p[3];
     Src::position(V, T, which, i, p);
-    return view_move_row(V.pose, 2, p[0], p[1], p[2]);
+    return move_row(V.pose, 2, p[0], p[1], p[2]);
 }
 // the pixel of a moved position w, if it is in view
 __device__ __forceinline__ bool project(const ViewDesc& V, const ViewParams& P, const float w[3], int* px, int* py) {
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(RB) void cvo_view_project_kernel(const ViewDesc* __
 #pragma unroll
         for (int k = 0; k < 8; ++k) ok &= fabsf(v[k]) < 32768.f;
 #pragma unroll
-        for (int r = 0; r < 3; ++r) { w[r] = view_move_row(V.pose, r, v[0], v[1], v[2]); ok &= fabsf(w[r]) < 32768.f; }
+        for (int r = 0; r < 3; ++r) { w[r] = move_row(V.pose, r, v[0], v[1], v[2]); ok &= fabsf(w[r]) < 32768.f; }
         c = CODE_INVALID;
         if (ok) {
             c = CODE_OUTSIDE;
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(RB) void cvo_view_write_kernel(const ViewDesc* __re
         float v[8], w[3];
         Src::point(V, T, blockIdx.y, i, v);
 #pragma unroll
-        for (int r = 0; r < 3; ++r) w[r] = view_move_row(V.pose, r, v[0], v[1], v[2]);
+        for (int r = 0; r < 3; ++r) w[r] = move_row(V.pose, r, v[0], v[1], v[2]);
         int px = 0, py = 0;
         project(V, P, w, &px, &py);                                   // (in view: project said so for these bits)
         if (V.observed) {

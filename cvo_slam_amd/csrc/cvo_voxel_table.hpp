@@ -1,7 +1,7 @@
 // cvo_voxel_table.hpp -- the device helpers the voxel-grid kernels share (cvo_reduce_kernels.hip, cvo_fuse_kernels.hip): reading a point of a
 // cvo_device_cloud or of a frame read in place (the two point sources), its validity and cell key, the open-addressing table's insert, the
-// runs of lanes with one cell, and -- each written once, over the record type -- the seven passes of a reduction and of a fusion.  Every one is
-// inlined into its kernel; nothing here has a symbol.
+// runs of lanes with one cell, -- each written once, over the record type -- the seven passes of a reduction and of a fusion, and the rules of
+// a resident map read in place (the map, view, probe and snapshot kernels).  Every one is inlined into its kernel; nothing here has a symbol.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -144,6 +144,9 @@ __device__ __forceinline__ void lane_runs(Id id, int lane, int* start, bool* tai
     *start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
     *tail = lane == 63 || ((heads >> (lane + 1)) & 1ull) != 0ull;
 }
+// the mean of `count` >= 1 values from the sum of their llrint(v * 2^24): a double product, a double division, one conversion to float -- MEAN's
+// write, extract's expression, and what a view and a probe of a map read of a row
+__device__ __forceinline__ float row_mean(long long sum, unsigned count) { return (float)((double)sum / ((double)count * 16777216.0)); }
 
 // ---- The passes of a reduction (cvo_reduce_kernels.hip: a record per cloud) and of a fusion (cvo_fuse_kernels.hip: a record per group of posed
 // members), each written once over the record type Rec -- ReduceDesc or FuseGroupDesc, which name their table, rows and outputs alike.  A kernel
@@ -158,7 +161,7 @@ __device__ __forceinline__ void lane_runs(Id id, int lane, int* start, bool* tai
 //            the row into its slot (-1 for the lowest member of a dropped cell), and the slot into row_slot[row] for rows below rows_cap
 //   gather   a lane per point again: map[g] = its cell's row; for rows below rows_cap, MEAN adds q = llrint((double)v * 2^24) of its 8 values
 //            into the row's 64-bit sums (|v| < 2^15 and n < 2^20: below 2^59), CENTRAL does a 64-bit atomicMin of (d2 bits << 32) | g
-//   write    a lane per (row, value): MEAN (float)((double)sum / ((double)count * 16777216.0)), CENTRAL the value of the winning member
+//   write    a lane per (row, value): MEAN row_mean of the row's sum and count, CENTRAL the value of the winning member
 // Every value that reaches an output is independent of the order in which points arrive: integer atomicAdd / atomicMin / compare-and-swap of a
 // key only, no float atomics, and the place of a cell in the table never shows.
 // Runs: neighbouring points of a dense cloud mostly share a cell, so in insert and gather a run of consecutive lanes of a wave with one cell acts
@@ -295,7 +298,7 @@ __device__ __forceinline__ void write_pass(const Rec& D, int g, int mode, Winner
     unsigned src; float val;
     if (mode == 0) {
         src = D.lowest[s];
-        val = (float)((double)D.sums[g] / ((double)cnt * 16777216.0));
+        val = row_mean(D.sums[g], cnt);
     } else {
         src = (unsigned)(D.best[r] & 0xFFFFFFFFull);
         val = winner(src, k);
@@ -306,6 +309,35 @@ __device__ __forceinline__ void write_pass(const Rec& D, int g, int mode, Winner
         if (D.out_source) D.out_source[r] = (int)src;
         row_too(r, s);
     }
+}
+
+// ---- A resident map read in place (cvo_map_kernels.hip, cvo_view_kernels.hip, cvo_probe_kernels.hip, cvo_map_snapshot_kernels.hip): the rules
+// that every kernel over a MapPlace (cvo_device.h) follows bit for bit, each written here once (a row's mean is row_mean, above).
+// row r of a moved position: x' = (M[r,0]*x + (M[r,1]*y + M[r,2]*z)) + M[r,3], every product and sum rounded (the fuser's move; the features
+// pass through)
+__device__ __forceinline__ float move_row(const float* M, int r, float x, float y, float z) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(M[4 * r], x), __fadd_rn(__fmul_rn(M[4 * r + 1], y), __fmul_rn(M[4 * r + 2], z))), M[4 * r + 3]);
+}
+// the row of `key` in the map, -1: absent.  The table is at most half full, and a slot's key never changes between two rebuilds.
+__device__ __forceinline__ int map_lookup(const MapPlace& P, u64 key) {
+    unsigned s = home_slot(key, (unsigned)P.slots);
+    for (;;) {
+        const u64 k = P.tkeys[s];
+        if (k == key) return P.trow[s];
+        if (k == KEY_EMPTY) return -1;
+        s = s + 1 == (unsigned)P.slots ? 0u : s + 1;
+    }
+}
+// extract's filter on row r of R: a kept row has count >= 1
+__device__ __forceinline__ bool row_kept(const MapRows& R, const MapRowFilter& F, int r) {
+    const unsigned c = R.count[r];
+    return c >= (unsigned)max(1, F.min_points) && __popcll(R.mask[r]) >= F.min_views && R.last_stamp[r] >= F.min_last_stamp;
+}
+// the table's keys to empty and `live` to 0, lane g of a grid of `lanes` lanes over the map (slots, and a grid sized for them or for the rows, are
+// below 2^22)
+__device__ __forceinline__ void table_empty(const MapPlace& P, int g, int lanes) {
+    if (g == 0) *P.live = 0;
+    for (; g < P.slots; g += lanes) P.tkeys[g] = KEY_EMPTY;
 }
 }  // namespace
 }  // namespace cvohip
