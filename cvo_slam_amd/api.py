@@ -151,6 +151,10 @@ class MapSnapshot(C.Structure):          # cvo_map_snapshot: one map's rows as s
                 ("born", C.c_void_p), ("rows", C.c_int), ("pad_", C.c_int)]
 
 
+class MapMerge(C.Structure):             # cvo_map_merge: one source map added into one destination map; all_rows: every row, else those `filter` keeps
+    _fields_ = [("dst_map", C.c_int), ("src_map", C.c_int), ("all_rows", C.c_int), ("pad_", C.c_int), ("filter", MapFilter)]
+
+
 class LcScores(C.Structure):
     _fields_ = [("inn_prior", InnP), ("inn_lc_prior", InnP), ("inn_pre", InnP), ("inn_post", InnP), ("inn_fixed_pcd", InnP),
                 ("inn_moving_pcd", InnP), ("post_hessian", C.c_double * 36), ("inliers_svd", C.c_int), ("inliers_pnpransac", C.c_int),
@@ -244,6 +248,7 @@ ABI_SYMBOLS = [
     "cvo_check_maps_compact", "cvo_maps_compact", "cvo_check_maps_view", "cvo_maps_view",
     "cvo_check_maps_probe_clouds", "cvo_maps_probe_clouds", "cvo_check_maps_probe_frames", "cvo_maps_probe_frames",
     "cvo_check_maps_snapshot", "cvo_maps_snapshot", "cvo_check_maps_restore", "cvo_maps_restore",
+    "cvo_check_maps_merge", "cvo_maps_merge",
     "cvo_selftest_voxel_slots",
 ]
 MAX_HYPOTHESES = 64                      # CVO_MAX_HYPOTHESES
@@ -267,6 +272,7 @@ PROBE_WANT = ("dist2", "count", "views", "last_stamp")      # what a probe retur
 PROBE_ABSENT, PROBE_INVALID, PROBE_FILTERED = -1, -3, -4     # a probed point's row when it has none
 SNAPSHOT_FIELDS = (("keys", 8, "iu", ()), ("sums", 8, "i", (8,)), ("count", 4, "iu", ()), ("view_mask", 8, "iu", ()), ("last_stamp", 4, "i", ()),
                    ("born", 4, "i", ()))    # a snapshot's arrays: name, item bytes, integer kinds that carry it, a row's shape
+MAP_MERGE_MAX_LEVEL = 4                  # CVO_MAP_MERGE_MAX_LEVEL: a merge's destination voxel is the source's times 2^0 .. 2^4
 RESTORE_BAD_KEY, RESTORE_BAD_COUNT, RESTORE_BAD_STAMP, RESTORE_BAD_SUM, RESTORE_DUPLICATE = 1, 2, 4, 8, 16   # a refused restore's bits
 
 _lib = None
@@ -519,6 +525,8 @@ def load_library():
     L.cvo_maps_snapshot.argtypes = [vp, C.c_int, ip, msp, ip, vp]
     L.cvo_check_maps_restore.argtypes = [vp, C.c_int, ip, msp, C.c_float]
     L.cvo_maps_restore.argtypes = [vp, C.c_int, ip, msp, C.c_float, vp]
+    L.cvo_check_maps_merge.argtypes = [vp, C.c_int, C.POINTER(MapMerge), vp, C.c_int]
+    L.cvo_maps_merge.argtypes = [vp, C.c_int, C.POINTER(MapMerge), vp, C.c_int, vp]
     _lib = L
     return L
 
@@ -1907,6 +1915,66 @@ class CvoMaps:
         new = CvoMaps(self.reducer, self.max_maps, int(max_rows), self.voxel)
         try:
             new.restore(None, self.snapshot(None))
+        except Exception:
+            new.close()
+            raise
+        return new
+
+    # -- merging (cvo_hip.h, "Merging maps")
+    def _merge_records(self, dst_maps, src, src_maps, level, all_rows, min_points, min_views, min_last_stamp):
+        """what a merge refuses before it touches the library, and the MapMerge array: this object is the destination"""
+        if not isinstance(src, CvoMaps):
+            raise ValueError("src: a CvoMaps expected")
+        if int(level) != level or not 0 <= int(level) <= MAP_MERGE_MAX_LEVEL:
+            raise ValueError(f"level {level!r}: an integer in 0 .. {MAP_MERGE_MAX_LEVEL} expected")
+        ds = self._maps(dst_maps)                                      # (each destination at most once)
+        ss = [src_maps] if isinstance(src_maps, (int, np.integer)) else list(range(src.max_maps)) if src_maps is None else list(src_maps)
+        if len(ss) != len(ds):
+            raise ValueError(f"{len(ds)} destination maps but {len(ss)} source maps")
+        if any(int(k) != k for k in ss):
+            raise ValueError("src_maps: integers expected")
+        ss = [int(k) for k in ss]                                      # (a source may stand in several merges)
+        bad = [k for k in ss if not 0 <= k < src.max_maps]
+        if bad:
+            raise ValueError(f"source map {bad[0]}: 0 .. {src.max_maps - 1} expected")
+        if src is self:
+            both = [k for k in ss if k in set(ds.tolist())]
+            if both:
+                raise ValueError(f"map {both[0]} is both a source and a destination of the call")
+        n = len(ds)
+        flt = self._filters(ds, min_points, min_views, min_last_stamp, ())
+        every = [all_rows] * n if isinstance(all_rows, (bool, int, np.integer)) else list(all_rows)
+        if len(every) != n:
+            raise ValueError("all_rows: one value or one per merge expected")
+        return (MapMerge * n)(*[MapMerge(int(d), s, 1 if a else 0, 0, f) for d, s, a, f in zip(ds, ss, every, flt)]), n
+
+    def check_merge(self, dst_maps, src, src_maps, level=0, all_rows=True, min_points=1, min_views=0, min_last_stamp=0):
+        """cvo_check_maps_merge: the validation of `merge` alone, nothing is launched"""
+        recs, n = self._merge_records(dst_maps, src, src_maps, level, all_rows, min_points, min_views, min_last_stamp)
+        _check(self.L.cvo_check_maps_merge(self.h, n, recs, src.h, int(level)))
+
+    def merge(self, dst_maps, src, src_maps, level=0, all_rows=True, min_points=1, min_views=0, min_last_stamp=0, stream=None):
+        """cvo_maps_merge: the kept rows of map src_maps[k] of `src` (a CvoMaps on this device; it may be this object) are added into this
+        object's map dst_maps[k], each into the cell that its own cell shifts to at this object's voxel, which must be ldexp(src.voxel,
+        level) bit for bit (level 0: the same voxel, a union).  all_rows (one value or one per merge): every row, dead ones included -- then
+        the result is, in every field but born, the map the source's own history would have built at this voxel; otherwise the rows that
+        extract's filter (min_points, min_views, min_last_stamp: one value or one per merge) keeps.  A destination stands at most once, a
+        source may stand in several merges.  Raises CvoError, with every map unchanged, when a destination would outgrow max_rows or a cell's
+        count 16777215, or when a source has more rows than this object's reducer's max_points.  Runs on this object's reducer's stream;
+        when src is on another reducer, its writes must be done."""
+        recs, n = self._merge_records(dst_maps, src, src_maps, level, all_rows, min_points, min_views, min_last_stamp)
+        _check(self.L.cvo_maps_merge(self.h, n, recs, src.h, int(level), _stream_arg(stream)))
+
+    def coarser(self, level: int, max_rows=None):
+        """A new CvoMaps on the same reducer at ldexp(voxel, level) with every map merged from this one with all rows: the whole map at a
+        voxel 2^level times as large, for an extract under the align kernel's point budget.  max_rows: None for this object's.  This
+        object stays as it is."""
+        if int(level) != level or not 0 <= int(level) <= MAP_MERGE_MAX_LEVEL:
+            raise ValueError(f"level {level!r}: an integer in 0 .. {MAP_MERGE_MAX_LEVEL} expected")
+        from .voxels import coarser_voxel
+        new = CvoMaps(self.reducer, self.max_maps, self.max_rows if max_rows is None else int(max_rows), coarser_voxel(self.voxel, int(level)))
+        try:
+            new.merge(None, self, None, level=int(level))
         except Exception:
             new.close()
             raise

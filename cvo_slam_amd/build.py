@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["cvo_kernels.hip", "cvo_score_kernels.hip", "cvo_support_kernels.hip", "cvo_match_kernels.hip", "cvo_hypothesis_kernels.hip", "cvo_pose_model_kernels.hip", "cvo_pcd_kernels.hip", "cvo_reduce_kernels.hip", "cvo_fuse_kernels.hip", "cvo_view_kernels.hip", "cvo_map_kernels.hip", "cvo_probe_kernels.hip", "cvo_map_snapshot_kernels.hip", "cvo_selftest.hip", "cvo_track_kernels.hip", "cvo_capi.hip", "cvo_hip.hpp", "cvo_eigen337.hpp"]
+SOURCES = ["cvo_kernels.hip", "cvo_score_kernels.hip", "cvo_support_kernels.hip", "cvo_match_kernels.hip", "cvo_hypothesis_kernels.hip", "cvo_pose_model_kernels.hip", "cvo_pcd_kernels.hip", "cvo_reduce_kernels.hip", "cvo_fuse_kernels.hip", "cvo_view_kernels.hip", "cvo_map_kernels.hip", "cvo_probe_kernels.hip", "cvo_map_snapshot_kernels.hip", "cvo_map_merge_kernels.hip", "cvo_selftest.hip", "cvo_track_kernels.hip", "cvo_capi.hip", "cvo_hip.hpp", "cvo_eigen337.hpp"]
 HEADERS = ["cvo_device.h", "cvo_math.hpp", "cvo_sweep.hpp", "cvo_queue_classes.hpp", "cvo_voxel_table.hpp", os.path.join("..", "..", "include", "cvo_hip.h")]
 
 

@@ -111,10 +111,11 @@ hipError_t launch_view_maps(const ViewDesc* views, const MapViewSrc* maps, int n
 hipError_t launch_fuse_cells(const FuseGroupDesc* groups, int n_groups, const FuseMemberDesc* mem, const FrameDesc* frames, int n_members, int n_max, int slots_max,
                              int rows_max, float voxel, hipStream_t s);
 hipError_t launch_map_lookup(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int n_max, hipStream_t s);
-hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, hipStream_t s);
+hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, bool from_map, hipStream_t s);
 hipError_t launch_map_extract(const MapDesc* maps, int n_maps, int rows_max, bool write, hipStream_t s);
 hipError_t launch_map_compact(const MapDesc* maps, int n_maps, int rows_max, hipStream_t s);
 hipError_t launch_map_clear(const void* records, size_t stride, int n_maps, int slots, hipStream_t s);
+hipError_t launch_map_merge_cells(const MapMergeDesc* merges, int n_merges, const FuseGroupDesc* groups, int rows_max, hipStream_t s);
 hipError_t launch_probe_clouds(const ProbeDesc* probes, int n_probes, int n_max, float voxel, hipStream_t s);
 hipError_t launch_probe_frames(const ProbeDesc* probes, const FrameDesc* frames, int n_probes, int n, float voxel, hipStream_t s);
 hipError_t launch_map_snapshot(const MapSnapDesc* maps, int n_maps, int rows_max, hipStream_t s);
@@ -4558,7 +4559,7 @@ int maps_update(cvo_maps m, int groups, const int* maps, const int* group_first,
             return fail(CVO_ERR_INVALID, who + "its " + std::to_string(m->rows[k]) + " rows and the integration's " + std::to_string(fig[1]) + " new cells are above max_rows " + std::to_string(m->max_rows));
         cells_max = std::max(cells_max, fig[0]);
     }
-    const hipError_t e = launch_map_merge(m->d_desc, live, dg, cells_max, r->stream);   // behind it runs every later call on the reducer
+    const hipError_t e = launch_map_merge(m->d_desc, live, dg, cells_max, false, r->stream);   // behind it runs every later call on the reducer
     if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("resident maps kernel launch: ") + hipGetErrorString(e));
     for (int q = 0; q < live; ++q) m->rows[maps[of[q]]] += r->h_total[MAP_FIGURES * q + 1];
     return CVO_OK;
@@ -4933,6 +4934,99 @@ int maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot*
     for (int q = 0; q < count; ++q) { m->rows[maps[q]] = src[q].rows; m->side[maps[q]] ^= 1; }
     return CVO_OK;
 }
+// -- merging maps (cvo_map_merge_kernels.hip; cvo_hip.h, "Merging maps").  An update whose call-cells come from a map's rows: merge q takes region q
+// of the destination's reducer's scratch (map_layout: one row per point of max_points, so a source has at most max_points rows), a FuseGroupDesc
+// and a MapMergeDesc in that reducer's descriptor table, the destination's MapDesc q and its four figures -- and from the lookup on it IS an update.
+static_assert(sizeof(FuseGroupDesc) + sizeof(MapMergeDesc) <= CVO_REDUCE_MAX_VOXELS * sizeof(CountDesc), "a FuseGroupDesc and a MapMergeDesc per merge fit the reducer's descriptor table");
+int maps_check_merge(cvo_maps dst, int count, const cvo_map_merge* merges, cvo_maps src, int level) {
+    if (!dst || !src) return fail(CVO_ERR_INVALID, "null maps object");
+    if (count < 1 || count > dst->max_maps) return fail(CVO_ERR_INVALID, "count " + std::to_string(count) + " is outside 1 .. the destination's max_maps " + std::to_string(dst->max_maps));
+    if (!merges) return fail(CVO_ERR_INVALID, "null argument: merges");
+    if (level < 0 || level > CVO_MAP_MERGE_MAX_LEVEL) return fail(CVO_ERR_INVALID, "level " + std::to_string(level) + " is outside 0 .. " + std::to_string(CVO_MAP_MERGE_MAX_LEVEL));
+    if (dst->r->device != src->r->device)
+        return fail(CVO_ERR_INVALID, "the source's device " + std::to_string(src->r->device) + " is not the destination's device " + std::to_string(dst->r->device));
+    const float want = std::ldexp(src->voxel, level);
+    if (std::memcmp(&want, &dst->voxel, sizeof(float)) != 0)
+        return fail(CVO_ERR_INVALID, "the destination's voxel " + std::to_string(dst->voxel) + " has not the bits of the source's voxel " + std::to_string(src->voxel) + " times 2^" +
+                                     std::to_string(level) + " (" + std::to_string(want) + "): cells nest only at exact powers of two");
+    std::vector<char> is_dst(dst->max_maps, 0);
+    for (int q = 0; q < count; ++q) {
+        const cvo_map_merge& g = merges[q];
+        const std::string who = "merge " + std::to_string(q) + ": ";
+        if (g.dst_map < 0 || g.dst_map >= dst->max_maps) return fail(CVO_ERR_INVALID, who + "dst_map " + std::to_string(g.dst_map) + " is outside 0 .. " + std::to_string(dst->max_maps - 1));
+        if (g.src_map < 0 || g.src_map >= src->max_maps) return fail(CVO_ERR_INVALID, who + "src_map " + std::to_string(g.src_map) + " is outside 0 .. " + std::to_string(src->max_maps - 1));
+        if (is_dst[g.dst_map]) return fail(CVO_ERR_INVALID, who + "destination map " + std::to_string(g.dst_map) + " appears twice in the call");
+        is_dst[g.dst_map] = 1;
+        if (g.all_rows != 0 && g.all_rows != 1) return fail(CVO_ERR_INVALID, who + "all_rows " + std::to_string(g.all_rows) + " is neither 0 nor 1");
+        int rc = maps_check_filter(who, g.filter.min_views); if (rc) return rc;
+        if (src->rows[g.src_map] > dst->r->max_points)
+            return fail(CVO_ERR_INVALID, who + "source map " + std::to_string(g.src_map) + " has " + std::to_string(src->rows[g.src_map]) + " rows, above the " + std::to_string(dst->r->max_points) +
+                                         " (max_points) that a group's region of the destination's reducer forms cells for: compact the source, or create that reducer with a larger max_points");
+    }
+    if (src == dst)
+        for (int q = 0; q < count; ++q)
+            if (is_dst[merges[q].src_map])
+                return fail(CVO_ERR_INVALID, "merge " + std::to_string(q) + ": map " + std::to_string(merges[q].src_map) + " is both a source and a destination of the call");
+    return CVO_OK;
+}
+// Three steps, as an update: the call-cells formed from the sources' rows and looked up in the destinations; the call's one host wait, for the
+// figures; then the launches that write the destinations.  The sources are read in the first step only.  A merge whose source has no rows changes nothing.
+int maps_merge(cvo_maps dst, int count, const cvo_map_merge* merges, cvo_maps src, int level, void* stream) {
+    cvo_reducer r = dst->r;
+    HIP_TRY(hipSetDevice(r->device));
+    const MapLayout L = map_layout(r->max_points);
+    std::vector<int> of; of.reserve(count);
+    for (int q = 0; q < count; ++q) if (src->rows[merges[q].src_map] > 0) of.push_back(q);
+    const int live = (int)of.size();
+    if (live == 0) return CVO_OK;
+    DescTable tab{r};
+    FuseGroupDesc* hg; const FuseGroupDesc* dg; MapMergeDesc* hs; const MapMergeDesc* ds;
+    int rc;
+    if ((rc = tab.take(live, &hg, &dg)) || (rc = tab.take(live, &hs, &ds))) return rc;
+    int rows_max = 0;
+    for (int q = 0; q < live; ++q) {
+        const cvo_map_merge& g = merges[of[q]];
+        FuseGroupDesc& G = hg[q];
+        std::memset(&G, 0, sizeof(G));                                // (no output arrays, no members: the cells stay in the scratch)
+        MapDesc& D = maps_desc(dst, q, g.dst_map);
+        MapMergeDesc& S = hs[q];
+        std::memset(&S, 0, sizeof(S));
+        static_cast<MapPlace&>(S) = map_place(src, g.src_map);
+        S.filter = map_row_filter(g.filter); S.all_rows = g.all_rows; S.level = level; S.group = q; S.figures = D.total;
+        const int n = S.rows;
+        char* base = static_cast<char*>(r->scratch) + (size_t)q * L.bytes;
+        G.keys = reinterpret_cast<unsigned long long*>(base + L.keys); G.masks = reinterpret_cast<unsigned long long*>(base + L.masks);
+        G.lowest = reinterpret_cast<unsigned*>(base + L.lowest); G.members = reinterpret_cast<unsigned*>(base + L.members);
+        G.row = reinterpret_cast<int*>(base + L.row); G.slot_of = reinterpret_cast<int*>(base + L.slot_of);
+        G.block_heads = reinterpret_cast<int*>(base + L.block_heads); G.row_slot = reinterpret_cast<int*>(base + L.row_slot);
+        G.sums = reinterpret_cast<long long*>(base + L.sums); G.best = reinterpret_cast<unsigned long long*>(base + L.best);
+        G.total = D.total;
+        G.n = n; G.slots = 2 * n; G.cap = n; G.rows_cap = n;          // (n <= max_points: checked)
+        G.n_blocks = (n + 255) / 256;
+        D.cell_row = reinterpret_cast<int*>(base + L.cell_row);
+        D.group = q; D.sign = CVO_MAP_INTEGRATE;
+        rows_max = std::max(rows_max, n);
+    }
+    if ((rc = maps_run(dst, live, tab.used, stream, [&] {
+            const hipError_t e = launch_map_merge_cells(ds, live, dg, rows_max, r->stream);
+            return e != hipSuccess ? e : launch_map_lookup(dst->d_desc, live, dg, rows_max, r->stream); })))
+        return rc;
+    int cells_max = 0;
+    for (int q = 0; q < live; ++q) {
+        const int* fig = r->h_total + MAP_FIGURES * q;
+        const int k = merges[of[q]].dst_map;
+        const std::string who = "map " + std::to_string(k) + " (merge " + std::to_string(of[q]) + "): ";
+        if (fig[2] & 1) return fail(CVO_ERR_INVALID, who + "the merge would take a cell's count above " + std::to_string(CVO_MAP_MAX_COUNT) + "; every map is unchanged");
+        if ((long long)dst->rows[k] + fig[1] > dst->max_rows)
+            return fail(CVO_ERR_INVALID, who + "its " + std::to_string(dst->rows[k]) + " rows and the merge's " + std::to_string(fig[1]) + " new cells are above max_rows " +
+                                         std::to_string(dst->max_rows) + "; every map is unchanged");
+        cells_max = std::max(cells_max, fig[0]);
+    }
+    const hipError_t e = launch_map_merge(dst->d_desc, live, dg, cells_max, true, r->stream);   // behind it runs every later call on the reducer
+    if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("resident maps kernel launch: ") + hipGetErrorString(e));
+    for (int q = 0; q < live; ++q) dst->rows[merges[of[q]].dst_map] += r->h_total[MAP_FIGURES * q + 1];
+    return CVO_OK;
+}
 }  // namespace
 }  // extern "C++"
 int cvo_maps_create(cvo_reducer r, int max_maps, int max_rows, float voxel, cvo_maps* out) {
@@ -5070,6 +5164,11 @@ int cvo_check_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map
 int cvo_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel, void* stream) {
     int rc = maps_check_restore(m, count, maps, src, voxel); if (rc) return rc;
     return maps_restore(m, count, maps, src, stream);
+}
+int cvo_check_maps_merge(cvo_maps dst, int count, const cvo_map_merge* merges, cvo_maps src, int level) { return maps_check_merge(dst, count, merges, src, level); }
+int cvo_maps_merge(cvo_maps dst, int count, const cvo_map_merge* merges, cvo_maps src, int level, void* stream) {
+    int rc = maps_check_merge(dst, count, merges, src, level); if (rc) return rc;
+    return maps_merge(dst, count, merges, src, level, stream);
 }
 int cvo_batch_advance_staged(cvo_batch b, int* points_out) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");

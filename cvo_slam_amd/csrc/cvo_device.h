@@ -416,6 +416,17 @@ struct MapSnapDesc : MapPlace {
     int pad_;
 };
 static_assert(sizeof(MapSnapDesc) == 192, "MapSnapDesc layout");
+// one merge of a merging call (cvo_map_merge_kernels.hip; not in the reference; cvo_hip.h, "Merging maps"): the SOURCE map where it lies (it may
+// belong to another cvo_maps object: it is only read), which of its rows are kept and by how many bits their cells are shifted.  The grid's
+// second dimension in the passes that form the merge's call-cells; the destination is the call's MapDesc of the same number, as in an update.
+struct MapMergeDesc : MapPlace {
+    MapRowFilter filter;           // extract's filter (row_kept), unless ...
+    int all_rows;                  // ... every row is kept, dead ones included
+    int level;                     // the destination's voxel is the source's times 2^level: a cell coordinate is shifted right by it
+    int group;                     // the merge's FuseGroupDesc in the launch's table: where its call-cells are formed
+    int* figures;                  // the destination's figures (MapDesc::total): [2] takes the refusal bit of a cell count that wrapped
+};
+static_assert(sizeof(MapMergeDesc) == 160, "MapMergeDesc layout");
 // what all views of a call share
 struct ViewParams {
     int width, height, cell, mode, gw, gh;

@@ -19,6 +19,8 @@
 //   extract      count, offsets, write: a block's 256 rows are ranked by ballot; the 8 values of a row are written by 8 lanes
 //   compact      mark, offsets, move (to the rows' other side; it also empties the table), rebuild (a lane per surviving row inserts its key)
 //   clear        the table's keys to empty, `live` to 0: of any record that starts with a MapPlace (a refused restore's undo uses it too)
+// A merge of maps (cvo_map_merge_kernels.hip) forms its call-cells from a map's rows and then runs lookup .. sums as they stand: what a call-cell
+// brings in stamps and mask bits (cell_stamps) is the one thing that differs by source, a template parameter of the merge kernel.
 // Integer atomics only (the key's compare-and-swap, a ballot's count added to `live`, an OR of refusal bits); no float atomics; no lane waits
 // for another.  Row order never depends on arrival: ranks come from block counts and ballots.
 #include <hip/hip_runtime.h>
@@ -42,8 +44,19 @@ __device__ __forceinline__ int block_rank(bool flag) {
     __syncthreads();
     return r;
 }
-// the stamps of the members that touched the call-cell in slot s of its group: their bits (1 << (stamp & 63)), the least and the largest
-__device__ __forceinline__ u64 cell_stamps(const MapDesc& M, const FuseGroupDesc& G, int s, int* lo, int* hi) {
+// What a call-cell brings besides its key, count and sums -- the bits it sets in view_mask, the least and the largest stamp -- is the one thing
+// that differs by where the call-cells come from.  FromMap == false, points (the fuser's passes): the members that touched the cell in slot s
+// of its group are its member mask's bits; each gives 1 << (stamp & 63), and lo / hi are the least and the largest of their stamps[].
+// FromMap == true, a map's rows (cvo_map_merge_kernels.hip): the slot's mask is the OR of the rows' view_mask as it stands, and the cell of
+// rank r keeps in best[r] the largest last_stamp (low word) and, in the high word, the least of ((count >= 1 ? 0 : 2^31) | born): the least born
+// among the rows with members, or among all when none has any
+template <bool FromMap>
+__device__ __forceinline__ u64 cell_stamps(const MapDesc& M, const FuseGroupDesc& G, int s, int r, int* lo, int* hi) {
+    if (FromMap) {
+        const u64 both = G.best[r];
+        *hi = (int)(unsigned)(both & 0xFFFFFFFFull); *lo = (int)((unsigned)(both >> 32) & 0x7FFFFFFFu);
+        return G.masks[s];
+    }
     u64 bits = 0ull; *lo = 0x7FFFFFFF; *hi = 0;
     for (u64 left = G.masks[s]; left; left &= left - 1ull) {
         const int st = M.stamps[__ffsll((long long)left) - 1];
@@ -74,13 +87,13 @@ __global__ __launch_bounds__(RB) void cvo_map_lookup_kernel(const MapDesc* __res
         int row = map_lookup(M, G.keys[s]);
         int bad = 0;
         if (M.sign > 0) {
-            born = row < 0;
-            if (!born && M.at.count[row] + mem > MAP_MAX_COUNT) bad = 1;   // (both below 2^24: no wrap)
+            born = row < 0;                                           // (a group of points has fewer than 2^24 members; a merge's cell may have more)
+            if (mem > MAP_MAX_COUNT || (!born && M.at.count[row] + mem > MAP_MAX_COUNT)) bad = 1;   // (then both below 2^24: no wrap)
         } else if (M.sign == -1) {
             if (row < 0) bad = 2; else if (mem > M.at.count[row]) bad = 4;
         } else if (row >= 0) {                                        // -2, remove what is still there: by the row's stamp bits
             int lo, hi;
-            const u64 bits = cell_stamps(M, G, s, &lo, &hi), have = M.at.mask[row] & bits;
+            const u64 bits = cell_stamps<false>(M, G, s, r, &lo, &hi), have = M.at.mask[row] & bits;   // (only points are removed)
             if (have == 0ull) row = -1;                               // none of these members is in the row: it was dropped and made again
             else if (have != bits) bad = 8;
             else if (mem > M.at.count[row]) bad = 4;
@@ -97,6 +110,7 @@ __global__ __launch_bounds__(RB) void cvo_map_offsets_kernel(const MapDesc* __re
     const int n = which ? *groups[M.group].total : M.rows;
     offsets_pass(BlockCounts{M.block_heads, M.total + which}, (n + RB - 1) / RB);
 }
+template <bool FromMap>
 __global__ __launch_bounds__(RB) void cvo_map_merge_kernel(const MapDesc* __restrict__ maps, const FuseGroupDesc* __restrict__ groups) {
     const MapDesc& M = maps[blockIdx.y];
     const FuseGroupDesc& G = groups[M.group];
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(RB) void cvo_map_merge_kernel(const MapDesc* __rest
         const int s = G.row_slot[r];
         const unsigned mem = G.members[s];
         int lo, hi;
-        const u64 bits = cell_stamps(M, G, s, &lo, &hi);              // the members that touched the cell
+        const u64 bits = cell_stamps<FromMap>(M, G, s, r, &lo, &hi);  // the members that touched the cell / the rows that went into it
         if (born) {
             row = M.rows + M.block_heads[blockIdx.x] + rank;          // (below max_rows: the host counted the births)
             const u64 key = G.keys[s];
@@ -120,11 +134,11 @@ __global__ __launch_bounds__(RB) void cvo_map_merge_kernel(const MapDesc* __rest
             M.trow[t] = row;
             M.at.keys[row] = key; M.at.count[row] = mem; M.at.mask[row] = bits; M.at.last_stamp[row] = hi; M.at.born[row] = lo;
             M.cell_row[r] = -row - 1;
-            change = 1;
+            change = mem >= 1u;                                       // (a merge's cell of dead rows alone is born dead)
         } else if (M.sign > 0) {
             const unsigned c = M.at.count[row];
             M.at.count[row] = c + mem; M.at.mask[row] |= bits; M.at.last_stamp[row] = max(M.at.last_stamp[row], hi);
-            if (c == 0u) { M.at.born[row] = lo; change = 1; }
+            if (c == 0u && mem >= 1u) { M.at.born[row] = lo; change = 1; }
         } else {
             const unsigned c = M.at.count[row] - mem;
             M.at.count[row] = c; M.at.mask[row] &= ~bits;
@@ -238,10 +252,12 @@ hipError_t launch_map_lookup(const MapDesc* maps, int n_maps, const FuseGroupDes
     hipLaunchKernelGGL(cvo_map_offsets_kernel, dim3(1, n_maps), dim3(RB), 0, s, maps, groups, 1);
     return hipGetLastError();
 }
-// cells_max: the most call-cells of a group, as counted
-hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, hipStream_t s) {
+// cells_max: the most call-cells of a group, as counted; from_map: the call-cells were formed from maps' rows (cell_stamps)
+hipError_t launch_map_merge(const MapDesc* maps, int n_maps, const FuseGroupDesc* groups, int cells_max, bool from_map, hipStream_t s) {
     if (n_maps <= 0 || cells_max <= 0) return hipSuccess;
-    hipLaunchKernelGGL(cvo_map_merge_kernel, dim3((cells_max + RB - 1) / RB, n_maps), dim3(RB), 0, s, maps, groups);
+    const dim3 grid((cells_max + RB - 1) / RB, n_maps);
+    if (from_map) hipLaunchKernelGGL(cvo_map_merge_kernel<true>, grid, dim3(RB), 0, s, maps, groups);
+    else hipLaunchKernelGGL(cvo_map_merge_kernel<false>, grid, dim3(RB), 0, s, maps, groups);
     hipLaunchKernelGGL(cvo_map_sums_kernel, dim3((unsigned)((8ll * cells_max + RB - 1) / RB), n_maps), dim3(RB), 0, s, maps, groups);
     return hipGetLastError();
 }

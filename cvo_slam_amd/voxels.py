@@ -223,3 +223,16 @@ def load_maps(path, device=None):
         for name, dt in SNAPSHOT_ARRAYS:
             sn[name] = torch.from_numpy(sn[name].view(signed.get(np.dtype(dt), dt))).to(dev)
     return snaps, voxel
+
+
+# ---- merging maps (cvo_hip.h, "Merging maps")
+def coarser_voxel(voxel: float, level: int) -> float:
+    """The float32 voxel size 2^level times `voxel` (level 0 .. 4), as a python float with exactly those bits: what a CvoMaps must be created
+    with to take CvoMaps.merge(..., level=level) from an object at `voxel`.  Cells nest only at exact powers of two."""
+    if int(level) != level or not 0 <= int(level) <= 4:
+        raise ValueError(f"level {level!r}: an integer in 0 .. 4 expected")
+    with np.errstate(over="ignore"):
+        out = np.ldexp(np.float32(voxel), int(level))
+    if not np.isfinite(out):
+        raise ValueError(f"voxel {voxel!r} times 2^{level} is not a finite float32")
+    return float(np.float32(out))

@@ -962,6 +962,62 @@ int cvo_check_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_ma
 int cvo_maps_snapshot(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* dst, int* rows_out /* count, host, may be NULL */, void* stream);
 int cvo_check_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src /* count */, float voxel);
 int cvo_maps_restore(cvo_maps m, int count, const int* maps, const cvo_map_snapshot* src, float voxel, void* stream);
+/* ---- Merging maps (not in the reference): the first call that takes a MAP, not points -- the kept rows of a source map are added into a
+ * destination map of the same voxel (level 0: the union of two streams' maps in one world frame, or of a fork and what it took in since) or of
+ * a voxel 2^level times as large (level 1 .. 4: the whole map at a coarser voxel, under extract's 65535 rows and the align kernel's point
+ * budget, without the keyframes it was made of).
+ *
+ * Why it is exact.  Cells nest: a cell coordinate is floorf(x / voxel) with a correctly rounded division; x / (voxel * 2^k) is x / voxel
+ * divided by 2^k exactly (barring underflow), and floor(q / 2^k) == floor(floor(q) / 2^k): the cell of a point at voxel * 2^k is the arithmetic
+ * right shift by k of its cell at voxel.  The sums are 64-bit integers: a coarse cell's sums, count and mask are the integer sum, sum and OR
+ * of its children's.  A coarse map made from a fine map's rows is therefore, in key, sums, count, view_mask and last_stamp, row for row and in
+ * order, dead rows included, the map that the same integrate and remove calls would have built at voxel * 2^k; born cannot be rebuilt from
+ * rows (a coarse cell that never died keeps a stamp that its revived child has lost) and is defined below.
+ *
+ * The statement, per merge { dst_map, src_map, all_rows, filter } of a call with one `level` (tests/map_merge_reading.py restates it on
+ * map_reading.Map; the kernels are held to it byte for byte): the kept rows of src_map are added into dst_map, each into the cell that its
+ * own cell shifts to.
+ *   which source rows are kept: with all_rows = 1 every row, dead rows included; otherwise those that extract's rule keeps under `filter`
+ *     (count >= max(1, min_points), popcount(view_mask) >= min_views, last_stamp >= min_last_stamp): a dead row never passes it.
+ *   where a row goes: its call-cell is its key with each of the three 21-bit cell fields c replaced by ((c - 2^20) >> level) + 2^20, an
+ *     arithmetic shift.
+ *   what a call-cell holds: sums and count, the integer sums over the kept rows it takes in; mask, the OR of their view_mask; hi, the largest
+ *     last_stamp among them; lo, the least born among those with count >= 1, or if there are none the least born among all of them.
+ *   order: call-cells are ordered by their lowest source row number.
+ *   writing into the destination: a call-cell goes in as an integrate's call-cell does.  Absent in dst_map: a row is born behind the map's
+ *     rows, in call-cell order, with the cell's key, sums, count and mask, last_stamp = hi and born = lo.  Present: the sums are added,
+ *     count += count, view_mask |= mask, last_stamp = max(last_stamp, hi), and born = lo when the row was dead and the incoming count is at
+ *     least 1.  The live count counts rows with count >= 1: a row that is born dead (a cell of dead rows alone) does not add to it.
+ *   level 0 needs dst and src to have the same voxel bits; level k needs dst's voxel bits to be ldexpf(src's voxel, k).
+ *   refusals after the count, as an update's: rows above dst's max_rows, or a resulting count above 16777215 (a call-cell's own count
+ *     included: at level 4 a cell may take 4096 rows of 16777215; the sum is watched for the carry out of 32 bits and cannot wrap out of
+ *     sight): CVO_ERR_INVALID naming the first offending merge and its destination map, with EVERY map unchanged.  A merge runs in an update's
+ *     three steps: the call-cells formed from the sources' rows in the reducer's scratch and looked up in the destinations; the call's one
+ *     host wait, for the figures; then the update's own launches that write the destinations, behind which every later call on the reducer
+ *     runs.  The sources are read in the first step only.
+ * dst and src are cvo_maps objects on one device; they may be the same object, and src may be on another reducer, with another max_rows.
+ * A destination map stands at most once in a call; a source map may stand in several merges (one map into two destinations); within one
+ * object a map that is both a source and a destination of the call is refused.  All merges go through the same launches, the merge in the
+ * grid's second dimension.  The source is only read; the destination's table and rows are written by an update's born and update paths.
+ * Integer atomics only (the key's compare-and-swap, the minimum of the lowest row, 32- and 64-bit integer adds, OR, max, min), no float atomics,
+ * no lane waits for another; row order comes from ranks, never from arrival.
+ *
+ * Scratch: merge q forms its cells in region q of the DESTINATION's reducer's scratch, an update's region (about 140 bytes per point of
+ * max_points): a source with more rows than that reducer's max_points is refused with both figures, as the views and probes refuse.
+ * stream: the call runs on dst's reducer's stream under the maps' rule (one event edge in and one out with a stream, everything done on return
+ * with NULL; one host wait, for the figures).  When src is on another reducer, ordering against src's writes is the caller's job: that is
+ * restore's rule for its arrays.
+ * Validation: CVO_ERR_INVALID, launching nothing, the message naming the merge and the field: a null object or argument; count outside 1 ..
+ * dst's max_maps; level outside 0 .. 4; objects on different devices; voxel bits that do not match (both figures); dst_map / src_map outside
+ * their object's maps; a destination listed twice; all_rows not 0 or 1; min_views outside 0 .. 64; a map that is source and destination; a
+ * source with more rows than the destination's reducer's max_points.
+ * Out of scope: merging under a pose (re-binning moved means is not exact); subtracting a merged map again; coarsening inside cvo_maps_view,
+ * the probes or cvo_maps_extract (merge into a coarser object and view, probe or extract that). */
+#define CVO_MAP_MERGE_MAX_LEVEL 4
+typedef struct cvo_map_merge { int dst_map; int src_map; int all_rows; int pad_; cvo_map_filter filter; } cvo_map_merge;   /* 32 bytes */
+/* the validation of cvo_maps_merge alone: launches nothing */
+int cvo_check_maps_merge(cvo_maps dst, int count, const cvo_map_merge* merges /* count */, cvo_maps src, int level);
+int cvo_maps_merge(cvo_maps dst, int count, const cvo_map_merge* merges, cvo_maps src, int level, void* stream);
 /* pair p's cloud in slot CVO_SLOT_FIXED / CVO_SLOT_MOVING, as cvo_get_cloud / cvo_get_selected_points give a handle's
  * (selected pixels: clouds made by cvo_batch_set_pairs_images only, *n = 0 otherwise) */
 int cvo_batch_get_cloud(cvo_batch b, int p, int slot, float* xyz, float* feat, int cap, int* n);
