@@ -1981,105 +1981,50 @@ class CvoMaps:
         return new
 
 
-# ---- per-point support (cvo_hip.h, "per-point support"): the output records of the batch and tracker forms
-_SUPPORT_KEYS = (("sum_moving", "<f4"), ("count_moving", "<i4"), ("sum_fixed", "<f4"), ("count_fixed", "<i4"))
-
-
-def _support_host_records(sizes):
-    """numpy arrays for pairs of (n_moving, n_fixed) points, and the records that point at them"""
-    arrays = [dict(sum_moving=np.zeros(nm, np.float32), count_moving=np.zeros(nm, np.int32),
-                   sum_fixed=np.zeros(nf, np.float32), count_fixed=np.zeros(nf, np.int32)) for nm, nf in sizes]
-    recs = (PointSupportDst * max(1, len(arrays)))()
-    for r, a in zip(recs, arrays):
-        for key, _ in _SUPPORT_KEYS:
-            setattr(r, key, a[key].ctypes.data)
-    return arrays, recs
-
-
-def _support_device_records(out, sizes):
-    """records over caller-owned device arrays: out[k] is a dict with sum_moving / count_moving and / or sum_fixed / count_fixed, each anything
-    with __cuda_array_interface__ (torch ROCm tensors): float32 / int32, one-dimensional, contiguous, one entry per point of its cloud"""
-    if len(out) != len(sizes):
-        raise ValueError("out: one dict per pair")
-    recs = (PointSupportDst * max(1, len(out)))()
-    for r, o, (nm, nf) in zip(recs, out, sizes):
-        if set(o) - {k for k, _ in _SUPPORT_KEYS}:
-            raise ValueError(f"out: unknown keys {sorted(set(o) - {k for k, _ in _SUPPORT_KEYS})}")
-        for key, typestr in _SUPPORT_KEYS:
-            a = o.get(key)
-            if a is None:
-                continue
-            if not hasattr(a, "__cuda_array_interface__"):
-                raise ValueError(f"out[{key}]: device memory wanted, an object with __cuda_array_interface__ (host arrays: out=None)")
-            cai = a.__cuda_array_interface__
-            n = nm if key.endswith("moving") else nf
-            if cai["typestr"] != typestr:
-                raise ValueError(f"out[{key}]: dtype {cai['typestr']}, wanted {typestr}")
-            if tuple(cai["shape"]) != (n,):
-                raise ValueError(f"out[{key}]: shape {tuple(cai['shape'])}, the cloud has {n} points")
-            if cai.get("strides") not in (None, (4,)):
-                raise ValueError(f"out[{key}]: not contiguous")
-            setattr(r, key, int(cai["data"][0]))
-    return recs
-
-
-def _settle_support_writer(out, out_stream):
-    """out_stream None: the arrays are taken as ready to be written.  torch tensors are touched on torch's current stream, so that stream is
-    synchronised first (as _settle_writer does for images that are read)."""
-    if out_stream is not None or "torch" not in sys.modules or not out:
-        return
-    torch = sys.modules["torch"]
-    for a in out[0].values():
-        if isinstance(a, torch.Tensor) and a.is_cuda:
-            torch.cuda.current_stream(a.device).synchronize()
-            return
-
-
-# ---- point matches (cvo_hip.h, "point matches"): the output records of all three forms
+# ---- per-point support and point matches (cvo_hip.h, "per-point support", "point matches"): the output records of all their forms.
+# A kind: its C record, its array keys (name, typestr, width), whether the record carries `fit`.
 _MATCH_FIELDS = (("best", "<i4", 1), ("best_value", "<f4", 1), ("mean", "<f4", 3), ("sum", "<f4", 1), ("count", "<i4", 1))
 _MATCH_KEYS = tuple((f"{name}_{side}", typestr, width) for side in ("moving", "fixed") for name, typestr, width in _MATCH_FIELDS)
+_SUPPORT_KEYS = tuple(k for k in _MATCH_KEYS if k[0].startswith(("sum", "count")))
 _MATCH_FIT_DTYPE = np.dtype([("rows", "<i4"), ("matched", "<i4"), ("sum_w", "<f8"), ("sum_w_res2", "<f8")])     # cvo_match_fit
+_SUPPORT = (PointSupportDst, _SUPPORT_KEYS, False)
+_MATCHES = (PointMatchesDst, _MATCH_KEYS, True)
 
 
-def match_fit_records(raw):
-    """(fit_moving, fit_fixed) as dicts out of the 48 bytes of a point-matches `fit` array (a host copy of the device form's)"""
-    rec = np.frombuffer(np.ascontiguousarray(raw).tobytes(), _MATCH_FIT_DTYPE, count=2)
-    return tuple({k: (int(r[k]) if k in ("rows", "matched") else float(r[k])) for k in _MATCH_FIT_DTYPE.names} for r in rec)
-
-
-def _match_host_records(sizes):
-    """numpy arrays for pairs of (n_moving, n_fixed) points, their fit records, and the C records that point at them"""
-    arrays, fits = [], np.zeros((max(1, len(sizes)), 2), _MATCH_FIT_DTYPE)
-    recs = (PointMatchesDst * max(1, len(sizes)))()
+def _host_records(kind, sizes):
+    """numpy arrays for pairs of (n_moving, n_fixed) points under the kind's keys, their fit records (None where the kind has none), and the C
+    records that point at them"""
+    Dst, keys, with_fit = kind
+    arrays, fits = [], np.zeros((max(1, len(sizes)), 2), _MATCH_FIT_DTYPE) if with_fit else None
+    recs = (Dst * max(1, len(sizes)))()
     for k, (r, (nm, nf)) in enumerate(zip(recs, sizes)):
         a = {}
-        for key, typestr, width in _MATCH_KEYS:
+        for key, typestr, width in keys:
             n = nm if key.endswith("moving") else nf
             a[key] = np.zeros(n if width == 1 else (n, width), np.dtype(typestr))
             setattr(r, key, a[key].ctypes.data)
-        r.fit = fits[k].ctypes.data
+        if with_fit:
+            r.fit = fits[k].ctypes.data
         arrays.append(a)
     return arrays, fits, recs
 
 
-def _match_host_results(arrays, fits):
-    for k, a in enumerate(arrays):
-        a["fit_moving"], a["fit_fixed"] = match_fit_records(fits[k])
-    return arrays
-
-
-def _match_device_records(out, sizes):
-    """records over caller-owned device arrays: out[k] is a dict with a direction's five arrays (best_*, best_value_*, mean_* (n, 3), sum_*, count_*;
-    a direction may be left out) and optionally `fit`, 48 bytes of device memory for the two fit records (six float64 or 48 uint8; read it back
-    with match_fit_records) -- each anything with __cuda_array_interface__ (torch ROCm tensors), contiguous"""
+def _device_records(kind, out, sizes):
+    """records over caller-owned device arrays: out[k] is a dict with a direction's arrays under the kind's keys (support: sum_*, count_*; matches:
+    best_*, best_value_*, mean_* (n, 3), sum_*, count_*; a direction may be left out) and, for matches, optionally `fit`, 48 bytes of device
+    memory for the two fit records (six float64 or 48 uint8; read it back with match_fit_records) -- each anything with
+    __cuda_array_interface__ (torch ROCm tensors), contiguous, one row per point of its cloud"""
+    Dst, keys, with_fit = kind
     if len(out) != len(sizes):
         raise ValueError("out: one dict per pair")
-    recs = (PointMatchesDst * max(1, len(out)))()
-    known = {k for k, _, _ in _MATCH_KEYS} | {"fit"}
+    recs = (Dst * max(1, len(out)))()
+    if with_fit:
+        keys = keys + (("fit", None, 0),)
+    known = {k for k, _, _ in keys}
     for r, o, (nm, nf) in zip(recs, out, sizes):
         if set(o) - known:
             raise ValueError(f"out: unknown keys {sorted(set(o) - known)}")
-        for key, typestr, width in _MATCH_KEYS + (("fit", None, 0),):
+        for key, typestr, width in keys:
             a = o.get(key)
             if a is None:
                 continue
@@ -2102,6 +2047,30 @@ def _match_device_records(out, sizes):
                 raise ValueError(f"out[{key}]: not contiguous")
             setattr(r, key, int(cai["data"][0]))
     return recs
+
+
+def _settle_support_writer(out, out_stream):
+    """out_stream None: the arrays are taken as ready to be written.  torch tensors are touched on torch's current stream, so that stream is
+    synchronised first (as _settle_writer does for images that are read)."""
+    if out_stream is not None or "torch" not in sys.modules or not out:
+        return
+    torch = sys.modules["torch"]
+    for a in out[0].values():
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            torch.cuda.current_stream(a.device).synchronize()
+            return
+
+
+def match_fit_records(raw):
+    """(fit_moving, fit_fixed) as dicts out of the 48 bytes of a point-matches `fit` array (a host copy of the device form's)"""
+    rec = np.frombuffer(np.ascontiguousarray(raw).tobytes(), _MATCH_FIT_DTYPE, count=2)
+    return tuple({k: (int(r[k]) if k in ("rows", "matched") else float(r[k])) for k in _MATCH_FIT_DTYPE.names} for r in rec)
+
+
+def _match_host_results(arrays, fits):
+    for k, a in enumerate(arrays):
+        a["fit_moving"], a["fit_fixed"] = match_fit_records(fits[k])
+    return arrays
 
 
 class Cvo:
@@ -2232,7 +2201,7 @@ class Cvo:
         (cvo_slam_amd.matches: fitness, rmse, mutual, residuals)."""
         na, nb = C.c_int(0), C.c_int(0)
         _check(self.L.cvo_get_cloud(self.h, slot_a, None, None, 0, C.byref(na))); _check(self.L.cvo_get_cloud(self.h, slot_b, None, None, 0, C.byref(nb)))
-        arrays, fits, recs = _match_host_records([(na.value, nb.value)])
+        arrays, fits, recs = _host_records(_MATCHES, [(na.value, nb.value)])
         t, tp = _tran(tran_a)
         _check(self.L.cvo_point_matches(self.h, slot_a, tp, slot_b, recs, na.value, nb.value))
         return _match_host_results(arrays, fits)[0]
@@ -2875,10 +2844,10 @@ class CvoBatch:
         pr, sizes = self._last_pair_sizes(pairs, out)
         ip = C.POINTER(C.c_int)
         if out is None:
-            arrays, recs = _support_host_records(sizes)
+            arrays, _, recs = _host_records(_SUPPORT, sizes)
             _check(self.L.cvo_batch_point_support(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
             return arrays
-        recs = _support_device_records(out, sizes)
+        recs = _device_records(_SUPPORT, out, sizes)
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_batch_point_support_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out
@@ -2891,10 +2860,10 @@ class CvoBatch:
         pr, sizes = self._last_pair_sizes(pairs, out)
         ip = C.POINTER(C.c_int)
         if out is None:
-            arrays, fits, recs = _match_host_records(sizes)
+            arrays, fits, recs = _host_records(_MATCHES, sizes)
             _check(self.L.cvo_batch_point_matches(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs))
             return _match_host_results(arrays, fits)
-        recs = _match_device_records(out, sizes)
+        recs = _device_records(_MATCHES, out, sizes)
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_batch_point_matches_device(self.h, pr.shape[0], pr.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out
@@ -3162,10 +3131,10 @@ class CvoTracks:
         sl, sizes = self._stream_pair_sizes(obj, streams)
         ip = C.POINTER(C.c_int)
         if out is None:
-            arrays, recs = _support_host_records(sizes)
+            arrays, _, recs = _host_records(_SUPPORT, sizes)
             _check(self.L.cvo_tracks_point_support(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs))
             return arrays
-        recs = _support_device_records(out, sizes)
+        recs = _device_records(_SUPPORT, out, sizes)
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_tracks_point_support_device(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out
@@ -3177,10 +3146,10 @@ class CvoTracks:
         sl, sizes = self._stream_pair_sizes(obj, streams)
         ip = C.POINTER(C.c_int)
         if out is None:
-            arrays, fits, recs = _match_host_records(sizes)
+            arrays, fits, recs = _host_records(_MATCHES, sizes)
             _check(self.L.cvo_tracks_point_matches(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs))
             return _match_host_results(arrays, fits)
-        recs = _match_device_records(out, sizes)
+        recs = _device_records(_MATCHES, out, sizes)
         _settle_support_writer(out, out_stream)
         _check(self.L.cvo_tracks_point_matches_device(self.h, int(obj), sl.shape[0], sl.ctypes.data_as(ip), recs, _stream_arg(out_stream)))
         return out

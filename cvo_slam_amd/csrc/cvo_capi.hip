@@ -637,17 +637,7 @@ struct Engine {
         if (last_stream && last_stream != stream) (void)hipStreamSynchronize(last_stream);
         release_slots();
         d_scoredescs.release(); h_scoredescs.release(); h_counts.release();
-        if (ev_support) { (void)hipEventSynchronize(ev_support); (void)hipEventDestroy(ev_support); ev_support = nullptr; }   // (a device-form call may sit on a caller's stream)
-        if (ev_support_in) { (void)hipEventDestroy(ev_support_in); ev_support_in = nullptr; }
-        support_queued = false;
-        d_support_tab.release(); d_support_moved.release(); d_support_out.release(); h_support_tab.release(); h_support_out.release();
-        if (ev_match) { (void)hipEventSynchronize(ev_match); (void)hipEventDestroy(ev_match); ev_match = nullptr; }
-        if (ev_match_in) { (void)hipEventDestroy(ev_match_in); ev_match_in = nullptr; }
-        match_queued = false;
-        d_match_tab.release(); d_match_moved.release(); d_match_out.release(); h_match_tab.release(); h_match_out.release();
-        if (ev_hyp) { (void)hipEventSynchronize(ev_hyp); (void)hipEventDestroy(ev_hyp); ev_hyp = nullptr; }
-        hyp_queued = false;
-        d_hyp_tab.release(); d_hyp_partials.release(); h_hyp_tab.release(); h_hyp_out.release();
+        for (SideCall* c : {&support_call, &match_call, &hyp_call, &pm_call}) c->release();
         for (DevBuf* b : {&d_bgr, &d_depth, &d_I0, &d_I1, &d_I2, &d_dx0, &d_dy0, &d_abs0, &d_abs1, &d_abs2, &d_ths, &d_thsS, &d_map, &d_pattern, &d_counts, &d_tiles}) b->release();
         for (DevBuf* b : {&d_descs, &d_states, &d_ybuf, &d_jT, &d_ent, &d_surv, &d_xch, &d_queue, &d_trace, &d_tracelen, &d_partials, &d_raw, &d_ring, &d_records}) b->release();
         for (PinBuf* b : {&h_descs, &h_states, &h_states_in, &h_stage, &h_partials, &h_tail, &h_packdesc, &h_rawtab}) b->release();
@@ -1355,6 +1345,21 @@ struct Engine {
         }
         return CVO_OK;
     }
+    // A counted sweep launch.  The workgroups of a score, support, match, hypothesis or pose-model sweep are queued work that the helpers of align
+    // launches in flight hold back for (AdoptCounters), and this is the one copy of what the host owes them: `wgs` joins `submitted` before the
+    // launch, leaves it again when the sweep was never handed to the runtime (nothing of it will start), and a launch call that reports an error
+    // after that re-synchronises the counters.  launch(wgs_started, sweep_submitted) -> hipError_t; both null on a device without counters.
+    template <class Launch> hipError_t counted_sweep(unsigned wgs, Launch&& launch) {
+        AdoptCounters* const qc = adopt_counters(device);
+        if (!qc) return launch(static_cast<unsigned*>(nullptr), static_cast<bool*>(nullptr));
+        std::lock_guard<std::mutex> lk(adopt_submit_mutex());
+        *qc->submitted_host += wgs;
+        bool sweep_submitted = false;
+        const hipError_t e = launch(qc->started_dev, &sweep_submitted);
+        if (!sweep_submitted) *qc->submitted_host -= wgs;
+        else if (e != hipSuccess) resync_adopt_counters(qc);
+        return e;
+    }
     // Queue the launch on stream s; the sums land in pinned memory when s has drained (score_collect).
     int score_enqueue(const ScoreReq* rq, int n, hipStream_t s) {
         HIP_TRY(hipSetDevice(device));
@@ -1404,16 +1409,9 @@ struct Engine {
             }
             more = static_cast<const ScoreDesc*>(d_scoredescs.p);
         }
-        hipError_t e;
-        if (AdoptCounters* const qc = adopt_counters(device)) {      // the score workgroups are queued work too: helpers of align launches in flight hold back for them
-            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            const unsigned wgs = (unsigned)row_blocks * (unsigned)chunks * (unsigned)n;
-            *qc->submitted_host += wgs;
-            bool sweep_submitted = false;
-            e = launch_score(B, more, n, row_blocks, chunks, P, static_cast<double*>(d_partials.p), static_cast<double*>(h_partials.p), s, qc->started_dev, &sweep_submitted);
-            if (!sweep_submitted) *qc->submitted_host -= wgs;       // nothing of it will start (the sweep was never handed to the runtime)
-            else if (e != hipSuccess) resync_adopt_counters(qc);
-        } else e = launch_score(B, more, n, row_blocks, chunks, P, static_cast<double*>(d_partials.p), static_cast<double*>(h_partials.p), s, nullptr, nullptr);
+        const hipError_t e = counted_sweep((unsigned)row_blocks * (unsigned)chunks * (unsigned)n, [&](unsigned* wgs_started, bool* sweep_submitted) {
+            return launch_score(B, more, n, row_blocks, chunks, P, static_cast<double*>(d_partials.p), static_cast<double*>(h_partials.p), s, wgs_started, sweep_submitted);
+        });
         if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("score kernel launch: ") + hipGetErrorString(e));
         score_stream = s; score_pending = n;
         return CVO_OK;
@@ -1433,297 +1431,293 @@ struct Engine {
         return score_collect(n, out);
     }
 
-    // Per-point support (cvo_support_kernels.hip; include/cvo_hip.h: cvo_point_support): for every request the rows of a against the columns of b
-    // (sum_a / count_a, a->n entries) and the roles swapped (sum_b / count_b, b->n entries); a direction whose two arrays are null is not computed.
-    // ell and the transform as a ScoreReq names them.  to_host: the arrays are host memory, filled by support_collect; else device memory the
-    // caller owns (checked by the entry point), written by the kernel itself.
-    struct SupportReq {
+    // ---- side calls: per-point support, point matches, pose hypotheses, pose models
+    // What one kind of side call keeps from its enqueue to its collect.  Every kind has a record of its own (support_call, match_call, hyp_call,
+    // pm_call): nothing in it is shared with another kind or with a score block, so a call of one kind may be in flight while another is queued.
+    // One call of a kind at a time: begin() waits for the one before.
+    struct SideCall {
+        struct Copy { void* dst; size_t off, bytes; };
+        const char* none_queued;                   // collect()'s error text when no call is queued
+        hipEvent_t done = nullptr, in = nullptr;   // done: the call has left the device; in: where the caller's out_stream stood when the call was queued
+        bool queued = false; hipStream_t stream = nullptr;
+        DevBuf d_tab; PinBuf h_tab;                // the call's table: filled in h_tab, uploaded to d_tab
+        DevBuf d_work;                             // moved planes and their boxes (support, matches); the sweep's partials (hypotheses, pose models)
+        DevBuf d_out; PinBuf h_out;                // answers: the kernels write h_out themselves (hypotheses, pose models), or d_out, copied to h_out behind
+        size_t out_bytes = 0; std::vector<Copy> copies;   // them (out_bytes > 0) and from there to the caller's host arrays by collect()
+        int (Engine::*before_reuse)();             // non-null: begin() calls it before the last call's answers are given up (hypotheses: hyp_keep)
+        explicit SideCall(const char* none_queued_text, int (Engine::*keep)() = nullptr) : none_queued(none_queued_text), before_reuse(keep) {}
+        int wait() {
+            if (queued) { HIP_TRY(hipEventSynchronize(done)); queued = false; }
+            return CVO_OK;
+        }
+        // the last call's table, work buffer and answers are free; s is ready for the clouds; wait_align: an align launch on a caller's stream packs
+        // clouds and writes states, so s waits for it
+        int begin(Engine& E, hipStream_t s, bool wait_align) {
+            if (!done) HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+            int rc;
+            if ((before_reuse && (rc = (E.*before_reuse)())) || (rc = wait())) return rc;
+            copies.clear(); out_bytes = 0;
+            if ((rc = E.flush_pending(s)) || (rc = E.settle_uploads(s))) return rc;
+            if (wait_align && E.launched && E.last_stream && E.last_stream != s) HIP_TRY(hipStreamWaitEvent(s, E.ev1, 0));
+            return CVO_OK;
+        }
+        // whatever out_stream still does to the caller's device arrays comes before the call on s
+        int order_after(hipStream_t out_stream, hipStream_t s) {
+            if (!out_stream || out_stream == s) return CVO_OK;
+            if (!in) HIP_TRY(hipEventCreateWithFlags(&in, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(in, out_stream));
+            HIP_TRY(hipStreamWaitEvent(s, in, 0));
+            return CVO_OK;
+        }
+        int upload(size_t tab_bytes, hipStream_t s) {
+            HIP_TRY(hipMemcpyAsync(d_tab.p, h_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
+            return CVO_OK;
+        }
+        int finish(hipStream_t s) {
+            if (out_bytes) HIP_TRY(hipMemcpyAsync(h_out.p, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(done, s));
+            queued = true; stream = s;
+            return CVO_OK;
+        }
+        // waits for the call queued last; its host arrays are filled here
+        int collect() {
+            if (!queued) return fail(CVO_ERR_INVALID, none_queued);
+            int rc = wait(); if (rc) return rc;
+            for (const Copy& c : copies) std::memcpy(c.dst, static_cast<const unsigned char*>(h_out.p) + c.off, c.bytes);
+            copies.clear();
+            return CVO_OK;
+        }
+        // the device form's ordering with an out_stream: that stream waits for the call and the host does not (Engine::side_publish)
+        int publish(hipStream_t out_stream) {
+            if (out_stream != stream) HIP_TRY(hipStreamWaitEvent(out_stream, done, 0));
+            return CVO_OK;
+        }
+        void release() {
+            if (done) { (void)hipEventSynchronize(done); (void)hipEventDestroy(done); done = nullptr; }   // (a device-form call may sit on a caller's stream)
+            if (in) { (void)hipEventDestroy(in); in = nullptr; }
+            queued = false;
+            d_tab.release(); d_work.release(); d_out.release(); h_tab.release(); h_out.release();
+        }
+    };
+    SideCall support_call{"no queued point support"}, match_call{"no queued point matches"}, hyp_call{"no queued hypothesis scores", &Engine::hyp_keep}, pm_call{"no queued pose models"};
+    int side_collect(SideCall& C) { HIP_TRY(hipSetDevice(device)); return C.collect(); }
+    // a call's end as its form asks: with an out_stream that stream waits, else the host does
+    int side_publish(SideCall& C, hipStream_t out_stream) { return out_stream ? C.publish(out_stream) : side_collect(C); }
+
+    // Per-point support (cvo_support_kernels.hip; include/cvo_hip.h: cvo_point_support) and point matches (cvo_match_kernels.hip; cvo_point_matches):
+    // for every request the rows of a against the columns of b (dst.*_moving, a->n rows) and the roles swapped (dst.*_fixed, b->n rows); a direction
+    // whose arrays are null is not computed.  ell and the transform as a ScoreReq names them.  to_host: the arrays are host memory, filled by
+    // side_collect; else device memory the caller owns (checked by the entry point), written by the kernels themselves.
+    template <class Dst> struct SideReq {
         const Cloud* a; const float* tran; const Cloud* b; float ell;
         int from; bool tran_from_state;
-        float* sum_a; int* count_a; float* sum_b; int* count_b;
+        Dst dst;
     };
-    struct SupportCopy { void* dst; size_t off, bytes; };
-    // buffers of its own: nothing here is shared with a score block in flight.  One call at a time: the next one waits for ev_support first.
-    DevBuf d_support_tab, d_support_moved, d_support_out; PinBuf h_support_tab, h_support_out;
-    hipEvent_t ev_support = nullptr, ev_support_in = nullptr; bool support_queued = false;
-    std::vector<SupportCopy> support_copies; hipStream_t support_stream = nullptr;
-    int support_enqueue(const SupportReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
-        HIP_TRY(hipSetDevice(device));
-        if (n <= 0) return fail(CVO_ERR_INVALID, "bad support request count");
-        for (int r = 0; r < n; ++r) {
-            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
-            if (!rq[r].sum_a != !rq[r].count_a || !rq[r].sum_b != !rq[r].count_b) return fail(CVO_ERR_INVALID, "point support: a direction needs its sum and its count array");
-            if (!rq[r].sum_a && !rq[r].sum_b) return fail(CVO_ERR_INVALID, "point support: no output array");
-            if (rq[r].tran_from_state && rq[r].from < 0) return fail(CVO_ERR_INVALID, "point support: transform from a state that is not named");
+    using SupportReq = SideReq<cvo_point_support_dst>;
+    using MatchReq = SideReq<cvo_point_matches_dst>;
+    static bool rows_moving(const cvo_point_support_dst& d) { return d.sum_moving != nullptr; }
+    static bool rows_fixed(const cvo_point_support_dst& d) { return d.sum_fixed != nullptr; }
+    static bool rows_moving(const cvo_point_matches_dst& d) { return d.best_moving != nullptr; }
+    static bool rows_fixed(const cvo_point_matches_dst& d) { return d.best_fixed != nullptr; }
+    // where a direction's outputs go: the caller's device memory as it is, or (to_host) a place in the call's d_out with its copy to the caller's array;
+    // per-direction records (the matches' fit records) lie first, so that they stay 8-byte aligned, the row arrays behind them
+    struct SideOut {
+        SideCall& C; bool to_host; size_t head_at, rows_at;
+        template <class T> T* put(T* dst, size_t& at, size_t bytes) {
+            if (!to_host) return dst;
+            C.copies.push_back(SideCall::Copy{dst, at, bytes});
+            T* const p = reinterpret_cast<T*>(static_cast<unsigned char*>(C.d_out.p) + at); at += bytes; return p;
         }
-        if (!ev_support) HIP_TRY(hipEventCreateWithFlags(&ev_support, hipEventDisableTiming));
-        if (support_queued) { HIP_TRY(hipEventSynchronize(ev_support)); support_queued = false; }   // the last call's tables, moved planes and outputs are free
-        support_copies.clear();
-        { int rcs = flush_pending(s); if (rcs) return rcs; }
-        { int rcs = settle_uploads(s); if (rcs) return rcs; }
-        // what the call needs: a moved {x, y, z, f0} plane and its boxes per transformed cloud, the tables, and (to_host) a place per output array
-        int n_moves = 0, n_move_max = 0, n_dirs = 0, row_blocks = 1;
+        template <class T> T* rows(T* dst, size_t bytes) { return put(dst, rows_at, bytes); }
+        template <class T> T* head(T* dst, size_t bytes) { return put(dst, head_at, bytes); }
+    };
+    // what a built call hands its launcher: the three parts of the device table (side calls of two directions) or the table itself (hypotheses, pose models)
+    struct SidePlan {
+        int n_moves = 0, n_move_max = 0, n_dirs = 0, row_blocks = 1; size_t tab_bytes = 0;
+        const SupportMoveDesc* d_mv = nullptr; const BoxDesc* d_bx = nullptr; const void* d_descs = nullptr;
+    };
+    // Everything a support and a matches call have in common between begin() and the launch: what the call needs -- a moved {x, y, z, f0} plane and
+    // its boxes per transformed cloud, the table (moves, boxes, one Desc per computed direction) and, to_host, a place per output (row_bytes a row,
+    // head_bytes a direction) -- then the moves, the boxes and each direction's SweepSide, the roles swapped for the second one.
+    // outputs(D, dst, swapped, rows, out) sets the kind's own output pointers of one direction.
+    template <class Desc, class Dst, class Outputs>
+    int build_sides(SideCall& C, const SideReq<Dst>* rq, int n, hipStream_t s, bool to_host, size_t row_bytes, size_t head_bytes, int (*row_blocks_of)(int),
+                    Outputs&& outputs, SidePlan& pl) {
         size_t moved_bytes = 0, out_bytes = 0;
         for (int r = 0; r < n; ++r) {
-            const bool moved = rq[r].tran || rq[r].tran_from_state;
             const int na = rq[r].a->n, nb = rq[r].b->n;
-            if (moved) { ++n_moves; n_move_max = std::max(n_move_max, na); moved_bytes += sizeof(float) * 4 * (size_t)na + score_box_bytes(na); }
-            if (rq[r].sum_a) { ++n_dirs; out_bytes += 8 * (size_t)na; row_blocks = std::max(row_blocks, support_row_blocks(na)); }
-            if (rq[r].sum_b) { ++n_dirs; out_bytes += 8 * (size_t)nb; row_blocks = std::max(row_blocks, support_row_blocks(nb)); }
+            if (rq[r].tran || rq[r].tran_from_state) { ++pl.n_moves; pl.n_move_max = std::max(pl.n_move_max, na); moved_bytes += sizeof(float) * 4 * (size_t)na + score_box_bytes(na); }
+            if (rows_moving(rq[r].dst)) { ++pl.n_dirs; out_bytes += row_bytes * (size_t)na; pl.row_blocks = std::max(pl.row_blocks, row_blocks_of(na)); }
+            if (rows_fixed(rq[r].dst)) { ++pl.n_dirs; out_bytes += row_bytes * (size_t)nb; pl.row_blocks = std::max(pl.row_blocks, row_blocks_of(nb)); }
         }
-        const size_t off_box = sizeof(SupportMoveDesc) * (size_t)n_moves, off_req = off_box + sizeof(BoxDesc) * (size_t)n_moves;
-        const size_t tab_bytes = off_req + sizeof(SupportDesc) * (size_t)n_dirs;
+        const size_t heads = head_bytes * (size_t)pl.n_dirs;
+        out_bytes += heads;
+        const size_t off_box = sizeof(SupportMoveDesc) * (size_t)pl.n_moves, off_req = off_box + sizeof(BoxDesc) * (size_t)pl.n_moves;
+        pl.tab_bytes = off_req + sizeof(Desc) * (size_t)pl.n_dirs;
         int rc;
-        if ((rc = h_support_tab.ensure(tab_bytes)) || (rc = d_support_tab.ensure(tab_bytes)) || (rc = d_support_moved.ensure(std::max(moved_bytes, (size_t)16)))) return rc;
-        if (to_host && ((rc = d_support_out.ensure(out_bytes)) || (rc = h_support_out.ensure(out_bytes)))) return rc;
-        unsigned char* const tab = static_cast<unsigned char*>(h_support_tab.p);
+        if ((rc = C.h_tab.ensure(pl.tab_bytes)) || (rc = C.d_tab.ensure(pl.tab_bytes)) || (rc = C.d_work.ensure(std::max(moved_bytes, (size_t)16)))) return rc;
+        if (to_host && ((rc = C.d_out.ensure(out_bytes)) || (rc = C.h_out.ensure(out_bytes)))) return rc;
+        if (to_host) C.out_bytes = out_bytes;
+        unsigned char* const tab = static_cast<unsigned char*>(C.h_tab.p);
         SupportMoveDesc* const mv = reinterpret_cast<SupportMoveDesc*>(tab);
         BoxDesc* const bx = reinterpret_cast<BoxDesc*>(tab + off_box);
-        SupportDesc* const sd = reinterpret_cast<SupportDesc*>(tab + off_req);
-        std::memset(tab, 0, tab_bytes);
-        size_t moved_at = 0, out_at = 0; int im = 0, id = 0;
-        auto place = [&](void* host_dst, size_t bytes) -> void* {     // an output array: the caller's device memory, or a place in d_support_out
-            if (!to_host) return host_dst;
-            support_copies.push_back(SupportCopy{host_dst, out_at, bytes});
-            void* p = static_cast<unsigned char*>(d_support_out.p) + out_at; out_at += bytes; return p;
-        };
+        Desc* const sd = reinterpret_cast<Desc*>(tab + off_req);
+        std::memset(tab, 0, pl.tab_bytes);
+        SideOut out{C, to_host, 0, heads};
+        size_t moved_at = 0; int im = 0, id = 0;
+        for (int r = 0; r < n; ++r) {
+            const SideReq<Dst>& q = rq[r]; const Cloud& a = *q.a; const Cloud& b = *q.b;
+            const PairState* from = q.from >= 0 ? static_cast<const PairState*>(d_states.p) + q.from : nullptr;
+            const float* a_lo = a.rec(); const float* a_box = nullptr;
+            if (q.tran || q.tran_from_state) {
+                float* plane = reinterpret_cast<float*>(static_cast<unsigned char*>(C.d_work.p) + moved_at);
+                float* gbox = plane + 4 * (size_t)a.n;
+                moved_at += sizeof(float) * 4 * (size_t)a.n + score_box_bytes(a.n);
+                SupportMoveDesc& M = mv[im]; BoxDesc& B = bx[im]; ++im;
+                M.src = a.rec(); M.dst = plane; M.n = a.n; M.from = q.tran_from_state ? from : nullptr;
+                for (int i = 0; i < 12; ++i) M.tran[i] = q.tran_from_state ? 0.f : q.tran[i];
+                B.rec = plane; B.gbox = gbox; B.self_cache = score_self_cache(gbox, a.n); B.n = a.n; B.ngroups = score_groups(a.n);
+                a_lo = plane; a_box = gbox;
+            } else if (rows_fixed(q.dst)) {
+                if ((rc = ensure_boxes(a, s))) return rc;
+                a_box = static_cast<const float*>(a.boxes.p);
+            }
+            auto side = [&](const float* rows_lo, const Cloud& rows, const float* cols_lo, const Cloud& cols, const float* cols_box, bool swapped) {
+                Desc& D = sd[id++];
+                D.a_lo = rows_lo; D.a_hi = rows.rec() + hi_off(rows.n, 0); D.na = rows.n;
+                D.b_lo = cols_lo; D.b_hi = cols.rec() + hi_off(cols.n, 0); D.nb = cols.n;
+                D.bbox = cols_box; D.nbox = score_groups(cols.n);
+                D.ell = q.ell; D.from = from;
+                outputs(D, q.dst, swapped, (size_t)rows.n, out);
+            };
+            if (rows_moving(q.dst)) {
+                if ((rc = ensure_boxes(b, s))) return rc;
+                side(a_lo, a, b.rec(), b, static_cast<const float*>(b.boxes.p), false);
+            }
+            if (rows_fixed(q.dst)) side(b.rec(), b, a_lo, a, a_box, true);
+        }
+        const unsigned char* const dtab = static_cast<const unsigned char*>(C.d_tab.p);
+        pl.d_mv = reinterpret_cast<const SupportMoveDesc*>(dtab); pl.d_bx = reinterpret_cast<const BoxDesc*>(dtab + off_box); pl.d_descs = dtab + off_req;
+        return CVO_OK;
+    }
+    // One support or matches call from its checks to its end, on stream s (one call of a kind at a time: begin() waits for the one before).  what /
+    // kernel: the kind as the messages name it; kind_check(dst): the kind's own check of a request, made between the clouds' and the transform's;
+    // launch(plan, wgs_started, sweep_submitted): the kind's launcher.  The call ends as its form asks (side_publish): with an out_stream, the
+    // stream the caller's device arrays are used on, that stream waits for it; else the host does, and to_host arrays are filled.
+    template <class Desc, class Dst, class KindCheck, class Outputs, class Launch>
+    int run_sides(SideCall& C, const SideReq<Dst>* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream, const char* what, const char* kernel,
+                  size_t row_bytes, size_t head_bytes, int (*row_blocks_of)(int), KindCheck&& kind_check, Outputs&& outputs, Launch&& launch) {
+        HIP_TRY(hipSetDevice(device));
+        if (n <= 0) return fail(CVO_ERR_INVALID, std::string("bad ") + kernel + " request count");
+        int rc;
+        for (int r = 0; r < n; ++r) {
+            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
+            if ((rc = kind_check(rq[r].dst))) return rc;
+            if (!rows_moving(rq[r].dst) && !rows_fixed(rq[r].dst)) return fail(CVO_ERR_INVALID, std::string(what) + ": no output array");
+            if (rq[r].tran_from_state && rq[r].from < 0) return fail(CVO_ERR_INVALID, std::string(what) + ": transform from a state that is not named");
+        }
+        SidePlan pl;
+        if ((rc = C.begin(*this, s, false)) || (rc = build_sides<Desc>(C, rq, n, s, to_host, row_bytes, head_bytes, row_blocks_of, outputs, pl)) ||
+            (rc = C.order_after(out_stream, s)) || (rc = C.upload(pl.tab_bytes, s))) return rc;
+        const hipError_t e = counted_sweep((unsigned)pl.row_blocks * (unsigned)pl.n_dirs, [&](unsigned* wgs_started, bool* sweep_submitted) { return launch(pl, wgs_started, sweep_submitted); });
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string(kernel) + " kernel launch: " + hipGetErrorString(e));
+        return (rc = C.finish(s)) ? rc : side_publish(C, out_stream);
+    }
+    // support: two arrays a direction, 8 bytes a row
+    int point_sides(const SupportReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
+        return run_sides<SupportDesc>(support_call, rq, n, s, to_host, out_stream, "point support", "support", 8, 0, support_row_blocks,
+            [](const cvo_point_support_dst& d) {
+                return !d.sum_moving != !d.count_moving || !d.sum_fixed != !d.count_fixed ? fail(CVO_ERR_INVALID, "point support: a direction needs its sum and its count array") : CVO_OK;
+            },
+            [](SupportDesc& D, const cvo_point_support_dst& d, bool swapped, size_t rows, SideOut& out) {
+                D.sum = out.rows(swapped ? d.sum_fixed : d.sum_moving, 4 * rows); D.count = out.rows(swapped ? d.count_fixed : d.count_moving, 4 * rows);
+            },
+            [&](const SidePlan& pl, unsigned* wgs_started, bool* sweep_submitted) {
+                return launch_support(pl.d_mv, pl.d_bx, pl.n_moves, pl.n_move_max, static_cast<const SupportDesc*>(pl.d_descs), pl.n_dirs, pl.row_blocks, P, s, wgs_started, sweep_submitted);
+            });
+    }
+    // matches: five arrays a direction, 28 bytes a row, and, where dst.fit is given, a fit record per computed direction (24 bytes)
+    int point_sides(const MatchReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
+        bool with_fit = false;
+        for (int r = 0; r < n; ++r) if (rq[r].dst.fit) with_fit = true;
+        return run_sides<MatchDesc>(match_call, rq, n, s, to_host, out_stream, "point matches", "match", 28, sizeof(MatchFit), match_row_blocks,
+            [](const cvo_point_matches_dst&) { return CVO_OK; },
+            [](MatchDesc& D, const cvo_point_matches_dst& d, bool swapped, size_t rows, SideOut& out) {
+                D.best = out.rows(swapped ? d.best_fixed : d.best_moving, 4 * rows); D.best_value = out.rows(swapped ? d.best_value_fixed : d.best_value_moving, 4 * rows);
+                D.mean = out.rows(swapped ? d.mean_fixed : d.mean_moving, 12 * rows);
+                D.sum = out.rows(swapped ? d.sum_fixed : d.sum_moving, 4 * rows); D.count = out.rows(swapped ? d.count_fixed : d.count_moving, 4 * rows);
+                D.fit = d.fit ? reinterpret_cast<MatchFit*>(out.head(d.fit + (swapped ? 1 : 0), sizeof(MatchFit))) : nullptr;
+            },
+            [&](const SidePlan& pl, unsigned* wgs_started, bool* sweep_submitted) {
+                return launch_match(pl.d_mv, pl.d_bx, pl.n_moves, pl.n_move_max, static_cast<const MatchDesc*>(pl.d_descs), pl.n_dirs, pl.row_blocks, with_fit, P, s, wgs_started, sweep_submitted);
+            });
+    }
+
+    // Pose hypotheses (cvo_hypothesis_kernels.hip; include/cvo_hip.h: cvo_score_hypotheses) and pose models (cvo_pose_model_kernels.hip; cvo_pose_models):
+    // for every request the moving cloud a under each of the k transforms trans[r][0 .. k) against the fixed cloud b at `ell`, all in ONE sweep launch,
+    // and the reduce launch behind it.  What the two have in common between begin() and the launch: the table -- one Desc per pair, then the pairs' k
+    // transforms each, copied from the caller's array before the call returns (trans null: none) -- the sweep's partials (`terms` doubles per pair,
+    // transform and row block), the pinned block the kernels write their answers to, and per pair the clouds and the fixed cloud's boxes.
+    // own(D, rq[r]) sets the kind's own fields.
+    template <class Desc, class Req, class Own>
+    int build_pairs(SideCall& C, const Req* rq, int n, int k, const float* trans, float ell, hipStream_t s, int (*row_blocks_of)(int), size_t terms, size_t answer_bytes,
+                    Own&& own, SidePlan& pl) {
+        for (int r = 0; r < n; ++r) pl.row_blocks = std::max(pl.row_blocks, row_blocks_of(rq[r].a->n));
+        const size_t off_tran = sizeof(Desc) * (size_t)n;
+        pl.tab_bytes = off_tran + (trans ? sizeof(float) * 12 * (size_t)n * k : 0);
+        int rc;
+        if ((rc = C.h_tab.ensure(pl.tab_bytes)) || (rc = C.d_tab.ensure(pl.tab_bytes)) || (rc = C.h_out.ensure(answer_bytes)) ||
+            (rc = C.d_work.ensure(sizeof(double) * terms * (size_t)n * k * pl.row_blocks))) return rc;
+        unsigned char* const tab = static_cast<unsigned char*>(C.h_tab.p);
+        Desc* const descs = reinterpret_cast<Desc*>(tab);
+        std::memset(tab, 0, off_tran);
+        if (trans) std::memcpy(tab + off_tran, trans, sizeof(float) * 12 * (size_t)n * k);
+        const float* const d_tran = reinterpret_cast<const float*>(static_cast<const unsigned char*>(C.d_tab.p) + off_tran);
         for (int r = 0; r < n; ++r) {
             const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
-            const PairState* from = rq[r].from >= 0 ? static_cast<const PairState*>(d_states.p) + rq[r].from : nullptr;
-            const float* a_lo = a.rec(); const float* a_box = nullptr;
-            if (rq[r].tran || rq[r].tran_from_state) {
-                float* plane = reinterpret_cast<float*>(static_cast<unsigned char*>(d_support_moved.p) + moved_at);
-                float* gbox = plane + 4 * (size_t)a.n;
-                moved_at += sizeof(float) * 4 * (size_t)a.n + score_box_bytes(a.n);
-                SupportMoveDesc& M = mv[im]; BoxDesc& B = bx[im]; ++im;
-                M.src = a.rec(); M.dst = plane; M.n = a.n; M.from = rq[r].tran_from_state ? from : nullptr;
-                for (int i = 0; i < 12; ++i) M.tran[i] = rq[r].tran_from_state ? 0.f : rq[r].tran[i];
-                B.rec = plane; B.gbox = gbox; B.self_cache = score_self_cache(gbox, a.n); B.n = a.n; B.ngroups = score_groups(a.n);
-                a_lo = plane; a_box = gbox;
-            } else if (rq[r].sum_b) {
-                if ((rc = ensure_boxes(a, s))) return rc;
-                a_box = static_cast<const float*>(a.boxes.p);
-            }
-            if (rq[r].sum_a) {
-                if ((rc = ensure_boxes(b, s))) return rc;
-                SupportDesc& D = sd[id++];
-                D.a_lo = a_lo; D.a_hi = a.rec() + hi_off(a.n, 0); D.na = a.n;
-                D.b_lo = b.rec(); D.b_hi = b.rec() + hi_off(b.n, 0); D.nb = b.n;
-                D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
-                D.ell = rq[r].ell; D.from = from;
-                D.sum = static_cast<float*>(place(rq[r].sum_a, 4 * (size_t)a.n)); D.count = static_cast<int*>(place(rq[r].count_a, 4 * (size_t)a.n));
-            }
-            if (rq[r].sum_b) {
-                SupportDesc& D = sd[id++];
-                D.a_lo = b.rec(); D.a_hi = b.rec() + hi_off(b.n, 0); D.na = b.n;
-                D.b_lo = a_lo; D.b_hi = a.rec() + hi_off(a.n, 0); D.nb = a.n;
-                D.bbox = a_box; D.nbox = score_groups(a.n);
-                D.ell = rq[r].ell; D.from = from;
-                D.sum = static_cast<float*>(place(rq[r].sum_b, 4 * (size_t)b.n)); D.count = static_cast<int*>(place(rq[r].count_b, 4 * (size_t)b.n));
-            }
+            if ((rc = ensure_boxes(b, s))) return rc;
+            Desc& D = descs[r];
+            D.a = a.rec(); D.na = a.n; D.b = b.rec(); D.nb = b.n;
+            D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
+            D.trans = trans ? d_tran + 12 * (size_t)r * k : nullptr; D.ell = ell;
+            if ((rc = own(D, rq[r]))) return rc;
         }
-        if (out_stream && out_stream != s) {                         // whatever out_stream still does to the arrays comes first
-            if (!ev_support_in) HIP_TRY(hipEventCreateWithFlags(&ev_support_in, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ev_support_in, out_stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_support_in, 0));
-        }
-        HIP_TRY(hipMemcpyAsync(d_support_tab.p, h_support_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        const unsigned char* const dtab = static_cast<const unsigned char*>(d_support_tab.p);
-        const SupportMoveDesc* d_mv = reinterpret_cast<const SupportMoveDesc*>(dtab);
-        const BoxDesc* d_bx = reinterpret_cast<const BoxDesc*>(dtab + off_box);
-        const SupportDesc* d_sd = reinterpret_cast<const SupportDesc*>(dtab + off_req);
-        hipError_t e;
-        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
-            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            const unsigned wgs = (unsigned)row_blocks * (unsigned)n_dirs;
-            *qc->submitted_host += wgs;
-            bool sweep_submitted = false;
-            e = launch_support(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, P, s, qc->started_dev, &sweep_submitted);
-            if (!sweep_submitted) *qc->submitted_host -= wgs;
-            else if (e != hipSuccess) resync_adopt_counters(qc);
-        } else e = launch_support(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, P, s, nullptr, nullptr);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("support kernel launch: ") + hipGetErrorString(e));
-        if (to_host) HIP_TRY(hipMemcpyAsync(h_support_out.p, d_support_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev_support, s));
-        support_queued = true; support_stream = s;
+        pl.d_descs = C.d_tab.p;
         return CVO_OK;
     }
-    // waits for the call queued last; its host arrays (to_host) are filled here
-    int support_collect() {
+    // One hypothesis or pose-model call from its checks to the event behind its launches.  kind: as the messages name it; req_check(rq[r]): the kind's
+    // own check of a request, after the clouds'; launch(plan, wgs_started, sweep_submitted): the kind's launcher.  s waits for an align launch on a
+    // caller's stream; nothing waits for the device here but the call before.
+    template <class Desc, class Req, class ReqCheck, class Own, class Launch>
+    int run_pairs(SideCall& C, const Req* rq, int n, int k, const float* trans, float ell, hipStream_t s, const char* kind, int (*row_blocks_of)(int), size_t terms,
+                  size_t answer_bytes, ReqCheck&& req_check, Own&& own, Launch&& launch) {
         HIP_TRY(hipSetDevice(device));
-        if (!support_queued) return fail(CVO_ERR_INVALID, "no queued point support");
-        HIP_TRY(hipEventSynchronize(ev_support));
-        support_queued = false;
-        for (const SupportCopy& c : support_copies) std::memcpy(c.dst, static_cast<const unsigned char*>(h_support_out.p) + c.off, c.bytes);
-        support_copies.clear();
-        return CVO_OK;
-    }
-    // the device form's ordering: with an out_stream that stream waits for the launch and the host does not; else the host waits
-    int support_publish(hipStream_t out_stream) {
-        if (!out_stream) return support_collect();
-        if (out_stream != support_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_support, 0));
-        return CVO_OK;
-    }
-
-    // Point matches (cvo_match_kernels.hip; include/cvo_hip.h: cvo_point_matches): the requests of a support call -- a, b, ell and the transform as a
-    // SupportReq names them -- with five arrays per direction (dst.*_moving: the rows of a, dst.*_fixed: the rows of b; a direction whose arrays
-    // are null is not computed) and, where dst.fit is given, a fit record per computed direction.  to_host as for support_enqueue.
-    // Buffers of its own (nothing is shared with a score block, a support, a hypothesis or a pose-model call in flight); one call at a time.
-    struct MatchReq {
-        const Cloud* a; const float* tran; const Cloud* b; float ell;
-        int from; bool tran_from_state;
-        cvo_point_matches_dst dst;
-    };
-    DevBuf d_match_tab, d_match_moved, d_match_out; PinBuf h_match_tab, h_match_out;
-    hipEvent_t ev_match = nullptr, ev_match_in = nullptr; bool match_queued = false;
-    std::vector<SupportCopy> match_copies; hipStream_t match_stream = nullptr;
-    static bool match_dir_moving(const cvo_point_matches_dst& d) { return d.best_moving != nullptr; }
-    static bool match_dir_fixed(const cvo_point_matches_dst& d) { return d.best_fixed != nullptr; }
-    int match_enqueue(const MatchReq* rq, int n, hipStream_t s, bool to_host, hipStream_t out_stream = nullptr) {
-        HIP_TRY(hipSetDevice(device));
-        if (n <= 0) return fail(CVO_ERR_INVALID, "bad match request count");
+        if (n <= 0 || k < 1 || k > hyp_max()) return fail(CVO_ERR_INVALID, std::string("bad ") + kind + " request");
+        int rc;
         for (int r = 0; r < n; ++r) {
             if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
-            if (!match_dir_moving(rq[r].dst) && !match_dir_fixed(rq[r].dst)) return fail(CVO_ERR_INVALID, "point matches: no output array");
-            if (rq[r].tran_from_state && rq[r].from < 0) return fail(CVO_ERR_INVALID, "point matches: transform from a state that is not named");
+            if ((rc = req_check(rq[r]))) return rc;
         }
-        if (!ev_match) HIP_TRY(hipEventCreateWithFlags(&ev_match, hipEventDisableTiming));
-        if (match_queued) { HIP_TRY(hipEventSynchronize(ev_match)); match_queued = false; }   // the last call's tables, moved planes and outputs are free
-        match_copies.clear();
-        { int rcs = flush_pending(s); if (rcs) return rcs; }
-        { int rcs = settle_uploads(s); if (rcs) return rcs; }
-        // what the call needs: a moved {x, y, z, f0} plane and its boxes per transformed cloud, the tables, and (to_host) a place per output array;
-        // a direction's arrays are 28 bytes a row, its fit record 24 bytes, placed first so that it stays 8-byte aligned
-        int n_moves = 0, n_move_max = 0, n_dirs = 0, row_blocks = 1; bool with_fit = false;
-        size_t moved_bytes = 0, out_bytes = 0;
-        for (int r = 0; r < n; ++r) {
-            const bool moved = rq[r].tran || rq[r].tran_from_state;
-            const int na = rq[r].a->n, nb = rq[r].b->n;
-            if (moved) { ++n_moves; n_move_max = std::max(n_move_max, na); moved_bytes += sizeof(float) * 4 * (size_t)na + score_box_bytes(na); }
-            if (match_dir_moving(rq[r].dst)) { ++n_dirs; out_bytes += 28 * (size_t)na; row_blocks = std::max(row_blocks, match_row_blocks(na)); }
-            if (match_dir_fixed(rq[r].dst)) { ++n_dirs; out_bytes += 28 * (size_t)nb; row_blocks = std::max(row_blocks, match_row_blocks(nb)); }
-            if (rq[r].dst.fit) with_fit = true;
-        }
-        const size_t fit_bytes = sizeof(MatchFit) * (size_t)n_dirs;
-        out_bytes += fit_bytes;
-        const size_t off_box = sizeof(SupportMoveDesc) * (size_t)n_moves, off_req = off_box + sizeof(BoxDesc) * (size_t)n_moves;
-        const size_t tab_bytes = off_req + sizeof(MatchDesc) * (size_t)n_dirs;
-        int rc;
-        if ((rc = h_match_tab.ensure(tab_bytes)) || (rc = d_match_tab.ensure(tab_bytes)) || (rc = d_match_moved.ensure(std::max(moved_bytes, (size_t)16)))) return rc;
-        if (to_host && ((rc = d_match_out.ensure(out_bytes)) || (rc = h_match_out.ensure(out_bytes)))) return rc;
-        unsigned char* const tab = static_cast<unsigned char*>(h_match_tab.p);
-        SupportMoveDesc* const mv = reinterpret_cast<SupportMoveDesc*>(tab);
-        BoxDesc* const bx = reinterpret_cast<BoxDesc*>(tab + off_box);
-        MatchDesc* const sd = reinterpret_cast<MatchDesc*>(tab + off_req);
-        std::memset(tab, 0, tab_bytes);
-        size_t moved_at = 0, out_at = fit_bytes, fit_at = 0; int im = 0, id = 0;
-        auto place_at = [&](void* host_dst, size_t& at, size_t bytes) -> void* {   // an output: the caller's device memory, or a place in d_match_out
-            if (!to_host) return host_dst;
-            match_copies.push_back(SupportCopy{host_dst, at, bytes});
-            void* p = static_cast<unsigned char*>(d_match_out.p) + at; at += bytes; return p;
-        };
-        auto place = [&](void* host_dst, size_t bytes) -> void* { return place_at(host_dst, out_at, bytes); };
-        for (int r = 0; r < n; ++r) {
-            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b; const cvo_point_matches_dst& d = rq[r].dst;
-            const PairState* from = rq[r].from >= 0 ? static_cast<const PairState*>(d_states.p) + rq[r].from : nullptr;
-            const float* a_lo = a.rec(); const float* a_box = nullptr;
-            if (rq[r].tran || rq[r].tran_from_state) {
-                float* plane = reinterpret_cast<float*>(static_cast<unsigned char*>(d_match_moved.p) + moved_at);
-                float* gbox = plane + 4 * (size_t)a.n;
-                moved_at += sizeof(float) * 4 * (size_t)a.n + score_box_bytes(a.n);
-                SupportMoveDesc& M = mv[im]; BoxDesc& B = bx[im]; ++im;
-                M.src = a.rec(); M.dst = plane; M.n = a.n; M.from = rq[r].tran_from_state ? from : nullptr;
-                for (int i = 0; i < 12; ++i) M.tran[i] = rq[r].tran_from_state ? 0.f : rq[r].tran[i];
-                B.rec = plane; B.gbox = gbox; B.self_cache = score_self_cache(gbox, a.n); B.n = a.n; B.ngroups = score_groups(a.n);
-                a_lo = plane; a_box = gbox;
-            } else if (match_dir_fixed(d)) {
-                if ((rc = ensure_boxes(a, s))) return rc;
-                a_box = static_cast<const float*>(a.boxes.p);
-            }
-            if (match_dir_moving(d)) {
-                if ((rc = ensure_boxes(b, s))) return rc;
-                MatchDesc& D = sd[id++];
-                D.a_lo = a_lo; D.a_hi = a.rec() + hi_off(a.n, 0); D.na = a.n;
-                D.b_lo = b.rec(); D.b_hi = b.rec() + hi_off(b.n, 0); D.nb = b.n;
-                D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
-                D.ell = rq[r].ell; D.from = from;
-                D.best = static_cast<int*>(place(d.best_moving, 4 * (size_t)a.n)); D.best_value = static_cast<float*>(place(d.best_value_moving, 4 * (size_t)a.n));
-                D.mean = static_cast<float*>(place(d.mean_moving, 12 * (size_t)a.n));
-                D.sum = static_cast<float*>(place(d.sum_moving, 4 * (size_t)a.n)); D.count = static_cast<int*>(place(d.count_moving, 4 * (size_t)a.n));
-                D.fit = d.fit ? static_cast<MatchFit*>(place_at(d.fit + 0, fit_at, sizeof(MatchFit))) : nullptr;
-            }
-            if (match_dir_fixed(d)) {
-                MatchDesc& D = sd[id++];
-                D.a_lo = b.rec(); D.a_hi = b.rec() + hi_off(b.n, 0); D.na = b.n;
-                D.b_lo = a_lo; D.b_hi = a.rec() + hi_off(a.n, 0); D.nb = a.n;
-                D.bbox = a_box; D.nbox = score_groups(a.n);
-                D.ell = rq[r].ell; D.from = from;
-                D.best = static_cast<int*>(place(d.best_fixed, 4 * (size_t)b.n)); D.best_value = static_cast<float*>(place(d.best_value_fixed, 4 * (size_t)b.n));
-                D.mean = static_cast<float*>(place(d.mean_fixed, 12 * (size_t)b.n));
-                D.sum = static_cast<float*>(place(d.sum_fixed, 4 * (size_t)b.n)); D.count = static_cast<int*>(place(d.count_fixed, 4 * (size_t)b.n));
-                D.fit = d.fit ? static_cast<MatchFit*>(place_at(d.fit + 1, fit_at, sizeof(MatchFit))) : nullptr;
-            }
-        }
-        if (out_stream && out_stream != s) {                         // whatever out_stream still does to the arrays comes first
-            if (!ev_match_in) HIP_TRY(hipEventCreateWithFlags(&ev_match_in, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(ev_match_in, out_stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_match_in, 0));
-        }
-        HIP_TRY(hipMemcpyAsync(d_match_tab.p, h_match_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        const unsigned char* const dtab = static_cast<const unsigned char*>(d_match_tab.p);
-        const SupportMoveDesc* d_mv = reinterpret_cast<const SupportMoveDesc*>(dtab);
-        const BoxDesc* d_bx = reinterpret_cast<const BoxDesc*>(dtab + off_box);
-        const MatchDesc* d_sd = reinterpret_cast<const MatchDesc*>(dtab + off_req);
-        hipError_t e;
-        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the support workgroups are
-            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            const unsigned wgs = (unsigned)row_blocks * (unsigned)n_dirs;
-            *qc->submitted_host += wgs;
-            bool sweep_submitted = false;
-            e = launch_match(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, with_fit, P, s, qc->started_dev, &sweep_submitted);
-            if (!sweep_submitted) *qc->submitted_host -= wgs;
-            else if (e != hipSuccess) resync_adopt_counters(qc);
-        } else e = launch_match(d_mv, d_bx, n_moves, n_move_max, d_sd, n_dirs, row_blocks, with_fit, P, s, nullptr, nullptr);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("match kernel launch: ") + hipGetErrorString(e));
-        if (to_host) HIP_TRY(hipMemcpyAsync(h_match_out.p, d_match_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev_match, s));
-        match_queued = true; match_stream = s;
-        return CVO_OK;
+        SidePlan pl;
+        if ((rc = C.begin(*this, s, true)) || (rc = build_pairs<Desc>(C, rq, n, k, trans, ell, s, row_blocks_of, terms, answer_bytes, own, pl)) ||
+            (rc = C.upload(pl.tab_bytes, s))) return rc;
+        const hipError_t e = counted_sweep((unsigned)pl.row_blocks * (unsigned)k * (unsigned)n, [&](unsigned* wgs_started, bool* sweep_submitted) { return launch(pl, wgs_started, sweep_submitted); });
+        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string(kind) + " kernel launch: " + hipGetErrorString(e));
+        return C.finish(s);
     }
-    // waits for the call queued last; its host arrays (to_host) are filled here
-    int match_collect() {
-        HIP_TRY(hipSetDevice(device));
-        if (!match_queued) return fail(CVO_ERR_INVALID, "no queued point matches");
-        HIP_TRY(hipEventSynchronize(ev_match));
-        match_queued = false;
-        for (const SupportCopy& c : match_copies) std::memcpy(c.dst, static_cast<const unsigned char*>(h_match_out.p) + c.off, c.bytes);
-        match_copies.clear();
-        return CVO_OK;
-    }
-    // the device form's ordering, as support_publish
-    int match_publish(hipStream_t out_stream) {
-        if (!out_stream) return match_collect();
-        if (out_stream != match_stream) HIP_TRY(hipStreamWaitEvent(out_stream, ev_match, 0));
-        return CVO_OK;
-    }
-
-    // Pose hypotheses (cvo_hypothesis_kernels.hip; include/cvo_hip.h: cvo_score_hypotheses): for every request the moving cloud a under each of the k
-    // transforms trans[r][0 .. k) against the fixed cloud b at `ell`, all in ONE sweep launch, and the reduce / select launch behind it.  seed: the
-    // select step also writes d_states[rq[r].state] -- R, T from reset_initial(best hypothesis), ell, transform and iter from rq[r].start.  The
-    // caller's trans array is copied into the pinned table before the call returns; nothing waits for the device here but the call before
-    // (one at a time, buffers of its own: the next one waits for ev_hyp first, as the support calls do for theirs).
+    // Hypotheses.  seed: the select step also writes d_states[rq[r].state] -- R, T from reset_initial(best hypothesis), ell, transform and iter from
+    // rq[r].start.
     struct HypReq { const Cloud* a; const Cloud* b; int state; const PairState* start; };
-    DevBuf d_hyp_tab, d_hyp_partials; PinBuf h_hyp_tab, h_hyp_out;
-    hipEvent_t ev_hyp = nullptr; bool hyp_queued = false; int hyp_n = 0, hyp_k = 0;
+    int hyp_n = 0, hyp_k = 0;
     bool hyp_seed = false;                  // the call in flight is a seeding call: its answers are kept for cvo_batch_hypothesis_results (hyp_keep)
     std::vector<cvo_inn_p> seed_scores; std::vector<int> seed_best; int seed_n = 0, seed_k = 0;   // the last seeding call's answers, once it has been waited for
-    // the call in flight has finished: a seeding call's answers move out of the pinned block the next call writes over
+    // the call in flight has finished: a seeding call's answers move out of the pinned block the next call writes over (hyp_call.before_reuse:
+    // begin() comes here before it frees the record)
     int hyp_keep() {
-        if (!hyp_queued) return CVO_OK;
-        HIP_TRY(hipEventSynchronize(ev_hyp));
-        hyp_queued = false;
+        if (!hyp_call.queued) return CVO_OK;
+        int rc = hyp_call.wait(); if (rc) return rc;
         if (hyp_seed) {
-            const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(h_hyp_out.p);
+            const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(hyp_call.h_out.p);
             const int* bs = reinterpret_cast<const int*>(sc + (size_t)hyp_n * hyp_k);
             seed_scores.assign(sc, sc + (size_t)hyp_n * hyp_k); seed_best.assign(bs, bs + hyp_n);
             seed_n = hyp_n; seed_k = hyp_k; hyp_seed = false;
@@ -1731,135 +1725,61 @@ struct Engine {
         return CVO_OK;
     }
     int hyp_enqueue(const HypReq* rq, int n, int k, const float* trans, float ell, hipStream_t s, bool seed) {
-        HIP_TRY(hipSetDevice(device));
-        if (n <= 0 || k < 1 || k > hyp_max()) return fail(CVO_ERR_INVALID, "bad hypothesis request");
-        for (int r = 0; r < n; ++r) if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
-        if (!ev_hyp) HIP_TRY(hipEventCreateWithFlags(&ev_hyp, hipEventDisableTiming));
-        int rc = hyp_keep(); if (rc) return rc;                       // the last call's table, records and answers are free
-        if ((rc = flush_pending(s)) || (rc = settle_uploads(s))) return rc;
-        if (launched && last_stream && last_stream != s) HIP_TRY(hipStreamWaitEvent(s, ev1, 0));   // an align launch on a caller's stream packs clouds and writes states
-        int row_blocks = 1;
-        for (int r = 0; r < n; ++r) row_blocks = std::max(row_blocks, hyp_row_blocks(rq[r].a->n));
-        const size_t off_tran = sizeof(HypDesc) * (size_t)n, tab_bytes = off_tran + sizeof(float) * 12 * (size_t)n * k;
-        const size_t out_bytes = sizeof(cvo_inn_p) * (size_t)n * k + sizeof(int) * (size_t)n;
-        if ((rc = h_hyp_tab.ensure(tab_bytes)) || (rc = d_hyp_tab.ensure(tab_bytes)) || (rc = h_hyp_out.ensure(out_bytes)) ||
-            (rc = d_hyp_partials.ensure(sizeof(double) * 2 * (size_t)n * k * row_blocks))) return rc;
-        if (seed && (rc = d_states.ensure(sizeof(PairState) * (size_t)std::max(1, state_slots)))) return rc;   // (the size every launch asks for: it stays where it is)
-        unsigned char* const tab = static_cast<unsigned char*>(h_hyp_tab.p);
-        HypDesc* const hd = reinterpret_cast<HypDesc*>(tab);
-        std::memset(tab, 0, off_tran);
-        std::memcpy(tab + off_tran, trans, sizeof(float) * 12 * (size_t)n * k);
-        const float* const d_tran = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d_hyp_tab.p) + off_tran);
-        for (int r = 0; r < n; ++r) {
-            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
-            if ((rc = ensure_boxes(b, s))) return rc;
-            HypDesc& D = hd[r];
-            D.a = a.rec(); D.na = a.n; D.b = b.rec(); D.nb = b.n;
-            D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
-            D.trans = d_tran + 12 * (size_t)r * k; D.ell = ell;
-            if (seed) {
-                if (rq[r].state < 0 || rq[r].state >= state_slots || !rq[r].start) return fail(CVO_ERR_INVALID, "hypothesis seed: no device state for the pair");
-                D.state = static_cast<PairState*>(d_states.p) + rq[r].state;
-                D.seed_ell = rq[r].start->ell; D.seed_iter = rq[r].start->iter;
-                std::memcpy(D.seed_transform, rq[r].start->transform, sizeof(D.seed_transform));
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(d_hyp_tab.p, h_hyp_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        cvo_inn_p* const sc = static_cast<cvo_inn_p*>(h_hyp_out.p);
-        HypScore* const d_sc = reinterpret_cast<HypScore*>(sc); int* const d_best = reinterpret_cast<int*>(sc + (size_t)n * k);
-        const HypDesc* const d_hd = static_cast<const HypDesc*>(d_hyp_tab.p);
-        hipError_t e;
-        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
-            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            const unsigned wgs = (unsigned)row_blocks * (unsigned)k * (unsigned)n;
-            *qc->submitted_host += wgs;
-            bool sweep_submitted = false;
-            e = launch_hypotheses(d_hd, n, k, row_blocks, P, static_cast<double*>(d_hyp_partials.p), d_sc, d_best, seed ? 1 : 0, s, qc->started_dev, &sweep_submitted);
-            if (!sweep_submitted) *qc->submitted_host -= wgs;
-            else if (e != hipSuccess) resync_adopt_counters(qc);
-        } else e = launch_hypotheses(d_hd, n, k, row_blocks, P, static_cast<double*>(d_hyp_partials.p), d_sc, d_best, seed ? 1 : 0, s, nullptr, nullptr);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("hypothesis kernel launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipEventRecord(ev_hyp, s));
-        hyp_queued = true; hyp_seed = seed; hyp_n = n; hyp_k = k;
+        SideCall& C = hyp_call;
+        int rc = run_pairs<HypDesc>(C, rq, n, k, trans, ell, s, "hypothesis", hyp_row_blocks, 2, sizeof(cvo_inn_p) * (size_t)n * k + sizeof(int) * (size_t)n,
+            [](const HypReq&) { return CVO_OK; },
+            [&](HypDesc& D, const HypReq& q) {
+                if (!seed) return (int)CVO_OK;
+                if (int rcs = d_states.ensure(sizeof(PairState) * (size_t)std::max(1, state_slots))) return rcs;   // (the size every launch asks for: it stays where it is)
+                if (q.state < 0 || q.state >= state_slots || !q.start) return fail(CVO_ERR_INVALID, "hypothesis seed: no device state for the pair");
+                D.state = static_cast<PairState*>(d_states.p) + q.state;
+                D.seed_ell = q.start->ell; D.seed_iter = q.start->iter;
+                std::memcpy(D.seed_transform, q.start->transform, sizeof(D.seed_transform));
+                return (int)CVO_OK;
+            },
+            [&](const SidePlan& pl, unsigned* wgs_started, bool* sweep_submitted) {
+                cvo_inn_p* const sc = static_cast<cvo_inn_p*>(C.h_out.p);
+                return launch_hypotheses(static_cast<const HypDesc*>(pl.d_descs), n, k, pl.row_blocks, P, static_cast<double*>(C.d_work.p), reinterpret_cast<HypScore*>(sc),
+                                         reinterpret_cast<int*>(sc + (size_t)n * k), seed ? 1 : 0, s, wgs_started, sweep_submitted);
+            });
+        if (rc) return rc;
+        hyp_seed = seed; hyp_n = n; hyp_k = k;
         return CVO_OK;
     }
     // waits for the scores-only call queued last and hands out its answers (best may be null)
     int hyp_collect(cvo_inn_p* scores, int* best) {
-        HIP_TRY(hipSetDevice(device));
-        if (!hyp_queued || hyp_seed) return fail(CVO_ERR_INVALID, "no queued hypothesis scores");
-        HIP_TRY(hipEventSynchronize(ev_hyp));
-        hyp_queued = false;
-        const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(h_hyp_out.p);
+        if (hyp_call.queued && hyp_seed) return fail(CVO_ERR_INVALID, hyp_call.none_queued);
+        int rc = side_collect(hyp_call); if (rc) return rc;
+        const cvo_inn_p* sc = static_cast<const cvo_inn_p*>(hyp_call.h_out.p);
         std::memcpy(scores, sc, sizeof(cvo_inn_p) * (size_t)hyp_n * hyp_k);
         if (best) std::memcpy(best, sc + (size_t)hyp_n * hyp_k, sizeof(int) * (size_t)hyp_n);
         return CVO_OK;
     }
 
-    // Pose models (cvo_pose_model_kernels.hip; include/cvo_hip.h: cvo_pose_models): for every request value, gradient and Hessian of the moving cloud a
-    // against the fixed cloud b at each of the k transforms trans[r][0 .. k) and `ell` -- or, from >= 0 (k = 1, trans null), at the transform and ell
-    // of d_states[from], so that the call can be queued behind the align launch that writes them.  ONE sweep launch and the reduce launch behind it.
-    // Buffers of its own (nothing is shared with a score block, a support call or a hypothesis call in flight); one call at a time, and every
-    // call is collected before its entry point returns.
+    // Pose models: value, gradient and Hessian at each of the k transforms -- or, from >= 0 (k = 1, trans null), at the transform and ell of
+    // d_states[from], so that the call can be queued behind the align launch that writes them.  Every call is collected before its entry point returns.
     struct PoseModelReq { const Cloud* a; const Cloud* b; int from; };
-    DevBuf d_pm_tab, d_pm_partials; PinBuf h_pm_tab, h_pm_out;
-    hipEvent_t ev_pm = nullptr; bool pm_queued = false; int pm_n = 0, pm_k = 0;
+    int pm_n = 0, pm_k = 0;
     int pm_enqueue(const PoseModelReq* rq, int n, int k, const float* trans, float ell, hipStream_t s) {
-        HIP_TRY(hipSetDevice(device));
-        if (n <= 0 || k < 1 || k > hyp_max()) return fail(CVO_ERR_INVALID, "bad pose model request");
-        for (int r = 0; r < n; ++r) {
-            if (!rq[r].a || !rq[r].b || rq[r].a->n <= 0 || rq[r].b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "empty cloud");
-            if (rq[r].from >= 0 ? (k != 1 || rq[r].from >= state_slots) : !trans) return fail(CVO_ERR_INVALID, "pose models: no transform for a pair");
-        }
-        if (!ev_pm) HIP_TRY(hipEventCreateWithFlags(&ev_pm, hipEventDisableTiming));
-        if (pm_queued) { HIP_TRY(hipEventSynchronize(ev_pm)); pm_queued = false; }   // the last call's table, records and answers are free
-        int rc;
-        if ((rc = flush_pending(s)) || (rc = settle_uploads(s))) return rc;
-        if (launched && last_stream && last_stream != s) HIP_TRY(hipStreamWaitEvent(s, ev1, 0));   // an align launch on a caller's stream packs clouds and writes states
-        int row_blocks = 1;
-        for (int r = 0; r < n; ++r) row_blocks = std::max(row_blocks, pose_model_row_blocks(rq[r].a->n));
-        const size_t off_tran = sizeof(PoseModelDesc) * (size_t)n, tab_bytes = off_tran + (trans ? sizeof(float) * 12 * (size_t)n * k : 0);
-        if ((rc = h_pm_tab.ensure(tab_bytes)) || (rc = d_pm_tab.ensure(tab_bytes)) || (rc = h_pm_out.ensure(sizeof(PoseModel) * (size_t)n * k)) ||
-            (rc = d_pm_partials.ensure(sizeof(double) * POSE_MODEL_TERMS * (size_t)n * k * row_blocks))) return rc;
-        unsigned char* const tab = static_cast<unsigned char*>(h_pm_tab.p);
-        PoseModelDesc* const pd = reinterpret_cast<PoseModelDesc*>(tab);
-        std::memset(tab, 0, off_tran);
-        if (trans) std::memcpy(tab + off_tran, trans, sizeof(float) * 12 * (size_t)n * k);
-        const float* const d_tran = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d_pm_tab.p) + off_tran);
-        for (int r = 0; r < n; ++r) {
-            const Cloud& a = *rq[r].a; const Cloud& b = *rq[r].b;
-            if ((rc = ensure_boxes(b, s))) return rc;
-            PoseModelDesc& D = pd[r];
-            D.a = a.rec(); D.na = a.n; D.b = b.rec(); D.nb = b.n;
-            D.bbox = static_cast<const float*>(b.boxes.p); D.nbox = score_groups(b.n);
-            D.ell = ell;
-            if (rq[r].from >= 0) D.from = static_cast<const PairState*>(d_states.p) + rq[r].from;
-            else D.trans = d_tran + 12 * (size_t)r * k;
-        }
-        HIP_TRY(hipMemcpyAsync(d_pm_tab.p, h_pm_tab.p, tab_bytes, hipMemcpyHostToDevice, s));
-        const PoseModelDesc* const d_pd = static_cast<const PoseModelDesc*>(d_pm_tab.p);
-        PoseModel* const d_out = static_cast<PoseModel*>(h_pm_out.p);
-        hipError_t e;
-        if (AdoptCounters* const qc = adopt_counters(device)) {      // queued work that helpers of align launches in flight must see, as the score workgroups are
-            std::lock_guard<std::mutex> lk(adopt_submit_mutex());
-            const unsigned wgs = (unsigned)row_blocks * (unsigned)k * (unsigned)n;
-            *qc->submitted_host += wgs;
-            bool sweep_submitted = false;
-            e = launch_pose_models(d_pd, n, k, row_blocks, P, static_cast<double*>(d_pm_partials.p), d_out, s, qc->started_dev, &sweep_submitted);
-            if (!sweep_submitted) *qc->submitted_host -= wgs;
-            else if (e != hipSuccess) resync_adopt_counters(qc);
-        } else e = launch_pose_models(d_pd, n, k, row_blocks, P, static_cast<double*>(d_pm_partials.p), d_out, s, nullptr, nullptr);
-        if (e != hipSuccess) return fail(CVO_ERR_HIP, std::string("pose model kernel launch: ") + hipGetErrorString(e));
-        HIP_TRY(hipEventRecord(ev_pm, s));
-        pm_queued = true; pm_n = n; pm_k = k;
+        SideCall& C = pm_call;
+        int rc = run_pairs<PoseModelDesc>(C, rq, n, k, trans, ell, s, "pose model", pose_model_row_blocks, POSE_MODEL_TERMS, sizeof(PoseModel) * (size_t)n * k,
+            [&](const PoseModelReq& q) { return (q.from >= 0 ? (k != 1 || q.from >= state_slots) : !trans) ? fail(CVO_ERR_INVALID, "pose models: no transform for a pair") : CVO_OK; },
+            [&](PoseModelDesc& D, const PoseModelReq& q) {
+                if (q.from >= 0) { D.from = static_cast<const PairState*>(d_states.p) + q.from; D.trans = nullptr; }
+                return (int)CVO_OK;
+            },
+            [&](const SidePlan& pl, unsigned* wgs_started, bool* sweep_submitted) {
+                return launch_pose_models(static_cast<const PoseModelDesc*>(pl.d_descs), n, k, pl.row_blocks, P, static_cast<double*>(C.d_work.p), static_cast<PoseModel*>(C.h_out.p), s,
+                                          wgs_started, sweep_submitted);
+            });
+        if (rc) return rc;
+        pm_n = n; pm_k = k;
         return CVO_OK;
     }
     // waits for the call queued last and hands out its models
     int pm_collect(cvo_pose_model* out) {
-        HIP_TRY(hipSetDevice(device));
-        if (!pm_queued) return fail(CVO_ERR_INVALID, "no queued pose models");
-        HIP_TRY(hipEventSynchronize(ev_pm));
-        pm_queued = false;
-        std::memcpy(out, h_pm_out.p, sizeof(cvo_pose_model) * (size_t)pm_n * pm_k);
+        int rc = side_collect(pm_call); if (rc) return rc;
+        std::memcpy(out, pm_call.h_out.p, sizeof(cvo_pose_model) * (size_t)pm_n * pm_k);
         return CVO_OK;
     }
 };
@@ -2456,9 +2376,8 @@ int cvo_point_support(cvo_handle h, int slot_a, const float* tran_a, int slot_b,
     Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
     if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point support: empty cloud slot");
     if ((sum_a && cap_a < a->n) || (sum_b && cap_b < b->n)) return fail(CVO_ERR_INVALID, "point support: an output array is shorter than its cloud");
-    const Engine::SupportReq rq[1] = {{a, tran_a, b, h->ell, -1, false, sum_a, count_a, sum_b, count_b}};
-    int rc = h->eng.support_enqueue(rq, 1, h->eng.stream, true); if (rc) return rc;
-    return h->eng.support_collect();
+    const Engine::SupportReq rq[1] = {{a, tran_a, b, h->ell, -1, false, {sum_a, count_a, sum_b, count_b}}};
+    return h->eng.point_sides(rq, 1, h->eng.stream, true);
 }
 
 namespace {
@@ -2829,7 +2748,7 @@ int batch_launch(cvo_batch b, const int* slots, int n, hipStream_t stream, bool 
         }
     }
     // a seed queued on the object's stream (cvo_batch_seed_hypotheses_async) comes before a launch on a caller's stream: it writes the start states
-    if (stream && stream != b->eng.stream && b->eng.hyp_queued) HIP_TRY(hipStreamWaitEvent(stream, b->eng.ev_hyp, 0));
+    if (stream && stream != b->eng.stream && b->eng.hyp_call.queued) HIP_TRY(hipStreamWaitEvent(stream, b->eng.hyp_call.done, 0));
     rc = b->eng.launch(pairs, st.data(), false, stream, false, 0, slots, up.data());
     if (rc) return rc;
     if (clean_all) std::fill(b->dirty.begin(), b->dirty.end(), (unsigned char)0);   // device states now evolve launch to launch (warm start) until reset
@@ -5532,125 +5451,101 @@ int cvo_batch_compute_innerproduct(cvo_batch b, int n, cvo_track_scores* out) {
     int rc = cvo_batch_enqueue_innerproduct(b, n); if (rc) return rc;
     return cvo_batch_innerproduct_results(b, n, out);
 }
+// ---- per-point support and point matches of a batch's last launch (include/cvo_hip.h, "per-point support", "point matches")
+extern "C++" {                                                        // (the helpers below have templates among them)
 namespace {
-// One pair's record of a point-support call: both directions' arrays, each direction whole or absent; on_device: every array is n x 4 bytes the
-// device can write (the rule of cvo_device_cloud: check_device_plane), 4-byte aligned.  Nothing is queued here.
-int support_check_dst(int device, const cvo_point_support_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
-    if (!d.sum_moving != !d.count_moving || !d.sum_fixed != !d.count_fixed) return fail(CVO_ERR_INVALID, who + "a direction needs its sum and its count array");
-    if (!d.sum_moving && !d.sum_fixed) return fail(CVO_ERR_INVALID, who + "no output array");
-    if (!on_device) return CVO_OK;
-    const struct { const void* p; int n; const char* name; } arr[4] = {{d.sum_moving, n_moving, "sum_moving"}, {d.count_moving, n_moving, "count_moving"},
-                                                                       {d.sum_fixed, n_fixed, "sum_fixed"}, {d.count_fixed, n_fixed, "count_fixed"}};
-    for (const auto& x : arr) {
-        if (!x.p) continue;
-        if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
-        int rc = check_device_plane(device, x.p, 4ll * x.n, 4ll * x.n, 1, who + x.name, "array"); if (rc) return rc;
+// Positions of b's last launch (pairs null: 0 .. count-1), none twice: each(k, slot) for the k-th listed one, in order, as soon as it has been checked.
+template <class Each>
+int last_launch_pairs(cvo_batch b, int count, const int* pairs, const std::string& what, Each&& each) {
+    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
+    int rc = check_last_clouds(b); if (rc) return rc;
+    std::vector<unsigned char> seen(b->last_n, 0);
+    for (int k = 0; k < count; ++k) {
+        const int i = pairs ? pairs[k] : k;
+        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, what + ": pair " + std::to_string(i) + " is not a position of the last launch");
+        if (seen[i]++) return fail(CVO_ERR_INVALID, what + ": pair " + std::to_string(i) + " listed twice");
+        if ((rc = each(k, b->last_slots[i]))) return rc;
     }
     return CVO_OK;
 }
-// The requests of the listed slots of b (their device states name transform and ell), checked; then one launch on the stream of b's last launch.
-int batch_support_run(cvo_batch b, const std::vector<int>& slots, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
-    Engine& E = b->eng;
-    if (on_device) HIP_TRY(hipSetDevice(E.device));
-    std::vector<Engine::SupportReq> rq(slots.size());
-    for (size_t k = 0; k < slots.size(); ++k) {
-        const int p = slots[k];
-        const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
-        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point support: empty cloud in the batch");
-        int rc = support_check_dst(E.device, dst[k], mv->n, fx->n, on_device, "point support, record " + std::to_string(k) + ": "); if (rc) return rc;
-        rq[k] = Engine::SupportReq{mv, nullptr, fx, 0.f, p, true, dst[k].sum_moving, dst[k].count_moving, dst[k].sum_fixed, dst[k].count_fixed};
+// The device form's arrays: every one that is given is aligned and memory the device can write (the rule of cvo_device_cloud: check_device_plane)
+struct DstArray { const void* p; long long bytes; const char* name; unsigned align; };
+int check_dst_arrays(int device, const DstArray* arr, int n, const std::string& who) {
+    for (int q = 0; q < n; ++q) {
+        const DstArray& x = arr[q];
+        if (!x.p) continue;
+        if (reinterpret_cast<uintptr_t>(x.p) & (x.align - 1u)) return fail(CVO_ERR_INVALID, who + x.name + " is not " + std::to_string(x.align) + "-byte aligned");
+        int rc = check_device_plane(device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"); if (rc) return rc;
     }
-    int rc = E.support_enqueue(rq.data(), (int)rq.size(), E.last_stream, !on_device, on_device ? static_cast<hipStream_t>(out_stream) : nullptr); if (rc) return rc;
-    return on_device ? E.support_publish(static_cast<hipStream_t>(out_stream)) : E.support_collect();
+    return CVO_OK;
 }
-int batch_support(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
-    if (!b || !dst) return fail(CVO_ERR_INVALID, "null argument");
-    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
-    int rc = check_last_clouds(b); if (rc) return rc;
-    std::vector<int> slots(count); std::vector<unsigned char> seen(b->last_n, 0);
-    for (int k = 0; k < count; ++k) {
-        const int i = pairs ? pairs[k] : k;
-        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "point support: pair " + std::to_string(i) + " is not a position of the last launch");
-        if (seen[i]++) return fail(CVO_ERR_INVALID, "point support: pair " + std::to_string(i) + " listed twice");
-        slots[k] = b->last_slots[i];
-    }
-    return batch_support_run(b, slots, dst, on_device, out_stream);
+// One pair's record of a point-support call: both directions' arrays, each direction whole or absent; on_device: every array is n x 4 bytes.
+// Nothing is queued here.
+int check_dst(int device, const cvo_point_support_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
+    if (!d.sum_moving != !d.count_moving || !d.sum_fixed != !d.count_fixed) return fail(CVO_ERR_INVALID, who + "a direction needs its sum and its count array");
+    if (!d.sum_moving && !d.sum_fixed) return fail(CVO_ERR_INVALID, who + "no output array");
+    const DstArray arr[4] = {{d.sum_moving, 4ll * n_moving, "sum_moving", 4}, {d.count_moving, 4ll * n_moving, "count_moving", 4},
+                             {d.sum_fixed, 4ll * n_fixed, "sum_fixed", 4}, {d.count_fixed, 4ll * n_fixed, "count_fixed", 4}};
+    return on_device ? check_dst_arrays(device, arr, 4, who) : CVO_OK;
 }
-}  // namespace
-int cvo_batch_point_support(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst) { return batch_support(b, count, pairs, dst, false, nullptr); }
-int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, void* out_stream) {
-    return batch_support(b, count, pairs, dst, true, out_stream);
-}
-// ---- point matches (include/cvo_hip.h, "point matches"; cvo_match_kernels.hip)
-namespace {
-// One pair's record of a point-matches call: a direction's five arrays all given or all absent, not both absent; on_device: every array is memory the
-// device can write (the rule of cvo_device_cloud: check_device_plane), 4-byte aligned, fit two records and 8-byte aligned.  Nothing is queued here.
-int match_check_dst(int device, const cvo_point_matches_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
-    const struct { const void* p; long long bytes; const char* name; } arr[10] = {
-        {d.best_moving, 4ll * n_moving, "best_moving"}, {d.best_value_moving, 4ll * n_moving, "best_value_moving"}, {d.mean_moving, 12ll * n_moving, "mean_moving"},
-        {d.sum_moving, 4ll * n_moving, "sum_moving"}, {d.count_moving, 4ll * n_moving, "count_moving"},
-        {d.best_fixed, 4ll * n_fixed, "best_fixed"}, {d.best_value_fixed, 4ll * n_fixed, "best_value_fixed"}, {d.mean_fixed, 12ll * n_fixed, "mean_fixed"},
-        {d.sum_fixed, 4ll * n_fixed, "sum_fixed"}, {d.count_fixed, 4ll * n_fixed, "count_fixed"}};
+// One pair's record of a point-matches call: a direction's five arrays all given or all absent, not both absent; on_device: fit is two records,
+// 8-byte aligned.  Nothing is queued here.
+int check_dst(int device, const cvo_point_matches_dst& d, int n_moving, int n_fixed, bool on_device, const std::string& who) {
+    const DstArray arr[11] = {
+        {d.best_moving, 4ll * n_moving, "best_moving", 4}, {d.best_value_moving, 4ll * n_moving, "best_value_moving", 4}, {d.mean_moving, 12ll * n_moving, "mean_moving", 4},
+        {d.sum_moving, 4ll * n_moving, "sum_moving", 4}, {d.count_moving, 4ll * n_moving, "count_moving", 4},
+        {d.best_fixed, 4ll * n_fixed, "best_fixed", 4}, {d.best_value_fixed, 4ll * n_fixed, "best_value_fixed", 4}, {d.mean_fixed, 12ll * n_fixed, "mean_fixed", 4},
+        {d.sum_fixed, 4ll * n_fixed, "sum_fixed", 4}, {d.count_fixed, 4ll * n_fixed, "count_fixed", 4},
+        {d.fit, 2ll * sizeof(cvo_match_fit), "fit", 8}};
     for (int side = 0; side < 2; ++side) {
         int given = 0;
         for (int q = 0; q < 5; ++q) given += arr[5 * side + q].p ? 1 : 0;
         if (given != 0 && given != 5) return fail(CVO_ERR_INVALID, who + "a direction needs all five of its arrays");
     }
     if (!d.best_moving && !d.best_fixed) return fail(CVO_ERR_INVALID, who + "no output array");
-    if (!on_device) return CVO_OK;
-    for (const auto& x : arr) {
-        if (!x.p) continue;
-        if (reinterpret_cast<uintptr_t>(x.p) & 3u) return fail(CVO_ERR_INVALID, who + x.name + " is not 4-byte aligned");
-        int rc = check_device_plane(device, x.p, x.bytes, x.bytes, 1, who + x.name, "array"); if (rc) return rc;
-    }
-    if (d.fit) {
-        if (reinterpret_cast<uintptr_t>(d.fit) & 7u) return fail(CVO_ERR_INVALID, who + "fit is not 8-byte aligned");
-        int rc = check_device_plane(device, d.fit, 2ll * sizeof(cvo_match_fit), 2ll * sizeof(cvo_match_fit), 1, who + "fit", "array"); if (rc) return rc;
-    }
-    return CVO_OK;
+    return on_device ? check_dst_arrays(device, arr, 11, who) : CVO_OK;
 }
 // The requests of the listed slots of b (their device states name transform and ell), checked; then one launch on the stream of b's last launch.
-int batch_match_run(cvo_batch b, const std::vector<int>& slots, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
+// what: "point support" / "point matches", as the messages name the call.
+template <class Dst>
+int batch_sides_run(cvo_batch b, const std::vector<int>& slots, const Dst* dst, bool on_device, void* out_stream, const std::string& what) {
     Engine& E = b->eng;
     if (on_device) HIP_TRY(hipSetDevice(E.device));
-    std::vector<Engine::MatchReq> rq(slots.size());
+    std::vector<Engine::SideReq<Dst>> rq(slots.size());
     for (size_t k = 0; k < slots.size(); ++k) {
         const int p = slots[k];
         const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
-        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point matches: empty cloud in the batch");
-        int rc = match_check_dst(E.device, dst[k], mv->n, fx->n, on_device, "point matches, record " + std::to_string(k) + ": "); if (rc) return rc;
-        rq[k] = Engine::MatchReq{mv, nullptr, fx, 0.f, p, true, dst[k]};
+        if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, what + ": empty cloud in the batch");
+        int rc = check_dst(E.device, dst[k], mv->n, fx->n, on_device, what + ", record " + std::to_string(k) + ": "); if (rc) return rc;
+        rq[k] = Engine::SideReq<Dst>{mv, nullptr, fx, 0.f, p, true, dst[k]};
     }
-    int rc = E.match_enqueue(rq.data(), (int)rq.size(), E.last_stream, !on_device, on_device ? static_cast<hipStream_t>(out_stream) : nullptr); if (rc) return rc;
-    return on_device ? E.match_publish(static_cast<hipStream_t>(out_stream)) : E.match_collect();
+    return E.point_sides(rq.data(), (int)rq.size(), E.last_stream, !on_device, on_device ? static_cast<hipStream_t>(out_stream) : nullptr);
 }
-int batch_match(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
+template <class Dst>
+int batch_sides(cvo_batch b, int count, const int* pairs, const Dst* dst, bool on_device, void* out_stream, const std::string& what) {
     if (!b || !dst) return fail(CVO_ERR_INVALID, "null argument");
-    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
-    int rc = check_last_clouds(b); if (rc) return rc;
-    std::vector<int> slots(count); std::vector<unsigned char> seen(b->last_n, 0);
-    for (int k = 0; k < count; ++k) {
-        const int i = pairs ? pairs[k] : k;
-        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "point matches: pair " + std::to_string(i) + " is not a position of the last launch");
-        if (seen[i]++) return fail(CVO_ERR_INVALID, "point matches: pair " + std::to_string(i) + " listed twice");
-        slots[k] = b->last_slots[i];
-    }
-    return batch_match_run(b, slots, dst, on_device, out_stream);
+    std::vector<int> slots;
+    int rc = last_launch_pairs(b, count, pairs, what, [&](int k, int slot) { if (k == 0) slots.reserve(count); slots.push_back(slot); return (int)CVO_OK; }); if (rc) return rc;
+    return batch_sides_run(b, slots, dst, on_device, out_stream, what);
 }
 }  // namespace
+}  // extern "C++"
+int cvo_batch_point_support(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst) { return batch_sides(b, count, pairs, dst, false, nullptr, "point support"); }
+int cvo_batch_point_support_device(cvo_batch b, int count, const int* pairs, const cvo_point_support_dst* dst, void* out_stream) {
+    return batch_sides(b, count, pairs, dst, true, out_stream, "point support");
+}
 int cvo_point_matches(cvo_handle h, int slot_a, const float* tran_a, int slot_b, const cvo_point_matches_dst* dst, int cap_a, int cap_b) {
     if (!h || !dst) return fail(CVO_ERR_INVALID, "null argument");
     Cloud* a = slot_cloud(h, slot_a); Cloud* b = slot_cloud(h, slot_b);
-    int rc = match_check_dst(h->eng.device, *dst, a ? a->n : 0, b ? b->n : 0, false, "point matches: "); if (rc) return rc;
+    int rc = check_dst(h->eng.device, *dst, a ? a->n : 0, b ? b->n : 0, false, "point matches: "); if (rc) return rc;
     if (!a || !b || a->n <= 0 || b->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "point matches: empty cloud slot");
     if ((dst->best_moving && cap_a < a->n) || (dst->best_fixed && cap_b < b->n)) return fail(CVO_ERR_INVALID, "point matches: an output array is shorter than its cloud");
     const Engine::MatchReq rq[1] = {{a, tran_a, b, h->ell, -1, false, *dst}};
-    rc = h->eng.match_enqueue(rq, 1, h->eng.stream, true); if (rc) return rc;
-    return h->eng.match_collect();
+    return h->eng.point_sides(rq, 1, h->eng.stream, true);
 }
-int cvo_batch_point_matches(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst) { return batch_match(b, count, pairs, dst, false, nullptr); }
+int cvo_batch_point_matches(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst) { return batch_sides(b, count, pairs, dst, false, nullptr, "point matches"); }
 int cvo_batch_point_matches_device(cvo_batch b, int count, const int* pairs, const cvo_point_matches_dst* dst, void* out_stream) {
-    return batch_match(b, count, pairs, dst, true, out_stream);
+    return batch_sides(b, count, pairs, dst, true, out_stream, "point matches");
 }
 int cvo_batch_results_to_device(cvo_batch b, void* dst_device, int n, void* stream) {
     if (!b || !dst_device || n <= 0 || n > b->last_n) return fail(CVO_ERR_INVALID, "bad argument");
@@ -6109,16 +6004,14 @@ int tracks_aligned_slots(cvo_tracks_s* t, int object, int count, const int* stre
     }
     return CVO_OK;
 }
-int tracks_support(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_support_dst* dst, bool on_device, void* out_stream) {
+extern "C++" {
+template <class Dst>
+int tracks_sides(cvo_tracks_s* t, int object, int count, const int* streams, const Dst* dst, bool on_device, void* out_stream, const std::string& what) {
     std::vector<int> slots;
-    int rc = tracks_aligned_slots(t, object, count, streams, dst, "point support", slots); if (rc) return rc;
-    return batch_support_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
+    int rc = tracks_aligned_slots(t, object, count, streams, dst, what, slots); if (rc) return rc;
+    return batch_sides_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream, what);
 }
-int tracks_match(cvo_tracks_s* t, int object, int count, const int* streams, const cvo_point_matches_dst* dst, bool on_device, void* out_stream) {
-    std::vector<int> slots;
-    int rc = tracks_aligned_slots(t, object, count, streams, dst, "point matches", slots); if (rc) return rc;
-    return batch_match_run(object == 0 ? t->odo : t->key, slots, dst, on_device, out_stream);
-}
+}  // extern "C++"
 }  // namespace
 // ---- pose hypotheses (include/cvo_hip.h, "pose hypotheses"; cvo_hypothesis_kernels.hip)
 namespace {
@@ -6181,7 +6074,7 @@ int cvo_batch_seed_hypotheses_async(cvo_batch b, int count, const int* pairs, in
 int cvo_batch_hypothesis_results(cvo_batch b, int count, cvo_inn_p* scores, int* best) {
     if (!b) return fail(CVO_ERR_INVALID, "null batch");
     Engine& E = b->eng;
-    const bool pending = E.hyp_queued && E.hyp_seed;
+    const bool pending = E.hyp_call.queued && E.hyp_seed;
     if (count < 1 || count > (pending ? E.hyp_n : E.seed_n)) return fail(CVO_ERR_INVALID, "hypothesis results: no seeding call of that many pairs");
     HIP_TRY(hipSetDevice(E.device));
     int rc = E.hyp_keep(); if (rc) return rc;                        // (waits for the seeding call's two kernels alone: their own event)
@@ -6212,33 +6105,30 @@ int cvo_batch_pose_models(cvo_batch b, int count, const int* pairs, int k, const
 }
 int cvo_batch_result_models(cvo_batch b, int count, const int* pairs, cvo_pose_model* out) {
     if (!b || !out) return fail(CVO_ERR_INVALID, "null argument");
-    if (!b->eng.launched || count <= 0 || count > b->last_n) return fail(CVO_ERR_INVALID, "more pairs than the last launch aligned");
-    int rc = check_last_clouds(b); if (rc) return rc;
-    std::vector<Engine::PoseModelReq> rq(count); std::vector<unsigned char> seen(b->last_n, 0);
-    for (int k = 0; k < count; ++k) {
-        const int i = pairs ? pairs[k] : k;
-        if (i < 0 || i >= b->last_n) return fail(CVO_ERR_INVALID, "result models: pair " + std::to_string(i) + " is not a position of the last launch");
-        if (seen[i]++) return fail(CVO_ERR_INVALID, "result models: pair " + std::to_string(i) + " listed twice");
-        const int p = b->last_slots[i];
+    std::vector<Engine::PoseModelReq> rq;
+    int rc = last_launch_pairs(b, count, pairs, "result models", [&](int k, int p) {
+        if (k == 0) rq.reserve(count);
         const Cloud* fx = b->fixed[p].get(); const Cloud* mv = b->moving[p].get();
         if (!fx || !mv || fx->n <= 0 || mv->n <= 0) return fail(CVO_ERR_EMPTY_CLOUD, "result models: empty cloud in the batch");
-        rq[k] = Engine::PoseModelReq{mv, fx, p};                     // transform and ell: the pair's device-resident state, as cvo_batch_point_support reads it
-    }
+        rq.push_back(Engine::PoseModelReq{mv, fx, p});               // transform and ell: the pair's device-resident state, as cvo_batch_point_support reads it
+        return (int)CVO_OK;
+    });
+    if (rc) return rc;
     if ((rc = b->eng.pm_enqueue(rq.data(), count, 1, nullptr, 0.f, b->eng.last_stream))) return rc;   // behind the align launch on its stream
     return b->eng.pm_collect(out);
 }
 
 int cvo_tracks_point_support(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst) {
-    return tracks_support(t, object, count, streams, dst, false, nullptr);
+    return tracks_sides(t, object, count, streams, dst, false, nullptr, "point support");
 }
 int cvo_tracks_point_support_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_support_dst* dst, void* out_stream) {
-    return tracks_support(t, object, count, streams, dst, true, out_stream);
+    return tracks_sides(t, object, count, streams, dst, true, out_stream, "point support");
 }
 int cvo_tracks_point_matches(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst) {
-    return tracks_match(t, object, count, streams, dst, false, nullptr);
+    return tracks_sides(t, object, count, streams, dst, false, nullptr, "point matches");
 }
 int cvo_tracks_point_matches_device(cvo_tracks t, int object, int count, const int* streams, const cvo_point_matches_dst* dst, void* out_stream) {
-    return tracks_match(t, object, count, streams, dst, true, out_stream);
+    return tracks_sides(t, object, count, streams, dst, true, out_stream, "point matches");
 }
 
 // ---------------------------------------------------------------- multi-GPU: RCCL all-gather of the result records

@@ -441,16 +441,20 @@ struct BoxDesc {
     int n, ngroups;
 };
 
-// per-point support (cvo_support_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds -- a {sum, count}
-// per ROW over the columns inside both gates.  Rows and columns are given plane by plane, so the rows (or columns) of a transformed cloud are a
-// scratch copy of its {x, y, z, f0} plane beside the cloud's own {f1..f4} plane.  The table lives in pinned host memory and is read where it is.
-struct SupportDesc {
+// One direction of one pair of clouds as the box-culled row sweeps read it (per-point support, point matches): rows and columns are given plane
+// by plane, so the rows (or columns) of a transformed cloud are a scratch copy of its {x, y, z, f0} plane beside the cloud's own {f1..f4} plane.
+struct SweepSide {
     const float* a_lo; const float* a_hi;   // rows: na float4 {x, y, z, f0} and na float4 {f1, f2, f3, f4}
     const float* b_lo; const float* b_hi;   // columns: nb float4 each
     const float* bbox;                      // boxes of the columns' 32-point groups (of b_lo as it is: planes of nbox floats, as ScoreDesc::bbox)
     int nbox, na, nb;
     float ell;
     const PairState* from;                  // non-null: ell comes from this device-resident state (ScoreDesc::from)
+};
+static_assert(sizeof(SweepSide) == 64, "SweepSide layout");
+// per-point support (cvo_support_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds -- a {sum, count}
+// per ROW over the columns inside both gates.  The table is copied to device memory by the call.
+struct SupportDesc : SweepSide {
     float* sum; int* count;                 // na each
 };
 static_assert(sizeof(SupportDesc) == 80, "SupportDesc layout");
@@ -463,18 +467,12 @@ struct SupportMoveDesc {
 };
 static_assert(sizeof(SupportMoveDesc) == 80, "SupportMoveDesc layout");
 
-// point matches (cvo_match_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds, rows and columns given
-// as a SupportDesc gives them -- per ROW the column of its largest a_ij, that value, the a-weighted mean of its partners' points, and the support's
-// {sum, count}; per request a fit record made from those arrays by a second kernel.  The table is copied to device memory by the call.
+// point matches (cvo_match_kernels.hip; not in the reference): one request of a launch is ONE direction of one pair of clouds (SweepSide) -- per ROW
+// the column of its largest a_ij, that value, the a-weighted mean of its partners' points, and the support's {sum, count}; per request a fit
+// record made from those arrays by a second kernel.  The table is copied to device memory by the call.
 struct MatchFit { int rows; int matched; double sum_w; double sum_w_res2; };    // cvo_match_fit (include/cvo_hip.h)
 static_assert(sizeof(MatchFit) == 24, "MatchFit layout");
-struct MatchDesc {
-    const float* a_lo; const float* a_hi;   // rows: na float4 {x, y, z, f0} and na float4 {f1, f2, f3, f4}
-    const float* b_lo; const float* b_hi;   // columns: nb float4 each
-    const float* bbox;                      // boxes of the columns' 32-point groups (SupportDesc::bbox)
-    int nbox, na, nb;
-    float ell;
-    const PairState* from;                  // non-null: ell comes from this device-resident state (ScoreDesc::from)
+struct MatchDesc : SweepSide {
     int* best; float* best_value;           // na each
     float* mean;                            // na x 3
     float* sum; int* count;                 // na each

@@ -109,7 +109,7 @@ def main(argv=None):
     from cvo_slam_amd import api
     idx = np.arange(P, dtype=np.int32); idx_p = idx.ctypes.data_as(C.POINTER(C.c_int))
     sizes = [(n, n)] * P
-    rec_sup, rec_mat, rec_nofit = api._support_device_records(sup_both, sizes), api._match_device_records(both, sizes), api._match_device_records(nofit, sizes)
+    rec_sup, rec_mat, rec_nofit = api._device_records(api._SUPPORT, sup_both, sizes), api._device_records(api._MATCHES, both, sizes), api._device_records(api._MATCHES, nofit, sizes)
 
     def c_call(fn, recs):
         def run():
